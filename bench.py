@@ -14,6 +14,12 @@ input copies and the host ring-buffer update + upload, exactly as the pipeline d
 
 N GPUs = N independent streams (weak scaling), weights broadcast once over RCCL; `value` = aggregate frames/s.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`).  `--full` adds everything
+else the line can carry, each in runs of its own after the timed steps: per-step latency distribution, whole-frame pipeline,
+streams per GPU, per-kernel breakdown and roofline figures, HBM copy / read bandwidth, and the CPU baseline with the
+full-size parity check against the fp32 oracle.  `--dump-outputs DIR` writes what the last timed step returned as
+DIR/<name>.npy (float32); with the same arguments the inputs are identical from run to run.
 """
 import argparse
 import json
@@ -255,6 +261,47 @@ def cpu_baseline(cfg, sd_cpu16, snap, frames=3, gpu_out=None):
     return out, parity
 
 
+def cpu_weights(cfg):
+    """`random_state_dict(cfg, dtype=torch.float16)` bit for bit, its keys filled in parallel (every key seeds its own
+    generator, so the order does not matter): seconds instead of about a minute for the 1.28 B parameters."""
+    from collections import OrderedDict
+    from concurrent.futures import ThreadPoolExecutor
+
+    from live2diff_amd.weights import _fill, unet_param_spec
+    spec = unet_param_spec(cfg)
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)              # one key per pool thread; no intra-op teams nested inside them
+    try:
+        with ThreadPoolExecutor(threads) as ex:
+            return OrderedDict(zip(spec, ex.map(lambda kv: _fill(kv[0], kv[1], 1.0).half(), spec.items())))
+    finally:
+        torch.set_num_threads(threads)
+
+
+def dump_outputs(out, path, per_tensor=1 << 16):
+    """What the timed path returned in its last step, one float32 DIR/<name>.npy per returned entry: a tensor of at most
+    `per_tensor` elements whole, a larger one or a list of tensors (the KV caches, GBs) as a fixed seeded sample of
+    `per_tensor` elements of every tensor, concatenated."""
+    import numpy as np
+
+    def sample(t, seed):
+        flat = t.detach().reshape(-1)
+        idx = torch.randint(flat.numel(), (per_tensor,), generator=torch.Generator().manual_seed(seed))
+        return flat[idx.to(flat.device)]
+
+    arrays = {}
+    for k, v in out.items():
+        if torch.is_tensor(v):
+            a = v.detach() if v.numel() <= per_tensor else sample(v, 0)
+        else:
+            a = torch.cat([t.detach().reshape(-1) if t.numel() <= per_tensor else sample(t, i) for i, t in enumerate(v)])
+        arrays[k] = a.float().cpu().numpy()
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20, "dumped outputs over 64 MB"
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, f"{k}.npy"), a)
+
+
 def baseline_metric() -> str:
     """BASELINE.json's metric string, verbatim (one streaming UNet step = one output frame)."""
     try:
@@ -416,6 +463,13 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--graph", type=int, default=0, help="replay the plan from a captured hipGraph")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beyond the headline figure (latency, "
+                         "whole frame, streams per GPU, per-kernel breakdown and roofline, CPU baseline and parity); "
+                         "--no-cpu-baseline, --breakdown, --multi-stream and --whole-frame select among them")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float32; rank 0): sample.npy whole, "
+                         "kv_cache.npy a fixed seeded sample of every cache")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-frames", type=int, default=3)
     ap.add_argument("--tattn-variant", type=int, default=0)
@@ -433,6 +487,8 @@ def main():
                     help="time the whole pipeline step on the device (UNet + LCM step + buffer shift + re-noising + ring "
                          "buffer as one plan, SURVEY 8f row F3) instead of the UNet boundary call; informational")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
@@ -441,7 +497,7 @@ def main():
     from live2diff_amd.config import sd15_config
     from live2diff_amd.pipeline_stream_animation_depth import ring_buffer_init, ring_buffer_update
     from live2diff_amd.unet_hip import HipStreamingUNet
-    from live2diff_amd.weights import device_random_state_dict, random_state_dict, unet_param_spec
+    from live2diff_amd.weights import device_random_state_dict, unet_param_spec
 
     rank, world, local = parallel.init_distributed()
     if world != args.gpus:
@@ -459,9 +515,11 @@ def main():
 
     # ---- weights: generated on rank 0, one-time RCCL broadcast (the only collective of the data path)
     spec = unet_param_spec(cfg)
-    need_cpu_weights = (world == 1 and not args.no_cpu_baseline)     # the CPU baseline runs the oracle on the same weights
+    # the CPU baseline (--full) runs the oracle on the same weights; a plain run generates the same ones, so that its outputs
+    # match the --full run's
+    need_cpu_weights = (world == 1 and not args.no_cpu_baseline)
     if rank == 0:
-        sd_cpu = random_state_dict(cfg, dtype=torch.float16) if need_cpu_weights else device_random_state_dict(cfg, dev)
+        sd_cpu = cpu_weights(cfg) if need_cpu_weights else device_random_state_dict(cfg, dev)
     else:
         sd_cpu = None
     if world > 1:
@@ -534,10 +592,12 @@ def main():
     finite = bool(torch.isfinite(out["sample"]).all())
     ms_per_step = 1e3 * elapsed / args.steps
     value = world * args.steps / elapsed
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(out, args.dump_outputs)
     # per-step latency distribution (BASELINE metric: "...; per-step latency"): a separate pass AFTER the timed region,
     # events on the stream the plan is launched on, one per frame boundary; never allowed to fail the benchmark
     latency = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             n_lat = max(2, min(50, args.steps))
             evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_lat + 1)]
@@ -556,14 +616,14 @@ def main():
     # TAESD encode of the frame, the depth path (384x384 resize, DPT-Hybrid depth detector, min-max + resize, TAESD encode of
     # the depth map), the UNet step, TAESD decode.  Random-init weights of the published architectures throughout.
     whole = None
-    if rank == 0 and args.whole_frame and dstep is None and (args.height % 8 == 0 and args.width % 8 == 0):
+    if rank == 0 and args.full and args.whole_frame and dstep is None and (args.height % 8 == 0 and args.width % 8 == 0):
         try:
             whole = pipeline_whole_frame(unet, cfg, args, dev, N, sink, kv)
         except Exception as e:  # noqa: BLE001  -- informational figure: never fails the benchmark
             whole = {"error": repr(e)}
 
     multi = None
-    if rank == 0 and world == 1 and args.multi_stream > 1:
+    if rank == 0 and world == 1 and args.full and args.multi_stream > 1:
         try:
             multi = multi_stream_sweep(unet, cfg, args, dev, N, args.multi_stream)
         except Exception as e:  # noqa: BLE001  -- informational figure: never fails the benchmark
@@ -573,7 +633,7 @@ def main():
     # and leave stale rows in the KV caches): same state for both legs = snapshot of (inputs, caches, ring buffer), then
     # ONE more GPU frame from exactly that state; the oracle starts from the snapshot after the JSON fields are assembled.
     snap = gpu_out = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         snap = {"kv": [c.cpu() for c in kv], "rb": [t.clone() for t in rb], "x": x.cpu(), "d": d.cpu(), "enc": enc.cpu(),
                 "ts": ts.cpu()}
         if dstep is None:          # (the device step owns its ring state / noise: no like-for-like frame to compare)
@@ -597,7 +657,8 @@ def main():
                                     if args.device_step else "UNet boundary call (+ host ring buffer and its upload)")},
     }
     my_frac = float("nan")
-    if args.breakdown and rank != 0 and world > 1:
+    breakdown = args.full and args.breakdown
+    if breakdown and rank != 0 and world > 1:
         # every rank replays its own kernel families: the N > 1 line carries each GPU's roofline fraction
         try:
             rows = per_kernel_breakdown(unet)
@@ -608,7 +669,7 @@ def main():
                 my_frac = r["bytes"] / r["launches"] / (r["avg_us"] * 1e-6) / 1e9 / HBM_PEAK_GBPS
         except Exception:  # noqa: BLE001
             pass
-    if rank == 0 and args.breakdown:
+    if rank == 0 and breakdown:
         rows = per_kernel_breakdown(unet)
         tot = sum(r["ms"] for r in rows.values())
         kernels = {}
@@ -758,7 +819,7 @@ def main():
             del a, b
         except Exception as e:  # noqa: BLE001
             result["hbm_copy_gbps_measured"] = f"error: {e}"
-    if world > 1 and args.breakdown:
+    if world > 1 and breakdown:
         result["per_rank_roofline_frac"] = [round(v, 4) for v in parallel.gather_floats(my_frac, device=dev)]
     if rank == 0 and args.per_op:
         per_op_table(unet, args.per_op)

@@ -1,16 +1,16 @@
 #!/bin/bash
 # Round-end evidence run on the GPU box: bench line, kernel-trace stats, in-frame per-launch trace, HBM traffic counters.
-#   tools/profile_round.sh <tag>     -> gpurun_out/<tag>/  (small CSV / JSON / txt only; the rocpd databases stay in /tmp)
+#   tools/profile_round.sh <tag> [dir]     -> <dir>/<tag>/, dir defaults to results  (small CSV / JSON / txt only; the rocpd databases stay in /tmp)
 # Copy what should be judged into profiles/ afterwards (profiles/README.md lists the files).
 set -u
 TAG=${1:-rX}
-OUT=gpurun_out/$TAG
+OUT=${2:-results}/$TAG
 export TMPDIR=/tmp
 mkdir -p "$OUT" /tmp/prof
 rm -rf /tmp/prof/*
 
-# 1. the driver's default bench line (with the CPU baseline leg)
-python bench.py > "$OUT/${TAG}_bench_cfg2.json" 2> "$OUT/bench_err.log"
+# 1. the full bench line (--full: latency, whole frame, streams per GPU, per-kernel roofline, CPU baseline leg)
+python bench.py --full > "$OUT/${TAG}_bench_cfg2.json" 2> "$OUT/bench_err.log"
 cut -c1-400 "$OUT/${TAG}_bench_cfg2.json"
 
 # 2. kernel trace of the same workload: per-kernel stats, per-shape table, in-frame duration of every launch
