@@ -232,6 +232,22 @@ enum {
  *   samples   p14 GroupNorm prologue on x: int64 [samples][G][2] fixed-point statistics filled by x's producers (as L2D_OP_ROWGEMM
  *   prologue 2), or 0   i7 passes (1 | 3) i8 transposed last pass (needs i7 = 3) i9 ldt i10 T tokens per sample i11 G
  *   f0 eps of the LayerNorm f1 eps of the GroupNorm
+ *
+ * CLIP text encoder (clip.hip; reference: transformers' CLIPTextModel as called by
+ * pipeline_animatediff_depth.py:149-248).  The residual stream is fp32 [rows][C]; everything else is fp16.
+ * L2D_OP_CLIP_EMBED  out[r][c] = float(tok[ids[r]][c]) + float(pos[r % T][c]):  p0 ids int64 [rows] p1 tok [V][C] half
+ *   p2 pos [P][C] half p3 out [rows][C] float ; i0 rows (% T) i1 T (<= P) i2 C (% 8) i3 V i4 P
+ * L2D_OP_CLIP_ATTN   causal (i6 = 1) or full softmax(Q K^T scale) V per (prompt, head), all T rows computed:  p0 qkv [B*T][ldq] half
+ *   (q | k | v at columns 0, H d, 2 H d) p1 out [B*T][ldo] half ; i0 B i1 T (<= 128) i2 H i3 d (= 64) i4 ldq (% 8) i5 ldo i6 causal
+ *   f0 scale
+ * L2D_OP_CLIP_LINEAR out[m][n] = epi( sum_k pro(x)[m][k] W[n][k] + b[n] ) for small M (weight streaming, MFMA; K <= 1024 with i5 = 1):
+ *   p0 x: [M][ldx] half (i5 = 0) or the fp32 residual stream [M][ldx] float (i5 = 1: LayerNorm over K with p4 / p5 applied)
+ *   p1 w half in MFMA-fragment order [Nout/32][K/16][64 lanes][8] (ops.pack_clip_linear)  p2 bias float [Nout] or 0
+ *   p3 out: half [M][ldo] (i6 = 0 none, 1 quick-GELU v sigmoid(1.702 v)) or float [M][ldo] (i6 = 2: out += v, in place)
+ *   p4 gamma p5 beta float [K] (i5 = 1) ; i0 M i1 K i2 Nout (% 32) i3 ldx (% 8) i4 ldo i5 pro i6 epi i7 NW waves per block
+ *   (1..8) i8 MT token tiles of 32 per block (1..4) ; K = NW * npass * 192 ; f0 eps
+ * L2D_OP_CLIP_LN     LayerNorm, fp32 in, fp16 out: p0 x [rows][ldx] float p1 gamma p2 beta float [C] p3 out [rows][ldo] half ;
+ *   i0 rows i1 C (<= 1024) i2 ldx i3 ldo ; f0 eps
  */
 enum {
     L2D_OP_IGEMM = 1,
@@ -261,6 +277,10 @@ enum {
     L2D_OP_WSGEMM = 25,
     L2D_OP_ROWCHAIN = 26,
     L2D_OP_CCONV = 27,
+    L2D_OP_CLIP_EMBED = 28,
+    L2D_OP_CLIP_ATTN = 29,
+    L2D_OP_CLIP_LINEAR = 30,
+    L2D_OP_CLIP_LN = 31,
 };
 
 typedef struct l2d_op {

@@ -248,3 +248,70 @@ def load_safetensors(path: str) -> Dict[str, torch.Tensor]:
     from safetensors import safe_open
     with safe_open(path, framework="pt", device="cpu") as f:
         return {k: f.get_tensor(k) for k in f.keys()}
+
+
+# ----------------------------------------------------------------------------- text encoder
+LDM_CLIP_PREFIX = "cond_stage_model.transformer."
+
+
+def convert_ldm_clip_checkpoint(dreambooth_sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """The text-encoder half of an LDM / CompVis checkpoint: `cond_stage_model.transformer.` stripped (reference
+    convert_from_ckpt.py:591-599; keys come out as transformers 4.x names, `text_model.` prefix included).  Divergence: the
+    reference loads the result with `strict=False` (converter/convert.py:47-50), so a checkpoint without these keys loads nothing
+    and says nothing; here a checkpoint with no text-encoder key raises."""
+    out = {k[len(LDM_CLIP_PREFIX):]: v for k, v in dreambooth_sd.items() if k.startswith(LDM_CLIP_PREFIX)}
+    if not out:
+        raise KeyError(f"no `{LDM_CLIP_PREFIX}*` key in the checkpoint: it carries no text encoder")
+    return out
+
+
+def merge_text_lora(sd: Dict[str, torch.Tensor], lora_sd: Dict[str, torch.Tensor], alpha: float = 0.6) -> List[str]:
+    """In place: W += alpha * up @ down for every `lora_te_*` pair of a kohya LoRA (reference
+    convert_lora_safetensor_to_diffusers.py:38-41, 88-91), the flattened module name resolved against the text-encoder keys
+    (with or without `text_model.`).  Per-module `.alpha` entries are skipped, as the reference does.  Returns the touched keys;
+    a pair whose module is not in `sd` raises (the reference's attribute walk would)."""
+    flat = {}
+    for k in sd:
+        if k.endswith(".weight"):
+            m = k[: -len(".weight")]
+            flat[_flatten(m if m.startswith("text_model.") else "text_model." + m)] = k
+    touched = []
+    for k in lora_sd:
+        if ".alpha" in k or "lora_down" not in k or not k.startswith("lora_te_"):
+            continue
+        name = k.split(".")[0][len("lora_te_"):]
+        key = flat.get(name)
+        if key is None:
+            raise KeyError(f"text LoRA module {name!r} not found in the text-encoder state dict")
+        up, down = lora_sd[k.replace("lora_down", "lora_up")].to(torch.float32), lora_sd[k].to(torch.float32)
+        w = sd[key]
+        delta = up.reshape(up.shape[0], -1) @ down.reshape(down.shape[0], -1)
+        sd[key] = (w.to(torch.float32) + alpha * delta.reshape(w.shape)).to(w.dtype)
+        touched.append(key)
+    return touched
+
+
+def build_text_encoder_state_dict(base_sd: Dict[str, torch.Tensor], dreambooth: Optional[Dict[str, torch.Tensor]] = None,
+                                  loras: Optional[List[Tuple[Dict[str, torch.Tensor], float]]] = None) -> Dict[str, torch.Tensor]:
+    """The text half of a style, in the reference's order: base text encoder, the DreamBooth checkpoint's text encoder over it
+    (converter/convert.py:47-50), then each LoRA's `lora_te_*` pairs at its strength (:72-88).  Keys of the result are the
+    base dict's; DreamBooth keys are matched with or without the `text_model.` prefix."""
+    sd = dict(base_sd)
+    if dreambooth is not None:
+        strip = lambda k: k[len("text_model."):] if k.startswith("text_model.") else k
+        by_stem = {strip(k): k for k in sd}
+        conv = convert_ldm_clip_checkpoint(dreambooth)
+        n = 0
+        for k, v in conv.items():
+            key = by_stem.get(strip(k))
+            if key is None:
+                continue                  # (the reference's strict=False: e.g. position_ids)
+            if tuple(v.shape) != tuple(sd[key].shape):
+                raise ValueError(f"{key}: DreamBooth tensor {tuple(v.shape)} != text-encoder parameter {tuple(sd[key].shape)}")
+            sd[key] = v.to(sd[key].dtype)
+            n += 1
+        if n == 0:
+            raise KeyError("the checkpoint's text-encoder keys match no parameter of the base text encoder")
+    for lora_sd, alpha in (loras or []):
+        merge_text_lora(sd, lora_sd, alpha)
+    return sd

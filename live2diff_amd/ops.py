@@ -1227,3 +1227,78 @@ def run(op_and_keep, stream=None):
     pl = _lib.OpList()
     pl.append(op, *keep)
     pl.run(stream)
+
+
+# ----------------------------------------------------------------------------- CLIP text encoder (clip.hip)
+CLIP_STEPS = 12          # k steps of 16 per wave and pass of clip_linear_kernel: K % 192 == 0
+
+
+def pack_clip_linear(w: torch.Tensor) -> torch.Tensor:
+    """[Nout, K] -> fp16 in MFMA-fragment order for L2D_OP_CLIP_LINEAR: flat (((t * S + s) * 64 + lane) * 8 + e) holds
+    W[32 t + lane % 32][16 s + 8 (lane // 32) + e], S = K / 16 (the permutation of pack_rowgemm, without its K limit)."""
+    n, k = w.shape
+    assert n % 32 == 0 and k % (16 * CLIP_STEPS) == 0, (n, k)
+    S = k // 16
+    return w.to(torch.float16).reshape(n // 32, 32, S, 2, 8).permute(0, 2, 3, 1, 4).contiguous().view(-1)
+
+
+def clip_linear_schedule(M: int, K: int):
+    """(NW waves per block, MT token tiles per block): K splits into NW x npass passes of 12 k steps (NW <= 8); the token tiles
+    of 32 go to as few blocks as hold them at <= 4 tiles each, spread evenly."""
+    n12 = K // (16 * CLIP_STEPS)
+    NW = max(d for d in range(1, 9) if n12 % d == 0)
+    mtiles = (M + 31) // 32
+    groups = (mtiles + 3) // 4
+    return NW, (mtiles + groups - 1) // groups
+
+
+def clip_embed(ids, tok, pos, out, *, rows, T, C, V, P):
+    op = L2dOp()
+    op.kind = _lib.OP_CLIP_EMBED
+    assert ids.dtype == torch.int64 and out.dtype == torch.float32
+    op.p[0], op.p[1], op.p[2], op.p[3] = _ptr(ids), _ptr(_h(tok)), _ptr(_h(pos)), _ptr(out)
+    for j, v in enumerate([rows, T, C, V, P]):
+        op.i[j] = int(v)
+    return op, (ids, tok, pos, out)
+
+
+def clip_attn(qkv, out, *, B, T, H, d, ldq, ldo, scale, causal=True, q_off=0, o_off=0):
+    op = L2dOp()
+    op.kind = _lib.OP_CLIP_ATTN
+    op.p[0], op.p[1] = _ptr(_h(qkv)) + 2 * q_off, _ptr(_h(out)) + 2 * o_off
+    for j, v in enumerate([B, T, H, d, ldq, ldo, 1 if causal else 0]):
+        op.i[j] = int(v)
+    op.f[0] = float(scale)
+    return op, (qkv, out)
+
+
+CLIP_EPI_NONE, CLIP_EPI_QUICK_GELU, CLIP_EPI_RESIDUAL = 0, 1, 2
+
+
+def clip_linear(x, w, out, *, M, K, Nout, ldx, ldo, bias=None, gamma=None, beta=None, epi=CLIP_EPI_NONE, eps=1e-5,
+                NW=None, MT=None):
+    """x fp16 [M][ldx], or the fp32 residual stream with gamma / beta given (LayerNorm prologue); out fp16, or fp32 with
+    epi = CLIP_EPI_RESIDUAL (out += x W^T + b in place)."""
+    op = L2dOp()
+    op.kind = _lib.OP_CLIP_LINEAR
+    pro = 1 if gamma is not None else 0
+    assert x.dtype == (torch.float32 if pro else torch.float16), x.dtype
+    assert out.dtype == (torch.float32 if epi == CLIP_EPI_RESIDUAL else torch.float16), out.dtype
+    nw, mt = clip_linear_schedule(M, K)
+    op.p[0], op.p[1], op.p[2], op.p[3] = _ptr(x), _ptr(_h(w)), _ptr(bias), _ptr(out)
+    op.p[4], op.p[5] = _ptr(gamma), _ptr(beta)
+    for j, v in enumerate([M, K, Nout, ldx, ldo, pro, epi, NW or nw, MT or mt]):
+        op.i[j] = int(v)
+    op.f[0] = float(eps)
+    return op, (x, w, bias, out, gamma, beta)
+
+
+def clip_ln(x, gamma, beta, out, *, rows, C, ldx, ldo, eps=1e-5, x_off=0, o_off=0):
+    op = L2dOp()
+    op.kind = _lib.OP_CLIP_LN
+    assert x.dtype == torch.float32 and gamma.dtype == torch.float32
+    op.p[0], op.p[1], op.p[2], op.p[3] = _ptr(x) + 4 * x_off, _ptr(gamma), _ptr(beta), _ptr(_h(out)) + 2 * o_off
+    for j, v in enumerate([rows, C, ldx, ldo]):
+        op.i[j] = int(v)
+    op.f[0] = float(eps)
+    return op, (x, gamma, beta, out)
