@@ -8,8 +8,6 @@
 //   pass 1 (gn_stats): per-(b, pixel-chunk) partial sum / sum-of-squares for each of the G groups (fixed summation order)
 //   pass 2 (gn_apply): deterministic reduction of the partials, then y = (x-mean)*rstd*gamma+beta (-> SiLU)
 // LayerNorm replaces nn.LayerNorm (attention.py:182,199,205; motion_module.py:355,361): one wave per row.
-#include <stdlib.h>
-
 #include "common.h"
 
 struct GNArgs {
@@ -338,14 +336,11 @@ int l2d_launch_gn_apply(const l2d_op *op, hipStream_t s) {
         return l2d_check_launch("gn_self", op->tag);
     }
     // One trip per block: the four passes of pixel rows the kernel requests before it looks at the statistics (8-32 KB of
-    // activations per block; 340-1000 blocks at the 64 x 64 level), one grid plane per band of 2048 channels.  L2D_GN_BLOCK16K=1
-    // restores the ~16 KB blocks of rounds 3-5 (a second, dependent trip of a row or two) for A/B: profiles/round6_s_*.
-    static int old_blocks = -1;
-    if (old_blocks < 0) { const char *e = getenv("L2D_GN_BLOCK16K"); old_blocks = e ? atoi(e) : 0; }
+    // activations per block; 340-1000 blocks at the 64 x 64 level), one grid plane per band of 2048 channels.  (The ~16 KB blocks of
+    // rounds 3-5, a second, dependent trip of a row or two, measured slower: profiles/round6_s_*.)
     int cols = (C / 8) < 256 ? (C / 8) : 256;
     int pr = 256 / cols;
-    int ppb = old_blocks ? (8192 + C - 1) / C : 4 * pr;
-    if (ppb < pr) ppb = pr;
+    int ppb = 4 * pr;
     if (ppb > a.T) ppb = a.T;
     int nb = (a.T + ppb - 1) / ppb;
     int nz = (C / 8 + cols - 1) / cols;

@@ -3,8 +3,10 @@ packers.  Everything here is plumbing: pointers, sizes and strides; the arithmet
 
 Each builder returns `(op, keepalive_tensors)` so that a plan (`_lib.OpList`) can keep the buffers alive.
 """
+import functools
+import json
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -17,6 +19,49 @@ def _ptr(t: Optional[torch.Tensor]):
 
 
 DRY_RUN = False   # set by the CPU test-suite together with l2d_set_dry_run(1): plans are built and validated, never launched
+
+
+class Overrides(NamedTuple):
+    igemm_force: str
+    igemm_no_table: bool
+    wsgemm: bool
+    wsgemm_force: str
+    wsgemm_large_all: bool
+    wsgemm_max_m: int
+    wsgemm_no_table: bool
+
+
+def overrides() -> Overrides:
+    """The tuning / diagnosis overrides: the only environment variables that change which kernel or schedule a plan takes (defaults
+    are the measured best).  Read on every call -- the tools set them mid-process or drive bench.py from the shell.
+      L2D_IGEMM_FORCE="tile,S,variant"  every implicit-GEMM launch it fits takes that schedule (tools/igemm_tune_each.py, igemm_pick.py)
+      L2D_IGEMM_NO_TABLE=1              ignore igemm_tuned.json: every shape on the fallback rule (tools/tune_igemm.sh)
+      L2D_WSGEMM=0                      no weight-streaming GEMM: every level packs and runs the round-3 kernels (the tuners' baseline)
+      L2D_WSGEMM_FORCE="NW,NT,NL,S"     every wsgemm launch it fits takes that schedule (tools/wsgemm_tune*.py)
+      L2D_WSGEMM_LARGE_ALL=1            every layer of the levels below L2D_WSGEMM_MAX_M is offered the weight-streaming packing (what
+                                        the tuners measure); without it the `skip` / `large` lists and the fallback rule decide
+      L2D_WSGEMM_MAX_M=4608             most stream tokens (N x pixels) of a level that may take the weight-streaming packing
+      L2D_WSGEMM_NO_TABLE=1             ignore wsgemm_tuned.json: cost-model schedules, the fallback rule packs (tools/flip_diag.py)"""
+    e = os.environ
+    return Overrides(igemm_force=e.get("L2D_IGEMM_FORCE", ""), igemm_no_table=bool(e.get("L2D_IGEMM_NO_TABLE")),
+                     wsgemm=e.get("L2D_WSGEMM", "1") != "0", wsgemm_force=e.get("L2D_WSGEMM_FORCE", ""),
+                     wsgemm_large_all=bool(e.get("L2D_WSGEMM_LARGE_ALL")), wsgemm_max_m=int(e.get("L2D_WSGEMM_MAX_M", "4608")),
+                     wsgemm_no_table=bool(e.get("L2D_WSGEMM_NO_TABLE")))
+
+
+@functools.lru_cache(maxsize=None)
+def _table_file(name: str) -> dict:
+    path = os.path.join(os.path.dirname(__file__), name)
+    if not os.path.exists(path):
+        return {}
+    with open(path) as f:
+        return json.load(f)
+
+
+def tuned_table(name: str, no_table: bool = False) -> dict:
+    """A table measured on MI355X (`name`: igemm_ / rowgemm_ / wsgemm_tuned.json beside this module, written by the tuners) as
+    {"shapes": {...}, ...}; empty when the file is missing or an override's NO_TABLE asks for none."""
+    return {} if no_table else _table_file(name)
 
 
 def _h(t: torch.Tensor) -> torch.Tensor:
@@ -67,6 +112,11 @@ def f32(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
 
 
 ROWGEMM_MAX_K = 2048
+# widest contraction the plan gives the row GEMM for a Linear with no norm to fuse: at K = 1280 every 32-token block streams 80 KB of
+# weights per 32-row tile and igemm is faster (profiles/round3_c_bench_plain640/2048.json); GEGLU projections (LayerNorm fused) up to
+# K = 1280 (routing levels 1 / 2 back to LayerNorm + igemm measured 0.6 % slower)
+ROWGEMM_PLAIN_MAX_K = 640
+ROWGEMM_FF1_MAX_K = 1280
 
 
 def rowgemm_ok(nout: int, k: int) -> bool:
@@ -252,13 +302,12 @@ ROWCHAIN_C = 320                # the width the chain kernel is instantiated for
 # M / 32 blocks.  Round 5 set 192 from the BASELINE configs (256+ blocks, or cfg-1's 32); round 6 measured the gap: 144 blocks (384 x 384,
 # N = 2) 7.70 -> 7.40 ms, 154 blocks (448 x 704, N = 1) 8.34 -> 7.98 ms, 100 blocks (320 x 320, N = 2) 7.09 -> 7.00 ms with the chain
 # (profiles/round6_v_*, round6_w_*); cfg-1 (32 blocks) keeps the separate launches: 5.14 ms against 5.31 with the chain (round6_ab_*)
-ROWCHAIN_MIN_BLOCKS = int(os.environ.get("L2D_ROWCHAIN_MIN_BLOCKS", "96"))
+ROWCHAIN_MIN_BLOCKS = 96
 
 
 def rowchain_ok(M: int, C: int, T: int) -> bool:
     """Shapes the token-resident block tail (csrc/rowchain.hip) takes"""
-    return (os.environ.get("L2D_ROWCHAIN", "1") != "0" and C == ROWCHAIN_C and M % 32 == 0 and T % 32 == 0
-            and M // 32 >= ROWCHAIN_MIN_BLOCKS)
+    return C == ROWCHAIN_C and M % 32 == 0 and T % 32 == 0 and M // 32 >= ROWCHAIN_MIN_BLOCKS
 
 
 def rowchain(a, res1, res2, out, *, M, C, w_out, b_out, w_ff1, b_ff1, w_ff2, b_ff2, w_po, b_po, eps=1e-5, lda=None, ldr1=None,
@@ -285,7 +334,7 @@ def pconv_patch(B: int, H: int, W: int, Nout: int, C1: int, C2: int = 0):
     """Patch (PH, PW) for the patch-resident 3x3 conv, or None when the implicit-GEMM kernel should take the launch: the largest
     of 8x16 / 8x8 / 4x8 that tiles the image and yields >= 256 blocks of (patch, 64 output channels).  Not for the lowest
     resolutions: with few tokens the launch is bound by its weight stream (9 C Nout x 2 bytes), which wants split-K."""
-    if os.environ.get("L2D_PCONV", "1") == "0" or Nout % 64 or C1 % 64 or C2 % 64 or C1 <= 0:
+    if Nout % 64 or C1 % 64 or C2 % 64 or C1 <= 0:
         return None
     for ph, pw in ((8, 16), (8, 8), (4, 8)):
         if H % ph or W % pw:
@@ -345,15 +394,9 @@ def rowgemm_schedule(M: int, K: int, Nout: int, ntr: int = 0, epi: int = 0, pro:
     through a ring of ~16 KB (latency bound: ~20 GB/s per wave) or NT * MT * K / 16 MFMAs of 32 cycles, whichever is longer;
     blocks run in rounds of 256 CUs x (blocks per CU by LDS and by 12 waves)."""
     tiles = Nout // 32
-    force = os.environ.get("L2D_ROWGEMM_FORCE")        # "NW,NT,MT" (tools): applied where it divides the shape
-    if force:
-        nw, nt, mt = (int(v) for v in force.split(","))
-        if tiles % (nw * nt) == 0 and (ntr // 32) % (nw * nt) == 0 and nw <= (5 if nt >= 3 else 8) and _rowgemm_mt_ok(mt, nt, K, T) \
-                and _rowgemm_lds(K, nw, nt, mt, epi, pro, ntr, gn) <= 163840:
-            return nw, nt, mt
-    key = f"{M},{K},{Nout},{ntr},{epi}"
-    if key in _RG_TUNED and _rowgemm_mt_ok(_RG_TUNED[key][2], _RG_TUNED[key][1], K, T):
-        return tuple(_RG_TUNED[key])
+    tuned = tuned_table("rowgemm_tuned.json").get("shapes", {}).get(f"{M},{K},{Nout},{ntr},{epi}")
+    if tuned and _rowgemm_mt_ok(tuned[2], tuned[1], K, T):
+        return tuple(tuned)
     cdiv = lambda a, b: (a + b - 1) // b
     best, best_t = None, None
     for mt in (1, 2):
@@ -382,18 +425,6 @@ def rowgemm_schedule(M: int, K: int, Nout: int, ntr: int = 0, epi: int = 0, pro:
                     best, best_t = (nw, nt, mt, blocks), t
     assert best is not None, (M, K, Nout, ntr)
     return best[:3]
-
-
-def _load_rg_tuned():
-    import json
-    path = os.path.join(os.path.dirname(__file__), "rowgemm_tuned.json")
-    if os.environ.get("L2D_ROWGEMM_NO_TABLE") or not os.path.exists(path):
-        return {}
-    with open(path) as f:
-        return json.load(f)["shapes"]
-
-
-_RG_TUNED = _load_rg_tuned()
 
 
 def rowgemm(x, w, out, *, M, K, Nout, ldx, ldo, bias=None, res=None, ldr=0, epi=0, pro=0, eps=1e-5, T=0, G=0, gn_acc_ptr=None,
@@ -497,7 +528,7 @@ def wsgemm_schedule(M: int, Ktot: int, Nout: int, ntr: int = 0, epi: int = 0, pr
     tiles = Nout // 32
     nm = (M + WS_BM - 1) // WS_BM
     nch = Ktot // 64
-    force = os.environ.get("L2D_WSGEMM_FORCE")        # "NW,NT,NL,S" (tools): applied where it divides the shape
+    o = overrides()
     ntw = nm == 1
     key = wsgemm_key(taps, M, Ktot, Nout, ntr, epi, pro)
     cands = []
@@ -509,12 +540,13 @@ def wsgemm_schedule(M: int, Ktot: int, Nout: int, ntr: int = 0, epi: int = 0, pr
                 continue
             cands.append((nw, nt))
     assert cands, (M, Ktot, Nout, ntr, epi, pro)
-    if force:
-        nw, nt, nl, S = (int(v) for v in force.split(","))
+    if o.wsgemm_force:                                 # (applied where it divides the shape)
+        nw, nt, nl, S = (int(v) for v in o.wsgemm_force.split(","))
         if (nw, nt) in cands and not (ntr and S > 1):
             return nw, nt, nl, max(1, min(S, nch)), ntw
-    if key in _WS_TUNED:
-        nw, nt, nl, S = _WS_TUNED[key][:4]
+    tuned = wsgemm_table(o).get("shapes", {})
+    if key in tuned:
+        nw, nt, nl, S = tuned[key][:4]
         if (nw, nt) in cands:
             return nw, nt, nl, max(1, min(S, nch)), ntw
     # default (shapes the table does not hold): two loader waves; about one block per CU (240-256 blocks); one weight tile per
@@ -541,20 +573,13 @@ def wsgemm_schedule(M: int, Ktot: int, Nout: int, ntr: int = 0, epi: int = 0, pr
     return best
 
 
-def _load_ws_tuned():
-    import json
-    path = os.environ.get("L2D_WSGEMM_TABLE") or os.path.join(os.path.dirname(__file__), "wsgemm_tuned.json")   # (override: A/B runs of tools)
-    if os.environ.get("L2D_WSGEMM_NO_TABLE") or not os.path.exists(path):
-        return {}, set(), set()
-    with open(path) as f:
-        d = json.load(f)
-    return d["shapes"], set(d.get("skip", [])), set(d.get("large", []))
+def wsgemm_table(o: Optional[Overrides] = None) -> dict:
+    """wsgemm_tuned.json: `shapes` -> schedule; `skip` = few-token shapes (M <= WS_SMALL_M) where the round-3 kernel measured faster;
+    `large` = shapes with MORE tokens where the weight-streaming kernel measured faster (there the round-3 kernels are the default:
+    opt-in, not opt-out)"""
+    return tuned_table("wsgemm_tuned.json", (o or overrides()).wsgemm_no_table)
 
 
-# shapes -> schedule; skip = few-token shapes (M <= WS_SMALL_M) where the round-3 kernel measured faster; large = shapes with MORE
-# tokens where the weight-streaming kernel measured faster (there the round-3 kernels are the default: opt-in, not opt-out)
-_WS_TUNED, _WS_SKIP, _WS_LARGE = _load_ws_tuned()
-_WS_TUNED_M = {int(k.split(",")[1]) for k in list(_WS_TUNED) + list(_WS_SKIP)}      # token counts the tuner measured (any shape class)
 WS_SMALL_M = 1280
 
 
@@ -568,14 +593,19 @@ def wsgemm_wanted(taps: int, M: int, Ktot: int, Nout: int, ntr: int = 0, epi: in
     BASELINE configs, 2048-4608 tokens): True only where the tuner measured the weight-streaming kernel faster (`large` list) --
     an untuned resolution keeps the round-3 kernels there.  The packer follows this."""
     key = wsgemm_key(taps, M, Ktot, Nout, ntr, epi, pro)
+    o = overrides()
+    d = wsgemm_table(o)
+    shapes, skip = d.get("shapes", {}), d.get("skip", [])
     # measured by the tuner?  few tokens: every candidate shape it saw is in `shapes` or `skip`; above 1280 tokens it records winners
     # only, so there the token count stands for "this level was offered"
-    tuned = (key in _WS_TUNED or key in _WS_SKIP) if M <= WS_SMALL_M else (M in _WS_TUNED_M)
-    if not tuned and os.environ.get("L2D_WSGEMM_RULE", "1") != "0" and not os.environ.get("L2D_WSGEMM_LARGE_ALL"):
+    tuned = (key in shapes or key in skip) if M <= WS_SMALL_M else any(int(k.split(",")[1]) == M for k in list(shapes) + skip)
+    if o.wsgemm_large_all:                     # (the tuner offers every shape and measures)
+        return key not in skip
+    if not tuned:
         return _wsgemm_wanted_rule(taps, M, Ktot, Nout, ntr, epi, pro)
-    if M > WS_SMALL_M and not os.environ.get("L2D_WSGEMM_LARGE_ALL"):      # (LARGE_ALL: the tuner offers every shape and measures)
-        return key in _WS_LARGE
-    return key not in _WS_SKIP
+    if M > WS_SMALL_M:
+        return key in d.get("large", [])
+    return key not in skip
 
 
 def _wsgemm_wanted_rule(taps: int, M: int, Ktot: int, Nout: int, ntr: int, epi: int, pro: int) -> bool:
@@ -583,8 +613,7 @@ def _wsgemm_wanted_rule(taps: int, M: int, Ktot: int, Nout: int, ntr: int, epi: 
     (122 of the 150 candidate shapes of the five plans follow it; the rest are within its 3 % threshold either way).  More than 1280
     tokens (level 1): LayerNorm + q|k|v and LayerNorm + GEGLU, the long plain contractions from 3072 tokens on, the long 3x3 convs
     that cconv.hip does not take.  Fewer: everything at the 1280-wide levels; at 640 wide the LayerNorm + q|k|v / GEGLU layers from
-    512 tokens on and the 640 -> 1280 shortcuts; nothing at 320 wide (cfg-1: the row GEMM wins every layer of its levels 0 / 1).
-    L2D_WSGEMM_RULE=0: the pre-round-6 default (every few-token shape, nothing above 1280 tokens; profiles/round6_w_*)."""
+    512 tokens on and the 640 -> 1280 shortcuts; nothing at 320 wide (cfg-1: the row GEMM wins every layer of its levels 0 / 1)."""
     K = Ktot // taps
     if M > 4608:                # (beyond every token count the kernel was measured at; the plan's own bound is L2D_WSGEMM_MAX_M)
         return False
@@ -714,13 +743,8 @@ def cconv_schedule(B: int, H: int, W: int, Nout: int, CinP: int, KG: Optional[in
     K slices of whole 64-channel chunks, from a cost model fitted to tools/cconv_time.py / tools/cconv_stamps.py (MI355X): the k loop
     of the longest slice at ~0.7 of the matrix rate, a fixed prologue / epilogue, per split the slab publish and the last arriver's
     sum, and a second round of blocks beyond one per CU.  `KG`: the packing's K-group count when it is already fixed (the warm-up
-    plan shares the stream plan's packed weights).  L2D_CCONV_FORCE="CG,KG,NLD,S" overrides (tuning)."""
-    force = os.environ.get("L2D_CCONV_FORCE")
+    plan shares the stream plan's packed weights)."""
     nch = CinP // 64
-    if force:
-        cg, kg, nld, S = (int(v) for v in force.split(","))
-        if (KG is None or kg == KG) and Nout % (64 * cg) == 0:
-            return cg, kg, nld, max(1, min(S, nch))
     npat = B * (H // 8) * (W // 16)
     best = None
     for cg, kg, nld in ((1, 4, 4), (2, 2, 4)):
@@ -749,13 +773,10 @@ def cconv_wanted(B: int, H: int, W: int, Cin: int, Nout: int, ups: int = 0) -> b
     """Whether the plan gives a 3x3 stride-1 conv to cconv.hip (H x W = output resolution).  Measured at cfg-2 against the kernel
     each launch had before (tools/cconv_time.py, profiles/round6_a_cconv_time.log): the up-samplers 1.4-1.5 x (igemm), the resnet
     convs of the 640- / 1280-wide levels 1.2-1.6 x (wsgemm); the 320-wide level keeps the patch conv by default (1.02-1.14 x in isolation,
-    nothing in the frame: 320 blocks of one 64-channel tile are two rounds over the chip; L2D_CCONV_L0=1 moves it too).  L2D_CCONV=0
-    switches the kernel off (A/B)."""
-    if os.environ.get("L2D_CCONV", "1") == "0" or not cconv_ok(H, W, Nout, Cin):
+    nothing in the frame: 320 blocks of one 64-channel tile are two rounds over the chip)."""
+    if not cconv_ok(H, W, Nout, Cin):
         return False
-    if ups:
-        return True
-    return B * H * W >= 512 and (Nout >= 640 or os.environ.get("L2D_CCONV_L0", "0") != "0")
+    return bool(ups) or (B * H * W >= 512 and Nout >= 640)
 
 
 def cconv_sizes(B: int, H: int, W: int, Nout: int, CG: int, S: int):
@@ -829,19 +850,20 @@ def igemm_schedule(M: int, Nout: int, Kp: int, batch: int = 1, epi: int = 0, tap
       * >= 384 big tiles: 128x128 (3 blocks/CU with the 48 KB BK32x3 ring when there are >= 768 tiles);
       * otherwise 64x64 tiles if that yields >= 256 blocks;
       * otherwise (low-resolution levels: M = 128..2048 tokens, K up to 23 040) split K over 128x128 tiles
-        (>= 8 BK64 steps per split, K >= 2048), reduced by igemm_splitk_epilogue."""
+        (>= 8 BK64 steps per split, K >= 2048), reduced by igemm_splitk_epilogue.
+    First the per-shape picks measured IN-FRAME (igemm_tuned.json, tools/igemm_pick.py over rocprofv3 traces of whole frames), then
+    _igemm_heuristic_r6 for the shapes the table does not hold."""
     key = f"{taps},{M},{Nout},{Kp},{epi},{batch}"
-    force = os.environ.get("L2D_IGEMM_FORCE")       # "tile,S,variant": exploration runs of tools/igemm_pick.py
-    if force:
-        t, S, v = (int(x) for x in force.split(","))
+    o = overrides()
+    tuned = tuned_table("igemm_tuned.json", o.igemm_no_table).get("shapes", {})
+    if o.igemm_force:                                  # (exploration runs of tools/igemm_pick.py)
+        t, S, v = (int(x) for x in o.igemm_force.split(","))
         S = max(1, min(S, Kp // 128))
         ok = not (v in (6, 7) and (Kp // taps) % 128) and not (t == 1 and v in (7, 8, 9)) and 0 <= v <= 10
         if ok:
             return t, S, v
-    elif key in _TUNED:
-        return tuple(_TUNED[key])
-    if os.environ.get("L2D_IGEMM_HEUR", "6") == "1":
-        return _igemm_heuristic_r1(M, Nout, Kp, batch, epi)
+    elif key in tuned:
+        return tuple(tuned[key])
     return _igemm_heuristic_r6(M, Nout, Kp, batch, epi)
 
 
@@ -850,8 +872,7 @@ def _igemm_heuristic_r6(M: int, Nout: int, Kp: int, batch: int, epi: int):
     in-frame picks of igemm_tuned.json follow, instead of the round-1 sweep's.  What the table says: few-token launches want
     64 x 64 tiles with K split until ~240 blocks exist (~480 for K >= 2560) but never below ~6 BK64 steps per split nor above 6
     splits unless a split would still be longer than ~30 steps; 128 x 128 tiles + split-K only for the long 3x3 contractions
-    (K >= 8640) at >= 512 tokens; no split for GEGLU epilogues.  L2D_IGEMM_HEUR=1 restores the round-1 rule (A/B:
-    profiles/round6_u_*)."""
+    (K >= 8640) at >= 512 tokens; no split for GEGLU epilogues.  (A/B against the round-1 rule: profiles/round6_u_*.)"""
     cdiv = lambda a, b: (a + b - 1) // b
     nk64 = Kp // 64
     t64 = cdiv(Nout, 64) * cdiv(M, 64) * batch
@@ -868,42 +889,6 @@ def _igemm_heuristic_r6(M: int, Nout: int, Kp: int, batch: int, epi: int):
         return 2, (max(1, min(nk64 // 24, 1280 // t64)) if nk64 >= 64 else 1), 1
     target = 240 if Kp <= 1920 else 480
     return 2, max(1, min(target // t64, max(6, cdiv(nk64, 30)), nk64 // 6, 16)), 1
-
-
-def _igemm_heuristic_r1(M: int, Nout: int, Kp: int, batch: int, epi: int):
-    """The round-1 rule (tools/igemm_sweep.py, isolated launches): kept for A/B."""
-    v_small, v_big = 1, 5           # BK64 x 3 stages: in-frame best (85.3 vs 79.9 fps with x2); 128x128 BK32 x 4 for the big shapes
-    cdiv = lambda a, b: (a + b - 1) // b
-    nk64 = Kp // 64
-    big = cdiv(Nout, 128) * cdiv(M, 128) * batch
-    if Nout <= 64 and M >= 16384:
-        # narrow outputs (TAESD: 64 channels everywhere, 3 / 4 at the ends): a 128-wide channel tile would be half empty
-        return 2, 1, (v_small if nk64 <= 18 else 2)
-    if big >= 384:
-        return 1, 1, (4 if big >= 768 else v_big)
-    if epi == 1:
-        return 2, 1, v_small
-    if nk64 >= 32:
-        # long K (3x3 convs below the top level, FF down-projections): 128x128 tiles + split-K beat 64x64 tiles
-        # (level-1 conv in the frame: 77 us with 320 small tiles vs 45 us with 80 big tiles x 3 splits)
-        s_big = max(1, min(nk64 // 8, round(256 / big), 64))
-        if s_big >= 2:
-            return 1, s_big, v_big
-    return 2, 1, v_small
-
-
-def _load_tuned():
-    """Per-shape (tile, split-K, pipeline variant) picks measured IN-FRAME on MI355X (tools/igemm_pick.py over
-    rocprofv3 traces of whole frames): the heuristic above is the fallback for shapes the table does not hold."""
-    import json
-    path = os.path.join(os.path.dirname(__file__), "igemm_tuned.json")
-    if os.environ.get("L2D_IGEMM_NO_TABLE") or not os.path.exists(path):
-        return {}
-    with open(path) as f:
-        return json.load(f)["shapes"]
-
-
-_TUNED = _load_tuned()
 
 
 def igemm(x1, w, out, *, M, Nout, C1, ldx1, CinP, ldo, x2=None, C2=0, ldx2=0, bias=None, rowbias=None, ldrb=0,
@@ -938,9 +923,8 @@ def igemm(x1, w, out, *, M, Nout, C1, ldx1, CinP, ldo, x2=None, C2=0, ldx2=0, bi
         op.p[11] = _ptr(cnt) + 4 * cnt_off
     elif splitk > 1:
         assert ws is not None and ws.dtype == torch.float32 and ws.numel() >= batch * splitk * M * round_up(Nout, 4)
-    direct_epi = 0                  # (bit 5 of i22 selects the round-1 register -> global epilogue: A/B settled in round 2)
     vals = [taps, C1, C2, ldx1, ldx2, CinP, B, Hin, Win, Hout, Wout, stride, ups, M, Nout, ldo, ldr, ldrb,
-            rows_per_bias, epi, batch, splitk, int(tile) + 16 * int(order) + direct_epi, variant]
+            rows_per_bias, epi, batch, splitk, int(tile) + 16 * int(order), variant]
     for j, v in enumerate(vals):
         op.i[j] = int(v)
     op.l[0], op.l[1], op.l[2], op.l[3] = int(sx1), int(sw), int(so), int(sres)
@@ -955,13 +939,12 @@ def splitk_sizes(M: int, Nout: int, splitk: int, batch: int, tile: int):
     return batch * ntiles * splitk * t * t, batch * ntiles
 
 
-SPLITK_FUSED = True              # (False = separate reduction launch, the round-1 form: A/B settled in round 3)
 SPLITK_FUSED_MAX = 16            # deeper splits keep the reduction launch: ONE block
 # per tile sums all S slabs in the fused form, which serialises when a launch has few tiles and many splits (8x8 levels)
 
 
 def splitk_fused(splitk: int) -> bool:
-    return SPLITK_FUSED and 1 < splitk <= SPLITK_FUSED_MAX
+    return 1 < splitk <= SPLITK_FUSED_MAX
 
 
 def gn_stats(x1, partial, *, B, T, C1, ld1, G, nchunk, x2=None, C2=0, ld2=0):
@@ -978,9 +961,8 @@ ACT_NONE, ACT_SILU, ACT_RELU, ACT_ADD_RELU = 0, 1, 2, 3
 
 def gn_self_ok(T: int, C: int, G: int) -> bool:
     """Shapes the ONE-launch GroupNorm takes (norm.hip gn_self_kernel: gn_apply with nchunk = 0 and no accumulator): a block holds all T
-    pixel rows of a band of whole groups (lcm(cpg, 8) <= 128 channels, <= 4 groups) in registers, <= 16 vectors per thread.
-    L2D_GN_SELF=0 keeps the two-launch fallback (A/B)."""
-    if os.environ.get("L2D_GN_SELF", "1") == "0" or G <= 0 or C % G:
+    pixel rows of a band of whole groups (lcm(cpg, 8) <= 128 channels, <= 4 groups) in registers, <= 16 vectors per thread."""
+    if G <= 0 or C % G:
         return False
     cpg = C // G
     band = cpg
@@ -1022,10 +1004,9 @@ def layernorm(x, gamma, beta, out, *, rows, C, ldx, ldo, eps=1e-5):
 
 
 def flash_attn(q, k, vt, out, *, B, H, d, Tq, Tk, ldq, ldk, ldvt, ldo, sq, sk, svt, so, q_off=0, k_off=0, vt_off=0,
-               variant=None):
+               variant=0):
     """variant: 0 auto (LDS-DMA ring kernel), 1 register-staged kernel (round 1), 2 / 3 ring with 32 / 16 query rows per
-    wave, 4 ring with 32 rows per wave and the software-pipelined loop (d <= 48; other head sizes run variant 2);
-    None = L2D_FLASH_VARIANT from the environment (A/B knob), default 0."""
+    wave, 4 ring with 32 rows per wave and the software-pipelined loop (d <= 48; other head sizes run variant 2)."""
     op = L2dOp()
     op.kind = _lib.OP_FLASH_ATTN
     zp = zero_page(q.device)
@@ -1034,8 +1015,6 @@ def flash_attn(q, k, vt, out, *, B, H, d, Tq, Tk, ldq, ldk, ldvt, ldo, sq, sk, s
     op.p[2] = _ptr(_h(vt)) + vt_off * 2
     op.p[3] = _ptr(_h(out))
     op.p[4] = _ptr(zp)
-    if variant is None:
-        variant = int(os.environ.get("L2D_FLASH_VARIANT", "0"))
     for j, v in enumerate([B, H, d, Tq, Tk, ldq, ldk, ldvt, ldo, variant]):
         op.i[j] = int(v)
     op.l[0], op.l[1], op.l[2], op.l[3] = int(sq), int(sk), int(svt), int(so)

@@ -120,7 +120,6 @@ class HipStreamingUNet:
         self.fresh_output = fresh_output   # True: return a private copy of the prediction (the reference's PyTorch path returns a
         #                                    fresh tensor); False (default): a view of the static output buffer, like a TensorRT binding
         self.tattn_variant = tattn_variant
-        self.igemm_splitk_off = False       # tuning knob: disable split-K schedules
         self.cond_cache = True           # False: re-run the conditioning launches every call (tests)
         assert 1 <= text_len <= TEXT_PAD
         self.text_len = text_len           # static number of text tokens (77 for CLIP)
@@ -129,12 +128,11 @@ class HipStreamingUNet:
         self.device_name = "dry-run" if ops.DRY_RUN else _lib.device_name()   # raises unless a gfx950 is present
         self.mm_layout = motion_module_layout(cfg, height, width)
         # levels whose stream batch is small enough for the weight-streaming GEMM (wsgemm.hip): N * T tokens <= L2D_WSGEMM_MAX_M and
-        # samples made of whole 32-token tiles.  Decides the PACKING of those levels' layers (and with it the plan's kernels).
-        ws_on = os.environ.get("L2D_WSGEMM", "1") != "0"             # A/B knob: 0 = the round-3 kernels everywhere
-        # (levels of up to 1280 tokens take it by default, larger ones -- up to this bound -- per measured shape: ops.wsgemm_wanted)
-        ws_max = int(os.environ.get("L2D_WSGEMM_MAX_M", "4608"))
-        self.ws_levels = [ws_on and denoising_steps_num * (height >> l) * (width >> l) <= ws_max and ((height >> l) * (width >> l)) % 32 == 0
-                          for l in range(cfg.num_levels)]
+        # samples made of whole 32-token tiles.  Decides the PACKING of those levels' layers (and with it the plan's kernels); levels of
+        # up to 1280 tokens take it by default, larger ones -- up to this bound -- per measured shape (ops.wsgemm_wanted)
+        o = ops.overrides()
+        self.ws_levels = [o.wsgemm and denoising_steps_num * (height >> l) * (width >> l) <= o.wsgemm_max_m
+                          and ((height >> l) * (width >> l)) % 32 == 0 for l in range(cfg.num_levels)]
         if isinstance(state_dict, HipStreamingUNet):
             o = state_dict
             if (o.cfg, o.h, o.w, o.device) != (cfg, self.h, self.w, self.device):
@@ -185,15 +183,11 @@ class HipStreamingUNet:
             W[name + ".w"] = ops.pack_conv3x3(g(name + ".weight"))
             W[name + ".b"] = ops.f32(g(name + ".bias"))
 
-        use_rg = os.environ.get("L2D_ROWGEMM", "1") != "0"     # A/B knob: 0 = every linear layer on igemm + separate norm launches
-        RG_PLAIN_MAX_K = int(os.environ.get("L2D_ROWGEMM_PLAIN_MAX_K", "640"))
-        RG_FF1_MAX_K = int(os.environ.get("L2D_ROWGEMM_FF1_MAX_K", "1280"))     # A/B knob: GEGLU GEMMs wider than this stay on igemm
         ws_lv = self.ws_levels
-        chain_on = os.environ.get("L2D_ROWCHAIN", "1") != "0"        # A/B knob: 0 = the four separate launches of a block's tail
 
         def rg_ok(wname):
             n, k = sd[wname].shape[0], sd[wname][0].numel()
-            return use_rg and ops.rowgemm_ok(n, k)
+            return ops.rowgemm_ok(n, k)
 
         def ws_ok(wname, lvl, n_mul=1, epi=0, pro=0, ntr=0, taps=1):
             """the weight-streaming GEMM (wsgemm.hip) takes this layer: a level of few tokens, 32-row weight tiles, 64-column chunks,
@@ -221,7 +215,7 @@ class HipStreamingUNet:
             # Row GEMM where it fuses a norm, and for the narrow levels (K <= 640).  A plain Linear at K = 1280 stays on the
             # implicit-GEMM kernel: with 32-token row tiles every block ingests its whole weight band (80 KB per 32-row tile), and
             # the probe (profiles/round3_b_rowgemm_block_phases_before.txt) shows those launches bound by ~30 B/clk of ingest per CU.
-            rg = rg_ok(name + ".weight") and (norm is not None or sd[name + ".weight"][0].numel() <= RG_PLAIN_MAX_K)
+            rg = rg_ok(name + ".weight") and (norm is not None or sd[name + ".weight"][0].numel() <= ops.ROWGEMM_PLAIN_MAX_K)
             if rg:
                 W[name + ".rw"], rb = ops.pack_rowgemm(g(name + ".weight"), g(name + ".bias") if bias else None,
                                                        g(norm + ".weight") if norm else None, g(norm + ".bias") if norm else None)
@@ -243,10 +237,10 @@ class HipStreamingUNet:
                                                                                          geglu=True)
                 lin(name + ".net.2", old=old, lvl=lvl)
                 return
-            rg = rg_ok(pw) and sd[pw].shape[0] % 64 == 0 and sd[pw][0].numel() <= RG_FF1_MAX_K
+            rg = rg_ok(pw) and sd[pw].shape[0] % 64 == 0 and sd[pw][0].numel() <= ops.ROWGEMM_FF1_MAX_K
             if rg:
                 W[name + ".rw1"], W[name + ".rb1"] = ops.pack_rowgemm(g(pw), g(pb), g(norm + ".weight"), g(norm + ".bias"), geglu=True)
-                if chain_on and sd[pw][0].numel() == ops.ROWCHAIN_C:
+                if sd[pw][0].numel() == ops.ROWCHAIN_C:
                     # the token-resident block tail (rowchain.hip) streams FF2 in the row GEMM's fragment order too (K = 4 C).  Its own
                     # keys (".chw" / ".chb"): `linear()` picks the row GEMM for a layer by the presence of ".rw", and a plain K = 1280
                     # Linear must stay on the implicit-GEMM kernel wherever the chain does not run (round-5 advisor finding)
@@ -436,8 +430,8 @@ class HipStreamingUNet:
         safetensors file.  The analogue of the reference's TensorRT engine cache (wrapper.py:300-332, :505-560): a style
         switch that was seen before skips the conversion.  Packed weights depend on the weights, on the window length and on
         WHICH KERNEL serves each layer: the levels with few stream tokens (`ws_levels`: denoising steps x latent size) hold the
-        weight-streaming forms, levels whose samples are not whole 32-token tiles the implicit-GEMM forms, and the L2D_ROWGEMM*
-        knobs move layers between kernels.  The file records all of that; `_load_packed` refuses a file packed for another layout
+        weight-streaming forms, levels whose samples are not whole 32-token tiles the implicit-GEMM forms, and the L2D_WSGEMM*
+        overrides move layers between kernels.  The file records all of that; `_load_packed` refuses a file packed for another layout
         with a "re-pack" error instead of failing on a missing tensor later."""
         from safetensors.torch import save_file
         save_file({k: v.detach().cpu().contiguous() for k, v in self.W.items()}, str(path), metadata=self._packed_meta())
@@ -473,7 +467,7 @@ class HipStreamingUNet:
                              f"this build ({self.PACK_FORMAT} / {_lib.ABI_VERSION}): re-pack from the state dict")
         if json.loads(meta.get("layout", "null")) != self._pack_layout():
             raise ValueError(f"{path}: packed for kernel layout {meta.get('layout')}, this instance needs {json.dumps(self._pack_layout())} "
-                             "(latent size / denoising steps / L2D_ROWGEMM* / L2D_WSGEMM* differ): re-pack from the state dict")
+                             "(latent size / denoising steps / L2D_WSGEMM* differ): re-pack from the state dict")
         if int(meta["window"]) != self.cfg.window_size or json.loads(meta["block_out_channels"]) != list(self.cfg.block_out_channels):
             raise ValueError(f"{path}: packed for window {meta['window']} / widths {meta['block_out_channels']}, "
                              f"this instance is window {self.cfg.window_size} / {list(self.cfg.block_out_channels)}")
@@ -492,14 +486,16 @@ class HipStreamingUNet:
     def _pack_layout(self) -> dict:
         """what decides which packed form each layer has (besides the weights themselves)"""
         nl = self.cfg.num_levels
+        o = ops.overrides()
+        t = ops.wsgemm_table(o)
         return dict(ws_levels=[bool(v) for v in self.ws_levels],
                     old_levels=[((self.h >> l) * (self.w >> l)) % 32 != 0 for l in range(nl)],
-                    ws_skip=sorted(ops._WS_SKIP), ws_large=sorted(ops._WS_LARGE), ws_tokens=[self.N * (self.h >> l) * (self.w >> l) if self.ws_levels[l] else 0 for l in range(nl)],
-                    cconv=os.environ.get("L2D_CCONV", "1"), rowgemm=os.environ.get("L2D_ROWGEMM", "1"), rowchain=os.environ.get("L2D_ROWCHAIN", "1"), rg_plain_max_k=os.environ.get("L2D_ROWGEMM_PLAIN_MAX_K", "640"),
-                    rg_ff1_max_k=os.environ.get("L2D_ROWGEMM_FF1_MAX_K", "1280"),
-                    # round 6: the fallback rules decide packed forms too (which layers take the weight-streaming form at token counts the
-                    # tuner never saw; from how many blocks a level packs the chain kernel's weights)
-                    ws_rule=os.environ.get("L2D_WSGEMM_RULE", "1"), rowchain_min_blocks=int(ops.ROWCHAIN_MIN_BLOCKS))
+                    ws_skip=sorted(t.get("skip", [])), ws_large=sorted(t.get("large", [])),
+                    ws_tokens=[self.N * (self.h >> l) * (self.w >> l) if self.ws_levels[l] else 0 for l in range(nl)],
+                    wsgemm=o.wsgemm, ws_max_m=o.wsgemm_max_m, ws_large_all=o.wsgemm_large_all,
+                    # the fallback rules decide packed forms too (which layers take the weight-streaming form at token counts the tuner
+                    # never saw; from how many blocks a level packs the chain kernel's weights)
+                    rowchain_min_blocks=ops.ROWCHAIN_MIN_BLOCKS)
 
     @staticmethod
     def packed_cache_name(model_name: str, few_step_model_type: str, window_size: int, lora_dict: Optional[dict] = None,
@@ -527,8 +523,7 @@ class HipStreamingUNet:
         # They run when the conditioning changes (first frame, update_prompt, a new warm-up row), not every frame.
         cond_pl = _lib.OpList()
         st = SimpleNamespace(mode=mode, B=B, Bt=Bt, pl=pl, cond_pl=cond_pl, cond_key=None, arena=ar, tattn_ops=[], warm=False,
-                             ident={}, rg=os.environ.get("L2D_ROWGEMM", "1") != "0", ws=any(self.ws_levels),
-                             chain_heads=os.environ.get("L2D_ROWCHAIN_HEADS", "1") != "0")
+                             ident={})
         cur = [cond_pl]
 
         def add(opk):
@@ -542,8 +537,6 @@ class HipStreamingUNet:
             batch, taps = kw.get("batch", 1), kw.get("taps", 1)
             epi = kw.get("epi", 0)
             tile, S, variant = ops.igemm_schedule(kw["M"], kw["Nout"], taps * kw["CinP"], batch, epi, taps)
-            if self.igemm_splitk_off:
-                S = 1
             if variant in (6, 7) and kw["CinP"] % 128:
                 variant = 1            # BK = 128 rings need K slices of 128
             if tile == 1 and variant in (7, 8, 9):
@@ -597,7 +590,7 @@ class HipStreamingUNet:
             """Ask the producers of x (and x2) to accumulate this GroupNorm's statistics; returns the accumulator pointer or
             None (then nothing is left attached)."""
             ins = [(x, 0)] + ([(x2, x.C)] if x2 is not None else [])
-            if not (st.gn_fuse and all(a_.producer is not None for a_, _ in ins) and st.gn_layers < st.gn_acc.shape[0]):
+            if not (all(a_.producer is not None for a_, _ in ins) and st.gn_layers < st.gn_acc.shape[0]):
                 return None
             acc_ptr = st.gn_acc.data_ptr() + st.gn_layers * B * G * 2 * 8
             saved = [(a_.producer, [a_.producer.p[9], a_.producer.p[10]], list(a_.producer.i[24:30])) for a_, _ in ins]
@@ -644,18 +637,15 @@ class HipStreamingUNet:
             ar.release(partial)
             return out
 
-        def conv3(x: _Act, name, stride=1, ups=0, epi=0, res: Optional[_Act] = None, rowbias=None, x2: Optional[_Act] = None,
-                  gnf=None) -> _Act:
-            """x2 / gnf = (acc_ptr, gamma, beta, eps): cconv only -- the conv of silu(GroupNorm(x | x2)), normalised inside the launch"""
+        def conv3(x: _Act, name, stride=1, ups=0, epi=0, res: Optional[_Act] = None, rowbias=None) -> _Act:
             if (name + ".cw") in W:
                 # patch-resident activations + register-streamed weights (cconv.hip): resnet convs of the wide levels, up-samplers
                 assert stride == 1 and epi == 0
                 cout = W[name + ".b"].numel()
                 Ho, Wo = x.H << ups, x.W << ups
                 out = new_act(cout, Ho, Wo)
-                cin = x.C + (x2.C if x2 is not None else 0)
-                kg = ops.cconv_schedule(self.N, Ho, Wo, cout, cin)[1]          # (the packing's: decided on the stream batch)
-                sched = ops.cconv_schedule(B, Ho, Wo, cout, cin, KG=kg)
+                kg = ops.cconv_schedule(self.N, Ho, Wo, cout, x.C)[1]          # (the packing's: decided on the stream batch)
+                sched = ops.cconv_schedule(B, Ho, Wo, cout, x.C, KG=kg)
                 ws_buf, kw = None, {}
                 if sched[3] > 1:
                     n_ws, n_cnt = ops.cconv_sizes(B, Ho, Wo, cout, sched[0], sched[3])
@@ -664,10 +654,6 @@ class HipStreamingUNet:
                     st.sk_used += n_cnt
                 if rowbias is not None:
                     kw.update(rowbias=st.temb_all, ldrb=self.temb_total, rows_per_bias=(Ho * Wo if mode == "stream" else B * Ho * Wo))
-                if gnf is not None:
-                    kw.update(gn_acc_ptr=gnf[0], gn_gamma=gnf[1], gn_beta=gnf[2], gn_G=G, gn_eps=gnf[3])
-                if x2 is not None:
-                    kw.update(x2=x2.buf, C2=x2.C, ldx2=x2.C)
                 op_ = add(ops.cconv(x.buf, W[name + ".cw"], out.buf, B=B, H=Ho, W=Wo, C1=x.C, ldx1=x.C, Nout=cout, ldo=cout, KG=kg, ups=ups,
                                     bias=W[name + ".b"], res=(res.buf if res is not None else None), ldr=(res.C if res is not None else 0),
                                     sched=sched, **kw))
@@ -676,7 +662,6 @@ class HipStreamingUNet:
                 ar.release(ws_buf)
                 out.producer = op_
                 return out
-            assert x2 is None and gnf is None
             if use_ws(name):
                 # resnet conv at a few-token level: weight-streaming GEMM over (tap, channel chunk) stages (wsgemm.hip)
                 assert stride == 1 and not ups and epi == 0
@@ -758,11 +743,13 @@ class HipStreamingUNet:
             ar.release(ws_buf)
             return op_
 
+        # the packed form of a layer picks its kernel: ".ww" exists only at the weight-streaming levels, ".rw" only where the row GEMM
+        # takes the shape (_pack_weights)
         def use_ws(key) -> bool:
-            return st.ws and (key + ".ww") in W
+            return (key + ".ww") in W
 
         def use_rg(key) -> bool:
-            return st.rg and (key + ".rw") in W
+            return (key + ".rw") in W
 
         def linear(x: _Act, name, bias=True, res: Optional[_Act] = None, wkey=None, x2: Optional[_Act] = None, **kw) -> _Act:
             """kw: pro / eps / T / G / gn_acc_ptr of a fused norm prologue (row GEMM only)"""
@@ -817,7 +804,7 @@ class HipStreamingUNet:
 
         def geglu_ff(x: _Act, name, res: _Act, nname=None) -> _Act:
             """x: the un-normalised input when `nname` names the LayerNorm to fuse (row GEMM), else the normalised one"""
-            if nname is not None and st.ws and (name + ".ww1") in W:
+            if nname is not None and (name + ".ww1") in W:
                 c4 = W[name + ".ww1"].numel() // x.C // 2
                 hid = new_act(c4, x.H, x.W)
                 wslin(x.buf, B * x.H * x.W, x.C, name + ".ww1", hid.buf, c4, T=x.H * x.W, bias=W[name + ".wb1"], colsum=W[name + ".wcs1"], epi=1, pro=1)
@@ -847,7 +834,7 @@ class HipStreamingUNet:
             token-resident launch (rowchain.hip) where the level's M / 32 blocks fill the chip (C = 320); None = not here."""
             T, C = ao.H * ao.W, ao.C
             keys = (to_out + ".rw", to_out + ".rb", ff + ".rw1", ff + ".rb1", ff + ".net.2.chw", ff + ".net.2.chb", proj_out + ".rw", proj_out + ".rb")
-            if not (st.rg and ops.rowchain_ok(B * T, C, T) and all(k in W for k in keys)):
+            if not (ops.rowchain_ok(B * T, C, T) and all(k in W for k in keys)):
                 return None
             out = new_act(C, ao.H, ao.W)
             out.producer = add(ops.rowchain(ao.buf, res1.buf, res2.buf, out.buf, M=B * T, C=C, w_out=W[keys[0]], b_out=W[keys[1]],
@@ -862,7 +849,7 @@ class HipStreamingUNet:
             or the cross-attention's query).  Returns h, or None when the segment does not run here (the caller emits the two launches)."""
             T, C = x.H * x.W, x.C
             keys = (a_name + ".rw", a_name + ".rb", b_name + ".rw")
-            if not (st.rg and st.chain_heads and ops.rowchain_ok(B * T, C, T) and all(k in W for k in keys)):
+            if not (ops.rowchain_ok(B * T, C, T) and all(k in W for k in keys)):
                 return None
             acc_ptr = None
             if gn_of is not None:
@@ -875,22 +862,9 @@ class HipStreamingUNet:
                                   eps_gn=cfg.transformer_norm_eps, eps_ln=1e-5, out_t=out_t, ldt=ldt, st=stt, ldo=ldo))
             return h
 
-        # L2D_CCONV_GN=1: the GroupNorm + SiLU in front of a cconv launch runs inside it (its loader waves normalise the patch in LDS).  Built,
-        # parity-tested (tests/test_gpu_cconv.py) and measured in the frame (round 6, profiles/round6_f_cconv_gn_fused_ab.txt): 20 GroupNorm
-        # launches and their 0.135 ms go, but every output-channel tile of a conv re-normalises its patch (10-20 x redundant arithmetic at
-        # the 640 / 1280-wide levels) and the cconv family pays 0.16 ms for it: 7.96-8.01 vs 7.99-8.00 ms per frame.  Off by default.
-        gn_in_conv = os.environ.get("L2D_CCONV_GN", "0") != "0"
-
         def gn_conv3(x: _Act, x2: Optional[_Act], nname, cname, **kw) -> _Act:
-            """conv3(silu(GroupNorm(x | x2))) (reference resnet.py:233-234, 249-250).  Where the conv is a cconv launch and the statistics
-            come from the producers' epilogues, the normalisation runs inside that launch (its loader waves normalise the patch in LDS):
-            no GroupNorm launch, no normalised tensor; else GroupNorm launch + conv."""
-            if gn_in_conv and (cname + ".cw") in W:
-                C_ = x.C + (x2.C if x2 is not None else 0)
-                if C_ % G == 0 and -(-(C_ // 64) // 1) <= 8 * 48:
-                    acc_ptr = gn_stats_target(x, x2, x.H * x.W, C_ // G)
-                    if acc_ptr is not None:
-                        return conv3(x, cname, x2=x2, gnf=(acc_ptr, W[nname + ".g"], W[nname + ".beta"], cfg.norm_eps), **kw)
+            """conv3(silu(GroupNorm(x | x2))) (reference resnet.py:233-234, 249-250): GroupNorm launch + conv.  (The cconv launch can
+            normalise its patch itself, ops.cconv gn_acc_ptr; in the frame that lost: profiles/round6_f_cconv_gn_fused_ab.txt.)"""
             hn = gn(x, nname, cfg.norm_eps, True, x2=x2)
             out_ = conv3(hn, cname, **kw)
             free(hn)
@@ -995,7 +969,7 @@ class HipStreamingUNet:
                 return tail
             y3 = lin(ao, b + ".attn2.to_out.0", res=y2)
             free(ao); free(y2)
-            if (st.ws and (b + ".ff.ww1") in W) or (st.rg and T % 32 == 0 and (b + ".ff.rw1") in W):
+            if (b + ".ff.ww1") in W or (T % 32 == 0 and (b + ".ff.rw1") in W):
                 y4 = geglu_ff(y3, b + ".ff", res=y3, nname=b + ".norm3")
             else:
                 n3 = layernorm(y3, b + ".norm3")
@@ -1059,7 +1033,7 @@ class HipStreamingUNet:
                     y2 = linear(ao, a + ".to_out.0", res=y)
                 free(ao); free(y)
                 y = y2
-            if (st.ws and (b + ".ff.ww1") in W) or use_rg(b + ".ff") or (st.rg and (b + ".ff.rw1") in W):
+            if (b + ".ff.ww1") in W or use_rg(b + ".ff") or (b + ".ff.rw1") in W:
                 y2 = geglu_ff(y, b + ".ff", res=y, nname=b + ".ff_norm")
             else:
                 nrm = layernorm(y, b + ".ff_norm")
@@ -1096,11 +1070,10 @@ class HipStreamingUNet:
 
         cur[0] = pl
         # ---- GroupNorm statistics accumulators (one [B][G][2] int64 block per fused GroupNorm), zeroed once per frame
-        st.gn_fuse = os.environ.get("L2D_GN_FUSE", "1") != "0"
         st.gn_layers, st.gn_stats_launches, st.gn_self_launches = 0, 0, 0
         st.gn_acc = torch.zeros(96, B, G, 2, dtype=torch.int64, device=dev)
         st.gn_zero = torch.zeros_like(st.gn_acc)
-        zero_op = add(ops.copy(st.gn_zero, st.gn_acc, st.gn_acc.numel() * 8)) if st.gn_fuse else None
+        zero_op = add(ops.copy(st.gn_zero, st.gn_acc, st.gn_acc.numel() * 8))
         # ---- input: NCHW latents -> channels-last (padded to 8 channels), conv_in + depth mapping network
         x_in = _Act(ar.alloc(B * h * w * 8), 8, h, w)
         d_in = _Act(ar.alloc(B * h * w * 8), 8, h, w)
@@ -1156,8 +1129,7 @@ class HipStreamingUNet:
         free(x)
         y = conv3(hn, "conv_out")
         add(ops.nhwc_to_nchw(y.buf, st.out_sample, B=B, C=cfg.out_channels, HW=h * w, ld=cfg.out_channels))
-        if zero_op is not None:
-            zero_op.l[0] = max(16, st.gn_layers * B * G * 2 * 8)          # only the blocks in use
+        zero_op.l[0] = max(16, st.gn_layers * B * G * 2 * 8)          # only the blocks in use
         st.kv_ptrs = [c.data_ptr() for c in kv_cache]
         st.arena_bytes = ar.nbytes()
         st.n_ops = len(pl)

@@ -240,7 +240,7 @@ def test_device_step_plan_validates_without_gpu(dry_run):
     validate(ops.ring_update(b, p, u, N=2, L=16, sink=8))
 
 
-def test_packed_weight_cache_round_trip(dry_run, tmp_path):
+def test_packed_weight_cache_round_trip(dry_run, tmp_path, monkeypatch):
     """save_packed / load from path: identical packed tensors and layout tables, the plan built from
     the cache file validates, and a file packed for another window or format is refused."""
     from live2diff_amd.config import tiny_config
@@ -264,6 +264,13 @@ def test_packed_weight_cache_round_trip(dry_run, tmp_path):
         HipStreamingUNet(path, cfg, 16, 32, 3, device="cpu")
     with pytest.raises(ValueError, match="re-pack"):
         HipStreamingUNet(path, cfg, 8, 24, 2, device="cpu")
+    # the kept tuning overrides that move layers between kernels are part of the layout too: without the weight-streaming GEMM the
+    # file's ".ww" forms would be the wrong ones
+    assert any(k.endswith(".ww") for k in a.W)
+    with monkeypatch.context() as m:
+        m.setenv("L2D_WSGEMM", "0")
+        with pytest.raises(ValueError, match="re-pack"):
+            HipStreamingUNet(path, cfg, 16, 16, 2, device="cpu")
     # ... and a shape change that leaves the layout alone reuses the file (the same levels take the same kernels)
     big = tiny_config(channels=(64, 128, 128, 128), cross_attention_dim=64)
     a2 = HipStreamingUNet(random_state_dict(big, dtype=torch.float16), big, 64, 64, 2, device="cpu")
@@ -389,25 +396,23 @@ def test_untuned_resolution_uses_the_fallback_rules(dry_run):
     assert st.n_ops <= 480, st.n_ops
 
 
-def test_igemm_fallback_rule_follows_the_tuned_table():
+def test_igemm_fallback_rule_reproduces_the_tuned_table():
     """Round 6: the rule behind igemm_tuned.json (`ops._igemm_heuristic_r6`, what every shape outside cfg-2 runs on) is fitted to the table's
-    in-frame picks and must keep reproducing them -- (tile, split-K) of at least 50 of the 60 shapes (the round-1 rule: 30), every
+    in-frame picks and must keep reproducing them -- (tile, split-K) of at least 50 of the 60 shapes, every
     few-token Linear / 8 x 8 conv among them, and always a schedule the launcher accepts (fused split-K <= 16, >= 2 BK64 steps per split)."""
     import json
 
     from live2diff_amd import ops
     shapes = json.load(open(os.path.join(os.path.dirname(ops.__file__), "igemm_tuned.json")))["shapes"]
-    hit_new = hit_old = 0
+    hit_new = 0
     for key, (tile, S, _v) in shapes.items():
         taps, M, N, Kp, epi, batch = (int(v) for v in key.split(","))
         t6, s6, v6 = ops._igemm_heuristic_r6(M, N, Kp, batch, epi)
-        t1, s1, _ = ops._igemm_heuristic_r1(M, N, Kp, batch, epi)
         assert t6 in (1, 2) and 1 <= s6 <= ops.SPLITK_FUSED_MAX and Kp // 64 >= 2 * s6 and 0 <= v6 <= 10, key
         hit_new += (t6, s6) == (tile, S)
-        hit_old += (t1, s1) == (tile, S)
         if M <= 128 and N == 1280:
             assert (t6, s6) == (tile, S), key                    # level 3 + mid of cfg-2: the launches the old rule lost most on
-    assert hit_new >= 50 and hit_old <= 32, (hit_new, hit_old)
+    assert hit_new >= 50, hit_new
     # shapes no table holds: few tokens -> 64 x 64 tiles, K split towards ~240-480 blocks
     assert ops._igemm_heuristic_r6(288, 1280, 1280, 1, 0)[:2] == (2, 2) and ops._igemm_heuristic_r6(72, 1280, 11520, 1, 0)[:2] == (2, 6)
 

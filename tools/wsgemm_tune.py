@@ -69,9 +69,7 @@ def main():
                 per[(key_of(op), (op.i[9], op.i[10], op.i[11], max(1, op.i[12])))].append(us[j])
         return {k: sum(v) / len(v) for k, v in per.items()}, {k: len(v) for k, v in per.items()}, sum(us)
 
-    ops._WS_TUNED.clear()                      # measure against the cost model, not against an older table
-    ops._WS_SKIP.clear()
-    ops._WS_LARGE.clear()
+    os.environ["L2D_WSGEMM_NO_TABLE"] = "1"    # measure against the cost model, not against an older table
     # ---- the round-3 kernels on the same layers (a second instance packed without wsgemm): in-frame time per shape key
     os.environ["L2D_WSGEMM"] = "0"
     unet0 = HipStreamingUNet(device_random_state_dict(cfg, dev), cfg, h, w, N, device=dev)
