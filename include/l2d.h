@@ -248,6 +248,15 @@ enum {
  *   (1..8) i8 MT token tiles of 32 per block (1..4) ; K = NW * npass * 192 ; f0 eps
  * L2D_OP_CLIP_LN     LayerNorm, fp32 in, fp16 out: p0 x [rows][ldx] float p1 gamma p2 beta float [C] p3 out [rows][ldo] half ;
  *   i0 rows i1 C (<= 1024) i2 ldx i3 ldo ; f0 eps
+ *
+ * SD AutoencoderKL (vae_attn.hip; reference: diffusers' AutoencoderKL, the `stream.vae` of a pipeline without the tiny VAE).
+ * L2D_OP_VAE_ATTN    single-head attention of d = 512, O = softmax(Q K^T f0) V per sample, masked tails, flash form with the keys
+ *   split over S blocks per query tile (merged in split-index order: bit-repeatable):  p0 qkv [B*T][ld] half (q | k | v at
+ *   columns 0, 512, 1024) p1 out [B*T][ldo] half p2 tile images half [B][ceil(T/32)][2][32*512] p3 (S > 1) fp32 workspace
+ *   [S][B][64 ceil(T/64)][514] ; i0 B i1 T i2 ld (>= 1536, % 8) i3 ldo (>= 512, % 8) i4 S (1..16, <= ceil(T/32), no split empty) ;
+ *   f0 scale
+ * L2D_OP_VAE_POSTERIOR  z = mean + exp(0.5 clamp(logvar, -30, 20)) eps:  p0 moments [B][8][HW] half (mean = channels 0-3,
+ *   logvar = 4-7) p1 eps [B][4][HW] half p2 z [B][4][HW] half ; i0 B i1 HW
  */
 enum {
     L2D_OP_IGEMM = 1,
@@ -281,6 +290,8 @@ enum {
     L2D_OP_CLIP_ATTN = 29,
     L2D_OP_CLIP_LINEAR = 30,
     L2D_OP_CLIP_LN = 31,
+    L2D_OP_VAE_ATTN = 32,
+    L2D_OP_VAE_POSTERIOR = 33,
 };
 
 typedef struct l2d_op {

@@ -315,3 +315,91 @@ def build_text_encoder_state_dict(base_sd: Dict[str, torch.Tensor], dreambooth: 
     for lora_sd, alpha in (loras or []):
         merge_text_lora(sd, lora_sd, alpha)
     return sd
+
+
+# ----------------------------------------------------------------------------- the VAE half of a style (SD AutoencoderKL)
+LDM_VAE_PREFIX = "first_stage_model."
+
+
+def ldm_vae_key_map() -> Dict[str, str]:
+    """LDM VAE key (without `first_stage_model.`) -> diffusers AutoencoderKL key, as the reference's convert_ldm_vae_checkpoint
+    (convert_from_ckpt.py:476) renames them: `down.i.block.j` -> `down_blocks.i.resnets.j`, `up.(3 - i)` -> `up_blocks.i`,
+    `mid.block_k` -> `mid_block.resnets.(k - 1)`, `mid.attn_1.{norm,q,k,v,proj_out}` -> `mid_block.attentions.0.{group_norm,
+    to_q,to_k,to_v,to_out.0}`, `nin_shortcut` -> `conv_shortcut`, `norm_out` -> `conv_norm_out`."""
+    from .vae_kl_hip import BLOCK_OUT, DEC_LAYERS, ENC_LAYERS
+    m: Dict[str, str] = {}
+    n = len(BLOCK_OUT)
+
+    def wb(old, new):
+        for leaf in ("weight", "bias"):
+            m[f"{old}.{leaf}"] = f"{new}.{leaf}"
+
+    def resnet(old, new, cin, cout):
+        for part in ("norm1", "conv1", "norm2", "conv2"):
+            wb(f"{old}.{part}", f"{new}.{part}")
+        if cin != cout:
+            wb(f"{old}.nin_shortcut", f"{new}.conv_shortcut")
+
+    def mid(side):
+        c = BLOCK_OUT[-1]
+        for k in (1, 2):
+            resnet(f"{side}.mid.block_{k}", f"{side}.mid_block.resnets.{k - 1}", c, c)
+        for old, new in (("norm", "group_norm"), ("q", "to_q"), ("k", "to_k"), ("v", "to_v"), ("proj_out", "to_out.0")):
+            wb(f"{side}.mid.attn_1.{old}", f"{side}.mid_block.attentions.0.{new}")
+
+    for side in ("encoder", "decoder"):
+        wb(f"{side}.conv_in", f"{side}.conv_in")
+        wb(f"{side}.conv_out", f"{side}.conv_out")
+        wb(f"{side}.norm_out", f"{side}.conv_norm_out")
+    cin = BLOCK_OUT[0]
+    for i, c in enumerate(BLOCK_OUT):
+        for j in range(ENC_LAYERS):
+            resnet(f"encoder.down.{i}.block.{j}", f"encoder.down_blocks.{i}.resnets.{j}", cin if j == 0 else c, c)
+        cin = c
+        if i < n - 1:
+            wb(f"encoder.down.{i}.downsample.conv", f"encoder.down_blocks.{i}.downsamplers.0.conv")
+    mid("encoder")
+    mid("decoder")
+    cin = BLOCK_OUT[-1]
+    for i, c in enumerate(reversed(BLOCK_OUT)):
+        blk = n - 1 - i
+        for j in range(DEC_LAYERS):
+            resnet(f"decoder.up.{blk}.block.{j}", f"decoder.up_blocks.{i}.resnets.{j}", cin if j == 0 else c, c)
+        cin = c
+        if i < n - 1:
+            wb(f"decoder.up.{blk}.upsample.conv", f"decoder.up_blocks.{i}.upsamplers.0.conv")
+    wb("quant_conv", "quant_conv")
+    wb("post_quant_conv", "post_quant_conv")
+    return m
+
+
+def convert_ldm_vae_checkpoint(checkpoint: Dict[str, torch.Tensor], prefix: str = LDM_VAE_PREFIX) -> Dict[str, torch.Tensor]:
+    """LDM VAE tensors (under `prefix`) -> diffusers names.  The attention projections, 1x1 convs in LDM checkpoints, come out
+    as [512, 512] linear weights, as the reference's converter leaves them.  A missing key raises KeyError."""
+    out = {}
+    for old, new in ldm_vae_key_map().items():
+        k = prefix + old
+        if k not in checkpoint:
+            raise KeyError(f"VAE checkpoint lacks {k}")
+        t = checkpoint[k]
+        if ".attentions.0.to_" in new and t.dim() == 4:
+            t = t[:, :, 0, 0]
+        out[new] = t
+    return out
+
+
+def build_vae_state_dict(base_vae_sd: Dict[str, torch.Tensor], dreambooth: Optional[Dict[str, torch.Tensor]] = None,
+                         vae: Optional[Dict] = None) -> Dict[str, torch.Tensor]:
+    """The VAE half of the reference's load_third_party_checkpoints (convert.py:40-45, :52-69): the base AutoencoderKL state dict
+    (diffusers names), replaced by a DreamBooth checkpoint's `first_stage_model.*` tensors and then by a standalone VAE file in LDM
+    layout (possibly under `state_dict`), in that order."""
+    sd = dict(base_vae_sd)
+    if dreambooth is not None:
+        if "state_dict" in dreambooth:
+            dreambooth = dreambooth["state_dict"]
+        sd.update(convert_ldm_vae_checkpoint(dreambooth))
+    if vae is not None:
+        if "state_dict" in vae:
+            vae = vae["state_dict"]
+        sd.update(convert_ldm_vae_checkpoint({LDM_VAE_PREFIX + k: v for k, v in vae.items()}))
+    return sd

@@ -60,6 +60,8 @@ static int run_one(const l2d_op *op, hipStream_t s) {
         case L2D_OP_CLIP_ATTN: return l2d_launch_clip_attn(op, s);
         case L2D_OP_CLIP_LINEAR: return l2d_launch_clip_linear(op, s);
         case L2D_OP_CLIP_LN: return l2d_launch_clip_ln(op, s);
+        case L2D_OP_VAE_ATTN: return l2d_launch_vae_attn(op, s);
+        case L2D_OP_VAE_POSTERIOR: return l2d_launch_vae_posterior(op, s);
         case L2D_OP_COPY: {
             if (!op->p[0] || !op->p[1] || op->l[0] <= 0) {
                 l2d_set_error("copy(tag %d): invalid arguments", op->tag);

@@ -1281,3 +1281,49 @@ def clip_ln(x, gamma, beta, out, *, rows, C, ldx, ldo, eps=1e-5, x_off=0, o_off=
         op.i[j] = int(v)
     op.f[0] = float(eps)
     return op, (x, gamma, beta, out)
+
+
+# ----------------------------------------------------------------------------- SD AutoencoderKL (csrc/vae_attn.hip)
+VAE_ATTN_D = 512        # the one head size vae_attn.hip runs
+VAE_ATTN_MAX_SPLITS = 16
+
+
+def vae_attn_schedule(B: int, T: int) -> int:
+    """Key splits per 64-row query tile: enough blocks for ~one round over the 256 CUs, every split at least one 32-key tile."""
+    nt, nqt = -(-T // 32), -(-T // 64)
+    S = max(1, min(256 // max(1, B * nqt), VAE_ATTN_MAX_SPLITS, nt))
+    tps = -(-nt // S)
+    return -(-nt // tps)                       # (no empty split)
+
+
+def vae_attn_sizes(B: int, T: int, S: int):
+    """(fp16 tile-image elements, fp32 workspace elements) of one vae_attn launch"""
+    nt, nqt = -(-T // 32), -(-T // 64)
+    return B * nt * 2 * 32 * VAE_ATTN_D, (S * B * nqt * 64 * (VAE_ATTN_D + 2) if S > 1 else 0)
+
+
+def vae_attn(qkv, out, img, ws=None, *, B, T, ld, ldo, S=None, scale=VAE_ATTN_D ** -0.5):
+    """softmax(Q K^T scale) V for one head of d = 512 per sample: qkv [B*T][ld] fp16 (q | k | v), out [B*T][ldo] fp16.
+    `img` / `ws`: workspaces of vae_attn_sizes (fp16 / fp32; ws only with S > 1)."""
+    op = L2dOp()
+    op.kind = _lib.OP_VAE_ATTN
+    S = vae_attn_schedule(B, T) if S is None else S
+    n_img, n_ws = vae_attn_sizes(B, T, S)
+    assert img.dtype == torch.float16 and img.numel() >= n_img, (img.numel(), n_img)
+    assert S == 1 or (ws is not None and ws.dtype == torch.float32 and ws.numel() >= n_ws)
+    op.p[0], op.p[1], op.p[2], op.p[3] = _ptr(_h(qkv)), _ptr(_h(out)), _ptr(_h(img)), (_ptr(ws) if S > 1 else None)
+    for j, v in enumerate([B, T, ld, ldo, S]):
+        op.i[j] = int(v)
+    op.f[0] = float(scale)
+    return op, (qkv, out, img, ws)
+
+
+def vae_posterior(moments, eps, out, *, B, HW):
+    """z = mean + exp(0.5 clamp(logvar, -30, 20)) eps on NCHW moments [B, 8, HW] (fp16), eps / z [B, 4, HW] fp16"""
+    op = L2dOp()
+    op.kind = _lib.OP_VAE_POSTERIOR
+    assert moments.dtype == eps.dtype == out.dtype == torch.float16
+    assert moments.numel() >= B * 8 * HW and eps.numel() >= B * 4 * HW and out.numel() >= B * 4 * HW
+    op.p[0], op.p[1], op.p[2] = _ptr(moments), _ptr(eps), _ptr(out)
+    op.i[0], op.i[1] = int(B), int(HW)
+    return op, (moments, eps, out)
