@@ -257,6 +257,17 @@ enum {
  *   f0 scale
  * L2D_OP_VAE_POSTERIOR  z = mean + exp(0.5 clamp(logvar, -30, 20)) eps:  p0 moments [B][8][HW] half (mean = channels 0-3,
  *   logvar = 4-7) p1 eps [B][4][HW] half p2 z [B][4][HW] half ; i0 B i1 HW
+ *
+ * Frame I/O (frame_io.hip; reference: what the callers of wrapper.py do on the host, test.py:106-112 and image_utils.py:9-37).
+ * L2D_OP_FRAME_INGEST  uint8 HWC frame -> the stream's fp16 NCHW input in [-1, 1], one launch: torchvision's Resize(min(H, W),
+ *   antialias=True) + CenterCrop((H, W)) geometry, antialiased bilinear filter (F.interpolate(mode="bilinear", antialias=True):
+ *   per axis scale = n_in / n_out, support = max(scale, 1), centre = scale (i + 0.5), taps [max(0, int(c - support + 0.5)),
+ *   min(n_in, int(c + support + 0.5))), w_j = max(0, 1 - |(j - c + 0.5) / support|) normalised), fp32 accumulation,
+ *   value = fp16(2 sum / 255 - 1):  p0 src uint8 [B][Hs][Ws][3] (RGB, dense) p1 dst half [B][3][H][W] (16-byte aligned) ;
+ *   i0 B i1 Hs i2 Ws i3 H i4 W (% 8) i5 nh i6 nw (size of the resized image) i7 top i8 left (crop window inside it: refused
+ *   otherwise).  Refused: Hs / nh or Ws / nw above 8 (17 taps), B Hs Ws 3 >= 2^31.  Hs == nh == H, Ws == nw == W is the identity.
+ * L2D_OP_FRAME_EGRESS  the decoder's fp16 NCHW output -> uint8 HWC: u = rint(255 clamp(fp16(fp16(x / 2) + 0.5), 0, 1)), round half
+ *   to even:  p0 src half [B][3][H][W] p1 dst uint8 [B][H][W][3] (both 16-byte aligned) ; i0 B i1 H i2 W (H W % 16 == 0)
  */
 enum {
     L2D_OP_IGEMM = 1,
@@ -292,6 +303,8 @@ enum {
     L2D_OP_CLIP_LN = 31,
     L2D_OP_VAE_ATTN = 32,
     L2D_OP_VAE_POSTERIOR = 33,
+    L2D_OP_FRAME_INGEST = 34,
+    L2D_OP_FRAME_EGRESS = 35,
 };
 
 typedef struct l2d_op {

@@ -22,6 +22,7 @@ OP_RESIZE_BILINEAR, OP_MINMAX, OP_DEPTH_NORM_RESIZE = 17, 18, 19
 OP_STEM7X7, OP_RESAMPLE_NHWC, OP_EW, OP_ROWGEMM, OP_PCONV, OP_WSGEMM, OP_ROWCHAIN, OP_CCONV = 20, 21, 22, 23, 24, 25, 26, 27
 OP_CLIP_EMBED, OP_CLIP_ATTN, OP_CLIP_LINEAR, OP_CLIP_LN = 28, 29, 30, 31
 OP_VAE_ATTN, OP_VAE_POSTERIOR = 32, 33
+OP_FRAME_INGEST, OP_FRAME_EGRESS = 34, 35
 ABI_VERSION = 6
 
 

@@ -403,3 +403,22 @@ def build_vae_state_dict(base_vae_sd: Dict[str, torch.Tensor], dreambooth: Optio
             vae = vae["state_dict"]
         sd.update(convert_ldm_vae_checkpoint({LDM_VAE_PREFIX + k: v for k, v in vae.items()}))
     return sd
+
+
+# ----------------------------------------------------------------------------- the `from_pretrained_2d` step
+def inflate_2d_unet(sd2d: Dict[str, torch.Tensor], cfg: UNetConfig, dtype=torch.float16) -> Dict[str, torch.Tensor]:
+    """The state-dict form of the reference's `UNet3DConditionStreamingModel.from_pretrained_2d` (unet_depth_streaming.py; called at
+    pipeline_animatediff_depth.py:273-277): every key of `weights.unet_param_spec(cfg)`, taken from the diffusers 2D UNet file
+    where it has it and a ZERO placeholder of the spec's shape otherwise (motion modules, the depth mapping network) --
+    `merge_motion_checkpoint` requires every key it sets to exist already.  The caller checks after `build_state_dict` that no
+    placeholder (a spec key absent from `sd2d`) survived: the reference would silently keep a random init."""
+    from .weights import unet_param_spec
+    out = {}
+    for k, shp in unet_param_spec(cfg).items():
+        if k in sd2d:
+            if tuple(sd2d[k].shape) != tuple(shp):
+                raise ValueError(f"{k}: 2D UNet tensor {tuple(sd2d[k].shape)} != streaming UNet parameter {tuple(shp)}")
+            out[k] = sd2d[k].to(dtype)
+        else:
+            out[k] = torch.zeros(shp, dtype=dtype)
+    return out

@@ -62,6 +62,8 @@ static int run_one(const l2d_op *op, hipStream_t s) {
         case L2D_OP_CLIP_LN: return l2d_launch_clip_ln(op, s);
         case L2D_OP_VAE_ATTN: return l2d_launch_vae_attn(op, s);
         case L2D_OP_VAE_POSTERIOR: return l2d_launch_vae_posterior(op, s);
+        case L2D_OP_FRAME_INGEST: return l2d_launch_frame_ingest(op, s);
+        case L2D_OP_FRAME_EGRESS: return l2d_launch_frame_egress(op, s);
         case L2D_OP_COPY: {
             if (!op->p[0] || !op->p[1] || op->l[0] <= 0) {
                 l2d_set_error("copy(tag %d): invalid arguments", op->tag);

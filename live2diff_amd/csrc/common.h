@@ -63,6 +63,8 @@ int l2d_launch_clip_linear(const l2d_op *op, hipStream_t s);
 int l2d_launch_clip_ln(const l2d_op *op, hipStream_t s);
 int l2d_launch_vae_attn(const l2d_op *op, hipStream_t s);
 int l2d_launch_vae_posterior(const l2d_op *op, hipStream_t s);
+int l2d_launch_frame_ingest(const l2d_op *op, hipStream_t s);
+int l2d_launch_frame_egress(const l2d_op *op, hipStream_t s);
 
 #ifdef __HIPCC__
 // SiLU / GELU are evaluated per output element inside GEMM epilogues and the GroupNorm apply pass (tens of millions of

@@ -1327,3 +1327,25 @@ def vae_posterior(moments, eps, out, *, B, HW):
     op.p[0], op.p[1], op.p[2] = _ptr(moments), _ptr(eps), _ptr(out)
     op.i[0], op.i[1] = int(B), int(HW)
     return op, (moments, eps, out)
+
+
+# ----------------------------------------------------------------------------- frame I/O (frame_io.hip)
+def frame_ingest(src, dst, *, B, Hs, Ws, H, W, nh, nw, top, left):
+    """uint8 [B,Hs,Ws,3] -> fp16 [B,3,H,W] in [-1, 1]: antialiased resize to (nh, nw) + crop at (top, left) (frame_io.geometry)."""
+    assert src.dtype == torch.uint8 and dst.dtype == torch.float16
+    op = L2dOp()
+    op.kind = _lib.OP_FRAME_INGEST
+    op.p[0], op.p[1] = _ptr(src), _ptr(dst)
+    for j, v in enumerate([B, Hs, Ws, H, W, nh, nw, top, left]):
+        op.i[j] = int(v)
+    return op, (src, dst)
+
+
+def frame_egress(src, dst, *, B, H, W):
+    """fp16 [B,3,H,W] in [-1, 1] -> uint8 [B,H,W,3] with the reference's rounding points (image_utils.py:13,30)."""
+    assert src.dtype == torch.float16 and dst.dtype == torch.uint8
+    op = L2dOp()
+    op.kind = _lib.OP_FRAME_EGRESS
+    op.p[0], op.p[1] = _ptr(src), _ptr(dst)
+    op.i[0], op.i[1], op.i[2] = int(B), int(H), int(W)
+    return op, (src, dst)

@@ -1,0 +1,403 @@
+"""`StreamAnimateDiffusionDepthWrapper` -- the reference's public interface (live2diff/utils/wrapper.py:17-297, driven by test.py
+and demo/vid2vid.py) on the native parts only: config path in, `prepare(warmup_frames, prompt)`, then `wrapper(image) -> image`.
+Model files in, camera-sized uint8 frames in, uint8 frames out; it imports neither diffusers, omegaconf, torchvision nor
+transformers.
+
+  * `load_config`      the reference's YAML schema (configs/*.yaml, `base:` inheritance) with PyYAML;
+  * `load_components`  the assembly order of wrapper.py:404-470 and pipeline_animatediff_depth.py:250-305 on state dicts:
+                       2D UNet -> inflate -> motion checkpoint -> DreamBooth -> few-step LoRA -> LoRAs -> `HipStreamingUNet`
+                       (through the packed-weight cache), text encoder, VAE, depth detector;
+  * the wrapper        frames go through `frame_io.HipFrameIO` (one launch in, one launch out); `prepare` enables the device step.
+
+Differences from the reference, all on purpose: nothing is fetched from a hub (`few_step_lora_path` / `taesd_path` are config
+keys), a missing file raises FileNotFoundError naming its config key (the reference prints a traceback and exits), keywords the
+backend cannot honour raise ValueError at construction, and `"u8"` is a fifth output type.
+"""
+import os
+from pathlib import Path
+from types import SimpleNamespace
+from typing import Dict, List, Optional, Union
+
+import numpy as np
+import torch
+
+from . import convert, ops
+from .config import UNetConfig
+from .pipeline_stream_animation_depth import StreamAnimateDiffusionDepth
+
+OUTPUT_TYPES = ("pil", "pt", "np", "latent", "u8")
+
+
+# ----------------------------------------------------------------------------- config
+def _merge(base: dict, over: dict) -> dict:
+    out = dict(base)
+    for k, v in over.items():
+        out[k] = _merge(out[k], v) if isinstance(v, dict) and isinstance(out.get(k), dict) else v
+    return out
+
+
+def load_config(path: Union[str, os.PathLike]) -> dict:
+    """The reference's `load_config` (live2diff/utils/config.py:10-17) as plain dicts: the file, recursively merged over the file
+    its `base:` key names.  The reference resolves `base` against the working directory (`./configs/base_config.yaml`); here it is
+    also looked for beside the config and one directory up, so a config directory works from anywhere."""
+    import yaml
+    path = str(path)
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"config_path: {path} does not exist")
+    with open(path) as f:
+        cfg = yaml.safe_load(f) or {}
+    base = cfg.pop("base", None)
+    if base:
+        here = os.path.dirname(os.path.abspath(path))
+        for cand in (base, os.path.join(here, base), os.path.join(os.path.dirname(here), base), os.path.join(here, os.path.basename(base))):
+            if os.path.isfile(cand):
+                return _merge(load_config(cand), cfg)
+        raise FileNotFoundError(f"base: {base} (named by {path}) does not exist")
+    return cfg
+
+
+def stream_sizes(cfg: dict):
+    """(window_size, sink_size, temporal_position_encoding_max_len) of a config"""
+    mm = (cfg.get("unet_additional_kwargs") or {}).get("motion_module_kwargs") or {}
+    att = mm.get("attention_kwargs") or {}
+    return int(att.get("window_size", 16)), int(att.get("sink_size", 8)), int(mm.get("temporal_position_encoding_max_len", 24))
+
+
+# ----------------------------------------------------------------------------- one loader per file kind (tests substitute them)
+def _need(key: str, path, kind=os.path.exists):
+    if path is None:
+        raise FileNotFoundError(f"{key}: not set in the config")
+    if not kind(str(path)):
+        raise FileNotFoundError(f"{key}: {path} does not exist")
+    return str(path)
+
+
+def load_tensors(path: str) -> dict:
+    """a .safetensors file, or a torch checkpoint (.ckpt / .pt / .bin) -- tensors only, on the CPU"""
+    if str(path).endswith(".safetensors"):
+        return convert.load_safetensors(str(path))
+    return torch.load(str(path), map_location="cpu", weights_only=True)
+
+
+def _model_file(folder: str) -> str:
+    for name in ("diffusion_pytorch_model.safetensors", "diffusion_pytorch_model.bin", "model.safetensors", "pytorch_model.bin"):
+        if os.path.isfile(os.path.join(folder, name)):
+            return os.path.join(folder, name)
+    raise FileNotFoundError(f"pretrained_model_path: no weight file in {folder}")
+
+
+def load_unet_config(model_dir: str, cfg: dict) -> UNetConfig:
+    """widths / text width from `unet/config.json` when the directory has one (SD-1.5 values otherwise); window, sink and the
+    PE length from the config's `unet_additional_kwargs`"""
+    import json
+    window, sink, max_len = stream_sizes(cfg)
+    kw = {}
+    p = os.path.join(model_dir, "unet", "config.json")
+    if os.path.isfile(p):
+        with open(p) as f:
+            j = json.load(f)
+        if "block_out_channels" in j:
+            kw["block_out_channels"] = tuple(j["block_out_channels"])
+        if "cross_attention_dim" in j:
+            kw["cross_attention_dim"] = int(j["cross_attention_dim"])
+    return UNetConfig(window_size=window, sink_size=sink, temporal_max_len=max(max_len, window), **kw)
+
+
+def load_unet_2d(model_dir: str) -> dict:
+    return load_tensors(_model_file(_need("pretrained_model_path", os.path.join(model_dir, "unet"), os.path.isdir)))
+
+
+def load_motion_checkpoint(path: str) -> dict:
+    return load_tensors(_need("motion_module_path", path, os.path.isfile))
+
+
+def load_depth_state_dict(path: str) -> dict:
+    sd = load_tensors(_need("depth_model_path", path, os.path.isfile))
+    return sd["model"] if "optimizer" in sd else sd            # (MiDaS' own loader, DPTDepthModel.load)
+
+
+def load_style_file(key: str, path: str) -> dict:
+    return load_tensors(_need(key, path, os.path.isfile))
+
+
+def load_taesd(path: str) -> dict:
+    path = _need("taesd_path", path)
+    return load_tensors(_model_file(path) if os.path.isdir(path) else path)
+
+
+def load_vae_kl(model_dir: str) -> dict:
+    return load_tensors(_model_file(_need("pretrained_model_path", os.path.join(model_dir, "vae"), os.path.isdir)))
+
+
+def load_prompt_encoder(model_dir: str, device, clip_skip, dreambooth=None, loras=None):
+    """`clip_hip.load_text_encoder` in pieces, with the style's text half merged in between (converter/convert.py:47-50, 72-88)"""
+    import json
+
+    from .clip_hip import HipClipTextEncoder, HipPromptEncoder, config_from_json
+    from .clip_tokenizer import ClipTokenizer
+    te = _need("pretrained_model_path", os.path.join(model_dir, "text_encoder"), os.path.isdir)
+    with open(os.path.join(te, "config.json")) as f:
+        ccfg = config_from_json(json.load(f))
+    has_te = dreambooth is not None and any(k.startswith(convert.LDM_CLIP_PREFIX) for k in dreambooth)
+    sd = convert.build_text_encoder_state_dict(load_tensors(_model_file(te)), dreambooth if has_te else None, loras)
+    tok = ClipTokenizer.from_dir(os.path.join(model_dir, "tokenizer"), max_length=ccfg.max_position_embeddings)
+    return HipPromptEncoder(HipClipTextEncoder(sd, device, ccfg), tok, clip_skip)
+
+
+# ----------------------------------------------------------------------------- assembly
+def _style(cfg: dict, dreambooth_path, lora_dict):
+    """(dreambooth path or None, {lora path: strength}) -- the keyword wins over the config; the config's lora_list comes first"""
+    third = cfg.get("third_party_dict") or {}
+    loras = {}
+    for item in third.get("lora_list") or []:
+        loras[item["lora"]] = item["lora_alpha"]
+    loras.update(lora_dict or {})
+    return dreambooth_path or third.get("dreambooth"), loras
+
+
+def load_components(cfg: dict, *, height: int, width: int, denoising_steps_num: int, device="cuda", dreambooth_path=None,
+                    lora_dict=None, few_step_model_type: str = "lcm", vae_id=None, use_tiny_vae: bool = True,
+                    engine_dir: Optional[Union[str, os.PathLike]] = "engines"):
+    """config dict -> the `pipe` namespace `StreamAnimateDiffusionDepth` takes (unet, vae, depth_model, `_encode_prompt`, scheduler)"""
+    from .midas_hip import HipMidas
+    from .unet_hip import HipStreamingUNet
+    model_dir = _need("pretrained_model_path", cfg.get("pretrained_model_path"), os.path.isdir)
+    ucfg = load_unet_config(model_dir, cfg)
+    db_path, loras = _style(cfg, dreambooth_path, lora_dict)
+    name = Path(db_path).stem if db_path else "sd15"
+    lat_h, lat_w = height // 8, width // 8
+    cache = None
+    if engine_dir is not None:
+        stem = HipStreamingUNet.packed_cache_name(name, few_step_model_type, ucfg.window_size, loras, lat_h, lat_w, denoising_steps_num)
+        cache = os.path.join(str(engine_dir), stem + ".safetensors")
+    # every file is looked at before anything is converted: a typo in the config costs no minutes of packing
+    _need("motion_module_path", cfg.get("motion_module_path"), os.path.isfile)
+    _need("few_step_lora_path", cfg.get("few_step_lora_path"), os.path.isfile)
+    dreambooth = load_style_file("third_party_dict.dreambooth", db_path) if db_path else None
+    if dreambooth is not None and "state_dict" in dreambooth:
+        dreambooth = dreambooth["state_dict"]
+    lora_sds = [(load_style_file("lora", p), float(a)) for p, a in loras.items()]
+    if cache is not None and os.path.isfile(cache):
+        unet = HipStreamingUNet(cache, ucfg, lat_h, lat_w, denoising_steps_num, device=device)
+    else:
+        sd2d = load_unet_2d(model_dir)
+        base = convert.inflate_2d_unet(sd2d, ucfg)
+        sd = convert.build_state_dict(base, ucfg, dreambooth=dreambooth, loras=lora_sds,
+                                      motion_ckpt=load_motion_checkpoint(cfg["motion_module_path"]),
+                                      few_step_lora=load_style_file("few_step_lora_path", cfg["few_step_lora_path"]))
+        left = [k for k in base if k not in sd2d and sd[k] is base[k]]       # zero placeholders nothing replaced
+        if left:
+            raise KeyError(f"{len(left)} UNet parameters come from neither the 2D UNet nor the motion checkpoint: {left[:8]}")
+        unet = HipStreamingUNet(sd, ucfg, lat_h, lat_w, denoising_steps_num, device=device)
+        if cache is not None:
+            os.makedirs(os.path.dirname(cache), exist_ok=True)
+            unet.save_packed(cache)
+    clip_skip = (cfg.get("third_party_dict") or {}).get("clip_skip", 1)
+    prompt_encoder = load_prompt_encoder(model_dir, device, clip_skip, dreambooth, lora_sds)
+    if use_tiny_vae:
+        from .vae_hip import HipTinyVAE
+        tsd = load_taesd(vae_id or cfg.get("taesd_path"))
+        vae = HipTinyVAE(tsd, device=device, width=int(tsd["encoder.layers.0.weight"].shape[0]))
+    else:
+        from .vae_kl_hip import HipAutoencoderKL
+        has_vae = dreambooth is not None and any(k.startswith(convert.LDM_VAE_PREFIX) for k in dreambooth)
+        vae = HipAutoencoderKL(convert.build_vae_state_dict(load_vae_kl(model_dir), dreambooth if has_vae else None), device=device)
+    depth = HipMidas(load_depth_state_dict(cfg.get("depth_model_path")), device=device)
+    return SimpleNamespace(device=torch.device(device), vae_scale_factor=8, unet=unet, vae=vae, depth_model=depth,
+                           text_encoder=prompt_encoder.encoder, tokenizer=prompt_encoder.tokenizer,
+                           _encode_prompt=prompt_encoder._encode_prompt, unet_config=ucfg,
+                           scheduler=SimpleNamespace(config=dict(cfg.get("noise_scheduler_kwargs") or {})))
+
+
+# ----------------------------------------------------------------------------- the wrapper
+class StreamAnimateDiffusionDepthWrapper:
+    def __init__(self, config_path: str, few_step_model_type: str, num_inference_steps: int,
+                 t_index_list: Optional[List[int]] = None, strength: Optional[float] = None,
+                 dreambooth_path: Optional[str] = None, lora_dict: Optional[Dict[str, float]] = None, output_type: str = "pil",
+                 vae_id: Optional[str] = None, device="cuda", dtype: torch.dtype = torch.float16, frame_buffer_size: int = 1,
+                 width: int = 512, height: int = 512, acceleration: str = "hip", do_add_noise: bool = True,
+                 device_ids: Optional[List[int]] = None, use_tiny_vae: bool = True, enable_similar_image_filter: bool = False,
+                 similar_image_filter_threshold: float = 0.98, similar_image_filter_max_skip_frame: int = 10,
+                 use_denoising_batch: bool = True, cfg_type: str = "none", seed: int = 42,
+                 engine_dir: Optional[Union[str, Path]] = "engines", opt_unet: bool = False, frame_pipelining: bool = False):
+        self._check_keywords(few_step_model_type=few_step_model_type, acceleration=acceleration, cfg_type=cfg_type,
+                             use_denoising_batch=use_denoising_batch, frame_buffer_size=frame_buffer_size, device_ids=device_ids,
+                             opt_unet=opt_unet, output_type=output_type, dtype=dtype)
+        cfg = load_config(config_path)
+        if t_index_list is None and strength is None:
+            t_index_list = cfg.get("t_index_list")
+        window, sink, _ = stream_sizes(cfg)
+        n = len(t_index_list) if strength is None else min(int(num_inference_steps * strength), num_inference_steps)
+        pipe = load_components(cfg, height=height, width=width, denoising_steps_num=n, device=device,
+                               dreambooth_path=dreambooth_path, lora_dict=lora_dict, few_step_model_type=few_step_model_type,
+                               vae_id=vae_id, use_tiny_vae=use_tiny_vae, engine_dir=engine_dir)
+        self._setup(pipe, num_inference_steps=num_inference_steps, t_index_list=t_index_list, strength=strength,
+                    output_type=output_type, device=device, dtype=dtype, width=width, height=height, do_add_noise=do_add_noise,
+                    seed=seed, clip_skip=(cfg.get("third_party_dict") or {}).get("clip_skip", 1), warmup_frames=sink,
+                    window_size=window, frame_pipelining=frame_pipelining, enable_similar_image_filter=enable_similar_image_filter,
+                    similar_image_filter_threshold=similar_image_filter_threshold,
+                    similar_image_filter_max_skip_frame=similar_image_filter_max_skip_frame)
+
+    @classmethod
+    def from_components(cls, pipe, *, num_inference_steps: int, t_index_list: Optional[List[int]] = None,
+                        strength: Optional[float] = None, **kw):
+        """The wrapper around an already assembled `pipe` namespace (tests, synthetic weights).  Keywords: those of the
+        constructor that do not name files, plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
+        self = cls.__new__(cls)
+        cls._check_keywords(**{k: kw.pop(k) for k in ("acceleration", "cfg_type", "use_denoising_batch", "frame_buffer_size",
+                                                      "device_ids", "opt_unet", "few_step_model_type") if k in kw},
+                            output_type=kw.get("output_type", "pil"), dtype=kw.get("dtype", torch.float16))
+        self._setup(pipe, num_inference_steps=num_inference_steps, t_index_list=t_index_list, strength=strength, **kw)
+        return self
+
+    @staticmethod
+    def _check_keywords(few_step_model_type="lcm", acceleration="hip", cfg_type="none", use_denoising_batch=True,
+                        frame_buffer_size=1, device_ids=None, opt_unet=False, output_type="pil", dtype=torch.float16):
+        def no(keyword, value, supported):
+            raise ValueError(f"{keyword}={value!r} is not supported by the HIP backend: use {keyword}={supported}")
+        if str(few_step_model_type).upper() != "LCM":
+            no("few_step_model_type", few_step_model_type, "'lcm'")
+        if acceleration != "hip":
+            no("acceleration", acceleration, "'hip'")
+        if cfg_type != "none":
+            no("cfg_type", cfg_type, "'none'")
+        if not use_denoising_batch:
+            no("use_denoising_batch", use_denoising_batch, "True")
+        if frame_buffer_size != 1:
+            no("frame_buffer_size", frame_buffer_size, "1")
+        if device_ids is not None:
+            no("device_ids", device_ids, "None")
+        if opt_unet:
+            no("opt_unet", opt_unet, "False")
+        if output_type not in OUTPUT_TYPES:
+            no("output_type", output_type, " | ".join(repr(t) for t in OUTPUT_TYPES))
+
+    def _setup(self, pipe, *, num_inference_steps, t_index_list, strength, output_type="pil", device=None, dtype=torch.float16,
+               width=512, height=512, do_add_noise=True, seed=42, clip_skip=1, warmup_frames=8, window_size=16,
+               scheduler_kwargs=None, frame_pipelining=False, enable_similar_image_filter=False,
+               similar_image_filter_threshold=0.98, similar_image_filter_max_skip_frame=10):
+        self.sd_turbo = False
+        self.device = pipe.device if device is None else device
+        self.dtype, self.width, self.height = dtype, width, height
+        self.output_type = output_type
+        self.frame_buffer_size = 1
+        self.use_denoising_batch = True
+        self.seed = seed
+        self.frame_pipelining = frame_pipelining
+        self.stream = StreamAnimateDiffusionDepth(pipe, num_inference_steps=num_inference_steps, t_index_list=t_index_list,
+                                                  strength=strength, torch_dtype=dtype, width=width, height=height,
+                                                  do_add_noise=do_add_noise, frame_buffer_size=1, use_denoising_batch=True,
+                                                  cfg_type="none", clip_skip=clip_skip, warmup_frames=warmup_frames,
+                                                  window_size=window_size, scheduler_kwargs=scheduler_kwargs)
+        self.batch_size = len(self.stream.t_list)
+        self.stream.load_warmup_unet(None)
+        self.stream.prepare_cache(height=height, width=width, denoising_steps_num=self.batch_size)
+        if enable_similar_image_filter:
+            self.stream.enable_similar_image_filter(similar_image_filter_threshold, similar_image_filter_max_skip_frame)
+        self.io = None
+        if torch.device(self.device).type == "cuda" and not ops.DRY_RUN:
+            from .frame_io import FrameProcessor, HipFrameIO
+            self.io = HipFrameIO(height, width, device=pipe.device)
+            self.stream.image_processor = FrameProcessor(self.io)
+
+    # ------------------------------------------------------------------ prepare
+    def prepare(self, warmup_frames, prompt: str, negative_prompt: str = "", guidance_scale: float = 1.2, delta: float = 1.0) -> torch.Tensor:
+        """warmup_frames: float [F,3,H,W] in [0, 1] as in the reference, or uint8 [F,Hs,Ws,3] (one batched ingest launch).
+        Returns the generated warm-up frames, [F,H,W,3] in [0, 1] (wrapper.py:197-199)."""
+        kw = dict(prompt=prompt, negative_prompt=negative_prompt, guidance_scale=guidance_scale, delta=delta, seed=self.seed)
+        dt = getattr(warmup_frames, "dtype", None)
+        if dt == torch.uint8 or dt == np.uint8:
+            from .frame_io import _PassThrough
+            if self.io is None:
+                raise ValueError("uint8 warm-up frames need the device-side frame I/O (a cuda device)")
+            x = self.io.ingest(warmup_frames)
+            # the pipeline preprocesses frame by frame and only then concatenates: through a static ingest slot all rows would be
+            # views of the last frame, and a normalised frame must never reach a [0, 1]-or-[-1, 1] probe
+            keep, self.stream.image_processor = self.stream.image_processor, _PassThrough()
+            try:
+                frames = self.stream.prepare(warmup_frames=x, **kw)
+            finally:
+                self.stream.image_processor = keep
+        else:
+            frames = self.stream.prepare(warmup_frames=warmup_frames, **kw)
+        from .unet_hip import HipStreamingUNet
+        if isinstance(self.stream.unet, HipStreamingUNet):
+            self.stream.enable_device_step(seed=self.seed)
+            if self.frame_pipelining:
+                self.stream.enable_frame_pipelining()
+        frames = frames.permute(0, 2, 3, 1)
+        return (frames.clip(-1, 1) + 1) / 2
+
+    # ------------------------------------------------------------------ frames
+    def __call__(self, image=None, prompt: Optional[str] = None):
+        return self.img2img(image, prompt)
+
+    def img2img(self, image, prompt: Optional[str] = None):
+        """image: a path, a PIL image (resized to (width, height) on the host like the reference, :264-267), a uint8 HWC array /
+        tensor of any size (resize + centre crop on the device), or a float [3,H,W] tensor in [0, 1] (the reference's input)."""
+        if prompt is not None:
+            self.stream.update_prompt(prompt)
+        return self.postprocess_image(self.stream(self.preprocess_image(image)), output_type=self.output_type)
+
+    def push(self, image, prompt: Optional[str] = None) -> None:
+        """pipelined mode (`frame_pipelining=True`): start a frame's encode / depth path; `pop()` returns the oldest frame's output"""
+        if prompt is not None:
+            self.stream.update_prompt(prompt)
+        self.stream.push(self.preprocess_image(image))
+        if self.io is not None and self.io.last_view is not None:
+            # push() ran the ingest on this stream before ordering the side stream behind it; the side stream reads the slot
+            # until the event push recorded behind its two encodes
+            self.io.release(self.io.last_view, self.stream._pending[-1][2])
+
+    def pop(self):
+        return self.postprocess_image(self.stream.pop(), output_type=self.output_type)
+
+    def preprocess_image(self, image):
+        """path / PIL image -> uint8 [height, width, 3] (host resize, as the reference); arrays and tensors pass through: the
+        pipeline's `image_processor` (frame_io.FrameProcessor) ingests them, so a normalised tensor never meets a range probe"""
+        if isinstance(image, (str, os.PathLike)):
+            from PIL import Image
+            image = Image.open(image)
+        if hasattr(image, "convert") and hasattr(image, "resize"):
+            arr = np.array(image.convert("RGB").resize((self.width, self.height)))
+            if self.io is None:
+                return torch.from_numpy(arr).permute(2, 0, 1).float() / 255.0
+            return arr
+        return image
+
+    def postprocess_image(self, image_tensor: torch.Tensor, output_type: str = "pil"):
+        """`image_utils.postprocess_image(x, output_type)[0]` (+ `.cpu()` for "pt" / "latent", wrapper.py:289-297); "u8" and "pil"
+        through the egress kernel when the tensor is on the device"""
+        if not torch.is_tensor(image_tensor):
+            raise ValueError(f"Input for postprocessing is in incorrect format: {type(image_tensor)}. We only support pytorch tensor")
+        if output_type == "latent":
+            return image_tensor[0].cpu()
+        if output_type == "pt":
+            return (image_tensor / 2 + 0.5).clamp(0, 1)[0].cpu()
+        if output_type == "np":
+            return (image_tensor / 2 + 0.5).clamp(0, 1).cpu().permute(0, 2, 3, 1).float().numpy()[0]
+        if output_type not in ("pil", "u8"):
+            raise ValueError(f"output_type={output_type!r}: use one of {OUTPUT_TYPES}")
+        if self.io is not None and image_tensor.is_cuda:
+            u8 = self.io.egress(image_tensor[0]).copy()          # (the pinned buffer is overwritten by the next frame)
+        else:
+            from .frame_io import egress_ref
+            u8 = egress_ref(image_tensor)[0].numpy()
+        if output_type == "u8":
+            return u8
+        from PIL import Image
+        return Image.fromarray(u8)
+
+    @staticmethod
+    def get_model_prefix(config_path: str, few_step_model_type: str, use_tiny_vae: bool, num_denoising_steps: int, height: int,
+                         width: int, dreambooth: Optional[str] = None, lora_dict: Optional[dict] = None) -> str:
+        """the reference's engine prefix (wrapper.py:299-332)"""
+        cfg = load_config(config_path)
+        db, loras = _style(cfg, dreambooth, None)
+        merged = dict(lora_dict or {})
+        for k, v in loras.items():
+            merged.setdefault(k, v)
+        prefix = f"{Path(db).stem if db else 'sd15'}--{few_step_model_type}--step{num_denoising_steps}--"
+        for k, v in merged.items():
+            prefix += f"{Path(k).stem}-{v}--"
+        return prefix + f"tiny_vae-{use_tiny_vae}--h-{height}--w-{width}"
