@@ -268,6 +268,23 @@ enum {
  *   otherwise).  Refused: Hs / nh or Ws / nw above 8 (17 taps), B Hs Ws 3 >= 2^31.  Hs == nh == H, Ws == nw == W is the identity.
  * L2D_OP_FRAME_EGRESS  the decoder's fp16 NCHW output -> uint8 HWC: u = rint(255 clamp(fp16(fp16(x / 2) + 0.5), 0, 1)), round half
  *   to even:  p0 src half [B][3][H][W] p1 dst uint8 [B][H][W][3] (both 16-byte aligned) ; i0 B i1 H i2 W (H W % 16 == 0)
+ *
+ * Baseline JPEG (jpeg.hip; reference: demo/util.py:27-37 encodes every output frame on the host).  8-bit YCbCr 4:2:0, MCU = 16 x 16
+ *   pixels = Y00 Y01 Y10 Y11 Cb Cr, libjpeg's accurate integer DCT, Annex K tables scaled by libjpeg's quality rule, Annex K.3 Huffman
+ *   tables, one restart interval per MCU row; integer arithmetic throughout -- the file equals live2diff_amd/jpeg.py `encode_ref`
+ *   (and Pillow's `save(format="JPEG", quality=q, restart_marker_rows=1)`) byte for byte.  H and W are multiples of 16 and
+ *   W <= 1920 in all three (refused otherwise); R = H / 16 MCU rows, M = W / 16 MCUs per row.
+ * L2D_OP_JPEG_DCT  colour conversion, 2 x 2 chroma down-sampling, both DCT passes and quantisation, one launch:  p0 src, either
+ *   half [B][3][H][W] in [-1, 1] (4-byte aligned; mapped to bytes with L2D_OP_FRAME_EGRESS' expression first) or uint8 [B][H][W][3]
+ *   p1 coef int16 [B][R][M][6][64], every block in zigzag order (16-byte aligned) ; i0 B i1 H i2 W i3 source kind (0 half, 1 uint8)
+ *   i4 quality (1..100: s = 5000 / q below 50, 200 - 2 q from 50; Q = clamp((base s + 50) / 100, 1, 255); divisor 8 Q)
+ * L2D_OP_JPEG_HUFF  entropy coding, one work-group per (frame, MCU row): Huffman codes, the last byte filled with 1-bits, 0x00
+ *   behind every 0xFF, then RSTn (EOI behind the last row):  p0 coef (as above) p1 tables uint32 [544]: dc [2][16] then ac [2][256],
+ *   `length << 16 | code` per symbol (jpeg.Tables.packed) p2 staging uint8 [B][R][row_stride] p3 len int32 [B][R] (bytes of every
+ *   row, marker included) ; i0 B i1 H i2 W i3 row_stride (>= M 6 432 + 4: 64 symbols of 27 bits per block, doubled by stuffing)
+ * L2D_OP_JPEG_PACK  the file:  p0 staging p1 len p2 header uint8 [hdr_len] (jpeg.header) p3 out uint8 [B][out_stride] (4-byte
+ *   aligned): per frame an int32 with the file's length, the file itself from byte 16 ; i0 B i1 H i2 row_stride i3 hdr_len ;
+ *   l0 out_stride (% 4, >= 16 + hdr_len + R row_stride)
  */
 enum {
     L2D_OP_IGEMM = 1,
@@ -305,6 +322,9 @@ enum {
     L2D_OP_VAE_POSTERIOR = 33,
     L2D_OP_FRAME_INGEST = 34,
     L2D_OP_FRAME_EGRESS = 35,
+    L2D_OP_JPEG_DCT = 36,
+    L2D_OP_JPEG_HUFF = 37,
+    L2D_OP_JPEG_PACK = 38,
 };
 
 typedef struct l2d_op {

@@ -23,6 +23,7 @@ OP_STEM7X7, OP_RESAMPLE_NHWC, OP_EW, OP_ROWGEMM, OP_PCONV, OP_WSGEMM, OP_ROWCHAI
 OP_CLIP_EMBED, OP_CLIP_ATTN, OP_CLIP_LINEAR, OP_CLIP_LN = 28, 29, 30, 31
 OP_VAE_ATTN, OP_VAE_POSTERIOR = 32, 33
 OP_FRAME_INGEST, OP_FRAME_EGRESS = 34, 35
+OP_JPEG_DCT, OP_JPEG_HUFF, OP_JPEG_PACK = 36, 37, 38
 ABI_VERSION = 6
 
 

@@ -64,6 +64,9 @@ static int run_one(const l2d_op *op, hipStream_t s) {
         case L2D_OP_VAE_POSTERIOR: return l2d_launch_vae_posterior(op, s);
         case L2D_OP_FRAME_INGEST: return l2d_launch_frame_ingest(op, s);
         case L2D_OP_FRAME_EGRESS: return l2d_launch_frame_egress(op, s);
+        case L2D_OP_JPEG_DCT: return l2d_launch_jpeg_dct(op, s);
+        case L2D_OP_JPEG_HUFF: return l2d_launch_jpeg_huff(op, s);
+        case L2D_OP_JPEG_PACK: return l2d_launch_jpeg_pack(op, s);
         case L2D_OP_COPY: {
             if (!op->p[0] || !op->p[1] || op->l[0] <= 0) {
                 l2d_set_error("copy(tag %d): invalid arguments", op->tag);

@@ -1349,3 +1349,47 @@ def frame_egress(src, dst, *, B, H, W):
     op.p[0], op.p[1] = _ptr(src), _ptr(dst)
     op.i[0], op.i[1], op.i[2] = int(B), int(H), int(W)
     return op, (src, dst)
+
+
+# ----------------------------------------------------------------------------- baseline JPEG (jpeg.hip, jpeg.py)
+JPEG_MAX_W = 1920      # jpeg.hip JPG_MAX_W: an MCU row is entropy-coded in LDS
+JPEG_HDR_OFF = 16      # jpeg.hip JPG_HDR_OFF: a frame's slot holds the file's length (int32) and, from byte 16, the file
+
+
+def jpeg_dct(src, coef, *, B, H, W, quality):
+    """fp16 [B,3,H,W] in [-1, 1] (the egress op's bytes first) or uint8 [B,H,W,3] -> int16 [B][H/16][W/16][6][64] quantised
+    coefficients, zigzag order (jpeg.coefficients)"""
+    assert src.dtype in (torch.float16, torch.uint8) and coef.dtype == torch.int16
+    assert src.numel() >= B * H * W * 3 and coef.numel() >= B * H * W * 3 // 2
+    op = L2dOp()
+    op.kind = _lib.OP_JPEG_DCT
+    op.p[0], op.p[1] = _ptr(src), _ptr(coef)
+    for j, v in enumerate([B, H, W, int(src.dtype == torch.uint8), quality]):
+        op.i[j] = int(v)
+    return op, (src, coef)
+
+
+def jpeg_huff(coef, tables, staging, lengths, *, B, H, W, row_stride):
+    """coefficients -> every MCU row entropy-coded, padded, stuffed and closed with its marker, in its slot of `staging`
+    (uint8 [B][H/16][row_stride]); `lengths` int32 [B][H/16]; `tables` int32 [544] (jpeg.Tables.packed)"""
+    assert coef.dtype == torch.int16 and tables.dtype == torch.int32 and staging.dtype == torch.uint8 and lengths.dtype == torch.int32
+    assert tables.numel() >= 544 and staging.numel() >= B * (H // 16) * row_stride and lengths.numel() >= B * (H // 16)
+    op = L2dOp()
+    op.kind = _lib.OP_JPEG_HUFF
+    op.p[0], op.p[1], op.p[2], op.p[3] = _ptr(coef), _ptr(tables), _ptr(staging), _ptr(lengths)
+    for j, v in enumerate([B, H, W, row_stride]):
+        op.i[j] = int(v)
+    return op, (coef, tables, staging, lengths)
+
+
+def jpeg_pack(staging, lengths, header, out, *, B, H, row_stride, out_stride):
+    """rows -> per frame `out[b]` = int32 length, 12 unused bytes, header, rows (uint8 [B][out_stride])"""
+    assert staging.dtype == header.dtype == out.dtype == torch.uint8 and lengths.dtype == torch.int32
+    assert out.numel() >= B * out_stride
+    op = L2dOp()
+    op.kind = _lib.OP_JPEG_PACK
+    op.p[0], op.p[1], op.p[2], op.p[3] = _ptr(staging), _ptr(lengths), _ptr(header), _ptr(out)
+    for j, v in enumerate([B, H, row_stride, header.numel()]):
+        op.i[j] = int(v)
+    op.l[0] = int(out_stride)
+    return op, (staging, lengths, header, out)

@@ -11,7 +11,8 @@ transformers.
 
 Differences from the reference, all on purpose: nothing is fetched from a hub (`few_step_lora_path` / `taesd_path` are config
 keys), a missing file raises FileNotFoundError naming its config key (the reference prints a traceback and exits), keywords the
-backend cannot honour raise ValueError at construction, and `"u8"` is a fifth output type.
+backend cannot honour raise ValueError at construction, `"u8"` is a fifth output type and `"jpeg"` (with `jpeg_quality`) a sixth:
+the frame leaves the device as the JPEG file the reference's demo makes of it on the host (jpeg_io.HipJpegEncoder).
 """
 import os
 from pathlib import Path
@@ -25,7 +26,7 @@ from . import convert, ops
 from .config import UNetConfig
 from .pipeline_stream_animation_depth import StreamAnimateDiffusionDepth
 
-OUTPUT_TYPES = ("pil", "pt", "np", "latent", "u8")
+OUTPUT_TYPES = ("pil", "pt", "np", "latent", "u8", "jpeg")
 
 
 # ----------------------------------------------------------------------------- config
@@ -219,10 +220,11 @@ class StreamAnimateDiffusionDepthWrapper:
                  device_ids: Optional[List[int]] = None, use_tiny_vae: bool = True, enable_similar_image_filter: bool = False,
                  similar_image_filter_threshold: float = 0.98, similar_image_filter_max_skip_frame: int = 10,
                  use_denoising_batch: bool = True, cfg_type: str = "none", seed: int = 42,
-                 engine_dir: Optional[Union[str, Path]] = "engines", opt_unet: bool = False, frame_pipelining: bool = False):
+                 engine_dir: Optional[Union[str, Path]] = "engines", opt_unet: bool = False, frame_pipelining: bool = False,
+                 jpeg_quality: int = 75):
         self._check_keywords(few_step_model_type=few_step_model_type, acceleration=acceleration, cfg_type=cfg_type,
                              use_denoising_batch=use_denoising_batch, frame_buffer_size=frame_buffer_size, device_ids=device_ids,
-                             opt_unet=opt_unet, output_type=output_type, dtype=dtype)
+                             opt_unet=opt_unet, output_type=output_type, dtype=dtype, jpeg_quality=jpeg_quality)
         cfg = load_config(config_path)
         if t_index_list is None and strength is None:
             t_index_list = cfg.get("t_index_list")
@@ -236,23 +238,24 @@ class StreamAnimateDiffusionDepthWrapper:
                     seed=seed, clip_skip=(cfg.get("third_party_dict") or {}).get("clip_skip", 1), warmup_frames=sink,
                     window_size=window, frame_pipelining=frame_pipelining, enable_similar_image_filter=enable_similar_image_filter,
                     similar_image_filter_threshold=similar_image_filter_threshold,
-                    similar_image_filter_max_skip_frame=similar_image_filter_max_skip_frame)
+                    similar_image_filter_max_skip_frame=similar_image_filter_max_skip_frame, jpeg_quality=jpeg_quality)
 
     @classmethod
     def from_components(cls, pipe, *, num_inference_steps: int, t_index_list: Optional[List[int]] = None,
                         strength: Optional[float] = None, **kw):
         """The wrapper around an already assembled `pipe` namespace (tests, synthetic weights).  Keywords: those of the
-        constructor that do not name files, plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
+        constructor that do not name files (`jpeg_quality` among them), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
         self = cls.__new__(cls)
         cls._check_keywords(**{k: kw.pop(k) for k in ("acceleration", "cfg_type", "use_denoising_batch", "frame_buffer_size",
                                                       "device_ids", "opt_unet", "few_step_model_type") if k in kw},
-                            output_type=kw.get("output_type", "pil"), dtype=kw.get("dtype", torch.float16))
+                            output_type=kw.get("output_type", "pil"), dtype=kw.get("dtype", torch.float16),
+                            jpeg_quality=kw.get("jpeg_quality", 75))
         self._setup(pipe, num_inference_steps=num_inference_steps, t_index_list=t_index_list, strength=strength, **kw)
         return self
 
     @staticmethod
     def _check_keywords(few_step_model_type="lcm", acceleration="hip", cfg_type="none", use_denoising_batch=True,
-                        frame_buffer_size=1, device_ids=None, opt_unet=False, output_type="pil", dtype=torch.float16):
+                        frame_buffer_size=1, device_ids=None, opt_unet=False, output_type="pil", dtype=torch.float16, jpeg_quality=75):
         def no(keyword, value, supported):
             raise ValueError(f"{keyword}={value!r} is not supported by the HIP backend: use {keyword}={supported}")
         if str(few_step_model_type).upper() != "LCM":
@@ -271,15 +274,22 @@ class StreamAnimateDiffusionDepthWrapper:
             no("opt_unet", opt_unet, "False")
         if output_type not in OUTPUT_TYPES:
             no("output_type", output_type, " | ".join(repr(t) for t in OUTPUT_TYPES))
+        if isinstance(jpeg_quality, bool) or not isinstance(jpeg_quality, int) or not 1 <= jpeg_quality <= 100:
+            raise ValueError(f"jpeg_quality={jpeg_quality!r}: use an integer from 1 to 100")
 
     def _setup(self, pipe, *, num_inference_steps, t_index_list, strength, output_type="pil", device=None, dtype=torch.float16,
                width=512, height=512, do_add_noise=True, seed=42, clip_skip=1, warmup_frames=8, window_size=16,
                scheduler_kwargs=None, frame_pipelining=False, enable_similar_image_filter=False,
-               similar_image_filter_threshold=0.98, similar_image_filter_max_skip_frame=10):
+               similar_image_filter_threshold=0.98, similar_image_filter_max_skip_frame=10, jpeg_quality=75):
         self.sd_turbo = False
         self.device = pipe.device if device is None else device
         self.dtype, self.width, self.height = dtype, width, height
         self.output_type = output_type
+        self.jpeg_quality = jpeg_quality
+        self.jpeg = None                    # jpeg_io.HipJpegEncoder, made by the first "jpeg" frame on the device
+        if output_type == "jpeg":
+            from . import jpeg
+            jpeg._check(height, width, jpeg_quality)       # a size that is no multiple of 16 is refused here, not at the first frame
         self.frame_buffer_size = 1
         self.use_denoising_batch = True
         self.seed = seed
@@ -367,7 +377,8 @@ class StreamAnimateDiffusionDepthWrapper:
 
     def postprocess_image(self, image_tensor: torch.Tensor, output_type: str = "pil"):
         """`image_utils.postprocess_image(x, output_type)[0]` (+ `.cpu()` for "pt" / "latent", wrapper.py:289-297); "u8" and "pil"
-        through the egress kernel when the tensor is on the device"""
+        through the egress kernel when the tensor is on the device; "jpeg" through the device-side encoder (no egress launch, no raw
+        frame on the host), the file of `encode_ref(egress_ref(x))` either way"""
         if not torch.is_tensor(image_tensor):
             raise ValueError(f"Input for postprocessing is in incorrect format: {type(image_tensor)}. We only support pytorch tensor")
         if output_type == "latent":
@@ -376,6 +387,15 @@ class StreamAnimateDiffusionDepthWrapper:
             return (image_tensor / 2 + 0.5).clamp(0, 1)[0].cpu()
         if output_type == "np":
             return (image_tensor / 2 + 0.5).clamp(0, 1).cpu().permute(0, 2, 3, 1).float().numpy()[0]
+        if output_type == "jpeg":
+            if self.io is not None and image_tensor.is_cuda:
+                if self.jpeg is None:
+                    from .jpeg_io import HipJpegEncoder
+                    self.jpeg = HipJpegEncoder(self.height, self.width, self.jpeg_quality, device=image_tensor.device)
+                return self.jpeg.encode(image_tensor[0])
+            from .frame_io import egress_ref
+            from .jpeg import encode_ref
+            return encode_ref(egress_ref(image_tensor)[0].numpy(), self.jpeg_quality)
         if output_type not in ("pil", "u8"):
             raise ValueError(f"output_type={output_type!r}: use one of {OUTPUT_TYPES}")
         if self.io is not None and image_tensor.is_cuda:
