@@ -285,6 +285,30 @@ enum {
  * L2D_OP_JPEG_PACK  the file:  p0 staging p1 len p2 header uint8 [hdr_len] (jpeg.header) p3 out uint8 [B][out_stride] (4-byte
  *   aligned): per frame an int32 with the file's length, the file itself from byte 16 ; i0 B i1 H i2 row_stride i3 hdr_len ;
  *   l0 out_stride (% 4, >= 16 + hdr_len + R row_stride)
+ *
+ * Baseline JPEG decoder (jpeg_dec.hip; reference: demo/app.py:81-85 and demo/util.py:22 decode every input frame on the host).
+ *   8-bit Y Cb Cr, SOF0, one interleaved scan, luminance sampling 1 x 1 / 2 x 1 / 2 x 2 (ny = 1 / 2 / 4 luminance blocks per MCU,
+ *   then Cb, Cr), any Huffman tables, any size, with or without restart markers; integer arithmetic throughout -- the frame equals
+ *   live2diff_amd/jpeg.py `decode_ref` (and Pillow's decode) byte for byte.  The scan is cut into CHUNKS of `chunk_mcus` consecutive
+ *   MCUs, counted from the start of every restart interval (jpeg.chunk_layout: a chunk never spans a restart marker); the host
+ *   finds where each begins (l2d_jpeg_index below), the device does the rest.
+ * L2D_OP_JPEG_ENTROPY_DEC  one lane per chunk:  p0 file uint8 [capacity] p1 bit_offsets int32 [C + 1] p2 dc_pred int16 [C][3]
+ *   (both as l2d_jpeg_index writes them) p3 table blob uint8 [4032] (jpeg.table_blob; 4-byte aligned) p4 params int32 [2] =
+ *   {byte offset of the scan in the file, length of the file}, read by the kernel and clamped to the capacity p5 coef int16
+ *   [n_mcu][ny + 2][64], DC absolute, natural order, every element written (16-byte aligned) p6 status int32, OR-ed into: 1 invalid
+ *   code, 2 coefficient index past 63, 4 a chunk does not end where the next begins, 8 bad index; zero before the launch ;
+ *   i0 n_mcu i1 ny i2 restart interval (0 none) i3 chunk_mcus i4 C (refused unless it follows from i0, i2, i3) i5 capacity of p0 in
+ *   bytes (< 2^28) i6..i8 DC table id of Y, Cb, Cr i9..i11 AC table id (0 | 1)
+ * L2D_OP_JPEG_IDCT  dequantisation and libjpeg's accurate integer IDCT (jidctint: 13 constant bits, 2 extra bits behind the column
+ *   pass, clamp(x + 128, 0, 255); 32-bit arithmetic that wraps: equal to libjpeg for |dequantised coefficient| <= 1024, which every
+ *   picture is far inside; beyond it -- only a damaged file -- the result is defined and repeatable but libjpeg's 64-bit one may differ):
+ *   p0 coef (as above) p1 quantisation tables uint16 [3][64], natural order (the blob at byte 3648)
+ *   p2 planes uint8 (8-byte aligned): Y [my vs 8][mx hs 8], Cb and Cr [my 8][mx 8] behind one another ; i0 n_mcu i1 mx (MCUs per
+ *   row) i2 hs i3 vs
+ * L2D_OP_JPEG_RGB  libjpeg's "fancy" chroma up-sampling (h2v1: (3 a + b + 1) >> 2 / (3 a + b + 2) >> 2; h2v2: 3 near + far, then
+ *   (3 this + last + 8) >> 4 / (3 this + next + 7) >> 4; edges copied, the bottom edge from the last REAL row; replication for planes
+ *   of one or two columns) and its 16-bit fixed-point colour conversion:  p0 planes (as above, mx = ceil(W / 8 hs), my = ceil(H / 8 vs))
+ *   p1 out uint8 [H][W][3] ; i0 H i1 W i2 hs i3 vs
  */
 enum {
     L2D_OP_IGEMM = 1,
@@ -325,6 +349,9 @@ enum {
     L2D_OP_JPEG_DCT = 36,
     L2D_OP_JPEG_HUFF = 37,
     L2D_OP_JPEG_PACK = 38,
+    L2D_OP_JPEG_ENTROPY_DEC = 39,
+    L2D_OP_JPEG_IDCT = 40,
+    L2D_OP_JPEG_RGB = 41,
 };
 
 typedef struct l2d_op {
@@ -369,6 +396,19 @@ int l2d_copy_bench(const void *src, void *dst, int64_t bytes, int reps, void *st
  * 256 x blocks_per_cu blocks of 256 threads; returns GB/s read. */
 int l2d_read_bench(const void *src, void *sink, int64_t bytes, int unroll, int blocks_per_cu, int reps, void *stream,
                    float *gbps_out);
+
+/* The host part of the JPEG decoder (plain C++, no device work): the entry point of every chunk of a baseline scan.
+ * file / len: the whole file (HOST memory); blob: jpeg.table_blob (host); layout int32 [12] = {byte offset of the scan, n_mcu, ny,
+ * restart interval, chunk_mcus, DC table id x 3, AC table id x 3, C}; out: bit_offsets int32 [C + 1] (bit offsets into the stuffed
+ * scan; the last is the EOI marker's) and dc_pred int16 [C][3].  Where every chunk is a whole restart interval the entries come
+ * from a byte search for the markers; otherwise from one walk over the Huffman symbols (code lengths and DC values only), which
+ * also validates the scan end to end.  Returns 0, or: -1 arguments, -2 invalid code, -3 coefficient index past 63, -4 the bits run
+ * out, -5 markers or MCU count do not match the frame.  Never reads outside [file, file + len). */
+int l2d_jpeg_index(const uint8_t *file, int64_t len, const uint8_t *blob, const int32_t *layout, int32_t *bit_offsets, int16_t *dc_pred);
+/* The lanes of L2D_OP_JPEG_ENTROPY_DEC run one after the other on the HOST: `op` is the record the kernel would be launched with,
+ * every pointer in it a host pointer.  The kernel's lane body is a host-and-device function, so this is the same code: the model
+ * the CPU test-suite checks the kernel's loop bounds, its writes and its status word with, on machines without a device. */
+int l2d_jpeg_entropy_model(const l2d_op *op);
 
 #ifdef __cplusplus
 }

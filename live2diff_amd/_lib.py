@@ -24,6 +24,7 @@ OP_CLIP_EMBED, OP_CLIP_ATTN, OP_CLIP_LINEAR, OP_CLIP_LN = 28, 29, 30, 31
 OP_VAE_ATTN, OP_VAE_POSTERIOR = 32, 33
 OP_FRAME_INGEST, OP_FRAME_EGRESS = 34, 35
 OP_JPEG_DCT, OP_JPEG_HUFF, OP_JPEG_PACK = 36, 37, 38
+OP_JPEG_ENTROPY_DEC, OP_JPEG_IDCT, OP_JPEG_RGB = 39, 40, 41
 ABI_VERSION = 6
 
 
@@ -64,6 +65,8 @@ def _load():
                                    ctypes.POINTER(ctypes.c_float)]
     lib.l2d_read_bench.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                    ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
+    lib.l2d_jpeg_index.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.l2d_jpeg_entropy_model.argtypes = [ctypes.POINTER(L2dOp)]
     if lib.l2d_abi_version() != ABI_VERSION:
         raise L2DError(f"libl2d_hip.so ABI {lib.l2d_abi_version()} != binding ABI {ABI_VERSION}: rebuild")
     return lib

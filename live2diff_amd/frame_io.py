@@ -118,6 +118,8 @@ class HipFrameIO:
         self._turn = 0
         self._egress = {}                  # B -> (device uint8, pinned uint8)
         self.last_view = None              # what the last single-frame ingest returned (for release())
+        self._device_plans = {}            # (source pointer, slot) -> plan: device frames out of static buffers (jpeg_io.HipJpegDecoder)
+        self._device_seen = ()             # the last four source pointers of device frames (integers: nothing is kept alive)
 
     # ------------------------------------------------------------------ ingest
     def _plan_source(self, Hs: int, Ws: int):
@@ -128,6 +130,7 @@ class HipFrameIO:
         self._src = (Hs, Ws)
         self._slots = [_Slot(Hs, Ws, self.height, self.width, self.device) for _ in range(2)]
         self._turn = 0
+        self._device_plans.clear()
 
     def _ingest_op(self, src, dst, B):
         (Hs, Ws), (nh, nw, top, left) = self._src, self._geo
@@ -173,7 +176,19 @@ class HipFrameIO:
         if src is slot.dev_u8:
             plan = slot.plan = slot.plan or self._ingest_op(src, slot.out, 1)
         else:
-            plan = self._ingest_op(src, slot.out, 1)     # a caller's device frame: a new pointer every time, one record to fill
+            # a caller's device frame.  A producer with static outputs (the JPEG decoder's two slots) meets its plan again: a source
+            # pointer seen before gets its plan kept, at most four (two sources x two ingest slots; a kept plan keeps its source
+            # alive, so its pointer cannot become another tensor's).  A pointer seen for the first time fills one record, as before.
+            ptr = src.data_ptr()
+            key = (ptr, self._turn)
+            plan = self._device_plans.get(key)
+            if plan is None:
+                plan = self._ingest_op(src, slot.out, 1)
+                if ptr in self._device_seen:
+                    if len(self._device_plans) >= 4:
+                        self._device_plans.clear()
+                    self._device_plans[key] = plan
+                self._device_seen = (self._device_seen + (ptr,))[-4:]
         plan.run()
         self.last_view = slot.out
         return slot.out

@@ -292,3 +292,435 @@ def encode_ref(u8: np.ndarray, quality: int = 75) -> bytes:
     u8 = np.asarray(u8)
     coef = coefficients(u8, quality)
     return header(u8.shape[0], u8.shape[1], quality) + encode_scan(coef, quality)
+
+
+# ============================================================================= the decoder (csrc/jpeg_dec.hip)
+# What arrives: the reference's demo receives every frame as a JPEG blob from the browser (demo/app.py:81-85, demo/util.py:22), a
+# UVC camera delivers MJPEG.  `parse` reads the subset the device decodes (baseline, 8-bit, three components, 4:4:4 / 4:2:2 / 4:2:0,
+# any Huffman tables, with or without restart markers), the `*_ref` functions restate libjpeg's decoder in numpy: integer arithmetic
+# throughout, `decode_ref` is byte for byte what Pillow returns (tests/test_jpeg_dec_cpu.py).
+class JpegUnsupported(ValueError):
+    """a valid JPEG file outside the subset the device decodes (the wrapper hands it to Pillow on the host)"""
+
+
+class JpegInfo(NamedTuple):
+    height: int
+    width: int
+    hs: int                    # luminance sampling factors: (1, 1) 4:4:4, (2, 1) 4:2:2, (2, 2) 4:2:0; chrominance is 1 x 1
+    vs: int
+    quant: np.ndarray          # int32 [3][64], natural order, per component
+    huffman: tuple             # 4 x (BITS tuple [16], values bytes) or None, slot = class * 2 + id: DC0 DC1 AC0 AC1
+    dc_tab: tuple              # DC / AC table id of each component
+    ac_tab: tuple
+    restart_interval: int      # MCUs, 0 = none
+    scan_offset: int           # byte offset of the entropy-coded data
+    scan_end: int              # byte offset of the EOI marker
+
+    @property
+    def mcus_x(self) -> int:
+        return -(-self.width // (8 * self.hs))
+
+    @property
+    def mcus_y(self) -> int:
+        return -(-self.height // (8 * self.vs))
+
+    @property
+    def n_mcu(self) -> int:
+        return self.mcus_x * self.mcus_y
+
+    @property
+    def blocks_per_mcu(self) -> int:
+        return self.hs * self.vs + 2
+
+    @property
+    def chroma_size(self):
+        """(rows, columns) of the real samples of a chrominance plane"""
+        return -(-self.height // self.vs), -(-self.width // self.hs)
+
+
+_SOF_NAMES = {0xC1: "extended sequential", 0xC2: "progressive", 0xC3: "lossless", 0xC5: "differential sequential",
+              0xC6: "differential progressive", 0xC7: "differential lossless", 0xC9: "arithmetic-coded sequential",
+              0xCA: "arithmetic-coded progressive", 0xCB: "arithmetic-coded lossless", 0xCD: "arithmetic-coded differential sequential",
+              0xCE: "arithmetic-coded differential progressive", 0xCF: "arithmetic-coded differential lossless"}
+
+
+def parse(data) -> JpegInfo:
+    """The headers of a baseline file: SOI, skipped APPn / COM, DQT, SOF0, DHT, DRI, one interleaved SOS, and the EOI behind the scan.
+    `JpegUnsupported` names what the device does not decode; structural damage is a plain ValueError."""
+    d = bytes(data)
+    n = len(d)
+    if n < 4 or d[0] != 0xFF or d[1] != 0xD8:
+        raise ValueError("jpeg: the data does not begin with SOI (FF D8)")
+    quant, huff = {}, [None] * 4
+    sof = sos = adobe = None
+    ri = 0
+    i = 2
+    while True:
+        if i + 2 > n:
+            raise ValueError("jpeg: the headers end before a start of scan")
+        if d[i] != 0xFF:
+            raise ValueError(f"jpeg: byte {i} is 0x{d[i]:02x} where a marker was expected")
+        while d[i + 1] == 0xFF:                                   # fill bytes
+            i += 1
+            if i + 2 > n:
+                raise ValueError("jpeg: the headers end inside fill bytes")
+        m = d[i + 1]
+        i += 2
+        if m == 0x01 or 0xD0 <= m <= 0xD7:
+            continue
+        if m == 0xD9:
+            raise ValueError("jpeg: EOI before any scan")
+        if i + 2 > n:
+            raise ValueError(f"jpeg: segment FF {m:02X} has no length")
+        L = (d[i] << 8) | d[i + 1]
+        if L < 2 or i + L > n:
+            raise ValueError(f"jpeg: segment FF {m:02X} at byte {i - 2} runs past the file ({L} bytes, {n - i} left)")
+        seg = d[i + 2:i + L]
+        i += L
+        if m == 0xC0:
+            if sof is not None:
+                raise ValueError("jpeg: two frame headers")
+            if len(seg) < 6 or len(seg) != 6 + 3 * seg[5]:
+                raise ValueError("jpeg: SOF0 has the wrong length")
+            if seg[0] != 8:
+                raise JpegUnsupported(f"jpeg: {seg[0]}-bit samples")
+            H, W, nf = (seg[1] << 8) | seg[2], (seg[3] << 8) | seg[4], seg[5]
+            if nf != 3:
+                raise JpegUnsupported(f"jpeg: {nf} component(s) ({'greyscale' if nf == 1 else 'CMYK / YCCK' if nf == 4 else 'not Y Cb Cr'})")
+            if H == 0 or W == 0:
+                raise JpegUnsupported("jpeg: a dimension of 0 (height given by a DNL segment)")
+            sof = (H, W, [(seg[6 + 3 * c], seg[7 + 3 * c] >> 4, seg[7 + 3 * c] & 15, seg[8 + 3 * c]) for c in range(3)])
+        elif m in _SOF_NAMES:
+            raise JpegUnsupported(f"jpeg: {_SOF_NAMES[m]} coding (SOF{m - 0xC0})")
+        elif m == 0xCC:
+            raise JpegUnsupported("jpeg: arithmetic coding (DAC segment)")
+        elif m == 0xDB:
+            k = 0
+            while k < len(seg):
+                pq, tq = seg[k] >> 4, seg[k] & 15
+                if pq != 0:
+                    raise JpegUnsupported("jpeg: a 16-bit quantisation table")
+                if tq > 3 or k + 65 > len(seg):
+                    raise ValueError("jpeg: damaged DQT segment")
+                t = np.zeros(64, np.int32)
+                t[ZIGZAG] = np.frombuffer(seg, np.uint8, 64, k + 1)
+                quant[tq] = t
+                k += 65
+        elif m == 0xC4:
+            k = 0
+            while k < len(seg):
+                if k + 17 > len(seg):
+                    raise ValueError("jpeg: damaged DHT segment")
+                tc, th = seg[k] >> 4, seg[k] & 15
+                bits = tuple(seg[k + 1:k + 17])
+                cnt = sum(bits)
+                if tc > 1 or th > 3 or cnt > 256 or k + 17 + cnt > len(seg):
+                    raise ValueError("jpeg: damaged DHT segment")
+                if th > 1:
+                    raise JpegUnsupported(f"jpeg: Huffman table id {th} (baseline has 0 and 1)")
+                vals = seg[k + 17:k + 17 + cnt]
+                code = 0
+                for length in range(16):
+                    code = (code + bits[length]) << 1
+                    if code > (2 << (length + 1)):
+                        raise ValueError("jpeg: a DHT segment holds more codes than a prefix code has")
+                if tc == 0 and any(v > 11 for v in vals):
+                    raise ValueError("jpeg: a DC table names a size category above 11")
+                huff[tc * 2 + th] = (bits, vals)
+                k += 17 + cnt
+        elif m == 0xDD:
+            if len(seg) != 2:
+                raise ValueError("jpeg: damaged DRI segment")
+            ri = (seg[0] << 8) | seg[1]
+        elif m == 0xEE:
+            if seg[:5] == b"Adobe" and len(seg) >= 12:
+                adobe = seg[11]
+        elif m == 0xDA:
+            if sof is None:
+                raise ValueError("jpeg: a scan before the frame header")
+            if len(seg) < 1 or len(seg) != 4 + 2 * seg[0]:
+                raise ValueError("jpeg: SOS has the wrong length")
+            if seg[0] != 3:
+                raise JpegUnsupported(f"jpeg: a scan of {seg[0]} component(s) (non-interleaved)")
+            if [seg[1 + 2 * c] for c in range(3)] != [c[0] for c in sof[2]]:
+                raise JpegUnsupported("jpeg: the scan lists the components in another order than the frame")
+            if tuple(seg[7:10]) != (0, 63, 0):
+                raise ValueError("jpeg: a baseline scan has Ss = 0, Se = 63, Ah = Al = 0")
+            sos = [(seg[2 + 2 * c] >> 4, seg[2 + 2 * c] & 15) for c in range(3)]
+            break
+    H, W, comps = sof
+    if adobe == 0:
+        raise JpegUnsupported("jpeg: Adobe APP14 segment with transform 0 (the three components are R G B, not Y Cb Cr)")
+    (_, hs, vs, _), c1, c2 = comps
+    if (c1[1], c1[2], c2[1], c2[2]) != (1, 1, 1, 1) or (hs, vs) not in ((1, 1), (2, 1), (2, 2)):
+        raise JpegUnsupported("jpeg: sampling factors " + ", ".join(f"{c[1]}x{c[2]}" for c in comps) + " (4:4:4, 4:2:2 and 4:2:0 are decoded)")
+    for c in range(3):
+        if comps[c][3] not in quant:
+            raise ValueError(f"jpeg: quantisation table {comps[c][3]} is missing")
+        td, ta = sos[c]
+        if td > 1 or ta > 1 or huff[td] is None or huff[2 + ta] is None:
+            raise ValueError(f"jpeg: Huffman table DC {td} or AC {ta} is missing")
+    end = d.rfind(b"\xff\xd9", i)
+    if end < 0:
+        raise ValueError("jpeg: no EOI behind the scan")
+    return JpegInfo(H, W, hs, vs, np.stack([quant[c[3]] for c in comps]), tuple(huff), tuple(s[0] for s in sos),
+                    tuple(s[1] for s in sos), ri, i, end)
+
+
+def _block_component(info: JpegInfo):
+    """component of every block of an MCU, in scan order"""
+    return [0] * (info.hs * info.vs) + [1, 2]
+
+
+def _decode_table(bits, vals):
+    """uint32 [65536]: `length << 8 | symbol` of the code the next 16 bits begin with, 0 where no code matches"""
+    out = np.zeros(65536, np.uint32)
+    code, k = 0, 0
+    for length in range(1, 17):
+        for _ in range(bits[length - 1]):
+            lo = code << (16 - length)
+            out[lo:lo + (1 << (16 - length))] = (length << 8) | vals[k]
+            code, k = code + 1, k + 1
+        code <<= 1
+    return out
+
+
+class _Walk(NamedTuple):
+    entry: np.ndarray          # int64 [n_mcu + 1]: bit offset of every MCU in the stuffed scan; [n_mcu] = 8 x the byte offset of the EOI
+    pred: np.ndarray           # int16 [n_mcu][3]: the DC predictors in force in front of every MCU
+    coef: np.ndarray           # int16 [n_mcu][blocks][64], absolute DC, natural order
+
+
+@functools.lru_cache(maxsize=8)
+def _walk_cached(d: bytes) -> _Walk:
+    info = parse(d)
+    scan = np.frombuffer(d, np.uint8, info.scan_end - info.scan_offset, info.scan_offset)
+    # markers inside the scan: an FF followed by anything but a stuffed 00 or a further FF (fill bytes in front of a marker)
+    ff = np.nonzero((scan[:-1] == 0xFF) & (scan[1:] != 0) & (scan[1:] != 0xFF))[0] if len(scan) > 1 else np.zeros(0, np.int64)
+    n_mcu, ri = info.n_mcu, info.restart_interval
+    n_int = -(-n_mcu // ri) if ri else 1
+    if len(ff) != n_int - 1 or any(scan[p + 1] != 0xD0 + (j & 7) for j, p in enumerate(ff)):
+        raise ValueError(f"jpeg: the scan holds {len(ff)} markers where {n_int - 1} restart markers in sequence were expected")
+    bounds = [0] + [int(p) + 2 for p in ff], [int(p) for p in ff] + [len(scan)]
+    tabs = [_decode_table(*t) if t is not None else None for t in info.huffman]
+    comp = _block_component(info)
+    entry = np.zeros(n_mcu + 1, np.int64)
+    pred_at = np.zeros((n_mcu, 3), np.int16)
+    coef = np.zeros((n_mcu, len(comp), 64), np.int16)
+    zz = [int(v) for v in ZIGZAG]
+    mcu = 0
+    for lo, hi in zip(*bounds):
+        while hi > lo and scan[hi - 1] == 0xFF:                       # fill bytes belong to the marker, not to the data
+            hi -= 1
+        raw = scan[lo:hi]
+        drop = np.nonzero((raw[:-1] == 0xFF) & (raw[1:] == 0))[0] + 1 if len(raw) > 1 else np.zeros(0, np.int64)
+        keep = np.ones(len(raw), bool)
+        keep[drop] = False
+        where = np.concatenate([np.nonzero(keep)[0] + lo, [hi]])        # raw byte of every unstuffed byte; behind the last: the marker
+        u = raw[keep].tobytes() + b"\0\0\0\0"
+        nbits = 8 * (len(u) - 4)
+        p = 0
+
+        def take(nb):
+            nonlocal p
+            w = int.from_bytes(u[p >> 3:(p >> 3) + 4], "big")
+            v = (w >> (32 - nb - (p & 7))) & ((1 << nb) - 1)
+            p += nb
+            return v
+
+        def symbol(tab):
+            nonlocal p
+            e = int(tab[take(16)])
+            if e == 0:
+                raise ValueError(f"jpeg: invalid Huffman code in MCU {mcu}")
+            p -= 16 - (e >> 8)
+            return e & 255
+
+        pred = [0, 0, 0]
+        count = min(ri, n_mcu - mcu) if ri else n_mcu
+        for _ in range(count):
+            entry[mcu] = int(where[p >> 3]) * 8 + (p & 7)
+            pred_at[mcu] = pred
+            for j, c in enumerate(comp):
+                s = symbol(tabs[info.dc_tab[c]])
+                v = take(s) if s else 0
+                if s and v < (1 << (s - 1)):
+                    v -= (1 << s) - 1
+                pred[c] += v
+                if not -32768 <= pred[c] <= 32767:
+                    raise ValueError(f"jpeg: DC value out of range in MCU {mcu}")
+                coef[mcu, j, 0] = pred[c]
+                k = 1
+                ac = tabs[2 + info.ac_tab[c]]
+                while k < 64:
+                    rs = symbol(ac)
+                    r, s = rs >> 4, rs & 15
+                    if s == 0:
+                        if r != 15:
+                            break
+                        k += 16                                   # (a run that reaches the end ends the block, as in libjpeg)
+                        continue
+                    k += r
+                    if k > 63:
+                        raise ValueError(f"jpeg: coefficient index past 63 in MCU {mcu}")
+                    v = take(s)
+                    if v < (1 << (s - 1)):
+                        v -= (1 << s) - 1
+                    coef[mcu, j, zz[k]] = v
+                    k += 1
+                if p > nbits:
+                    raise ValueError(f"jpeg: the bits run out in MCU {mcu}")
+            mcu += 1
+        if nbits - p >= 8:
+            raise ValueError(f"jpeg: {nbits - p} bits are left behind MCU {mcu - 1}")
+    if mcu != n_mcu:
+        raise ValueError(f"jpeg: the scan holds {mcu} MCUs, the frame {n_mcu}")
+    entry[n_mcu] = info.scan_end * 8 - info.scan_offset * 8
+    for a in (entry, pred_at, coef):
+        a.setflags(write=False)
+    return _Walk(entry, pred_at, coef)
+
+
+def chunk_layout(n_mcu: int, restart_interval: int, chunk_mcus: int):
+    """(interval, chunk, chunks per interval, chunks): a chunk is `chunk` consecutive MCUs in raster order and never spans a restart
+    marker -- chunks are counted from the start of every restart interval (without markers the scan is one interval), so a restart
+    interval of at most `chunk_mcus` MCUs is a chunk itself.  Chunk c starts at MCU (c // per) * interval + (c % per) * chunk."""
+    if chunk_mcus < 1:
+        raise ValueError(f"jpeg: chunk_mcus={chunk_mcus!r} must be at least 1")
+    interval = restart_interval if 0 < restart_interval < n_mcu else n_mcu
+    chunk = min(int(chunk_mcus), interval)
+    per = -(-interval // chunk)
+    full = (n_mcu - 1) // interval
+    return interval, chunk, per, full * per + -(-(n_mcu - full * interval) // chunk)
+
+
+def index_ref(info: JpegInfo, data, chunk_mcus: int):
+    """(bit_offsets int32 [C + 1], dc_pred int16 [C][3]): where every chunk (`chunk_layout`) begins, as a bit offset into the raw,
+    still byte-stuffed scan (a position at a byte boundary behind an FF 00 pair counts behind the 00), and the three DC predictors
+    in force there.  Behind a restart marker the offset is byte-aligned behind the RSTn and the predictors are 0.  The last offset
+    is the EOI marker's."""
+    w = _walk_cached(bytes(data))
+    interval, chunk, per, C = chunk_layout(info.n_mcu, info.restart_interval, chunk_mcus)
+    first = np.array([(c // per) * interval + (c % per) * chunk for c in range(C)], np.int64)
+    return np.concatenate([w.entry[first], w.entry[-1:]]).astype(np.int32), w.pred[first].copy()
+
+
+def decode_coefficients_ref(data) -> np.ndarray:
+    """int16 [n_mcu][blocks per MCU][64]: the quantised coefficients, DC absolute, natural (de-zigzagged) order"""
+    return _walk_cached(bytes(data)).coef
+
+
+def _idct_pass(d, shift: int):
+    """one pass of jidctint.c along the last axis, int32 arithmetic"""
+    i0, i1, i2, i3, i4, i5, i6, i7 = (d[..., i] for i in range(8))
+    z1 = (i2 + i6) * 4433
+    t2, t3 = z1 + i6 * -15137, z1 + i2 * 6270
+    t0, t1 = (i0 + i4) << 13, (i0 - i4) << 13
+    t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+    t0, t1, t2, t3 = i7, i5, i3, i1
+    z1, z2, z3, z4 = t0 + t3, t1 + t2, t0 + t2, t1 + t3
+    z5 = (z3 + z4) * 9633
+    t0, t1, t2, t3 = t0 * 2446, t1 * 16819, t2 * 25172, t3 * 12299
+    z1, z2, z3, z4 = z1 * -7373, z2 * -20995, z3 * -16069 + z5, z4 * -3196 + z5
+    t0, t1, t2, t3 = t0 + z1 + z3, t1 + z2 + z4, t2 + z2 + z3, t3 + z1 + z4
+    o = (t10 + t3, t11 + t2, t12 + t1, t13 + t0, t13 - t0, t12 - t1, t11 - t2, t10 - t3)
+    return np.stack([(v + (1 << (shift - 1))) >> shift for v in o], -1)
+
+
+def idct_ref(blocks: np.ndarray) -> np.ndarray:
+    """dequantised coefficients int [..., 64] (natural order) -> uint8 [..., 8, 8]: libjpeg's accurate integer IDCT (jidctint.c:
+    13 constant bits, 2 extra bits kept after the column pass), `clamp(x + 128, 0, 255)` as its range limit.  int32 arithmetic that
+    wraps, as the kernel's: |dequantised| <= 1024 cannot pass 2^31 anywhere, only a damaged file holds more."""
+    b = np.asarray(blocks).astype(np.int32).reshape(blocks.shape[:-1] + (8, 8))
+    ws = np.swapaxes(_idct_pass(np.swapaxes(b, -1, -2), 11), -1, -2)              # columns first
+    return (np.clip(_idct_pass(ws, 18), -128, 127) + 128).astype(np.uint8)
+
+
+def planes_ref(coef: np.ndarray, info: JpegInfo):
+    """coefficients [n_mcu][blocks][64] -> the three uint8 component planes at their padded sizes (what L2D_OP_JPEG_IDCT writes)"""
+    my, mx, hs, vs = info.mcus_y, info.mcus_x, info.hs, info.vs
+    c = coef.astype(np.int32)
+    ny = hs * vs
+    y = idct_ref(c[:, :ny] * info.quant[0]).reshape(my, mx, vs, hs, 8, 8).transpose(0, 2, 4, 1, 3, 5).reshape(my * vs * 8, mx * hs * 8)
+    out = [y]
+    for k in (1, 2):
+        out.append(idct_ref(c[:, ny + k - 1] * info.quant[k]).reshape(my, mx, 8, 8).transpose(0, 2, 1, 3).reshape(my * 8, mx * 8))
+    return out
+
+
+def upsample_ref(plane: np.ndarray, hs: int, vs: int, rows: int, cols: int) -> np.ndarray:
+    """a chrominance plane with `rows` x `cols` real samples -> [rows * vs][cols * hs]: libjpeg's "fancy" triangle filters
+    (jdsample.c).  h2v1: `(3 a + b + 1) >> 2` in even, `(3 a + b + 2) >> 2` in odd columns, the first and the last column copied.
+    h2v2: `3 near + far` vertically (the row above row 0 is row 0, the row below the last REAL row is that row), then
+    `(3 this + last + 8) >> 4` / `(3 this + next + 7) >> 4`, at the ends `(4 this + 8) >> 4` / `(4 this + 7) >> 4`.  A plane of
+    one or two columns is replicated instead, as libjpeg does."""
+    p = np.asarray(plane)[:rows, :cols].astype(np.int32)
+    if hs == 1 and vs == 1:
+        return p.astype(np.uint8)
+    if cols <= 2:
+        return np.repeat(np.repeat(p, vs, 0), hs, 1).astype(np.uint8)
+    if vs == 1:
+        last, nxt = np.concatenate([p[:, :1], p[:, :-1]], 1), np.concatenate([p[:, 1:], p[:, -1:]], 1)
+        even, odd = (3 * p + last + 1) >> 2, (3 * p + nxt + 2) >> 2
+        even[:, 0], odd[:, -1] = p[:, 0], p[:, -1]
+        return np.stack([even, odd], -1).reshape(rows, 2 * cols).astype(np.uint8)
+    up, down = np.concatenate([p[:1], p[:-1]], 0), np.concatenate([p[1:], p[-1:]], 0)
+    s = np.stack([3 * p + up, 3 * p + down], 1).reshape(2 * rows, cols)           # column sums of output rows 2 r, 2 r + 1
+    last, nxt = np.concatenate([s[:, :1], s[:, :-1]], 1), np.concatenate([s[:, 1:], s[:, -1:]], 1)
+    even, odd = (3 * s + last + 8) >> 4, (3 * s + nxt + 7) >> 4
+    return np.stack([even, odd], -1).reshape(2 * rows, 2 * cols).astype(np.uint8)
+
+
+def ycc_to_rgb_ref(y, cb, cr) -> np.ndarray:
+    """three uint8 planes -> uint8 [H][W][3] with libjpeg's 16-bit fixed-point tables (jdcolor.c)"""
+    y, cb, cr = (np.asarray(a).astype(np.int32) for a in (y, cb, cr))
+    cb, cr = cb - 128, cr - 128
+    r = y + ((91881 * cr + 32768) >> 16)
+    g = y + ((-22554 * cb - 46802 * cr + 32768) >> 16)
+    b = y + ((116130 * cb + 32768) >> 16)
+    return np.clip(np.stack([r, g, b], -1), 0, 255).astype(np.uint8)
+
+
+def decode_ref(data) -> np.ndarray:
+    """the file -> uint8 [H][W][3], byte for byte `np.asarray(Image.open(BytesIO(data)).convert("RGB"))`"""
+    d = bytes(data)
+    info = parse(d)
+    y, cb, cr = planes_ref(decode_coefficients_ref(d), info)
+    rows, cols = info.chroma_size
+    H, W = info.height, info.width
+    cb, cr = (upsample_ref(p, info.hs, info.vs, rows, cols)[:H, :W] for p in (cb, cr))
+    return ycc_to_rgb_ref(y[:H, :W], cb, cr)
+
+
+# ----------------------------------------------------------------------------- what the device side uploads
+DEC_LOOK_BITS = 8
+DEC_TABLE_BYTES = 2 * 256 + 4 * 18 + 4 * 18 + 256         # lookahead uint16 [256], maxcode int32 [18], valoffset int32 [18], values [256]
+DEC_QUANT_OFF = 4 * DEC_TABLE_BYTES
+DEC_BLOB_BYTES = DEC_QUANT_OFF + 3 * 64 * 2               # + the quantisation tables, uint16 [3][64], natural order
+
+
+@functools.lru_cache(maxsize=16)
+def _huffman_blob(bits, vals) -> bytes:
+    look = np.zeros(256, np.uint16)
+    maxcode = np.full(18, -1, np.int32)
+    valoff = np.zeros(18, np.int32)
+    code, k = 0, 0
+    for length in range(1, 17):
+        if bits[length - 1]:
+            valoff[length] = k - code
+            if length <= DEC_LOOK_BITS:
+                sym = np.frombuffer(vals, np.uint8, bits[length - 1], k).astype(np.uint16)
+                lo = code << (DEC_LOOK_BITS - length)
+                n = 1 << (DEC_LOOK_BITS - length)
+                look[lo:lo + n * len(sym)] = np.repeat((length << 8) | sym, n)
+            code, k = code + bits[length - 1], k + bits[length - 1]
+            maxcode[length] = code - 1
+        code <<= 1
+    return look.tobytes() + maxcode.tobytes() + valoff.tobytes() + bytes(vals) + bytes(256 - len(vals))
+
+
+def table_blob(info: JpegInfo) -> np.ndarray:
+    """uint8 [DEC_BLOB_BYTES]: per Huffman table slot (DC0 DC1 AC0 AC1) the 8-bit lookahead table (`length << 8 | symbol`, 0 = longer
+    than 8 bits), libjpeg's maxcode / valoffset arrays for the longer codes and the values; then the quantisation tables"""
+    parts = [_huffman_blob(*t) if t is not None else bytes(DEC_TABLE_BYTES) for t in info.huffman]
+    return np.frombuffer(b"".join(parts) + info.quant.astype(np.uint16).tobytes(), np.uint8)

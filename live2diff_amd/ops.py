@@ -8,6 +8,7 @@ import json
 import os
 from typing import NamedTuple, Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1393,3 +1394,62 @@ def jpeg_pack(staging, lengths, header, out, *, B, H, row_stride, out_stride):
         op.i[j] = int(v)
     op.l[0] = int(out_stride)
     return op, (staging, lengths, header, out)
+
+
+# ----------------------------------------------------------------------------- baseline JPEG decoder (jpeg_dec.hip, jpeg.py)
+def jpeg_index(info, data, chunk_mcus, blob=None, offsets=None, dc_pred=None):
+    """l2d_jpeg_index (host): (bit_offsets int32 [C + 1], dc_pred int16 [C][3]) of `jpeg.index_ref`, written into the given numpy
+    arrays when there are any (the decoder's pinned staging buffer).  A damaged scan raises ValueError."""
+    from . import jpeg
+    C = jpeg.chunk_layout(info.n_mcu, info.restart_interval, chunk_mcus)[3]
+    blob = jpeg.table_blob(info) if blob is None else blob
+    offsets = np.empty(C + 1, np.int32) if offsets is None else offsets
+    dc_pred = np.empty((C, 3), np.int16) if dc_pred is None else dc_pred
+    assert offsets.dtype == np.int32 and offsets.size == C + 1 and dc_pred.dtype == np.int16 and dc_pred.size == 3 * C
+    assert offsets.flags.c_contiguous and dc_pred.flags.c_contiguous and blob.dtype == np.uint8 and blob.size == jpeg.DEC_BLOB_BYTES
+    file = data if isinstance(data, np.ndarray) else np.frombuffer(data, np.uint8)
+    lay = np.array([info.scan_offset, info.n_mcu, info.hs * info.vs, info.restart_interval, chunk_mcus, *info.dc_tab, *info.ac_tab, C], np.int32)
+    rc = _lib.lib.l2d_jpeg_index(file.ctypes.data, file.size, blob.ctypes.data, lay.ctypes.data, offsets.ctypes.data, dc_pred.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"jpeg: the scan is damaged: {_lib.lib.l2d_last_error().decode(errors='replace')}")
+    return offsets, dc_pred
+
+
+def jpeg_entropy_dec(file, offsets, dc_pred, blob, params, coef, status, *, n_mcu, ny, restart_interval, chunk_mcus, C, dc_tab, ac_tab):
+    """the stuffed scan -> int16 [n_mcu][ny + 2][64] coefficients (jpeg.decode_coefficients_ref), one lane per chunk"""
+    assert file.dtype == blob.dtype == torch.uint8 and offsets.dtype == params.dtype == status.dtype == torch.int32
+    assert dc_pred.dtype == coef.dtype == torch.int16
+    assert offsets.numel() >= C + 1 and dc_pred.numel() >= 3 * C and blob.numel() >= 3648 and params.numel() >= 2
+    assert coef.numel() >= n_mcu * (ny + 2) * 64
+    op = L2dOp()
+    op.kind = _lib.OP_JPEG_ENTROPY_DEC
+    keep = (file, offsets, dc_pred, blob, params, coef, status)
+    for j, t in enumerate(keep):
+        op.p[j] = _ptr(t)
+    for j, v in enumerate([n_mcu, ny, restart_interval, chunk_mcus, C, file.numel(), *dc_tab, *ac_tab]):
+        op.i[j] = int(v)
+    return op, keep
+
+
+def jpeg_idct(coef, quant, planes, *, n_mcu, mcus_x, hs, vs):
+    """coefficients -> the three uint8 component planes at their padded sizes (jpeg.planes_ref); `quant` uint16 [3][64] as bytes"""
+    assert coef.dtype == torch.int16 and planes.dtype == torch.uint8 and quant.numel() * quant.element_size() >= 384
+    assert coef.numel() >= n_mcu * (hs * vs + 2) * 64 and planes.numel() >= n_mcu * (hs * vs + 2) * 64
+    op = L2dOp()
+    op.kind = _lib.OP_JPEG_IDCT
+    op.p[0], op.p[1], op.p[2] = _ptr(coef), _ptr(quant), _ptr(planes)
+    for j, v in enumerate([n_mcu, mcus_x, hs, vs]):
+        op.i[j] = int(v)
+    return op, (coef, quant, planes)
+
+
+def jpeg_rgb(planes, out, *, H, W, hs, vs):
+    """component planes -> uint8 [H][W][3]: fancy up-sampling and colour conversion (jpeg.upsample_ref, jpeg.ycc_to_rgb_ref)"""
+    assert planes.dtype == out.dtype == torch.uint8 and out.numel() >= H * W * 3
+    assert planes.numel() >= (-(-W // (8 * hs))) * (-(-H // (8 * vs))) * (hs * vs + 2) * 64
+    op = L2dOp()
+    op.kind = _lib.OP_JPEG_RGB
+    op.p[0], op.p[1] = _ptr(planes), _ptr(out)
+    for j, v in enumerate([H, W, hs, vs]):
+        op.i[j] = int(v)
+    return op, (planes, out)

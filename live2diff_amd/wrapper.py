@@ -12,7 +12,9 @@ transformers.
 Differences from the reference, all on purpose: nothing is fetched from a hub (`few_step_lora_path` / `taesd_path` are config
 keys), a missing file raises FileNotFoundError naming its config key (the reference prints a traceback and exits), keywords the
 backend cannot honour raise ValueError at construction, `"u8"` is a fifth output type and `"jpeg"` (with `jpeg_quality`) a sixth:
-the frame leaves the device as the JPEG file the reference's demo makes of it on the host (jpeg_io.HipJpegEncoder).
+the frame leaves the device as the JPEG file the reference's demo makes of it on the host (jpeg_io.HipJpegEncoder).  A frame may
+also ARRIVE as a JPEG file (`bytes`, what the reference's demo receives from the browser, demo/util.py:22): it is decoded on the
+device (jpeg_io.HipJpegDecoder) and ingested there like a uint8 frame (`jpeg_decode="host"` decodes with Pillow instead).
 """
 import os
 from pathlib import Path
@@ -210,8 +212,16 @@ def load_components(cfg: dict, *, height: int, width: int, denoising_steps_num: 
                            scheduler=SimpleNamespace(config=dict(cfg.get("noise_scheduler_kwargs") or {})))
 
 
+def _is_jpeg(x) -> bool:
+    return isinstance(x, (bytes, bytearray, memoryview)) and bytes(x[:2]) == b"\xff\xd8"
+
+
 # ----------------------------------------------------------------------------- the wrapper
 class StreamAnimateDiffusionDepthWrapper:
+    jpeg_decode = "device"                  # where a JPEG input frame is decoded ("device" | "host"); `_setup` sets the instance's
+    jpeg_dec = None                         # jpeg_io.HipJpegDecoder, made by the first JPEG input frame on the device
+    jpeg_host_decodes = 0                   # JPEG input frames Pillow decoded on the host (no device, "host", or an unsupported file)
+
     def __init__(self, config_path: str, few_step_model_type: str, num_inference_steps: int,
                  t_index_list: Optional[List[int]] = None, strength: Optional[float] = None,
                  dreambooth_path: Optional[str] = None, lora_dict: Optional[Dict[str, float]] = None, output_type: str = "pil",
@@ -221,10 +231,10 @@ class StreamAnimateDiffusionDepthWrapper:
                  similar_image_filter_threshold: float = 0.98, similar_image_filter_max_skip_frame: int = 10,
                  use_denoising_batch: bool = True, cfg_type: str = "none", seed: int = 42,
                  engine_dir: Optional[Union[str, Path]] = "engines", opt_unet: bool = False, frame_pipelining: bool = False,
-                 jpeg_quality: int = 75):
+                 jpeg_quality: int = 75, jpeg_decode: str = "device"):
         self._check_keywords(few_step_model_type=few_step_model_type, acceleration=acceleration, cfg_type=cfg_type,
                              use_denoising_batch=use_denoising_batch, frame_buffer_size=frame_buffer_size, device_ids=device_ids,
-                             opt_unet=opt_unet, output_type=output_type, dtype=dtype, jpeg_quality=jpeg_quality)
+                             opt_unet=opt_unet, output_type=output_type, dtype=dtype, jpeg_quality=jpeg_quality, jpeg_decode=jpeg_decode)
         cfg = load_config(config_path)
         if t_index_list is None and strength is None:
             t_index_list = cfg.get("t_index_list")
@@ -238,24 +248,26 @@ class StreamAnimateDiffusionDepthWrapper:
                     seed=seed, clip_skip=(cfg.get("third_party_dict") or {}).get("clip_skip", 1), warmup_frames=sink,
                     window_size=window, frame_pipelining=frame_pipelining, enable_similar_image_filter=enable_similar_image_filter,
                     similar_image_filter_threshold=similar_image_filter_threshold,
-                    similar_image_filter_max_skip_frame=similar_image_filter_max_skip_frame, jpeg_quality=jpeg_quality)
+                    similar_image_filter_max_skip_frame=similar_image_filter_max_skip_frame, jpeg_quality=jpeg_quality,
+                    jpeg_decode=jpeg_decode)
 
     @classmethod
     def from_components(cls, pipe, *, num_inference_steps: int, t_index_list: Optional[List[int]] = None,
                         strength: Optional[float] = None, **kw):
         """The wrapper around an already assembled `pipe` namespace (tests, synthetic weights).  Keywords: those of the
-        constructor that do not name files (`jpeg_quality` among them), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
+        constructor that do not name files (`jpeg_quality` and `jpeg_decode` among them), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
         self = cls.__new__(cls)
         cls._check_keywords(**{k: kw.pop(k) for k in ("acceleration", "cfg_type", "use_denoising_batch", "frame_buffer_size",
                                                       "device_ids", "opt_unet", "few_step_model_type") if k in kw},
                             output_type=kw.get("output_type", "pil"), dtype=kw.get("dtype", torch.float16),
-                            jpeg_quality=kw.get("jpeg_quality", 75))
+                            jpeg_quality=kw.get("jpeg_quality", 75), jpeg_decode=kw.get("jpeg_decode", "device"))
         self._setup(pipe, num_inference_steps=num_inference_steps, t_index_list=t_index_list, strength=strength, **kw)
         return self
 
     @staticmethod
     def _check_keywords(few_step_model_type="lcm", acceleration="hip", cfg_type="none", use_denoising_batch=True,
-                        frame_buffer_size=1, device_ids=None, opt_unet=False, output_type="pil", dtype=torch.float16, jpeg_quality=75):
+                        frame_buffer_size=1, device_ids=None, opt_unet=False, output_type="pil", dtype=torch.float16, jpeg_quality=75,
+                        jpeg_decode="device"):
         def no(keyword, value, supported):
             raise ValueError(f"{keyword}={value!r} is not supported by the HIP backend: use {keyword}={supported}")
         if str(few_step_model_type).upper() != "LCM":
@@ -276,17 +288,20 @@ class StreamAnimateDiffusionDepthWrapper:
             no("output_type", output_type, " | ".join(repr(t) for t in OUTPUT_TYPES))
         if isinstance(jpeg_quality, bool) or not isinstance(jpeg_quality, int) or not 1 <= jpeg_quality <= 100:
             raise ValueError(f"jpeg_quality={jpeg_quality!r}: use an integer from 1 to 100")
+        if jpeg_decode not in ("device", "host"):
+            raise ValueError(f"jpeg_decode={jpeg_decode!r}: use 'device' or 'host'")
 
     def _setup(self, pipe, *, num_inference_steps, t_index_list, strength, output_type="pil", device=None, dtype=torch.float16,
                width=512, height=512, do_add_noise=True, seed=42, clip_skip=1, warmup_frames=8, window_size=16,
                scheduler_kwargs=None, frame_pipelining=False, enable_similar_image_filter=False,
-               similar_image_filter_threshold=0.98, similar_image_filter_max_skip_frame=10, jpeg_quality=75):
+               similar_image_filter_threshold=0.98, similar_image_filter_max_skip_frame=10, jpeg_quality=75, jpeg_decode="device"):
         self.sd_turbo = False
         self.device = pipe.device if device is None else device
         self.dtype, self.width, self.height = dtype, width, height
         self.output_type = output_type
         self.jpeg_quality = jpeg_quality
         self.jpeg = None                    # jpeg_io.HipJpegEncoder, made by the first "jpeg" frame on the device
+        self.jpeg_decode = jpeg_decode
         if output_type == "jpeg":
             from . import jpeg
             jpeg._check(height, width, jpeg_quality)       # a size that is no multiple of 16 is refused here, not at the first frame
@@ -312,9 +327,16 @@ class StreamAnimateDiffusionDepthWrapper:
 
     # ------------------------------------------------------------------ prepare
     def prepare(self, warmup_frames, prompt: str, negative_prompt: str = "", guidance_scale: float = 1.2, delta: float = 1.0) -> torch.Tensor:
-        """warmup_frames: float [F,3,H,W] in [0, 1] as in the reference, or uint8 [F,Hs,Ws,3] (one batched ingest launch).
+        """warmup_frames: float [F,3,H,W] in [0, 1] as in the reference, uint8 [F,Hs,Ws,3] (one batched ingest launch), or a list
+        of JPEG files of one size (decoded like `img2img`'s, then the uint8 route).
         Returns the generated warm-up frames, [F,H,W,3] in [0, 1] (wrapper.py:197-199)."""
         kw = dict(prompt=prompt, negative_prompt=negative_prompt, guidance_scale=guidance_scale, delta=delta, seed=self.seed)
+        if isinstance(warmup_frames, (list, tuple)) and warmup_frames and all(_is_jpeg(f) for f in warmup_frames):
+            # (a device frame is a view of one of the decoder's two static slots: it is copied before the slot's next turn)
+            decoded = [d.clone() if torch.is_tensor(d) else torch.from_numpy(d).to(self.io.device) if self.io is not None else d
+                       for d in map(self._decode_jpeg, warmup_frames)]
+            warmup_frames = torch.stack(decoded) if torch.is_tensor(decoded[0]) else np.stack(decoded)
+            self._check_jpeg()
         dt = getattr(warmup_frames, "dtype", None)
         if dt == torch.uint8 or dt == np.uint8:
             from .frame_io import _PassThrough
@@ -344,7 +366,9 @@ class StreamAnimateDiffusionDepthWrapper:
 
     def img2img(self, image, prompt: Optional[str] = None):
         """image: a path, a PIL image (resized to (width, height) on the host like the reference, :264-267), a uint8 HWC array /
-        tensor of any size (resize + centre crop on the device), or a float [3,H,W] tensor in [0, 1] (the reference's input)."""
+        tensor of any size (resize + centre crop on the device), a JPEG file as `bytes` / `bytearray` / `memoryview` (decoded on the
+        device, then treated as that uint8 frame; a damaged scan raises ValueError where the output is fetched), or a float
+        [3,H,W] tensor in [0, 1] (the reference's input)."""
         if prompt is not None:
             self.stream.update_prompt(prompt)
         return self.postprocess_image(self.stream(self.preprocess_image(image)), output_type=self.output_type)
@@ -362,9 +386,35 @@ class StreamAnimateDiffusionDepthWrapper:
     def pop(self):
         return self.postprocess_image(self.stream.pop(), output_type=self.output_type)
 
+    def _decode_jpeg(self, data):
+        """a JPEG file -> its uint8 [Hs,Ws,3] frame: a device tensor (a view of a static slot of `jpeg_io.HipJpegDecoder`), or Pillow's
+        array where there is no device, `jpeg_decode="host"`, or the file is outside the device's subset (progressive, greyscale...)"""
+        if self.io is not None and self.jpeg_decode == "device":
+            from .jpeg import JpegUnsupported
+            if self.jpeg_dec is None:
+                from .jpeg_io import HipJpegDecoder
+                self.jpeg_dec = HipJpegDecoder(device=self.io.device)
+            try:
+                return self.jpeg_dec.decode(data)
+            except JpegUnsupported:
+                pass
+        import io
+
+        from PIL import Image
+        self.jpeg_host_decodes += 1
+        return np.array(Image.open(io.BytesIO(data)).convert("RGB"))
+
+    def _check_jpeg(self) -> None:
+        if self.jpeg_dec is not None:
+            self.jpeg_dec.check()
+
     def preprocess_image(self, image):
         """path / PIL image -> uint8 [height, width, 3] (host resize, as the reference); arrays and tensors pass through: the
         pipeline's `image_processor` (frame_io.FrameProcessor) ingests them, so a normalised tensor never meets a range probe"""
+        if isinstance(image, (bytes, bytearray, memoryview)):
+            if not _is_jpeg(image):
+                raise ValueError("a bytes frame must be a JPEG file (it does not begin with FF D8)")
+            return self._decode_jpeg(image)
         if isinstance(image, (str, os.PathLike)):
             from PIL import Image
             image = Image.open(image)
@@ -381,6 +431,11 @@ class StreamAnimateDiffusionDepthWrapper:
         frame on the host), the file of `encode_ref(egress_ref(x))` either way"""
         if not torch.is_tensor(image_tensor):
             raise ValueError(f"Input for postprocessing is in incorrect format: {type(image_tensor)}. We only support pytorch tensor")
+        out = self._postprocess(image_tensor, output_type)
+        self._check_jpeg()                 # behind the copy to the host every output type ends in: the status words are there too
+        return out
+
+    def _postprocess(self, image_tensor: torch.Tensor, output_type: str):
         if output_type == "latent":
             return image_tensor[0].cpu()
         if output_type == "pt":

@@ -2,12 +2,19 @@
 
     python tools/mjpeg_server.py --config configs/toonyou.yaml --input frames/ [--prompt "..."] [--height 512 --width 512]
                                  [--port 8000] [--quality 75]
+    python tools/mjpeg_server.py --config configs/toonyou.yaml --input post     # the browser's camera is the input
 
 `/` is a page with one <img>; `/stream` is `multipart/x-mixed-replace; boundary=frame`, every part laid out as the reference's
 demo does (demo/util.py:27-37, `jpeg.mjpeg_part`).  The input (a folder of images or an .npy stack, `stream_frames.read_frames`)
 is looped for ever.  One producer thread owns the wrapper and the GPU; the HTTP handlers only ever read the latest part, so a
 slow viewer drops frames instead of holding the stream back.  Standard library only (http.server).  The frame is encoded on
-the device (jpeg_io.HipJpegEncoder): what crosses to the host is the JPEG file."""
+the device (jpeg_io.HipJpegEncoder): what crosses to the host is the JPEG file.
+
+`--input post` closes the loop of the reference's demo (demo/app.py:81-85: `canvas.toBlob('image/jpeg')` -> websocket ->
+`bytes_to_pil`): the page captures the camera with `getUserMedia`, draws it on a canvas and sends every frame as the body of
+`POST /frame`; the wrapper takes the bytes as they are (decoded on the device, jpeg_io.HipJpegDecoder).  The first `sink` frames
+posted are the warm-up; after that the producer always takes the NEWEST posted frame, and a frame that raises (a damaged file)
+is dropped and counted."""
 import argparse
 import os
 import sys
@@ -21,6 +28,62 @@ for p in (ROOT, os.path.dirname(os.path.abspath(__file__))):
 
 PAGE = (b"<!doctype html><html><head><title>live2diff_amd</title></head>"
         b"<body style=\"margin:0;background:#111\"><img src=\"/stream\" style=\"display:block;margin:auto;max-width:100%\"></body></html>\n")
+
+
+CAMERA_PAGE = (b"<!doctype html><html><head><title>live2diff_amd</title></head>"
+               b"<body style=\"margin:0;background:#111\"><img src=\"/stream\" style=\"display:block;margin:auto;max-width:100%\">"
+               b"<video id=\"v\" autoplay playsinline muted style=\"display:none\"></video><canvas id=\"c\" style=\"display:none\"></canvas>"
+               b"<script>\n"
+               b"const v = document.getElementById('v'), c = document.getElementById('c');\n"
+               b"async function send() {\n"
+               b"  if (v.videoWidth) {\n"
+               b"    c.width = v.videoWidth; c.height = v.videoHeight; c.getContext('2d').drawImage(v, 0, 0);\n"
+               b"    const blob = await new Promise(r => c.toBlob(r, 'image/jpeg', 0.9));\n"
+               b"    try { await fetch('/frame', {method: 'POST', body: blob}); } catch (e) {}\n"
+               b"  }\n"
+               b"  setTimeout(send, v.videoWidth ? 0 : 100);\n"
+               b"}\n"
+               b"navigator.mediaDevices.getUserMedia({video: true}).then(s => { v.srcObject = s; send(); });\n"
+               b"</script></body></html>\n")
+MAX_POST = 16 << 20            # bytes of one posted frame
+
+
+class Inbox:
+    """What `POST /frame` delivers.  The first `warmup` frames are all kept, in order (`warmup_frames()` blocks until they are
+    there); of the later ones only the newest: `take(timeout)` returns it once, or None when nothing new came in time or the
+    inbox was closed.  `posted` / `replaced` / `failed` count frames posted, overwritten before anyone took them, and dropped by the
+    producer because the wrapper raised."""
+
+    def __init__(self, warmup: int):
+        self._cond = threading.Condition()
+        self._need, self._warm, self._frame, self._closed = int(warmup), [], None, False
+        self.posted = self.replaced = self.failed = 0
+
+    def put(self, data: bytes) -> None:
+        with self._cond:
+            self.posted += 1
+            if len(self._warm) < self._need:
+                self._warm.append(data)
+            else:
+                self.replaced += self._frame is not None
+                self._frame = data
+            self._cond.notify_all()
+
+    def close(self) -> None:
+        with self._cond:
+            self._closed = True
+            self._cond.notify_all()
+
+    def warmup_frames(self):
+        with self._cond:
+            self._cond.wait_for(lambda: len(self._warm) >= self._need or self._closed)
+            return list(self._warm) if len(self._warm) >= self._need else None
+
+    def take(self, timeout=None):
+        with self._cond:
+            self._cond.wait_for(lambda: self._frame is not None or self._closed, timeout)
+            data, self._frame = self._frame, None
+            return data
 
 
 class Latest:
@@ -47,7 +110,9 @@ class Latest:
             return (self._seq, self._part) if self._seq > seen else None
 
 
-def make_handler(latest: Latest):
+def make_handler(latest: Latest, inbox: "Inbox" = None):
+    page = PAGE if inbox is None else CAMERA_PAGE
+
     class Handler(BaseHTTPRequestHandler):
         protocol_version = "HTTP/1.0"          # no keep-alive: the stream ends when either side closes the connection
 
@@ -58,9 +123,9 @@ def make_handler(latest: Latest):
             if self.path in ("/", "/index.html"):
                 self.send_response(200)
                 self.send_header("Content-Type", "text/html; charset=utf-8")
-                self.send_header("Content-Length", str(len(PAGE)))
+                self.send_header("Content-Length", str(len(page)))
                 self.end_headers()
-                self.wfile.write(PAGE)
+                self.wfile.write(page)
             elif self.path == "/stream":
                 self.send_response(200)
                 self.send_header("Content-Type", "multipart/x-mixed-replace; boundary=frame")
@@ -80,6 +145,26 @@ def make_handler(latest: Latest):
             else:
                 self.send_error(404)
 
+        def do_POST(self):
+            if inbox is None or self.path != "/frame":
+                self.send_error(404)
+                return
+            try:
+                n = int(self.headers.get("Content-Length", ""))
+            except ValueError:
+                self.send_error(411)
+                return
+            if not 2 <= n <= MAX_POST:
+                self.send_error(413 if n > MAX_POST else 400)
+                return
+            body = self.rfile.read(n)
+            if len(body) != n or body[:2] != b"\xff\xd8":
+                self.send_error(400, "the body is no JPEG file")
+                return
+            inbox.put(body)
+            self.send_response(204)
+            self.end_headers()
+
     return Handler
 
 
@@ -95,10 +180,32 @@ def produce(wrapper, frames, latest: Latest, stop: threading.Event) -> None:
         latest.close()
 
 
+def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: threading.Event) -> None:
+    """the producer of `--input post`: the first frames posted warm the stream up, then the newest posted frame goes through the
+    wrapper, for ever; a frame the wrapper refuses (ValueError: a damaged file) is dropped and counted in `inbox.failed`"""
+    from live2diff_amd.jpeg import mjpeg_part
+    try:
+        warm = inbox.warmup_frames()
+        if warm is None:
+            return
+        wrapper.prepare(warm, prompt)
+        while not stop.is_set():
+            frame = inbox.take(timeout=0.5)
+            if frame is None:
+                continue
+            try:
+                latest.put(mjpeg_part(wrapper(frame)))
+            except ValueError:
+                inbox.failed += 1
+    finally:
+        latest.close()
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--config", required=True)
-    ap.add_argument("--input", required=True, help="folder of images, or .npy uint8 [F,H,W,3]; looped")
+    ap.add_argument("--input", required=True, help="folder of images, or .npy uint8 [F,H,W,3]; looped -- or `post`: JPEG frames arrive as "
+                    "bodies of POST /frame (the page captures the camera)")
     ap.add_argument("--prompt", default=None, help="default: the config's `prompt`")
     ap.add_argument("--height", type=int, default=512)
     ap.add_argument("--width", type=int, default=512)
@@ -114,17 +221,23 @@ def main(argv=None):
     from live2diff_amd.wrapper import StreamAnimateDiffusionDepthWrapper, load_config, stream_sizes
     cfg = load_config(args.config)
     sink = stream_sizes(cfg)[1]
-    frames = read_frames(args.input)
-    if len(frames) < sink:
+    post = args.input == "post"
+    frames = None if post else read_frames(args.input)
+    if not post and len(frames) < sink:
         raise ValueError(f"{len(frames)} frames: need at least the {sink} warm-up frames")
     w = StreamAnimateDiffusionDepthWrapper(args.config, few_step_model_type="lcm", num_inference_steps=cfg.get("num_inference_steps", 50),
                                            t_index_list=cfg.get("t_index_list"), strength=cfg.get("strength"), output_type="jpeg",
                                            jpeg_quality=args.quality, height=args.height, width=args.width, seed=args.seed,
                                            engine_dir=args.engine_dir)
-    w.prepare(frames[:sink], args.prompt if args.prompt is not None else str(cfg.get("prompt", "")))
+    prompt = args.prompt if args.prompt is not None else str(cfg.get("prompt", ""))
     latest, stop = Latest(), threading.Event()
-    producer = threading.Thread(target=produce, args=(w, frames, latest, stop), name="producer", daemon=True)
-    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest))
+    inbox = Inbox(sink) if post else None
+    if post:
+        producer = threading.Thread(target=produce_posted, args=(w, prompt, inbox, latest, stop), name="producer", daemon=True)
+    else:
+        w.prepare(frames[:sink], prompt)
+        producer = threading.Thread(target=produce, args=(w, frames, latest, stop), name="producer", daemon=True)
+    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest, inbox))
     server.daemon_threads = True
     producer.start()
     print(f"http://{args.host}:{args.port}/  ({args.height}x{args.width}, quality {args.quality}; Ctrl-C stops)")
@@ -134,6 +247,9 @@ def main(argv=None):
         pass
     finally:
         stop.set()
+        if inbox is not None:
+            inbox.close()
+            print(f"{inbox.posted} frames posted, {inbox.replaced} replaced by a newer one before their turn, {inbox.failed} dropped as damaged")
         server.server_close()
         producer.join(timeout=10)
 
