@@ -22,14 +22,13 @@ oracle/midas_ref.py) maps onto the kernels the UNet and the VAE already use:
     bilinear x2, and an add / ReLU elementwise kernel for the decoder's pre-activation residual units.
 One static plan per (batch, H, W), replayed through the C ABI.
 """
-from types import SimpleNamespace
 from typing import Dict
 
 import torch
 
 from . import _lib, ops
 from .ops import round_up
-from .unet_hip import _Arena
+from .plan import PlanBuilder
 
 from .midas_spec import (DEPTH, DIM, FEAT, G, HEADS, HOOKS, MLP, STAGE_CH, STAGES, midas_param_spec,  # noqa: E402,F401  (re-exported)
                          random_midas_state_dict)
@@ -125,15 +124,9 @@ class HipMidas:
         if H % 32 or W_ % 32:
             raise ValueError(f"DPT-Hybrid input {H}x{W_} must be a multiple of 32")
         dev, W = self.device, self.W
-        ar = _Arena(dev)
-        pl = _lib.OpList()
-        st = SimpleNamespace(pl=pl, arena=ar, gn_layers=0)
+        st = PlanBuilder(dev, B, sk_counters=1 << 14, gn_layers=64, G=G, xcd_order=False)
+        ar, add, gemm = st.arena, st.add, st.gemm
         st.inp = torch.zeros(B, 3, H, W_, dtype=torch.float16, device=dev)
-        st.gn_acc = torch.zeros(64, B, G, 2, dtype=torch.int64, device=dev)
-        st.gn_zero = torch.zeros_like(st.gn_acc)
-        st.sk_cnt, st.sk_used = torch.zeros(1 << 14, dtype=torch.int32, device=dev), 0      # split-K arrival counters (igemm.hip)
-        zero_op = pl.append(*ops.copy(st.gn_zero, st.gn_acc, st.gn_acc.numel() * 8))
-        add = lambda opk: pl.append(*opk)
         st.taps = {}
 
         def tap(name, buf, *shape):
@@ -141,25 +134,6 @@ class HipMidas:
                 t = torch.zeros(*shape, dtype=torch.float16, device=dev)
                 add(ops.copy(buf, t, t.numel() * 2))
                 st.taps[name] = t
-
-        def gemm(x, wt, out, **kw):
-            taps = kw.get("taps", 1)
-            tile, S, variant = ops.igemm_schedule(kw["M"], kw["Nout"], taps * kw["CinP"], kw.get("batch", 1), kw.get("epi", 0), taps)
-            if variant in (6, 7) and kw["CinP"] % 128:
-                variant = 1
-            if tile == 1 and variant in (7, 8, 9):
-                variant = 5
-            ws, cnt_kw = None, {}
-            if ops.splitk_fused(S):
-                n_ws, n_cnt = ops.splitk_sizes(kw["M"], kw["Nout"], S, kw.get("batch", 1), tile)
-                ws = ar.alloc(n_ws, torch.float32)
-                cnt_kw = dict(cnt=st.sk_cnt, cnt_off=st.sk_used)
-                st.sk_used += n_cnt
-            elif S > 1:
-                ws = ar.alloc(kw.get("batch", 1) * S * kw["M"] * round_up(kw["Nout"], 4), torch.float32)
-            op = add(ops.igemm(x, wt, out, splitk=S, tile=tile, ws=ws, variant=variant, **cnt_kw, **kw))
-            ar.release(ws)
-            return op
 
         def lin(x, M, K, name, out=None, bias=True, epi=0, res=None, ldr=0, **kw):
             wt = W[name + ".w"]
@@ -187,21 +161,8 @@ class HipMidas:
         def gnorm(x, op_prod, C, T, name, act, res=None):
             """GroupNorm(32) (+ ReLU / + shortcut + ReLU) of a tensor just written by `op_prod` (statistics from its epilogue)."""
             out = ar.alloc(B * T * C)
-            acc_ptr = st.gn_acc.data_ptr() + st.gn_layers * B * G * 2 * 8
-            if st.gn_layers < st.gn_acc.shape[0] and ops.gn_target(op_prod, acc_ptr, T=T, G=G, cpg=C // G, choff=0):
-                st.gn_layers += 1
-                add(ops.gn_apply(x, None, W[name + ".g"], W[name + ".beta"], out, eps=1e-5, silu=act, B=B, T=T, C1=C, ld1=C, G=G, nchunk=0,
-                                 acc_ptr=acc_ptr, res=res))
-            elif ops.gn_self_ok(T, C, G):           # small tensor behind split-K tiles: statistics + apply in one launch (norm.hip, round 6)
-                add(ops.gn_apply(x, None, W[name + ".g"], W[name + ".beta"], out, eps=1e-5, silu=act, B=B, T=T, C1=C, ld1=C, G=G, nchunk=0,
-                                 res=res))
-            else:
-                nchunk = max(1, min(64, T // 16))
-                partial = ar.alloc(B * nchunk * G * 2, torch.float32)
-                kw = dict(B=B, T=T, C1=C, ld1=C, G=G, nchunk=nchunk)
-                add(ops.gn_stats(x, partial, **kw))
-                add(ops.gn_apply(x, partial, W[name + ".g"], W[name + ".beta"], out, eps=1e-5, silu=act, res=res, **kw))
-                ar.release(partial)
+            st.groupnorm(x, W[name + ".g"], W[name + ".beta"], out, T=T, C1=C, eps=1e-5, act=act, res=res,
+                         acc_ptr=st.gn_acc_for([(op_prod, 0)], T=T, cpg=C // G))
             return out
 
         # ---- ResNetV2 stem: 7x7 s2 (std, SAME) -> GN + ReLU -> 3x3 s2 max pool (SAME)
@@ -362,9 +323,7 @@ class HipMidas:
         st.out = torch.zeros(B, 1, hh * ww, dtype=torch.float16, device=dev)
         add(ops.nhwc_to_nchw(d1, st.out, B=B, C=1, HW=hh * ww, ld=4))
         st.out_shape = (B, hh, ww)
-        zero_op.l[0] = max(16, st.gn_layers * B * G * 2 * 8)
-        st.arena_bytes = ar.nbytes()
-        return st
+        return st.finish()
 
     @torch.no_grad()
     def __call__(self, images: torch.Tensor) -> torch.Tensor:
@@ -381,4 +340,4 @@ class HipMidas:
         return st.out.view(st.out_shape)
 
     def plan_summary(self):
-        return {k: dict(n_ops=len(st.pl), gn_fused=st.gn_layers, arena_bytes=st.arena_bytes) for k, st in self._plans.items()}
+        return {k: st.summary() for k, st in self._plans.items()}

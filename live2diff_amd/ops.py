@@ -183,11 +183,11 @@ def zero_page(device) -> torch.Tensor:
     return _ZERO_PAGES[key]
 
 
-def igemm_gn_target(op, acc_ptr: int, *, T: int, G: int, cpg: int, choff: int) -> bool:
-    """Ask an igemm op to accumulate the GroupNorm statistics of its output for one consumer GroupNorm (up to two per op):
-    `acc_ptr` -> int64 [samples][G][2], cpg / choff = channels per group and channel offset of this tensor in the consumer's
-    (concatenated) channel axis.  Returns False when both slots are taken or the launch cannot do it (include/l2d.h)."""
-    assert op.kind == _lib.OP_IGEMM
+# ---- GroupNorm statistics from a producer's epilogue.  Each GEMM / conv kernel can accumulate sum / sum of squares of its output for
+# up to two consumer GroupNorms (include/l2d.h: p[9], p[10] = the accumulators, i[24] / i[25] = T / G shared by both slots,
+# i[26 + 2 slot] / i[27 + 2 slot] = channels per group / channel offset of this tensor in the consumer's channel axis).  Per kernel
+# only the eligibility differs:
+def _igemm_gn_ok(op, T, cpg, choff) -> bool:
     splitk, tile = max(1, op.i[21]), op.i[22] & 15
     fused = bool(op.p[11])
     tm = 64 if ((splitk > 1 and not fused) or tile == 2) else 128
@@ -195,83 +195,62 @@ def igemm_gn_target(op, acc_ptr: int, *, T: int, G: int, cpg: int, choff: int) -
     direct = (op.i[22] >> 5) & 1
     vec_ok = ((not direct) and Nout % 8 == 0 and ldo % 8 == 0 and not (op.p[5] and ldr % 8) and epi != 1
               and (op.p[6] or 0) % 16 == 0 and (op.p[5] or 0) % 16 == 0)     # 16-byte aligned out / residual (sub-views)
-    if T % tm or batch != 1 or ((splitk == 1 or fused) and not vec_ok) or op.i[13] % T or G > 32:
-        return False
-    if op.p[9] and (op.i[24], op.i[25]) != (T, G):
-        return False
-    slot = 0 if not op.p[9] else (1 if not op.p[10] else -1)
-    if slot < 0:
-        return False
-    op.p[9 + slot] = int(acc_ptr)
-    op.i[24], op.i[25] = int(T), int(G)
-    op.i[26 + 2 * slot], op.i[27 + 2 * slot] = int(cpg), int(choff)
-    return True
+    return not (T % tm or batch != 1 or ((splitk == 1 or fused) and not vec_ok) or op.i[13] % T)
 
 
-def rowgemm_gn_target(op, acc_ptr: int, *, T: int, G: int, cpg: int, choff: int) -> bool:
-    """The same request to a rowgemm op (its epilogue accumulates like igemm's LDS-staged one)."""
-    assert op.kind == _lib.OP_ROWGEMM
+def _rowgemm_gn_ok(op, T, cpg, choff) -> bool:
+    """(its epilogue accumulates like igemm's LDS-staged one)"""
     MT, ntr, epi = op.i[14], op.i[15], op.i[6]
-    if T % (32 * MT) or op.i[0] % T or ntr or epi == 1 or G > 32 or (cpg | choff) & 1:
+    return not (T % (32 * MT) or op.i[0] % T or ntr or epi == 1 or (cpg | choff) & 1)
+
+
+def _patch_gn_ok(op, T, cpg, choff) -> bool:
+    """pconv and cconv: a patch never straddles samples"""
+    return T == op.i[7] * op.i[8] and not (cpg | choff) & 1
+
+
+def _rowchain_gn_ok(op, T, cpg, choff) -> bool:
+    """(its row phase accumulates like the row GEMM's; a block is 32 tokens of one sample; head segments feed attention, never a
+    GroupNorm)"""
+    return not (op.i[6] != 0 or T % 32 or op.i[0] % T or (cpg | choff) & 1)
+
+
+def _wsgemm_gn_ok(op, T, cpg, choff) -> bool:
+    """(a 128-token tile may span samples: T % 32)"""
+    NW, NT, ntr, epi, M = op.i[9], op.i[10], op.i[21], op.i[19], op.i[13]
+    bno = NW * NT * 32
+    return not (T % 32 or M % T or ntr or epi == 1 or (cpg | choff) & 1 or 64 * NW < bno // 2)
+
+
+_GN_PRODUCER_OK = {_lib.OP_IGEMM: _igemm_gn_ok, _lib.OP_ROWGEMM: _rowgemm_gn_ok, _lib.OP_PCONV: _patch_gn_ok, _lib.OP_CCONV: _patch_gn_ok,
+                   _lib.OP_ROWCHAIN: _rowchain_gn_ok, _lib.OP_WSGEMM: _wsgemm_gn_ok}
+
+
+def gn_target_ok(op, *, T: int, G: int, cpg: int, choff: int) -> bool:
+    """Would `gn_target` succeed?  Changes nothing: the launch can accumulate these statistics, a slot is free, and an occupied
+    slot 0 has the same (T, G)."""
+    ok = _GN_PRODUCER_OK.get(op.kind)
+    if ok is None or G > 32 or not ok(op, T, cpg, choff):
         return False
-    if op.p[9] and (op.i[24], op.i[25]) != (T, G):
+    return not op.p[9] or ((op.i[24], op.i[25]) == (T, G) and not op.p[10])
+
+
+def gn_target(op, acc_ptr: int, *, T: int, G: int, cpg: int, choff: int) -> bool:
+    """Ask the GEMM / conv op that produced a tensor to accumulate that tensor's GroupNorm statistics for one consumer GroupNorm
+    (up to two per op): `acc_ptr` -> int64 [samples][G][2], cpg / choff = channels per group and channel offset of this tensor in
+    the consumer's (concatenated) channel axis.  Returns False when both slots are taken or the launch cannot do it."""
+    if not gn_target_ok(op, T=T, G=G, cpg=cpg, choff=choff):
         return False
-    slot = 0 if not op.p[9] else (1 if not op.p[10] else -1)
-    if slot < 0:
-        return False
+    slot = 1 if op.p[9] else 0
     op.p[9 + slot] = int(acc_ptr)
     op.i[24], op.i[25] = int(T), int(G)
     op.i[26 + 2 * slot], op.i[27 + 2 * slot] = int(cpg), int(choff)
     return True
 
 
-def pconv_gn_target(op, acc_ptr: int, *, T: int, G: int, cpg: int, choff: int) -> bool:
-    """The same request to a patch-conv op (a patch never straddles samples)."""
-    assert op.kind == _lib.OP_PCONV
-    if T != op.i[7] * op.i[8] or G > 32 or (cpg | choff) & 1:
-        return False
-    if op.p[9] and (op.i[24], op.i[25]) != (T, G):
-        return False
-    slot = 0 if not op.p[9] else (1 if not op.p[10] else -1)
-    if slot < 0:
-        return False
-    op.p[9 + slot] = int(acc_ptr)
-    op.i[24], op.i[25] = int(T), int(G)
-    op.i[26 + 2 * slot], op.i[27 + 2 * slot] = int(cpg), int(choff)
-    return True
-
-
-def gn_target(op, acc_ptr: int, **kw) -> bool:
-    """Ask the GEMM op that produced a tensor to accumulate that tensor's GroupNorm statistics (igemm, rowgemm or pconv)."""
-    if op.kind == _lib.OP_IGEMM:
-        return igemm_gn_target(op, acc_ptr, **kw)
-    if op.kind == _lib.OP_ROWGEMM:
-        return rowgemm_gn_target(op, acc_ptr, **kw)
-    if op.kind == _lib.OP_PCONV:
-        return pconv_gn_target(op, acc_ptr, **kw)
-    if op.kind == _lib.OP_WSGEMM:
-        return wsgemm_gn_target(op, acc_ptr, **kw)
-    if op.kind == _lib.OP_ROWCHAIN:
-        return rowchain_gn_target(op, acc_ptr, **kw)
-    if op.kind == _lib.OP_CCONV:
-        return cconv_gn_target(op, acc_ptr, **kw)
-    return False
-
-
-def rowchain_gn_target(op, acc_ptr: int, *, T: int, G: int, cpg: int, choff: int) -> bool:
-    """The same request to a rowchain op (its row phase accumulates like the row GEMM's; a block is 32 tokens of one sample)."""
-    assert op.kind == _lib.OP_ROWCHAIN
-    if op.i[6] != 0 or T % 32 or op.i[0] % T or G > 32 or (cpg | choff) & 1:          # (head segments feed attention, never a GroupNorm)
-        return False
-    if op.p[9] and (op.i[24], op.i[25]) != (T, G):
-        return False
-    slot = 0 if not op.p[9] else (1 if not op.p[10] else -1)
-    if slot < 0:
-        return False
-    op.p[9 + slot] = int(acc_ptr)
-    op.i[24], op.i[25] = int(T), int(G)
-    op.i[26 + 2 * slot], op.i[27 + 2 * slot] = int(cpg), int(choff)
-    return True
+def igemm_gn_target(op, acc_ptr: int, *, T: int, G: int, cpg: int, choff: int) -> bool:
+    assert op.kind == _lib.OP_IGEMM
+    return gn_target(op, acc_ptr, T=T, G=G, cpg=cpg, choff=choff)
 
 
 def rowchain_head(x, hout, out, *, M, C, wA, bA, wB, bB=None, passes=1, resA=None, gn_acc_ptr=None, T=0, G=0, eps_gn=1e-6, eps_ln=1e-5,
@@ -688,24 +667,6 @@ def wsgemm(x1, w, out, *, M, Nout, C1, ldx1, ldo, x2=None, C2=0, ldx2=0, bias=No
     return op, (x1, x2, w, bias, colsum, rowbias, res, out, out_t, zp, ws, cnt)
 
 
-def wsgemm_gn_target(op, acc_ptr: int, *, T: int, G: int, cpg: int, choff: int) -> bool:
-    """GroupNorm statistics of a wsgemm launch's output for a consumer GroupNorm (a 128-token tile may span samples: T % 32)."""
-    assert op.kind == _lib.OP_WSGEMM
-    NW, NT, ntr, epi, M = op.i[9], op.i[10], op.i[21], op.i[19], op.i[13]
-    bno = NW * NT * 32
-    if T % 32 or M % T or ntr or epi == 1 or G > 32 or (cpg | choff) & 1 or 64 * NW < bno // 2:
-        return False
-    if op.p[9] and (op.i[24], op.i[25]) != (T, G):
-        return False
-    slot = 0 if not op.p[9] else (1 if not op.p[10] else -1)
-    if slot < 0:
-        return False
-    op.p[9 + slot] = int(acc_ptr)
-    op.i[24], op.i[25] = int(T), int(G)
-    op.i[26 + 2 * slot], op.i[27 + 2 * slot] = int(cpg), int(choff)
-    return True
-
-
 # ----------------------------------------------------------------------------- cconv (csrc/cconv.hip, round 6)
 CCONV_RING = 9          # weight ring depth of the kernel in k steps: the packed tensor is padded by this many 2 KB steps
 
@@ -826,22 +787,6 @@ def cconv(x1, w, out, *, B, H, W, C1, ldx1, Nout, ldo, KG, x2=None, C2=0, ldx2=0
     for j, v in vals.items():
         op.i[j] = int(v)
     return op, (x1, x2, w, bias, rowbias, res, out, zp, ws, cnt, gn_gamma, gn_beta)
-
-
-def cconv_gn_target(op, acc_ptr: int, *, T: int, G: int, cpg: int, choff: int) -> bool:
-    """GroupNorm statistics of a cconv launch's output for a consumer GroupNorm (a patch never straddles samples)."""
-    assert op.kind == _lib.OP_CCONV
-    if T != op.i[7] * op.i[8] or G > 32 or (cpg | choff) & 1:
-        return False
-    if op.p[9] and (op.i[24], op.i[25]) != (T, G):
-        return False
-    slot = 0 if not op.p[9] else (1 if not op.p[10] else -1)
-    if slot < 0:
-        return False
-    op.p[9 + slot] = int(acc_ptr)
-    op.i[24], op.i[25] = int(T), int(G)
-    op.i[26 + 2 * slot], op.i[27 + 2 * slot] = int(cpg), int(choff)
-    return True
 
 
 def igemm_schedule(M: int, Nout: int, Kp: int, batch: int = 1, epi: int = 0, taps: int = 1):

@@ -20,7 +20,7 @@ No torch compute ops are used on the path (torch provides HBM allocations, the s
 host-to-static-buffer input copies).
 """
 from types import SimpleNamespace
-from typing import Dict, List, Optional
+from typing import List, Optional
 
 import os
 import torch
@@ -28,6 +28,7 @@ import torch
 from . import _lib, ops
 from .config import UNetConfig, motion_module_layout
 from .ops import round_up
+from .plan import Act, PlanBuilder
 
 TEXT_PAD = 80   # 77 CLIP tokens padded to a multiple of 4 (igemm stores 4 channels per lane)
 
@@ -56,40 +57,6 @@ def sinusoid_pe(max_len: int, dim: int, device) -> torch.Tensor:
     pe[:, 0::2] = torch.sin(pos * div)
     pe[:, 1::2] = torch.cos(pos * div)
     return pe
-
-
-class _Arena:
-    """Size-keyed free list of device buffers: intermediates of a static plan reuse HBM (and stay hot in the
-    256 MB Infinity Cache) instead of every op getting a private allocation."""
-
-    def __init__(self, device):
-        self.device = device
-        self.free: Dict[tuple, List[torch.Tensor]] = {}
-        self.all: List[torch.Tensor] = []
-
-    def alloc(self, numel: int, dtype=torch.float16) -> torch.Tensor:
-        key = (int(numel), dtype)
-        lst = self.free.get(key)
-        if lst:
-            return lst.pop()
-        t = torch.empty(int(numel), dtype=dtype, device=self.device)
-        self.all.append(t)
-        return t
-
-    def release(self, t: Optional[torch.Tensor]):
-        if t is not None:
-            self.free.setdefault((t.numel(), t.dtype), []).append(t)
-
-    def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in self.all)
-
-
-class _Act:
-    """channels-last activation: buf holds [B*H*W, C] halfs (ld == C); `producer` = the igemm op that wrote it (if any)."""
-    __slots__ = ("buf", "C", "H", "W", "producer")
-
-    def __init__(self, buf, C, H, W, producer=None):
-        self.buf, self.C, self.H, self.W, self.producer = buf, C, H, W, producer
 
 
 class PackedWeights:
@@ -516,51 +483,14 @@ class HipStreamingUNet:
         Bt = self.N if mode == "stream" else 1              # rows of timestep / text inputs
         h, w = self.h, self.w
         L, G = cfg.window_size, cfg.norm_num_groups
-        ar = _Arena(dev)
-        pl = _lib.OpList()
         # `cond_pl`: the launches that depend on (timestep, text) only -- time-embedding MLP + every resnet's
         # time_emb_proj, and the K / V^T text projections of all 16 cross-attention layers (frame-invariant).
         # They run when the conditioning changes (first frame, update_prompt, a new warm-up row), not every frame.
-        cond_pl = _lib.OpList()
-        st = SimpleNamespace(mode=mode, B=B, Bt=Bt, pl=pl, cond_pl=cond_pl, cond_key=None, arena=ar, tattn_ops=[], warm=False,
-                             ident={})
-        cur = [cond_pl]
-
-        def add(opk):
-            op, keep = opk
-            cur[0].append(op, *keep)
-            return op
-
-        def gemm(x1, wt, out, **kw):
-            """igemm with the (tile, split-K) schedule chosen for its shape; the fp32 split-K workspace comes from
-            the arena and is released right after (stream order makes the reuse safe)."""
-            batch, taps = kw.get("batch", 1), kw.get("taps", 1)
-            epi = kw.get("epi", 0)
-            tile, S, variant = ops.igemm_schedule(kw["M"], kw["Nout"], taps * kw["CinP"], batch, epi, taps)
-            if variant in (6, 7) and kw["CinP"] % 128:
-                variant = 1            # BK = 128 rings need K slices of 128
-            if tile == 1 and variant in (7, 8, 9):
-                variant = 5            # deep rings exist for the 64x64 tile only (LDS)
-            if epi == 1:
-                S = 1                  # GEGLU pairs value and gate in one block's registers: no split-K
-            ws, cnt_kw = None, {}
-            if ops.splitk_fused(S):
-                n_ws, n_cnt = ops.splitk_sizes(kw["M"], kw["Nout"], S, batch, tile)
-                ws = ar.alloc(n_ws, torch.float32)
-                cnt_kw = dict(cnt=st.sk_cnt, cnt_off=st.sk_used)
-                st.sk_used += n_cnt
-            elif S > 1:
-                ws = ar.alloc(batch * S * kw["M"] * round_up(kw["Nout"], 4), torch.float32)
-            # XCD tile order: weight-tile major when the weight matrix outweighs the activations (L2 fills, see igemm.hip)
-            wbytes = kw["Nout"] * taps * kw["CinP"]
-            xbytes = kw["M"] * (kw["C1"] + kw.get("C2", 0))
-            order = int(wbytes > xbytes)
-            op = add(ops.igemm(x1, wt, out, splitk=S, tile=tile, ws=ws, variant=variant, order=order, **cnt_kw, **kw))
-            ar.release(ws)
-            return op
-
-        # arrival counters of the split-K launches (fused reduction): zero now, every launch leaves them zero
-        st.sk_cnt, st.sk_used = torch.zeros(1 << 20, dtype=torch.int32, device=dev), 0
+        # `pl` starts with the zeroing of the GroupNorm statistics accumulators, once per frame.
+        st = PlanBuilder(dev, B, sk_counters=1 << 20, gn_layers=96, G=G)
+        st.mode, st.Bt, st.cond_pl, st.cond_key, st.tattn_ops, st.warm, st.ident = mode, Bt, _lib.OpList(), None, [], False, {}
+        ar, pl, add, gemm, new_act, free = st.arena, st.pl, st.add, st.gemm, st.act, st.free
+        st.use(st.cond_pl)
 
         # ---- static inputs
         st.in_sample = torch.zeros(B, cfg.in_channels, h * w, dtype=torch.float16, device=dev)
@@ -574,70 +504,26 @@ class HipStreamingUNet:
         st.out_sample = torch.zeros(B, cfg.out_channels, h * w, dtype=torch.float16, device=dev)
 
         # ---- helpers
-        def new_act(C, H_, W_):
-            return _Act(ar.alloc(B * H_ * W_ * C), C, H_, W_)
-
-        def free(a: Optional[_Act]):
-            if a is not None:
-                ar.release(a.buf)
-
         def ident_affine(C):
             if C not in st.ident:
                 st.ident[C] = (torch.ones(C, dtype=torch.float16, device=dev), torch.zeros(C, dtype=torch.float16, device=dev))
             return st.ident[C]
 
-        def gn_stats_target(x: _Act, x2: Optional[_Act], T, cpg):
-            """Ask the producers of x (and x2) to accumulate this GroupNorm's statistics; returns the accumulator pointer or
-            None (then nothing is left attached)."""
-            ins = [(x, 0)] + ([(x2, x.C)] if x2 is not None else [])
-            if not (all(a_.producer is not None for a_, _ in ins) and st.gn_layers < st.gn_acc.shape[0]):
-                return None
-            acc_ptr = st.gn_acc.data_ptr() + st.gn_layers * B * G * 2 * 8
-            saved = [(a_.producer, [a_.producer.p[9], a_.producer.p[10]], list(a_.producer.i[24:30])) for a_, _ in ins]
-            if all(ops.gn_target(a_.producer, acc_ptr, T=T, G=G, cpg=cpg, choff=off) for a_, off in ins):
-                st.gn_layers += 1
-                return acc_ptr
-            for op_, ps, is_ in saved:                   # undo a half-attached layer
-                op_.p[9], op_.p[10] = ps
-                for j, v in enumerate(is_):
-                    op_.i[24 + j] = v
-            return None
+        def gn_stats_target(x: Act, x2: Optional[Act], T, cpg):
+            """Ask the producers of x (and x2) to accumulate this GroupNorm's statistics; the accumulator pointer or None"""
+            return st.gn_acc_for([(x.producer, 0)] + ([(x2.producer, x.C)] if x2 is not None else []), T=T, cpg=cpg)
 
-        def gn(x: _Act, name, eps, silu, x2: Optional[_Act] = None, affine: bool = True) -> _Act:
+        def gn(x: Act, name, eps, silu, x2: Optional[Act] = None, affine: bool = True) -> Act:
             """affine=False: normalise only (gamma = 1, beta = 0): the consumer's packed weights carry the affine part."""
             T = x.H * x.W
             C2 = x2.C if x2 is not None else 0
             out = new_act(x.C + C2, x.H, x.W)
             gam, bet = (W[name + ".g"], W[name + ".beta"]) if affine else ident_affine(x.C + C2)
-            # Statistics from the producers: the igemm launches that wrote x (and x2) accumulate sum / sum of squares per
-            # (sample, group of THIS GroupNorm) in their epilogues as fixed-point integer atomics -- no gn_stats launch, no
-            # second pass over the tensor.  Falls back to the stats kernel when a producer cannot (tile straddles samples,
-            # both of its target slots taken, direct epilogue forced).
-            cpg = (x.C + C2) // G
-            acc_ptr = gn_stats_target(x, x2, T, cpg)
-            if acc_ptr is not None:
-                add(ops.gn_apply(x.buf, None, gam, bet, out.buf, eps=eps, silu=silu, B=B, T=T, C1=x.C,
-                                 ld1=x.C, G=G, nchunk=0, x2=(x2.buf if x2 is not None else None), C2=C2, ld2=C2,
-                                 acc_ptr=acc_ptr))
-                return out
-            if ops.gn_self_ok(T, x.C + C2, G):
-                # small tensor whose producers cannot deliver the statistics (tokens per sample are no whole number of their tiles: any
-                # resolution with 12 x 12, 6 x 6, 10 x 10 ... pixel levels): statistics + apply in ONE launch, the tensor read once
-                st.gn_self_launches += 1
-                add(ops.gn_apply(x.buf, None, gam, bet, out.buf, eps=eps, silu=silu, B=B, T=T, C1=x.C, ld1=x.C, G=G, nchunk=0,
-                                 x2=(x2.buf if x2 is not None else None), C2=C2, ld2=C2))
-                return out
-            nchunk = max(1, min(64, T // 16))
-            partial = ar.alloc(B * nchunk * G * 2, torch.float32)
-            kw = dict(B=B, T=T, C1=x.C, ld1=x.C, G=G, nchunk=nchunk, x2=(x2.buf if x2 is not None else None), C2=C2,
-                      ld2=C2)
-            st.gn_stats_launches += 1
-            add(ops.gn_stats(x.buf, partial, **kw))
-            add(ops.gn_apply(x.buf, partial, gam, bet, out.buf, eps=eps, silu=silu, **kw))
-            ar.release(partial)
+            st.groupnorm(x.buf, gam, bet, out.buf, T=T, C1=x.C, eps=eps, act=silu, acc_ptr=gn_stats_target(x, x2, T, (x.C + C2) // G),
+                         x2=(x2.buf if x2 is not None else None), C2=C2)
             return out
 
-        def conv3(x: _Act, name, stride=1, ups=0, epi=0, res: Optional[_Act] = None, rowbias=None) -> _Act:
+        def conv3(x: Act, name, stride=1, ups=0, epi=0, res: Optional[Act] = None, rowbias=None) -> Act:
             if (name + ".cw") in W:
                 # patch-resident activations + register-streamed weights (cconv.hip): resnet convs of the wide levels, up-samplers
                 assert stride == 1 and epi == 0
@@ -646,20 +532,14 @@ class HipStreamingUNet:
                 out = new_act(cout, Ho, Wo)
                 kg = ops.cconv_schedule(self.N, Ho, Wo, cout, x.C)[1]          # (the packing's: decided on the stream batch)
                 sched = ops.cconv_schedule(B, Ho, Wo, cout, x.C, KG=kg)
-                ws_buf, kw = None, {}
-                if sched[3] > 1:
-                    n_ws, n_cnt = ops.cconv_sizes(B, Ho, Wo, cout, sched[0], sched[3])
-                    ws_buf = ar.alloc(n_ws, torch.float32)
-                    kw = dict(ws=ws_buf, cnt=st.sk_cnt, cnt_off=st.sk_used)
-                    st.sk_used += n_cnt
+                kw = {}
                 if rowbias is not None:
                     kw.update(rowbias=st.temb_all, ldrb=self.temb_total, rows_per_bias=(Ho * Wo if mode == "stream" else B * Ho * Wo))
-                op_ = add(ops.cconv(x.buf, W[name + ".cw"], out.buf, B=B, H=Ho, W=Wo, C1=x.C, ldx1=x.C, Nout=cout, ldo=cout, KG=kg, ups=ups,
-                                    bias=W[name + ".b"], res=(res.buf if res is not None else None), ldr=(res.C if res is not None else 0),
-                                    sched=sched, **kw))
+                op_ = st.cconv(x.buf, W[name + ".cw"], out.buf, B=B, H=Ho, W=Wo, C1=x.C, ldx1=x.C, Nout=cout, ldo=cout, KG=kg, ups=ups,
+                               bias=W[name + ".b"], res=(res.buf if res is not None else None), ldr=(res.C if res is not None else 0),
+                               sched=sched, **kw)
                 if rowbias is not None:
                     op_.p[4] = st.temb_all.data_ptr() + 4 * rowbias
-                ar.release(ws_buf)
                 out.producer = op_
                 return out
             if use_ws(name):
@@ -719,28 +599,19 @@ class HipStreamingUNet:
 
         def wslin(xbuf, M, C1, wkey, outbuf, ldo, *, T, bias=None, colsum=None, res=None, ldr=0, x2buf=None, C2=0, epi=0, pro=0,
                   taps=1, Bc=1, H=1, Wd=1, rowbias_off=None, out_t=None, ntr=0, ldt=0, stt=0):
-            """one weight-streaming GEMM launch (wsgemm.hip) on weights packed by ops.pack_wsgemm / pack_wsgemm_conv3x3; the split-K
-            slabs come from the arena (released right after: stream order makes the reuse safe), the arrival counters from the
-            plan's counter block"""
+            """one weight-streaming GEMM launch (wsgemm.hip) on weights packed by ops.pack_wsgemm / pack_wsgemm_conv3x3"""
             wt = W[wkey]
             Ktot = taps * (C1 + C2)
             nout = wt.numel() // Ktot
             sched = ops.wsgemm_schedule(M, Ktot, nout, ntr, epi, pro, taps)
-            NW_, NT_, NL_, S_, ntw_ = sched
-            ws_buf, kw = None, {}
-            if S_ > 1:
-                n_ws, n_cnt = ops.wsgemm_sizes(M, nout, NW_, NT_, S_)
-                ws_buf = ar.alloc(n_ws, torch.float32)
-                kw = dict(ws=ws_buf, cnt=st.sk_cnt, cnt_off=st.sk_used)
-                st.sk_used += n_cnt
+            kw = {}
             if rowbias_off is not None:
                 kw.update(rowbias=st.temb_all, ldrb=self.temb_total, rows_per_bias=(T if mode == "stream" else B * T))
-            op_ = add(ops.wsgemm(xbuf, wt, outbuf, M=M, Nout=nout, C1=C1, ldx1=C1, ldo=ldo, x2=x2buf, C2=C2, ldx2=C2, bias=bias, colsum=colsum,
-                                 res=res, ldr=ldr, taps=taps, B=Bc, H=H, W=Wd, epi=epi, pro=pro, eps=1e-5, T=T, out_t=out_t, ntr=ntr, ldt=ldt,
-                                 st=stt, sched=sched, **kw))
+            op_ = st.wsgemm(xbuf, wt, outbuf, M=M, Nout=nout, C1=C1, ldx1=C1, ldo=ldo, x2=x2buf, C2=C2, ldx2=C2, bias=bias, colsum=colsum,
+                            res=res, ldr=ldr, taps=taps, B=Bc, H=H, W=Wd, epi=epi, pro=pro, eps=1e-5, T=T, out_t=out_t, ntr=ntr, ldt=ldt,
+                            st=stt, sched=sched, **kw)
             if rowbias_off is not None:
                 op_.p[4] = st.temb_all.data_ptr() + 4 * rowbias_off
-            ar.release(ws_buf)
             return op_
 
         # the packed form of a layer picks its kernel: ".ww" exists only at the weight-streaming levels, ".rw" only where the row GEMM
@@ -751,7 +622,7 @@ class HipStreamingUNet:
         def use_rg(key) -> bool:
             return (key + ".rw") in W
 
-        def linear(x: _Act, name, bias=True, res: Optional[_Act] = None, wkey=None, x2: Optional[_Act] = None, **kw) -> _Act:
+        def linear(x: Act, name, bias=True, res: Optional[Act] = None, wkey=None, x2: Optional[Act] = None, **kw) -> Act:
             """kw: pro / eps / T / G / gn_acc_ptr of a fused norm prologue (row GEMM only)"""
             if wkey is None and use_ws(name) and not kw:
                 nout = W[name + ".ww"].numel() // (x.C + (x2.C if x2 is not None else 0))
@@ -775,12 +646,12 @@ class HipStreamingUNet:
                                       ldx2=(x2.C if x2 is not None else 0))
             return out
 
-        def layernorm(x: _Act, name) -> _Act:
+        def layernorm(x: Act, name) -> Act:
             out = new_act(x.C, x.H, x.W)
             add(ops.layernorm(x.buf, W[name + ".g"], W[name + ".beta"], out.buf, rows=B * x.H * x.W, C=x.C, ldx=x.C, ldo=x.C))
             return out
 
-        def gn_linear(x: _Act, nname, eps, lname) -> _Act:
+        def gn_linear(x: Act, nname, eps, lname) -> Act:
             """GroupNorm -> Linear.  Row GEMM path: the normalisation is the GEMM's prologue (statistics from x's producers),
             the affine part lives in the packed weights; if the statistics cannot come from the producers or a sample is not a
             whole number of 32-token tiles, a normalise-only GroupNorm launch runs in front."""
@@ -798,11 +669,11 @@ class HipStreamingUNet:
             free(hn)
             return y
 
-        def ln_rowlin(x: _Act, wkey, outbuf, ldo, **kw):
+        def ln_rowlin(x: Act, wkey, outbuf, ldo, **kw):
             """LayerNorm -> Linear as one row GEMM launch (LayerNorm eps = 1e-5: nn.LayerNorm default, as ops.layernorm)"""
             return rowlin(x.buf, B * x.H * x.W, x.C, wkey + ".rw", wkey + ".rb", outbuf, ldo, pro=1, eps=1e-5, **kw)
 
-        def geglu_ff(x: _Act, name, res: _Act, nname=None) -> _Act:
+        def geglu_ff(x: Act, name, res: Act, nname=None) -> Act:
             """x: the un-normalised input when `nname` names the LayerNorm to fuse (row GEMM), else the normalised one"""
             if nname is not None and (name + ".ww1") in W:
                 c4 = W[name + ".ww1"].numel() // x.C // 2
@@ -820,7 +691,7 @@ class HipStreamingUNet:
                 return out
             return geglu_ff_old(x, name, res)
 
-        def geglu_ff_old(x: _Act, name, res: _Act) -> _Act:
+        def geglu_ff_old(x: Act, name, res: Act) -> Act:
             w1 = W[name + ".w1"]
             c4 = w1.shape[0] // 2
             hid = new_act(c4, x.H, x.W)
@@ -829,7 +700,7 @@ class HipStreamingUNet:
             free(hid)
             return out
 
-        def block_tail(ao: _Act, res1: _Act, res2: _Act, to_out, ff, proj_out) -> Optional[_Act]:
+        def block_tail(ao: Act, res1: Act, res2: Act, to_out, ff, proj_out) -> Optional[Act]:
             """attention output projection + residual -> LayerNorm -> GEGLU -> FF2 + residual -> proj_out + block residual as ONE
             token-resident launch (rowchain.hip) where the level's M / 32 blocks fill the chip (C = 320); None = not here."""
             T, C = ao.H * ao.W, ao.C
@@ -842,8 +713,8 @@ class HipStreamingUNet:
                                             b_po=W[keys[7]], eps=1e-5))
             return out
 
-        def block_head(x: _Act, a_name, b_name, outbuf, passes, *, res: Optional[_Act] = None, gn_of: Optional[_Act] = None, out_t=None,
-                       ldt=0, stt=0, ldo=None) -> Optional[_Act]:
+        def block_head(x: Act, a_name, b_name, outbuf, passes, *, res: Optional[Act] = None, gn_of: Optional[Act] = None, out_t=None,
+                       ldt=0, stt=0, ldo=None) -> Optional[Act]:
             """Two dependent layers as one token-resident launch (rowchain.hip head segment): h = A(x) (+ res) -- or A(GroupNorm(x)) with
             the statistics from x's producers -- stored as the residual stream, then B(LayerNorm(h)) -> outbuf (q | k | v, q | k + V^T,
             or the cross-attention's query).  Returns h, or None when the segment does not run here (the caller emits the two launches)."""
@@ -862,7 +733,7 @@ class HipStreamingUNet:
                                   eps_gn=cfg.transformer_norm_eps, eps_ln=1e-5, out_t=out_t, ldt=ldt, st=stt, ldo=ldo))
             return h
 
-        def gn_conv3(x: _Act, x2: Optional[_Act], nname, cname, **kw) -> _Act:
+        def gn_conv3(x: Act, x2: Optional[Act], nname, cname, **kw) -> Act:
             """conv3(silu(GroupNorm(x | x2))) (reference resnet.py:233-234, 249-250): GroupNorm launch + conv.  (The cconv launch can
             normalise its patch itself, ops.cconv gn_acc_ptr; in the frame that lost: profiles/round6_f_cconv_gn_fused_ab.txt.)"""
             hn = gn(x, nname, cfg.norm_eps, True, x2=x2)
@@ -870,7 +741,7 @@ class HipStreamingUNet:
             free(hn)
             return out_
 
-        def resnet(x: _Act, name, skip: Optional[_Act] = None) -> _Act:
+        def resnet(x: Act, name, skip: Optional[Act] = None) -> Act:
             h1 = gn_conv3(x, skip, name + ".norm1", name + ".conv1", rowbias=self.temb_offsets[name])
             if (name + ".conv_shortcut.w") in W or (name + ".conv_shortcut.ww") in W:
                 sc = linear(x, name + ".conv_shortcut", x2=skip)
@@ -882,7 +753,7 @@ class HipStreamingUNet:
             free(h1)
             return out
 
-        def spatial(x: _Act, name) -> _Act:
+        def spatial(x: Act, name) -> Act:
             T, C = x.H * x.W, x.C
             d = C // cfg.num_heads
             b = name + ".transformer_blocks.0"
@@ -980,7 +851,7 @@ class HipStreamingUNet:
             free(y4)
             return out
 
-        def motion(x: _Act, name, idx_base: int) -> _Act:
+        def motion(x: Act, name, idx_base: int) -> Act:
             T, C = x.H * x.W, x.C
             t = name + ".temporal_transformer"
             b = t + ".transformer_blocks.0"
@@ -1068,15 +939,9 @@ class HipStreamingUNet:
                       CinP=self.text_kp, ldo=TEXT_PAD, batch=Bt, sx1=0, sw=TEXT_PAD * self.text_kp,
                       so=self.text_total * TEXT_PAD)
 
-        cur[0] = pl
-        # ---- GroupNorm statistics accumulators (one [B][G][2] int64 block per fused GroupNorm), zeroed once per frame
-        st.gn_layers, st.gn_stats_launches, st.gn_self_launches = 0, 0, 0
-        st.gn_acc = torch.zeros(96, B, G, 2, dtype=torch.int64, device=dev)
-        st.gn_zero = torch.zeros_like(st.gn_acc)
-        zero_op = add(ops.copy(st.gn_zero, st.gn_acc, st.gn_acc.numel() * 8))
+        st.use(pl)
         # ---- input: NCHW latents -> channels-last (padded to 8 channels), conv_in + depth mapping network
-        x_in = _Act(ar.alloc(B * h * w * 8), 8, h, w)
-        d_in = _Act(ar.alloc(B * h * w * 8), 8, h, w)
+        x_in, d_in = new_act(8, h, w), new_act(8, h, w)
         add(ops.nchw_to_nhwc(st.in_sample, x_in.buf, B=B, C=cfg.in_channels, HW=h * w, Cpad=8))
         add(ops.nchw_to_nhwc(st.in_depth, d_in.buf, B=B, C=cfg.in_channels, HW=h * w, Cpad=8))
         x0 = conv3(x_in, "conv_in")
@@ -1129,11 +994,8 @@ class HipStreamingUNet:
         free(x)
         y = conv3(hn, "conv_out")
         add(ops.nhwc_to_nchw(y.buf, st.out_sample, B=B, C=cfg.out_channels, HW=h * w, ld=cfg.out_channels))
-        zero_op.l[0] = max(16, st.gn_layers * B * G * 2 * 8)          # only the blocks in use
         st.kv_ptrs = [c.data_ptr() for c in kv_cache]
-        st.arena_bytes = ar.nbytes()
-        st.n_ops = len(pl)
-        return st
+        return st.finish()
 
     def _plan(self, mode, kv_cache):
         st = self._plans.get(mode)
@@ -1254,7 +1116,4 @@ class HipStreamingUNet:
     # ------------------------------------------------------------------ introspection for bench / tests
     def plan_summary(self, mode="stream"):
         st = self._plans[mode]
-        kinds = {}
-        for j in range(len(st.pl)):
-            kinds[st.pl[j].kind] = kinds.get(st.pl[j].kind, 0) + 1
-        return dict(n_ops=len(st.pl), n_cond_ops=len(st.cond_pl), gn_fused=st.gn_layers, gn_stats_launches=st.gn_stats_launches, gn_self_launches=st.gn_self_launches, kinds=kinds, arena_bytes=st.arena_bytes, weight_bytes=self.weight_bytes())
+        return dict(st.summary(), n_cond_ops=len(st.cond_pl), weight_bytes=self.weight_bytes())

@@ -21,7 +21,7 @@ from typing import Dict, Tuple
 import torch
 
 from . import _lib, ops
-from .unet_hip import _Arena
+from .plan import PlanBuilder
 
 ENC_BLOCKS = (1, 3, 3, 3)
 DEC_BLOCKS = (3, 3, 3, 1)
@@ -107,17 +107,16 @@ class HipTinyVAE:
     def _build(self, side: str, B: int, H: int, W_: int):
         """side 'enc': static input [B,3,H,W] -> static output [B,4,H/8,W/8]; 'dec': [B,4,H,W] latent -> [B,3,8H,8W]."""
         dev, W = self.device, self.W
-        ar = _Arena(dev)
-        pl = _lib.OpList()
+        st = PlanBuilder(dev, B, xcd_order=False)          # (no split-K, no GroupNorm: 64-wide 3x3 convs only)
+        ar, add = st.arena, st.add
         cin0 = 3 if side == "enc" else 4
-        st = SimpleNamespace(pl=pl, arena=ar)
         st.inp = torch.zeros(B, cin0, H * W_, dtype=torch.float16, device=dev)
         h, w = H, W_
         x = ar.alloc(B * h * w * 8)
         if side == "enc":
-            pl.append(*ops.nchw_to_nhwc(st.inp, x, B=B, C=3, HW=h * w, Cpad=8, mode=ops.MAP_ADD_SCALE, a=0.5, b=1.0))
+            add(ops.nchw_to_nhwc(st.inp, x, B=B, C=3, HW=h * w, Cpad=8, mode=ops.MAP_ADD_SCALE, a=0.5, b=1.0))
         else:
-            pl.append(*ops.nchw_to_nhwc(st.inp, x, B=B, C=4, HW=h * w, Cpad=8, mode=ops.MAP_TANH3))
+            add(ops.nchw_to_nhwc(st.inp, x, B=B, C=4, HW=h * w, Cpad=8, mode=ops.MAP_TANH3))
         C = 8
 
         def conv(x, C, name, h, w, stride=1, ups=0, epi=0, res=None):
@@ -130,13 +129,12 @@ class HipTinyVAE:
             patch = ops.pconv_patch(B, h, w, cout, C) if (stride == 1 and not ups and Kp == 9 * C) else None
             if patch is not None:
                 # 64 -> 64 convs at the upper resolutions: the activation patch stays in LDS for all nine taps (csrc/pconv.hip)
-                pl.append(*ops.pconv(x, wt, out, B=B, H=h, W=w, C1=C, ldx1=C, CinP=C, Nout=cout, ldo=ldo, patch=patch,
-                                     bias=W.get(name + "bias"), res=res, ldr=(cout if res is not None else 0), epi=epi))
+                add(ops.pconv(x, wt, out, B=B, H=h, W=w, C1=C, ldx1=C, CinP=C, Nout=cout, ldo=ldo, patch=patch,
+                              bias=W.get(name + "bias"), res=res, ldr=(cout if res is not None else 0), epi=epi))
                 return out, cout, ho, wo
-            tile, S, variant = ops.igemm_schedule(M, cout, Kp, 1, epi, 9)
-            pl.append(*ops.igemm(x, wt, out, M=M, Nout=cout, C1=C, ldx1=C, CinP=Kp // 9, ldo=ldo, bias=W.get(name + "bias"),
-                                 res=res, ldr=(cout if res is not None else 0), taps=9, B=B, Hin=h, Win=w, Hout=ho, Wout=wo,
-                                 stride=stride, ups=ups, epi=epi, splitk=1, tile=tile, variant=variant))
+            st.gemm(x, wt, out, M=M, Nout=cout, C1=C, ldx1=C, CinP=Kp // 9, ldo=ldo, bias=W.get(name + "bias"),
+                    res=res, ldr=(cout if res is not None else 0), taps=9, B=B, Hin=h, Win=w, Hout=ho, Wout=wo,
+                    stride=stride, ups=ups, epi=epi)
             return out, cout, ho, wo
 
         def block(x, C, name, h, w):
@@ -161,7 +159,7 @@ class HipTinyVAE:
             y, C, h, w = conv(x, C, f"encoder.layers.{i}.", h, w)
             ar.release(x)
             st.out = torch.zeros(B, 4, h * w, dtype=torch.float16, device=dev)
-            pl.append(*ops.nhwc_to_nchw(y, st.out, B=B, C=4, HW=h * w, ld=4))
+            add(ops.nhwc_to_nchw(y, st.out, B=B, C=4, HW=h * w, ld=4))
             st.out_shape = (B, 4, h, w)
         else:
             y, C, h, w = conv(x, C, "decoder.layers.0.", h, w, epi=3)
@@ -180,10 +178,9 @@ class HipTinyVAE:
                 x = y
                 i += 1
             st.out = torch.zeros(B, 3, h * w, dtype=torch.float16, device=dev)
-            pl.append(*ops.nhwc_to_nchw(x, st.out, B=B, C=3, HW=h * w, ld=4, mode=ops.MAP_SCALE_ADD, a=2.0, b=-1.0))
+            add(ops.nhwc_to_nchw(x, st.out, B=B, C=3, HW=h * w, ld=4, mode=ops.MAP_SCALE_ADD, a=2.0, b=-1.0))
             st.out_shape = (B, 3, h, w)
-        st.arena_bytes = ar.nbytes()
-        return st
+        return st.finish()
 
     def _plan(self, side, B, H, W_):
         key = (side, B, H, W_)
@@ -221,7 +218,7 @@ class HipTinyVAE:
         return _Out(sample=img) if return_dict else (img,)
 
     def plan_summary(self):
-        return {k: dict(n_ops=len(st.pl), arena_bytes=st.arena_bytes) for k, st in self._plans.items()}
+        return {k: st.summary() for k, st in self._plans.items()}
 
 
 class HipDepthGlue:

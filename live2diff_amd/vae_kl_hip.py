@@ -8,7 +8,7 @@ and `vae.decode(z, return_dict=False)[0]` (:322), and reads `vae.config.scaling_
 
 The network (block_out_channels 128, 256, 512, 512; 2 resnets per encoder level, 3 per decoder level; GroupNorm 32 / eps 1e-6;
 one single-head attention of d = 512 in each mid block) runs on the UNet's kernels, one static plan per (side, batch, H, W):
-  * channels-last fp16 activations `[B*H*W, C]` from an `_Arena`; the image / latent are padded to 8 channels by the layout op;
+  * channels-last fp16 activations `[B*H*W, C]` from the plan's `Arena`; the image / latent are padded to 8 channels by the layout op;
   * resnet: the GroupNorm statistics come from the epilogue of the op that wrote x (`ops.gn_target`); where `ops.cconv_ok`
     holds the conv is `cconv` with its GroupNorm + SiLU prologue, elsewhere `gn_apply` + the implicit-GEMM / patch conv (the
     `gn_stats` / one-launch forms when no producer can take the statistics); conv2 adds the shortcut (a 1x1 igemm when the
@@ -29,7 +29,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import _lib, ops
-from .unet_hip import _Act, _Arena
+from .plan import Act, PlanBuilder
 
 BLOCK_OUT = (128, 256, 512, 512)
 ENC_LAYERS, DEC_LAYERS = 2, 3
@@ -243,80 +243,21 @@ class HipAutoencoderKL:
     def _build(self, side: str, B: int, H: int, W_: int):
         """side 'enc': static input [B,3,H,W] -> moments [B,8,H/8,W/8]; 'dec': [B,4,h,w] latent -> [B,3,8h,8w]."""
         dev = self.device
-        ar = _Arena(dev)
-        pl = _lib.OpList()
-        st = SimpleNamespace(pl=pl, arena=ar, B=B, kinds={}, gn_layers=0, gn_fallback=0, cconv_gn=0)
-        st.sk_cnt, st.sk_used = torch.zeros(1 << 16, dtype=torch.int32, device=dev), 0
-        st.gn_acc = torch.zeros(96, B, GROUPS, 2, dtype=torch.int64, device=dev)
-        st.gn_zero = torch.zeros_like(st.gn_acc)
-        ident = {}
+        st = PlanBuilder(dev, B, sk_counters=1 << 16, gn_layers=96, G=GROUPS)
+        st.cconv_gn = 0
+        ar, add, gemm, new_act, free = st.arena, st.add, st.gemm, st.act, st.free
 
-        def add(opk):
-            op, keep = opk
-            pl.append(op, *keep)
-            st.kinds[op.kind] = st.kinds.get(op.kind, 0) + 1
-            return op
-
-        add(ops.copy(st.gn_zero, st.gn_acc, st.gn_acc.numel() * 8))
-
-        def new_act(C, h, w, ld=None):
-            return _Act(ar.alloc(B * h * w * (ld or C)), C, h, w)
-
-        def free(a: Optional[_Act]):
-            if a is not None:
-                ar.release(a.buf)
-
-        def gemm(x1, wt, out, **kw):
-            """igemm with its schedule; split-K workspaces from the arena, fused-reduction counters from st.sk_cnt"""
-            taps, epi = kw.get("taps", 1), kw.get("epi", 0)
-            tile, S, variant = ops.igemm_schedule(kw["M"], kw["Nout"], taps * kw["CinP"], 1, epi, taps)
-            if variant in (6, 7) and kw["CinP"] % 128:
-                variant = 1
-            if tile == 1 and variant in (7, 8, 9):
-                variant = 5
-            ws, cnt_kw = None, {}
-            if ops.splitk_fused(S):
-                n_ws, n_cnt = ops.splitk_sizes(kw["M"], kw["Nout"], S, 1, tile)
-                ws = ar.alloc(n_ws, torch.float32)
-                cnt_kw = dict(cnt=st.sk_cnt, cnt_off=st.sk_used)
-                st.sk_used += n_cnt
-            elif S > 1:
-                ws = ar.alloc(S * kw["M"] * ops.round_up(kw["Nout"], 4), torch.float32)
-            order = int(kw["Nout"] * taps * kw["CinP"] > kw["M"] * kw["C1"])
-            op = add(ops.igemm(x1, wt, out, splitk=S, tile=tile, ws=ws, variant=variant, order=order, **cnt_kw, **kw))
-            ar.release(ws)
-            return op
-
-        def gn_acc_of(x: _Act):
+        def gn_acc_of(x: Act):
             """ask x's producer to accumulate this GroupNorm's statistics; the accumulator pointer or None"""
-            if x.producer is None or st.gn_layers >= st.gn_acc.shape[0]:
-                return None
-            acc_ptr = st.gn_acc.data_ptr() + st.gn_layers * B * GROUPS * 2 * 8
-            if ops.gn_target(x.producer, acc_ptr, T=x.H * x.W, G=GROUPS, cpg=x.C // GROUPS, choff=0):
-                st.gn_layers += 1
-                return acc_ptr
-            return None
+            return st.gn_acc_for([(x.producer, 0)], T=x.H * x.W, cpg=x.C // GROUPS)
 
-        def gn(x: _Act, name, silu, acc_ptr=None) -> _Act:
-            T = x.H * x.W
+        def gn(x: Act, name, silu, acc_ptr=None) -> Act:
             out = new_act(x.C, x.H, x.W)
-            gam, bet = self.sd[name + ".weight"], self.sd[name + ".bias"]
-            kw = dict(B=B, T=T, C1=x.C, ld1=x.C, G=GROUPS, eps=EPS, silu=silu)
-            if acc_ptr is not None:
-                add(ops.gn_apply(x.buf, None, gam, bet, out.buf, nchunk=0, acc_ptr=acc_ptr, **kw))
-            elif ops.gn_self_ok(T, x.C, GROUPS):
-                st.gn_fallback += 1
-                add(ops.gn_apply(x.buf, None, gam, bet, out.buf, nchunk=0, **kw))
-            else:
-                st.gn_fallback += 1
-                nchunk = max(1, min(64, T // 16))
-                partial = ar.alloc(B * nchunk * GROUPS * 2, torch.float32)
-                add(ops.gn_stats(x.buf, partial, B=B, T=T, C1=x.C, ld1=x.C, G=GROUPS, nchunk=nchunk))
-                add(ops.gn_apply(x.buf, partial, gam, bet, out.buf, nchunk=nchunk, **kw))
-                ar.release(partial)
+            st.groupnorm(x.buf, self.sd[name + ".weight"], self.sd[name + ".bias"], out.buf, T=x.H * x.W, C1=x.C, eps=EPS, act=silu,
+                         acc_ptr=acc_ptr)
             return out
 
-        def conv3(x: _Act, name, stride=1, ups=0, res: Optional[_Act] = None, gn_name=None, ldo=None) -> _Act:
+        def conv3(x: Act, name, stride=1, ups=0, res: Optional[Act] = None, gn_name=None, ldo=None) -> Act:
             """3x3 conv (of silu(GroupNorm(x)) when gn_name is given)"""
             cout = self.sd[name + ".weight"].shape[0]
             Ho, Wo = (x.H * 2, x.W * 2) if ups else ((x.H // 2, x.W // 2) if stride == 2 else (x.H, x.W))
@@ -325,19 +266,13 @@ class HipAutoencoderKL:
             if stride == 1 and ops.cconv_ok(Ho, Wo, cout, x.C) and (gn_name is None or acc_ptr is not None):
                 out = new_act(cout, Ho, Wo)
                 sched = ops.cconv_schedule(B, Ho, Wo, cout, x.C)
-                ws_buf, kw = None, {}
-                if sched[3] > 1:
-                    n_ws, n_cnt = ops.cconv_sizes(B, Ho, Wo, cout, sched[0], sched[3])
-                    ws_buf = ar.alloc(n_ws, torch.float32)
-                    kw = dict(ws=ws_buf, cnt=st.sk_cnt, cnt_off=st.sk_used)
-                    st.sk_used += n_cnt
+                kw = {}
                 if gn_name is not None:
                     st.cconv_gn += 1
                     kw.update(gn_acc_ptr=acc_ptr, gn_gamma=self.sd[gn_name + ".weight"], gn_beta=self.sd[gn_name + ".bias"],
                               gn_G=GROUPS, gn_eps=EPS)
-                out.producer = add(ops.cconv(x.buf, self._cconv_w(name, sched[1]), out.buf, B=B, H=Ho, W=Wo, C1=x.C, ldx1=x.C,
-                                             Nout=cout, ldo=cout, KG=sched[1], ups=ups, bias=self._bias(name), sched=sched, **rk, **kw))
-                ar.release(ws_buf)
+                out.producer = st.cconv(x.buf, self._cconv_w(name, sched[1]), out.buf, B=B, H=Ho, W=Wo, C1=x.C, ldx1=x.C,
+                                        Nout=cout, ldo=cout, KG=sched[1], ups=ups, bias=self._bias(name), sched=sched, **rk, **kw)
                 return out
             hn = gn(x, gn_name, True, acc_ptr) if gn_name else x
             wt = self._conv3_w(name)
@@ -356,14 +291,14 @@ class HipAutoencoderKL:
                 free(hn)
             return out
 
-        def linear(x: _Act, wt, bias, nout, res: Optional[_Act] = None, ldo=None) -> _Act:
+        def linear(x: Act, wt, bias, nout, res: Optional[Act] = None, ldo=None) -> Act:
             ldo = ldo or nout
             out = new_act(nout, x.H, x.W, ld=ldo)
             out.producer = gemm(x.buf, wt, out.buf, M=B * x.H * x.W, Nout=nout, C1=x.C, ldx1=x.C, CinP=wt.shape[1], ldo=ldo,
                                 bias=bias, res=(res.buf if res is not None else None), ldr=(res.C if res is not None else 0))
             return out
 
-        def resnet(x: _Act, p) -> _Act:
+        def resnet(x: Act, p) -> Act:
             h1 = conv3(x, p + ".conv1", gn_name=p + ".norm1")
             sc = None
             if (p + ".conv_shortcut.weight") in self.sd:
@@ -374,7 +309,7 @@ class HipAutoencoderKL:
             free(x)
             return out
 
-        def attention(x: _Act, p) -> _Act:
+        def attention(x: Act, p) -> Act:
             T = x.H * x.W
             hn = gn(x, p + ".group_norm", ops.ACT_NONE, gn_acc_of(x))
             wqkv, bqkv = self._qkv(p)
@@ -394,7 +329,7 @@ class HipAutoencoderKL:
             free(x)
             return out
 
-        def mid(x: _Act, p) -> _Act:
+        def mid(x: Act, p) -> Act:
             x = resnet(x, p + ".resnets.0")
             x = attention(x, p + ".attentions.0")
             return resnet(x, p + ".resnets.1")
@@ -441,9 +376,7 @@ class HipAutoencoderKL:
             st.out = torch.zeros(B, 3, y.H * y.W, dtype=torch.float16, device=dev)
             add(ops.nhwc_to_nchw(y.buf, st.out, B=B, C=3, HW=y.H * y.W, ld=4))
             st.out_shape = (B, 3, y.H, y.W)
-        assert st.sk_used <= st.sk_cnt.numel()
-        st.arena_bytes = ar.nbytes()
-        return st
+        return st.finish()
 
     def _plan(self, side, B, H, W_):
         if side == "enc" and (H % 8 or W_ % 8):
@@ -487,6 +420,6 @@ class HipAutoencoderKL:
 
     def plan_summary(self):
         names = {v: k[3:].lower() for k, v in vars(_lib).items() if k.startswith("OP_") and isinstance(v, int)}
-        return {k: dict(n_ops=len(st.pl), arena_bytes=st.arena_bytes, batch=st.B, gn_fused=st.gn_layers, gn_fallback=st.gn_fallback,
-                        cconv_gn=st.cconv_gn, kinds={names.get(kd, kd): n for kd, n in sorted(st.kinds.items())})
+        return {k: dict(st.summary(), batch=st.B, gn_fallback=st.gn_self_launches + st.gn_stats_launches, cconv_gn=st.cconv_gn,
+                        kinds={names.get(kd, kd): n for kd, n in sorted(st.kinds.items())})
                 for k, st in self._plans.items()}

@@ -691,3 +691,33 @@ def test_cconv_patch_image_is_bank_conflict_free():
                             addr = p * 128 + ((q ^ (((p % 18) >> 1) & 7)) * 16)
                             slots.add((addr // 16) % 16)
                         assert len(slots) == 16, (kk, dy, dx, mt, g)
+
+
+def test_groupnorm_statistics_attach_to_all_producers_or_none(dry_run):
+    """PlanBuilder.gn_acc_for: a concat GroupNorm's statistics come from BOTH producers or from neither; a refused request leaves
+    no producer changed (ops.gn_target_ok checks without claiming), and an op serves at most two consumers of one (T, G)."""
+    from live2diff_amd import ops
+    from live2diff_amd.plan import PlanBuilder
+    st = PlanBuilder("cpu", 4, sk_counters=16, gn_layers=3, G=32)
+    x, w, o = (torch.zeros(256 * 64, dtype=torch.float16) for _ in range(3))
+
+    def igemm(tile):
+        return st.add(ops.igemm(x, w, o, M=256, Nout=64, C1=64, ldx1=64, CinP=64, ldo=64, tile=tile, variant=1))
+
+    def fields(op):
+        return [op.p[9], op.p[10]] + list(op.i[24:30])
+
+    a, b, c = igemm(2), igemm(1), igemm(2)             # 64-row tiles, 128-row tiles, 64-row tiles
+    clean = fields(a)
+    assert ops.gn_target_ok(a, T=64, G=32, cpg=4, choff=0) and fields(a) == clean
+    assert not ops.gn_target_ok(b, T=64, G=32, cpg=4, choff=64)                  # a 128-row tile straddles 64-token samples
+    assert st.gn_acc_for([(a, 0), (b, 64)], T=64, cpg=4) is None and fields(a) == clean and st.gn_layers == 0
+    assert st.gn_acc_for([(a, 0), (None, 64)], T=64, cpg=4) is None and fields(a) == clean
+    p0 = st.gn_acc_for([(a, 0), (c, 64)], T=64, cpg=4)
+    assert p0 == st.gn_acc.data_ptr() and st.gn_layers == 1
+    assert fields(a) == [p0, None, 64, 32, 4, 0, 0, 0] and fields(c) == [p0, None, 64, 32, 4, 64, 0, 0]
+    assert st.gn_acc_for([(a, 0)], T=128, cpg=2) is None and st.gn_layers == 1   # slot 0 holds another T
+    p1 = st.gn_acc_for([(a, 0)], T=64, cpg=2)
+    assert p1 == p0 + 4 * 32 * 16 and fields(a) == [p0, p1, 64, 32, 4, 0, 2, 0]
+    assert st.gn_acc_for([(a, 0), (c, 64)], T=64, cpg=4) is None and fields(c)[1] is None and st.gn_layers == 2     # a is full
+    assert st.finish()._zero_op.l[0] == 2 * 4 * 32 * 16 and st.kinds == {13: 1, 1: 3}
