@@ -309,6 +309,18 @@ enum {
  *   (3 this + last + 8) >> 4 / (3 this + next + 7) >> 4; edges copied, the bottom edge from the last REAL row; replication for planes
  *   of one or two columns) and its 16-bit fixed-point colour conversion:  p0 planes (as above, mx = ceil(W / 8 hs), my = ceil(H / 8 vs))
  *   p1 out uint8 [H][W][3] ; i0 H i1 W i2 hs i3 vs
+ *
+ * Style switch / style blend (wblend.hip; the reference changes style by building a new wrapper and a new engine).
+ * L2D_OP_WEIGHT_BLEND  dst_t = sum_k a_k src_{k,t} over every tensor t of a packed weight set, ONE launch however many tensors:
+ *   p0 table of l2d_wblend_rec in DEVICE memory (16-byte aligned) p1 the same table in HOST memory (read by the launcher only, to
+ *   validate) ; i0 number of records i1 K (1..4 sources) i2 cache policy (0 plain loads / stores, 1 non-temporal) ; f0..f3 the
+ *   weights a_k (finite).  A record is one TILE of one tensor (below): the host cuts every tensor into tiles of at most
+ *   L2D_WBLEND_TILE_BYTES, a work-group takes records blockIdx.x, blockIdx.x + gridDim.x, ...  Arithmetic, fixed so that numpy restates
+ *   it bit for bit (style_bank.blend_ref): acc = a_0 s_0, then acc = acc + a_k s_k for k = 1, 2, ... in source order, every product
+ *   and every sum rounded to fp32 on its own (no fma), one round-to-nearest-even to the tensor's dtype at the end; K = 1 with
+ *   a_0 = 1 is a copy, and moves the bits as they are (1 x would quieten a signalling NaN in padding nobody initialised).  16-byte accesses over the whole vectors of a tile, one lane per element for the up to 7 elements behind
+ *   them; nothing outside [dst, dst + n elements) is written.  Refused: a null or not 16-byte aligned dst / src[k < K], n <= 0 or
+ *   more than a tile, an unknown dtype, K outside 1..4, a non-finite weight.  dst may be one of the sources (same offsets only).
  */
 enum {
     L2D_OP_IGEMM = 1,
@@ -352,6 +364,7 @@ enum {
     L2D_OP_JPEG_ENTROPY_DEC = 39,
     L2D_OP_JPEG_IDCT = 40,
     L2D_OP_JPEG_RGB = 41,
+    L2D_OP_WEIGHT_BLEND = 42,
 };
 
 typedef struct l2d_op {
@@ -362,6 +375,19 @@ typedef struct l2d_op {
     int64_t l[4];
     float f[4];
 } l2d_op;
+
+/* One record of L2D_OP_WEIGHT_BLEND's table: one tile of one tensor, 64 bytes.  src[k] for k >= K is ignored. */
+#define L2D_WBLEND_MAX_SRC 4
+#define L2D_WBLEND_TILE_BYTES 65536 /* a multiple of 16: every tile of an aligned tensor is aligned */
+#define L2D_WBLEND_F16 0
+#define L2D_WBLEND_F32 1
+typedef struct l2d_wblend_rec {
+    void *dst;
+    const void *src[L2D_WBLEND_MAX_SRC];
+    int64_t n;            /* elements of this tile: 1 .. L2D_WBLEND_TILE_BYTES / element size */
+    int32_t dtype;        /* L2D_WBLEND_F16 | L2D_WBLEND_F32 */
+    int32_t pad[3];
+} l2d_wblend_rec;
 
 /* library / device ------------------------------------------------------------------------------ */
 int l2d_abi_version(void);

@@ -25,6 +25,7 @@ OP_VAE_ATTN, OP_VAE_POSTERIOR = 32, 33
 OP_FRAME_INGEST, OP_FRAME_EGRESS = 34, 35
 OP_JPEG_DCT, OP_JPEG_HUFF, OP_JPEG_PACK = 36, 37, 38
 OP_JPEG_ENTROPY_DEC, OP_JPEG_IDCT, OP_JPEG_RGB = 39, 40, 41
+OP_WEIGHT_BLEND = 42
 ABI_VERSION = 6
 
 

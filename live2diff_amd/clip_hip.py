@@ -145,8 +145,49 @@ class HipClipTextEncoder:
                 L[f"ln{n}.g"], L[f"ln{n}.b"] = f32(p + f"layer_norm{n}.weight"), f32(p + f"layer_norm{n}.bias")
             self.layers.append(L)
         self.ln_g, self.ln_b = f32("final_layer_norm.weight"), f32("final_layer_norm.bias")
+        from .unet_hip import own_storage
+        top = {"tok": self.tok, "pos": self.pos, "ln_g": self.ln_g, "ln_b": self.ln_b}
+        for d in [top] + self.layers:                  # (load_mix overwrites these in place: never the caller's tensors)
+            own_storage(d, sd)
+        self.tok, self.pos, self.ln_g, self.ln_b = top["tok"], top["pos"], top["ln_g"], top["ln_b"]
         self.layer_weight_bytes = sum(t.numel() * t.element_size() for L in self.layers for t in L.values())
         self._plans = {}
+        self._blender = None
+
+    # ------------------------------------------------------------------ packed weights / style switch (style_bank.py)
+    def _flat(self) -> Dict[str, torch.Tensor]:
+        W = {"tok": self.tok, "pos": self.pos, "ln_g": self.ln_g, "ln_b": self.ln_b}
+        for i, L in enumerate(self.layers):
+            for k, t in L.items():
+                W[f"layers.{i}.{k}"] = t
+        return W
+
+    def _packed_meta(self) -> dict:
+        return dict(kind="clip_text", abi=str(_lib.ABI_VERSION), config=json.dumps(self.cfg.__dict__, sort_keys=True))
+
+    def packed_state(self):
+        """The packed weights of this instance as (tensors, metadata): `tok`, `pos`, every tensor of `layers[i]`, `ln_g`, `ln_b`."""
+        from .unet_hip import PackedWeights
+        return PackedWeights(self._flat(), self._packed_meta())
+
+    def load_mix(self, sets, weights) -> None:
+        """Overwrite the weights IN PLACE with sum_k weights[k] * sets[k] (each the `packed_state()` of an encoder of this
+        configuration), one launch on the current stream.  Plans and captured graphs keep their pointers."""
+        from .style_bank import WeightBlender
+        from .unet_hip import PackedWeights
+        sets, weights = list(sets), list(weights)
+        own = self._packed_meta()
+        flat = self._flat()
+        for j, ps in enumerate(sets):
+            if not isinstance(ps, PackedWeights):
+                raise TypeError(f"load_mix: set {j} is {type(ps).__name__}, need PackedWeights (packed_state())")
+            if dict(ps.meta) != own:
+                raise ValueError(f"style set {j}: packed for text encoder {ps.meta}, this instance is {own}: re-pack from the state dict")
+            if any(ps.W.get(k) is t for k, t in flat.items()):
+                raise ValueError(f"load_mix: set {j} holds this instance's own tensors (the destination): blend from a copy")
+        if self._blender is None:
+            self._blender = WeightBlender(flat, self.device)
+        self._blender.apply([ps.W for ps in sets], weights)
 
     # ------------------------------------------------------------------ plan
     def _layers_run(self, clip_skip: Optional[int]) -> int:

@@ -1398,3 +1398,25 @@ def jpeg_rgb(planes, out, *, H, W, hs, vs):
     for j, v in enumerate([H, W, hs, vs]):
         op.i[j] = int(v)
     return op, (planes, out)
+
+
+# ----------------------------------------------------------------------------- style switch / blend (wblend.hip, style_bank.py)
+WBLEND_MAX_SRC = 4              # l2d.h L2D_WBLEND_MAX_SRC
+WBLEND_TILE_BYTES = 65536       # l2d.h L2D_WBLEND_TILE_BYTES
+WBLEND_DTYPES = {torch.float16: 0, torch.float32: 1}
+WBLEND_REC = np.dtype([("dst", "<u8"), ("src", "<u8", (4,)), ("n", "<i8"), ("dtype", "<i4"), ("pad", "<i4", (3,))])    # l2d_wblend_rec
+WBLEND_NT = 1                   # cache policy of the launch: 0 plain, 1 non-temporal -- the faster one for K = 1, 2, 3 (profiles/style_switch_time.txt)
+
+
+def weight_blend(table_dev, table_host, weights, *, nt=None):
+    """dst = sum_k weights[k] * src_k over every record of the table, one launch.  `table_dev`: the l2d_wblend_rec records as a
+    uint8 tensor on the device; `table_host`: the same records as a numpy array of WBLEND_REC (the launcher validates on it)."""
+    assert table_host.dtype == WBLEND_REC and table_host.flags["C_CONTIGUOUS"]
+    assert table_dev.dtype == torch.uint8 and table_dev.numel() == table_host.nbytes
+    op = L2dOp()
+    op.kind = _lib.OP_WEIGHT_BLEND
+    op.p[0], op.p[1] = _ptr(table_dev), table_host.ctypes.data
+    op.i[0], op.i[1], op.i[2] = len(table_host), len(weights), int(WBLEND_NT if nt is None else nt)
+    for k, a in enumerate(list(weights)[:4]):
+        op.f[k] = float(a)
+    return op, (table_dev, table_host)

@@ -69,6 +69,16 @@ class PackedWeights:
         self.W, self.meta = W, meta
 
 
+def own_storage(W: dict, state_dict) -> None:
+    """Packed tensors that are the state dict's own tensors or views of them (a state dict already on the device in the packed
+    dtype: `.to()`, `.contiguous()` and `reshape` copy nothing) are replaced by copies, in place in `W`.  `load_mix` overwrites
+    the packed tensors; it must reach neither the caller's state dict nor another instance packed from the same one."""
+    theirs = {v.untyped_storage().data_ptr() for v in state_dict.values() if torch.is_tensor(v) and v.numel()}
+    for k, t in W.items():
+        if torch.is_tensor(t) and t.numel() and t.untyped_storage().data_ptr() in theirs:
+            W[k] = t.clone()
+
+
 class HipStreamingUNet:
     def __init__(self, state_dict, cfg: UNetConfig, height: int, width: int,
                  denoising_steps_num: int, device="cuda", warmup_frames: Optional[int] = None, use_graph: bool = False,
@@ -110,6 +120,7 @@ class HipStreamingUNet:
                 raise ValueError(f"shared packed weights were packed for denoising_steps_num = {o.N} (weight-streaming levels "
                                  f"{o.ws_levels}), this instance has {self.N} ({self.ws_levels}): re-pack")
             self.W, self.temb_offsets, self.text_offsets = o.W, o.temb_offsets, o.text_offsets
+            self._w_gen = o._w_gen           # (shared together with W: a blend through any sharer makes every sharer's conditioning stale)
             self.n_map_blocks, self.temb_total, self.text_total, self.text_kp = o.n_map_blocks, o.temb_total, o.text_total, o.text_kp
         elif isinstance(state_dict, (str, os.PathLike)):
             self._load_packed(state_dict)          # a file written by save_packed(): skips the packing pass
@@ -117,8 +128,12 @@ class HipStreamingUNet:
             self._adopt_packed(state_dict.W, state_dict.meta, "packed weights")     # received from another rank
         else:
             self._pack_weights(state_dict)
+            own_storage(self.W, state_dict)
         self._plans = {}
         self._graph = {}
+        if not hasattr(self, "_w_gen"):
+            self._w_gen = [0]                # generation of the contents of W: bumped by load_mix
+        self._blender = None
 
     # ------------------------------------------------------------------ reference-compatible surface
     def to(self, *a, **k):
@@ -413,6 +428,33 @@ class HipStreamingUNet:
     def packed_state(self) -> "PackedWeights":
         """The packed weights of this instance as (tensors, metadata) -- what a packed-weight file holds, without the file."""
         return PackedWeights(self.W, self._packed_meta())
+
+    def load_mix(self, sets, weights) -> None:
+        """Overwrite the packed weights IN PLACE with sum_k weights[k] * sets[k] (each a `PackedWeights` of this configuration, stream
+        shape and kernel layout), one launch on the current stream (style_bank.WeightBlender).  Plans and captured graphs keep
+        their pointers and are not rebuilt; everything derived from weights at run time (time-embedding rows, text K / V^T) is
+        recomputed before the next frame of EVERY instance that shares this W.  The sets must not be this instance's own W."""
+        from .style_bank import WeightBlender
+        sets, weights = list(sets), list(weights)
+        own = self._packed_meta()
+        for j, ps in enumerate(sets):
+            if not isinstance(ps, PackedWeights):
+                raise TypeError(f"load_mix: set {j} is {type(ps).__name__}, need PackedWeights (packed_state())")
+            self._check_packed_meta(ps.meta, f"style set {j}")
+            for k in ("temb_offsets", "text_offsets", "n_map_blocks"):
+                if ps.meta.get(k) != own[k]:
+                    raise ValueError(f"style set {j}: {k} = {ps.meta.get(k)}, this instance has {own[k]}: re-pack from the state dict")
+            if ps.W is self.W:
+                raise ValueError(f"load_mix: set {j} is this instance's own W (the destination): blend from a copy")
+        if self._blender is None:
+            self._blender = WeightBlender(self.W, self.device)
+        self._blender.apply([ps.W for ps in sets], weights)
+        self._w_gen[0] += 1
+
+    def _cond_fresh(self, st) -> None:
+        """the conditioning launches read W: stale after a blend through any instance that shares it"""
+        if getattr(st, "w_gen", None) != self._w_gen[0]:
+            st.cond_key, st.w_gen = None, self._w_gen[0]
 
     def _load_packed(self, path) -> None:
         import json
@@ -1033,6 +1075,7 @@ class HipStreamingUNet:
         (re-bound only by update_prompt) and one `sub_timesteps_tensor` for the whole stream; a caller that builds fresh
         tensors every call simply gets the launches every call."""
         cfg = self.cfg
+        self._cond_fresh(st)
         key = (timestep, encoder_hidden_states, timestep._version, encoder_hidden_states._version)
         old = st.cond_key
         if (self.cond_cache and old is not None and len(old) == 4 and old[0] is key[0] and old[1] is key[1]
@@ -1045,6 +1088,7 @@ class HipStreamingUNet:
 
     def _ensure_cond(self, st):
         """For callers that own the static inputs (HipStreamStep): run the conditioning launches if they are stale."""
+        self._cond_fresh(st)
         if st.cond_key is None:
             st.cond_pl.run()
             st.cond_key = ("external",)

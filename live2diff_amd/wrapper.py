@@ -141,8 +141,7 @@ def load_prompt_encoder(model_dir: str, device, clip_skip, dreambooth=None, lora
     te = _need("pretrained_model_path", os.path.join(model_dir, "text_encoder"), os.path.isdir)
     with open(os.path.join(te, "config.json")) as f:
         ccfg = config_from_json(json.load(f))
-    has_te = dreambooth is not None and any(k.startswith(convert.LDM_CLIP_PREFIX) for k in dreambooth)
-    sd = convert.build_text_encoder_state_dict(load_tensors(_model_file(te)), dreambooth if has_te else None, loras)
+    sd = text_encoder_state_dict(model_dir, dreambooth, loras)
     tok = ClipTokenizer.from_dir(os.path.join(model_dir, "tokenizer"), max_length=ccfg.max_position_embeddings)
     return HipPromptEncoder(HipClipTextEncoder(sd, device, ccfg), tok, clip_skip)
 
@@ -158,17 +157,15 @@ def _style(cfg: dict, dreambooth_path, lora_dict):
     return dreambooth_path or third.get("dreambooth"), loras
 
 
-def load_components(cfg: dict, *, height: int, width: int, denoising_steps_num: int, device="cuda", dreambooth_path=None,
-                    lora_dict=None, few_step_model_type: str = "lcm", vae_id=None, use_tiny_vae: bool = True,
+def load_style_unet(cfg: dict, ucfg: UNetConfig, lat_h: int, lat_w: int, denoising_steps_num: int, *, device="cuda",
+                    dreambooth_path=None, lora_dict=None, few_step_model_type: str = "lcm",
                     engine_dir: Optional[Union[str, os.PathLike]] = "engines"):
-    """config dict -> the `pipe` namespace `StreamAnimateDiffusionDepth` takes (unet, vae, depth_model, `_encode_prompt`, scheduler)"""
-    from .midas_hip import HipMidas
+    """One style's `HipStreamingUNet` (through the packed-weight cache) plus its DreamBooth state dict and [(LoRA, strength)]: what
+    `load_components` builds the stream from and `add_style` a resident weight set."""
     from .unet_hip import HipStreamingUNet
     model_dir = _need("pretrained_model_path", cfg.get("pretrained_model_path"), os.path.isdir)
-    ucfg = load_unet_config(model_dir, cfg)
     db_path, loras = _style(cfg, dreambooth_path, lora_dict)
     name = Path(db_path).stem if db_path else "sd15"
-    lat_h, lat_w = height // 8, width // 8
     cache = None
     if engine_dir is not None:
         stem = HipStreamingUNet.packed_cache_name(name, few_step_model_type, ucfg.window_size, loras, lat_h, lat_w, denoising_steps_num)
@@ -195,6 +192,26 @@ def load_components(cfg: dict, *, height: int, width: int, denoising_steps_num: 
         if cache is not None:
             os.makedirs(os.path.dirname(cache), exist_ok=True)
             unet.save_packed(cache)
+    return unet, dreambooth, lora_sds
+
+
+def text_encoder_state_dict(model_dir: str, dreambooth=None, loras=None) -> dict:
+    """the text encoder's state dict with the style's text half merged in (converter/convert.py:47-50, 72-88)"""
+    te = _need("pretrained_model_path", os.path.join(model_dir, "text_encoder"), os.path.isdir)
+    has_te = dreambooth is not None and any(k.startswith(convert.LDM_CLIP_PREFIX) for k in dreambooth)
+    return convert.build_text_encoder_state_dict(load_tensors(_model_file(te)), dreambooth if has_te else None, loras)
+
+
+def load_components(cfg: dict, *, height: int, width: int, denoising_steps_num: int, device="cuda", dreambooth_path=None,
+                    lora_dict=None, few_step_model_type: str = "lcm", vae_id=None, use_tiny_vae: bool = True,
+                    engine_dir: Optional[Union[str, os.PathLike]] = "engines"):
+    """config dict -> the `pipe` namespace `StreamAnimateDiffusionDepth` takes (unet, vae, depth_model, `_encode_prompt`, scheduler)"""
+    from .midas_hip import HipMidas
+    model_dir = _need("pretrained_model_path", cfg.get("pretrained_model_path"), os.path.isdir)
+    ucfg = load_unet_config(model_dir, cfg)
+    unet, dreambooth, lora_sds = load_style_unet(cfg, ucfg, height // 8, width // 8, denoising_steps_num, device=device,
+                                                 dreambooth_path=dreambooth_path, lora_dict=lora_dict,
+                                                 few_step_model_type=few_step_model_type, engine_dir=engine_dir)
     clip_skip = (cfg.get("third_party_dict") or {}).get("clip_skip", 1)
     prompt_encoder = load_prompt_encoder(model_dir, device, clip_skip, dreambooth, lora_sds)
     if use_tiny_vae:
@@ -210,6 +227,21 @@ def load_components(cfg: dict, *, height: int, width: int, denoising_steps_num: 
                            text_encoder=prompt_encoder.encoder, tokenizer=prompt_encoder.tokenizer,
                            _encode_prompt=prompt_encoder._encode_prompt, unet_config=ucfg,
                            scheduler=SimpleNamespace(config=dict(cfg.get("noise_scheduler_kwargs") or {})))
+
+
+def build_style_sets(cfg: dict, like_unet, like_text, *, dreambooth_path=None, lora_dict=None, few_step_model_type: str = "lcm",
+                     engine_dir: Optional[Union[str, os.PathLike]] = "engines"):
+    """The packed weight sets (UNet, text encoder) of one style, through the path `load_components` takes: `build_state_dict` and
+    the packed-weight cache under the same `packed_cache_name`, `build_text_encoder_state_dict`.  They come from second, plan-less
+    instances of the configuration of `like_unet` / `like_text` (plans are built lazily: such an instance costs only its weights),
+    so the running instances are not disturbed."""
+    from .clip_hip import HipClipTextEncoder
+    unet, dreambooth, lora_sds = load_style_unet(cfg, like_unet.cfg, like_unet.h, like_unet.w, like_unet.N, device=like_unet.device,
+                                                 dreambooth_path=dreambooth_path, lora_dict=lora_dict,
+                                                 few_step_model_type=few_step_model_type, engine_dir=engine_dir)
+    tsd = text_encoder_state_dict(cfg["pretrained_model_path"], dreambooth, lora_sds)
+    text = HipClipTextEncoder(tsd, like_text.device, like_text.cfg, use_graph=False)
+    return unet.packed_state(), text.packed_state()
 
 
 def _is_jpeg(x) -> bool:
@@ -243,6 +275,7 @@ class StreamAnimateDiffusionDepthWrapper:
         pipe = load_components(cfg, height=height, width=width, denoising_steps_num=n, device=device,
                                dreambooth_path=dreambooth_path, lora_dict=lora_dict, few_step_model_type=few_step_model_type,
                                vae_id=vae_id, use_tiny_vae=use_tiny_vae, engine_dir=engine_dir)
+        self._style_src = dict(cfg=cfg, few_step_model_type=few_step_model_type, engine_dir=engine_dir)    # what add_style builds from
         self._setup(pipe, num_inference_steps=num_inference_steps, t_index_list=t_index_list, strength=strength,
                     output_type=output_type, device=device, dtype=dtype, width=width, height=height, do_add_noise=do_add_noise,
                     seed=seed, clip_skip=(cfg.get("third_party_dict") or {}).get("clip_skip", 1), warmup_frames=sink,
@@ -324,6 +357,100 @@ class StreamAnimateDiffusionDepthWrapper:
             from .frame_io import FrameProcessor, HipFrameIO
             self.io = HipFrameIO(height, width, device=pipe.device)
             self.stream.image_processor = FrameProcessor(self.io)
+        self._init_styles(pipe)
+
+    # ------------------------------------------------------------------ styles (style_bank.py)
+    def _init_styles(self, pipe) -> None:
+        """The style the wrapper was built with becomes "default", as a copy: the active weights are scratch that the next switch
+        overwrites.  Needs the native UNet and text encoder; with other components the bank stays empty and `set_style` refuses."""
+        from .clip_hip import HipClipTextEncoder
+        from .style_bank import StyleBank, clone_set
+        from .unet_hip import HipStreamingUNet
+        self._bank = StyleBank()
+        self._prompt = None
+        text = getattr(pipe, "text_encoder", None)
+        if text is None:
+            text = getattr(getattr(getattr(pipe, "_encode_prompt", None), "__self__", None), "encoder", None)
+        self._text_encoder = text if isinstance(text, HipClipTextEncoder) else None
+        if isinstance(self.stream.unet, HipStreamingUNet) and self._text_encoder is not None:
+            self._bank.add("default", clone_set(self.stream.unet.packed_state()), clone_set(self._text_encoder.packed_state()))
+            self._bank.current = {"default": 1.0}
+
+    def _need_bank(self):
+        if not self._bank.sets:
+            raise ValueError("styles need the native UNet and text encoder (HipStreamingUNet, HipClipTextEncoder)")
+        return self._bank
+
+    @property
+    def styles(self) -> List[str]:
+        """names of the registered styles"""
+        return self._bank.names
+
+    @property
+    def style(self) -> Dict[str, float]:
+        """the current mix as {name: weight}"""
+        return dict(self._bank.current)
+
+    def add_style(self, name: str, dreambooth_path: Optional[str] = None, lora_dict: Optional[Dict[str, float]] = None, *,
+                  unet_state_dict=None, text_state_dict=None) -> None:
+        """Register a style and keep its packed UNet and text-encoder sets resident.  From files: the path `load_components` takes
+        (`build_state_dict`, the packed-weight cache under the same name, `build_text_encoder_state_dict`).  From state dicts
+        (`from_components` callers): `unet_state_dict` in the reference's key names, `text_state_dict` in transformers'.  Either
+        way the sets come from second, plan-less instances; the running stream is not touched.  With `use_tiny_vae=False` a style
+        that carries its own VAE keeps the constructor's VAE."""
+        from .clip_hip import HipClipTextEncoder
+        from .unet_hip import HipStreamingUNet
+        bank = self._need_bank()
+        if not isinstance(name, str) or not name:
+            raise ValueError(f"style name {name!r}: use a non-empty string")
+        if name in bank.sets:
+            raise ValueError(f"style {name!r} is registered already: remove_style it first")
+        unet, text = self.stream.unet, self._text_encoder
+        from_sd = unet_state_dict is not None or text_state_dict is not None
+        if from_sd:
+            if dreambooth_path is not None or lora_dict is not None:
+                raise ValueError("add_style: give files (dreambooth_path / lora_dict) or state dicts, not both")
+            if unet_state_dict is None or text_state_dict is None:
+                raise ValueError("add_style: unet_state_dict and text_state_dict go together")
+            usrc = HipStreamingUNet(unet_state_dict, unet.cfg, unet.h, unet.w, unet.N, device=unet.device)
+            tsrc = HipClipTextEncoder(text_state_dict, text.device, text.cfg, use_graph=False)
+            sets = (usrc.packed_state(), tsrc.packed_state())
+        else:
+            src = getattr(self, "_style_src", None)
+            if src is None:
+                raise ValueError("add_style: this wrapper was made from components, not from a config: pass unet_state_dict and "
+                                 "text_state_dict")
+            sets = build_style_sets(src["cfg"], unet, text, dreambooth_path=dreambooth_path, lora_dict=lora_dict,
+                                    few_step_model_type=src["few_step_model_type"], engine_dir=src["engine_dir"])
+        bank.add(name, *sets)
+
+    def remove_style(self, name: str) -> None:
+        """Forget a style and free its sets; a style that is part of the current mix is refused."""
+        bank = self._need_bank()
+        sets = bank.sets.get(name)
+        bank.remove(name)
+        for inst, ps in zip((self.stream.unet, self._text_encoder), sets):
+            if inst._blender is not None:
+                inst._blender.forget(ps.W)             # (a blend table keeps the sets it reads alive)
+
+    def set_style(self, style) -> None:
+        """Switch to a registered style (a name) or to an affine mix of up to four ({name: weight}, weights summing to 1) between
+        two frames: one blend launch each over the UNet's and the text encoder's packed weights on the current stream, then the
+        current prompt re-encoded by the new text encoder and handed to the stream like `update_prompt` does.  No plan or graph is
+        rebuilt; the VAE, the depth detector, the KV caches, the stream batch, the ring state and the noise counter are not
+        touched.  Takes effect with the next frame, in `__call__` and in push / pop mode (the side stream of `push` never touches
+        these weights).  K / V of earlier frames were projected by the old weights: window slots age out within `window_size`
+        frames -- that is the cross-fade -- and the sink slots written by `prepare` keep the old projections until `prepare` runs
+        again."""
+        from .style_bank import drop_zero_terms, parse_style
+        bank = self._need_bank()
+        mix = parse_style(style, bank.sets)
+        names, weights = drop_zero_terms(list(mix), list(mix.values()))
+        self.stream.unet.load_mix([bank.sets[n][0] for n in names], weights)
+        self._text_encoder.load_mix([bank.sets[n][1] for n in names], weights)
+        bank.current = dict(zip(names, weights))
+        if self._prompt is not None:
+            self.stream.update_prompt(self._prompt)
 
     # ------------------------------------------------------------------ prepare
     def prepare(self, warmup_frames, prompt: str, negative_prompt: str = "", guidance_scale: float = 1.2, delta: float = 1.0) -> torch.Tensor:
@@ -331,6 +458,7 @@ class StreamAnimateDiffusionDepthWrapper:
         of JPEG files of one size (decoded like `img2img`'s, then the uint8 route).
         Returns the generated warm-up frames, [F,H,W,3] in [0, 1] (wrapper.py:197-199)."""
         kw = dict(prompt=prompt, negative_prompt=negative_prompt, guidance_scale=guidance_scale, delta=delta, seed=self.seed)
+        self._prompt = prompt
         if isinstance(warmup_frames, (list, tuple)) and warmup_frames and all(_is_jpeg(f) for f in warmup_frames):
             # (a device frame is a view of one of the decoder's two static slots: it is copied before the slot's next turn)
             decoded = [d.clone() if torch.is_tensor(d) else torch.from_numpy(d).to(self.io.device) if self.io is not None else d
@@ -370,13 +498,13 @@ class StreamAnimateDiffusionDepthWrapper:
         device, then treated as that uint8 frame; a damaged scan raises ValueError where the output is fetched), or a float
         [3,H,W] tensor in [0, 1] (the reference's input)."""
         if prompt is not None:
-            self.stream.update_prompt(prompt)
+            self._update_prompt(prompt)
         return self.postprocess_image(self.stream(self.preprocess_image(image)), output_type=self.output_type)
 
     def push(self, image, prompt: Optional[str] = None) -> None:
         """pipelined mode (`frame_pipelining=True`): start a frame's encode / depth path; `pop()` returns the oldest frame's output"""
         if prompt is not None:
-            self.stream.update_prompt(prompt)
+            self._update_prompt(prompt)
         self.stream.push(self.preprocess_image(image))
         if self.io is not None and self.io.last_view is not None:
             # push() ran the ingest on this stream before ordering the side stream behind it; the side stream reads the slot
@@ -385,6 +513,10 @@ class StreamAnimateDiffusionDepthWrapper:
 
     def pop(self):
         return self.postprocess_image(self.stream.pop(), output_type=self.output_type)
+
+    def _update_prompt(self, prompt: str) -> None:
+        self.stream.update_prompt(prompt)
+        self._prompt = prompt              # (what set_style re-encodes with the new text encoder)
 
     def _decode_jpeg(self, data):
         """a JPEG file -> its uint8 [Hs,Ws,3] frame: a device tensor (a view of a static slot of `jpeg_io.HipJpegDecoder`), or Pillow's

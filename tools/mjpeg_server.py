@@ -14,8 +14,14 @@ the device (jpeg_io.HipJpegEncoder): what crosses to the host is the JPEG file.
 `bytes_to_pil`): the page captures the camera with `getUserMedia`, draws it on a canvas and sends every frame as the body of
 `POST /frame`; the wrapper takes the bytes as they are (decoded on the device, jpeg_io.HipJpegDecoder).  The first `sink` frames
 posted are the warm-up; after that the producer always takes the NEWEST posted frame, and a frame that raises (a damaged file)
-is dropped and counted."""
+is dropped and counted.
+
+`--style NAME=DREAMBOOTH[,LORA:ALPHA...]` (repeatable) registers further styles beside the config's own (`"default"`); their packed
+weights stay resident on the device.  `POST /style` with a JSON body `{name: weight}` (up to four names, weights summing to 1)
+switches or blends the running stream: the producer thread applies it between two frames (`wrapper.set_style`), without a
+re-warm.  `GET /style` answers `{"styles": [...], "current": {...}}`."""
 import argparse
+import json
 import os
 import sys
 import threading
@@ -86,6 +92,52 @@ class Inbox:
             return data
 
 
+class StyleBox:
+    """What `POST /style` delivers: the newest requested mix, applied by the producer between two frames.  `names` are the styles the
+    wrapper knows; `current` is the mix last applied; `failed` counts requests the wrapper refused."""
+
+    def __init__(self, names, current=None):
+        self._lock = threading.Lock()
+        self.names, self.current, self._want, self.failed = list(names), dict(current or {}), None, 0
+
+    def put(self, mix: dict) -> None:
+        with self._lock:
+            self._want = dict(mix)
+
+    def take(self):
+        with self._lock:
+            mix, self._want = self._want, None
+            return mix
+
+    def apply(self, wrapper) -> None:
+        """(producer thread, between frames)"""
+        mix = self.take()
+        if mix is None:
+            return
+        try:
+            wrapper.set_style(mix)
+            self.current = dict(wrapper.style)
+        except (KeyError, ValueError):
+            self.failed += 1
+
+
+def parse_style_arg(text: str):
+    """`NAME=DREAMBOOTH[,LORA:ALPHA...]` -> (name, dreambooth path or None, {lora path: alpha})"""
+    name, eq, rest = text.partition("=")
+    if not eq or not name:
+        raise ValueError(f"--style {text!r}: use NAME=DREAMBOOTH[,LORA:ALPHA...]")
+    db, *loras = rest.split(",")
+    lora_dict = {}
+    for item in loras:
+        path, colon, alpha = item.rpartition(":")
+        if not colon or not path:
+            raise ValueError(f"--style {text!r}: a LoRA is written LORA:ALPHA, got {item!r}")
+        lora_dict[path] = float(alpha)
+    if not db and not lora_dict:
+        raise ValueError(f"--style {text!r}: names neither a DreamBooth file nor a LoRA")
+    return name, (db or None), lora_dict
+
+
 class Latest:
     """The newest part and its sequence number.  `put` replaces it; `wait(seen)` blocks until there is a part newer than `seen`
     and returns `(seq, part)`, or None once the stream is closed and nothing newer is left."""
@@ -110,7 +162,7 @@ class Latest:
             return (self._seq, self._part) if self._seq > seen else None
 
 
-def make_handler(latest: Latest, inbox: "Inbox" = None):
+def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = None):
     page = PAGE if inbox is None else CAMERA_PAGE
 
     class Handler(BaseHTTPRequestHandler):
@@ -142,10 +194,39 @@ def make_handler(latest: Latest, inbox: "Inbox" = None):
                         self.wfile.flush()
                 except (BrokenPipeError, ConnectionResetError):
                     pass                       # the viewer went away
+            elif self.path == "/style" and styles is not None:
+                body = json.dumps({"styles": styles.names, "current": styles.current}).encode()
+                self.send_response(200)
+                self.send_header("Content-Type", "application/json")
+                self.send_header("Content-Length", str(len(body)))
+                self.end_headers()
+                self.wfile.write(body)
             else:
                 self.send_error(404)
 
+        def do_style(self):
+            from live2diff_amd.style_bank import parse_style
+            try:
+                n = int(self.headers.get("Content-Length", ""))
+            except ValueError:
+                self.send_error(411)
+                return
+            if not 2 <= n <= 4096:
+                self.send_error(413 if n > 4096 else 400)
+                return
+            try:
+                mix = parse_style(json.loads(self.rfile.read(n).decode()), styles.names)
+            except (KeyError, ValueError) as e:           # (json.JSONDecodeError and UnicodeDecodeError are ValueErrors)
+                self.send_error(400, str(e.args[0] if e.args else e)[:200])
+                return
+            styles.put(mix)
+            self.send_response(204)
+            self.end_headers()
+
         def do_POST(self):
+            if self.path == "/style" and styles is not None:
+                self.do_style()
+                return
             if inbox is None or self.path != "/frame":
                 self.send_error(404)
                 return
@@ -168,19 +249,21 @@ def make_handler(latest: Latest, inbox: "Inbox" = None):
     return Handler
 
 
-def produce(wrapper, frames, latest: Latest, stop: threading.Event) -> None:
-    """the producer: loops `frames` through the wrapper until `stop` is set"""
+def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: StyleBox = None) -> None:
+    """the producer: loops `frames` through the wrapper until `stop` is set; a posted style is applied between two frames"""
     from live2diff_amd.jpeg import mjpeg_part
     try:
         i = 0
         while not stop.is_set():
+            if styles is not None:
+                styles.apply(wrapper)
             latest.put(mjpeg_part(wrapper(frames[i % len(frames)])))
             i += 1
     finally:
         latest.close()
 
 
-def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: threading.Event) -> None:
+def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: threading.Event, styles: StyleBox = None) -> None:
     """the producer of `--input post`: the first frames posted warm the stream up, then the newest posted frame goes through the
     wrapper, for ever; a frame the wrapper refuses (ValueError: a damaged file) is dropped and counted in `inbox.failed`"""
     from live2diff_amd.jpeg import mjpeg_part
@@ -193,6 +276,8 @@ def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: thr
             frame = inbox.take(timeout=0.5)
             if frame is None:
                 continue
+            if styles is not None:
+                styles.apply(wrapper)
             try:
                 latest.put(mjpeg_part(wrapper(frame)))
             except ValueError:
@@ -214,7 +299,10 @@ def main(argv=None):
     ap.add_argument("--quality", type=int, default=75)
     ap.add_argument("--engine-dir", default="engines")
     ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--style", action="append", default=[], metavar="NAME=DREAMBOOTH[,LORA:ALPHA...]",
+                    help="register a further style (repeatable); POST /style {name: weight} switches or blends between frames")
     args = ap.parse_args(argv)
+    style_args = [parse_style_arg(t) for t in args.style]
 
     from stream_frames import read_frames
 
@@ -229,15 +317,18 @@ def main(argv=None):
                                            t_index_list=cfg.get("t_index_list"), strength=cfg.get("strength"), output_type="jpeg",
                                            jpeg_quality=args.quality, height=args.height, width=args.width, seed=args.seed,
                                            engine_dir=args.engine_dir)
+    for name, db, loras in style_args:
+        w.add_style(name, dreambooth_path=db, lora_dict=loras or None)
+    styles = StyleBox(w.styles, w.style)
     prompt = args.prompt if args.prompt is not None else str(cfg.get("prompt", ""))
     latest, stop = Latest(), threading.Event()
     inbox = Inbox(sink) if post else None
     if post:
-        producer = threading.Thread(target=produce_posted, args=(w, prompt, inbox, latest, stop), name="producer", daemon=True)
+        producer = threading.Thread(target=produce_posted, args=(w, prompt, inbox, latest, stop, styles), name="producer", daemon=True)
     else:
         w.prepare(frames[:sink], prompt)
-        producer = threading.Thread(target=produce, args=(w, frames, latest, stop), name="producer", daemon=True)
-    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest, inbox))
+        producer = threading.Thread(target=produce, args=(w, frames, latest, stop, styles), name="producer", daemon=True)
+    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest, inbox, styles))
     server.daemon_threads = True
     producer.start()
     print(f"http://{args.host}:{args.port}/  ({args.height}x{args.width}, quality {args.quality}; Ctrl-C stops)")
