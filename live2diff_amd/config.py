@@ -5,7 +5,7 @@ Mirrors the constructor arguments of the reference's `UNet3DConditionStreamingMo
 configs/base_config.yaml:6-28) restricted to the values the Live2Diff path actually uses.
 """
 from dataclasses import dataclass, field
-from typing import List, Tuple
+from typing import List, NamedTuple, Tuple
 
 
 @dataclass(frozen=True)
@@ -50,6 +50,40 @@ def tiny_config(window_size: int = 16, sink_size: int = 8, channels=(64, 128, 25
                       temporal_max_len=max(24, window_size))
 
 
+class Block(NamedTuple):
+    kind: str           # "resnet" | "spatial" | "motion" | "down" (down-sampler conv) | "up" (up-sampler conv)
+    name: str           # the reference's module name
+    level: int          # the block's input has resolution 2^-level
+    channels: int       # output channels
+    skip: str = ""      # "push": the output is also a skip connection; "pop": a resnet that takes one as its second input
+
+
+def unet_blocks(cfg: UNetConfig) -> List[Block]:
+    """The blocks between the input convolutions and conv_norm_out, in execution order (down -> mid -> up): what the HIP
+    backend's weight packer and plan builder both walk.  (weights.unet_param_spec and the oracle restate the topology
+    independently, on purpose.)"""
+    nl, ch = cfg.num_levels, cfg.block_out_channels
+    out = []
+    for i, c in enumerate(ch):
+        for j in range(cfg.layers_per_block):
+            out.append(Block("resnet", f"down_blocks.{i}.resnets.{j}", i, c))
+            if i != nl - 1:
+                out.append(Block("spatial", f"down_blocks.{i}.attentions.{j}", i, c))
+            out.append(Block("motion", f"down_blocks.{i}.motion_modules.{j}", i, c, "push"))
+        if i != nl - 1:
+            out.append(Block("down", f"down_blocks.{i}.downsamplers.0.conv", i, c, "push"))
+    out += [Block(k, f"mid_block.{n}", nl - 1, ch[-1]) for k, n in (("resnet", "resnets.0"), ("spatial", "attentions.0"), ("resnet", "resnets.1"))]
+    for i, c in enumerate(reversed(ch)):
+        for j in range(cfg.layers_per_block + 1):
+            out.append(Block("resnet", f"up_blocks.{i}.resnets.{j}", nl - 1 - i, c, "pop"))
+            if i != 0:
+                out.append(Block("spatial", f"up_blocks.{i}.attentions.{j}", nl - 1 - i, c))
+            out.append(Block("motion", f"up_blocks.{i}.motion_modules.{j}", nl - 1 - i, c))
+        if i != nl - 1:
+            out.append(Block("up", f"up_blocks.{i}.upsamplers.0.conv", nl - 1 - i, c))
+    return out
+
+
 def motion_module_layout(cfg: UNetConfig, h: int, w: int) -> List[Tuple[int, int, int, int]]:
     """(channels, h, w, level) of every temporal attention, in `motion_module_idx` order.
 
@@ -59,17 +93,12 @@ def motion_module_layout(cfg: UNetConfig, h: int, w: int) -> List[Tuple[int, int
     resolution 2^-i; up block i has `layers_per_block + 1` at resolution 2^-(3-i).
     """
     out = []
-    nl = cfg.num_levels
     hh, ww = h, w
-    for i, c in enumerate(cfg.block_out_channels):
-        for _ in range(cfg.layers_per_block):
-            out += [(c, hh, ww, i)] * 2
-        if i != nl - 1:
+    for blk in unet_blocks(cfg):
+        if blk.kind == "motion":
+            out += [(blk.channels, hh, ww, blk.level)] * 2
+        elif blk.kind == "down":
             hh, ww = hh // 2, ww // 2
-    rev = list(reversed(cfg.block_out_channels))
-    for i, c in enumerate(rev):
-        for _ in range(cfg.layers_per_block + 1):
-            out += [(c, hh, ww, nl - 1 - i)] * 2
-        if i != nl - 1:
+        elif blk.kind == "up":
             hh, ww = hh * 2, ww * 2
     return out
