@@ -321,6 +321,20 @@ enum {
  *   a_0 = 1 is a copy, and moves the bits as they are (1 x would quieten a signalling NaN in padding nobody initialised).  16-byte accesses over the whole vectors of a tile, one lane per element for the up to 7 elements behind
  *   them; nothing outside [dst, dst + n elements) is written.  Refused: a null or not 16-byte aligned dst / src[k < K], n <= 0 or
  *   more than a tile, an unknown dtype, K outside 1..4, a non-finite weight.  dst may be one of the sources (same offsets only).
+ *
+ * Depth matte (matte.hip; no counterpart in the reference, which drops its depth map behind the conditioning encode).
+ * L2D_OP_FRAME_MATTE  the stream's output composited over its source frame by a matte of the frame's depth map, as the uint8 HWC
+ *   frame L2D_OP_FRAME_EGRESS writes, one launch:  p0 styled half [B][3][H][W] p1 source half [B][3][H][W] p2 depth half, plane b at
+ *   p2 + b l0 elements, [H][W], in [-1, 1] with 1 nearest p3 dst uint8 [B][H][W][3] (all four 16-byte aligned) ; i0 B i1 H i2 W
+ *   (W % 8 == 0, H W % 16 == 0) i3 r (feather radius, 0..L2D_MATTE_MAX_R) i4 flags (L2D_MATTE_HARD | _FAR | _SHOW) ; l0 depth plane
+ *   stride in elements (>= H W, % 8: 3 H W reads channel 0 of a [B][3][H][W] tensor in place) ; f0 lo (in [-1, 1]) f1 inv (1 / (hi -
+ *   lo); 0 exactly when HARD is set).  Arithmetic, every step one fp32 operation with one rounding and no fma, so that numpy restates
+ *   it bit for bit (live2diff_amd/matte.py composite_ref): t = clamp((d - lo) inv, 0, 1) (HARD: d >= lo ? 1 : 0);
+ *   m = (t t) (3 - 2 t); FAR: m = 1 - m; r > 0: a (2r+1) x (2r+1) box filter as a horizontal then a vertical pass, coordinates
+ *   clamped to the image, the taps added in increasing coordinate order, each pass divided (correctly rounded) by float(2r + 1);
+ *   v = clamp(fp16(fp16(x / 2) + 0.5), 0, 1) on styled and source (L2D_OP_FRAME_EGRESS' chain); o = v_c + m (v_s - v_c);
+ *   byte = rint(255 o), half to even.  SHOW writes rint(255 m) to all three channels and reads neither frame.  m == 1 gives
+ *   L2D_OP_FRAME_EGRESS(styled) and m == 0 L2D_OP_FRAME_EGRESS(source) byte for byte.  Refused: B H W 3 >= 2^31, B > 65535.
  */
 enum {
     L2D_OP_IGEMM = 1,
@@ -365,7 +379,14 @@ enum {
     L2D_OP_JPEG_IDCT = 40,
     L2D_OP_JPEG_RGB = 41,
     L2D_OP_WEIGHT_BLEND = 42,
+    L2D_OP_FRAME_MATTE = 43,
 };
+
+/* flag bits of L2D_OP_FRAME_MATTE (i4) */
+#define L2D_MATTE_HARD 1
+#define L2D_MATTE_FAR 2
+#define L2D_MATTE_SHOW 4
+#define L2D_MATTE_MAX_R 8
 
 typedef struct l2d_op {
     int32_t kind;

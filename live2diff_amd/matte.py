@@ -1,0 +1,238 @@
+"""Depth matte (csrc/matte.hip): stylise the near or the far part of the frame only.  Every frame pays
+for a depth map that `encode_depth` turns into the UNet's conditioning and drops; here it also becomes a matte that composites
+the stream's output over the stream's own source frame, on the device, in the launch that writes the uint8 frame.
+
+  * `matte_params`, `matte_ref`, `composite_ref`   the arithmetic of L2D_OP_FRAME_MATTE in numpy float32 -- the kernel's oracle,
+                      as `frame_io.egress_ref` and `style_bank.blend_ref` are.  Every step is one fp32 operation with one rounding
+                      and no fused multiply-add, so the kernel is held to equality;
+  * `check_settings`  the argument checks of `StreamAnimateDiffusionDepthWrapper.set_matte`;
+  * `MatteLine`       the delay line: with N denoising steps the frame that leaves the stream at call t entered it at call
+                      t - (N - 1), the ingested frame lives in a two-slot buffer, and in push / pop mode the depth path runs on
+                      a side stream -- so source frames and depth planes are kept, delayed and consumed on the device;
+  * `HipMatte`        the static output buffers and the one-op launch of one stream.
+"""
+import collections
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+
+MAX_FEATHER = ops.MATTE_MAX_R
+SERVED_OUTPUT_TYPES = ("u8", "pil", "jpeg")
+
+
+# ----------------------------------------------------------------------------- reference arithmetic (CPU, numpy fp32)
+def matte_params(lo: float, hi: float) -> Tuple[np.float32, np.float32, bool]:
+    """(lo32, inv32, hard) of a ramp from `lo` to `hi`, both in [0, 1] in units of normalised inverse depth (0 = the farthest point
+    of the frame, 1 = the nearest).  They are mapped to the depth tensor's [-1, 1] scale in Python doubles: lo_d = 2 lo - 1,
+    hi_d = 2 hi - 1, lo32 = float32(lo_d), inv32 = float32(1 / (hi_d - lo_d)); hi_d <= lo_d is a step (`hard`, inv32 = 0)."""
+    lo, hi = float(lo), float(hi)
+    if not (0.0 <= lo <= 1.0 and 0.0 <= hi <= 1.0):
+        raise ValueError(f"matte: lo={lo!r}, hi={hi!r} must lie in [0, 1]")
+    if lo > hi:
+        raise ValueError(f"matte: lo={lo!r} is above hi={hi!r}")
+    lo_d, hi_d = 2.0 * lo - 1.0, 2.0 * hi - 1.0
+    hard = hi_d <= lo_d
+    inv = np.float32(0.0) if hard else np.float32(1.0 / (hi_d - lo_d))
+    if not np.isfinite(inv):
+        hard, inv = True, np.float32(0.0)
+    return np.float32(lo_d), inv, bool(hard)
+
+
+def _np16(x) -> np.ndarray:
+    if torch.is_tensor(x):
+        x = x.detach().cpu().to(torch.float16).numpy()
+    return np.asarray(x, dtype=np.float16)
+
+
+def _box_pass(m: np.ndarray, r: int, axis: int) -> np.ndarray:
+    """one pass of the (2r+1) box along `axis`: edge replication, the taps added in increasing coordinate order, one division"""
+    pad = [(0, 0)] * m.ndim
+    pad[axis] = (r, r)
+    p = np.pad(m, pad, mode="edge")
+    n = m.shape[axis]
+    acc = np.take(p, np.arange(0, n), axis=axis)
+    for k in range(1, 2 * r + 1):
+        acc = acc + np.take(p, np.arange(k, k + n), axis=axis)
+    return acc / np.float32(2 * r + 1)
+
+
+def matte_ref(depth, lo: float, hi: float, feather: int = 0, keep: str = "near") -> np.ndarray:
+    """fp16 [B,H,W] depth planes (channel 0 of `encode_depth`'s `dn`: min-max normalised, in [-1, 1], at frame size) -> fp32
+    [B,H,W] matte in [0, 1]: t = clamp((d - lo32) inv32, 0, 1) (hard: d >= lo32), m = (t t) (3 - 2 t), `keep="far"`: 1 - m, then
+    the (2r+1) x (2r+1) box filter as a horizontal and a vertical pass."""
+    check_settings(lo, hi, keep=keep, feather=feather)
+    lo32, inv32, hard = matte_params(lo, hi)
+    d = _np16(depth).astype(np.float32)
+    if d.ndim == 2:
+        d = d[None]
+    one, zero = np.float32(1.0), np.float32(0.0)
+    if hard:
+        t = np.where(d >= lo32, one, zero).astype(np.float32)
+    else:
+        t = np.minimum(np.maximum((d - lo32) * inv32, zero), one)
+    m = (t * t) * (np.float32(3.0) - np.float32(2.0) * t)
+    if keep == "far":
+        m = one - m
+    if feather:
+        m = _box_pass(_box_pass(m, feather, 2), feather, 1)
+    assert m.dtype == np.float32
+    return m
+
+
+def _unit(x) -> np.ndarray:
+    """the egress op's fp16 chain, `(x * 0.5 + 0.5).clamp(0, 1)` with its two fp16 roundings, widened to fp32: [B,H,W,3]"""
+    x = torch.from_numpy(_np16(x))
+    if x.ndim == 3:
+        x = x[None]
+    return (x * 0.5 + 0.5).clamp(0, 1).permute(0, 2, 3, 1).float().numpy()
+
+
+def composite_ref(styled, source, depth, lo: float, hi: float, feather: int = 0, keep: str = "near", show: bool = False) -> np.ndarray:
+    """L2D_OP_FRAME_MATTE on the host: fp16 [B,3,H,W] `styled` and `source` in [-1, 1] + fp16 [B,H,W] `depth` -> uint8 [B,H,W,3].
+    o = v_c + m (v_s - v_c) in three fp32 operations, byte = round_half_even(255 o); `show` writes round_half_even(255 m) to all
+    three channels.  Both v are multiples of 2^-24 in [0, 1], so v_s - v_c is exact: m == 1 gives the bytes of
+    `egress_ref(styled)` and m == 0 those of `egress_ref(source)`, whatever the feather radius."""
+    m = matte_ref(depth, lo, hi, feather, keep)[..., None]
+    scale = np.float32(255.0)
+    if show:
+        return np.rint(np.repeat(m, 3, axis=-1) * scale).astype(np.uint8)
+    vs, vc = _unit(styled), _unit(source)
+    o = vc + m * (vs - vc)
+    assert o.dtype == np.float32
+    return np.rint(o * scale).astype(np.uint8)
+
+
+def check_settings(lo, hi, *, keep="near", feather=0, show=False) -> dict:
+    """the settings as a dict, or ValueError: lo > hi, values outside [0, 1], `feather` no integer in 0..8, `keep` not near / far"""
+    for name, v in (("lo", lo), ("hi", hi)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) <= 1.0:
+            raise ValueError(f"matte: {name}={v!r}: use a number in [0, 1]")
+    if float(lo) > float(hi):
+        raise ValueError(f"matte: lo={lo!r} is above hi={hi!r}")
+    if isinstance(feather, bool) or not isinstance(feather, (int, np.integer)) or not 0 <= int(feather) <= MAX_FEATHER:
+        raise ValueError(f"matte: feather={feather!r}: use an integer from 0 to {MAX_FEATHER}")
+    if keep not in ("near", "far"):
+        raise ValueError(f"matte: keep={keep!r}: use 'near' or 'far'")
+    return dict(lo=float(lo), hi=float(hi), keep=keep, feather=int(feather), show=bool(show))
+
+
+# ----------------------------------------------------------------------------- the delay line
+class _Slot:
+    def __init__(self, height, width, device):
+        self.source = torch.empty(3, height, width, dtype=torch.float16, device=device)
+        self.depth = torch.empty(height, width, dtype=torch.float16, device=device)
+
+
+class MatteLine:
+    """A ring of static slots, each one source frame (fp16 [3,H,W]) and its depth plane (fp16 [H,W]), that delays them by the
+    stream batch: the output of the k-th accepted frame is the frame that entered N - 1 accepted frames earlier, so `take()` for
+    it returns the slot of frame k - (N - 1).
+
+    The line is the tap of `StreamAnimateDiffusionDepth.matte_tap`: the pipeline calls it with the preprocessed frame and `dn`
+    for every frame the near-duplicate filter lets through (`__call__`) and for every pushed frame (`push`, on the side stream
+    and in front of the event `push` records, so `pop`'s `wait_event` covers the copies).  The copies are needed: the frame is a
+    view of an ingest slot that is overwritten two frames later, `dn` a static buffer of the depth glue.  A dropped frame never
+    reaches the tap and does not advance the line; the repeated output is composited with `last`, the slot of the output before.
+
+    `prime` (called by `prepare`) clears the line and fills the N - 1 positions behind the first frame with the last warm-up
+    frame and its depth.  That is a definition, not parity: the reference's first N - 1 outputs come from zeroed latent rows and
+    correspond to no frame at all.  A line that starts mid-stream has no such positions: `take` then returns the oldest entry
+    it has.
+
+    Slots in use: the N - 1 frames behind the newest taken one, the one taken last, and the tapped-but-not-taken frames of
+    push / pop mode.  The ring grows when a caller pushes deeper than before; in steady state nothing is allocated."""
+
+    def __init__(self, n_steps: int, height: int, width: int, device="cpu"):
+        self.n, self.height, self.width, self.device = int(n_steps), int(height), int(width), torch.device(device)
+        self.slots = []
+        self.clear()
+
+    def clear(self) -> None:
+        self._hist = collections.deque()       # slot ids of frames first .. first + len - 1, oldest first
+        self._first = 0                        # the accepted-frame number of _hist[0] (negative: warm-up positions)
+        self.tapped = 0                        # accepted frames copied in
+        self.taken = 0                         # outputs composited
+        self.last: Optional[_Slot] = None
+        self._last_id = None
+
+    def _free_slot(self) -> int:
+        used = set(self._hist)
+        used.add(self._last_id)
+        for i in range(len(self.slots)):
+            if i not in used:
+                return i
+        self.slots.append(_Slot(self.height, self.width, self.device))
+        return len(self.slots) - 1
+
+    def _store(self, x: torch.Tensor, dn: torch.Tensor) -> int:
+        i = self._free_slot()
+        s = self.slots[i]
+        s.source.copy_(x[-1], non_blocking=True)
+        s.depth.copy_(dn[-1, 0] if dn.ndim == 4 else dn[-1], non_blocking=True)
+        return i
+
+    def prime(self, x: torch.Tensor, dn: torch.Tensor) -> None:
+        """`x` [F,3,H,W], `dn` [F,3,H,W]: the warm-up frames of `prepare` and their normalised depth; the last one is kept"""
+        self.clear()
+        if self.n > 1:
+            i = self._store(x, dn)
+            self._hist.extend([i] * (self.n - 1))
+            self._first = -(self.n - 1)
+
+    def __call__(self, x: torch.Tensor, dn: torch.Tensor) -> None:
+        """the tap: `x` [1,3,H,W] in [-1, 1], `dn` [1,3,H,W] (or [1,H,W]) in [-1, 1]; runs on the current stream"""
+        if not self._hist:
+            self._first = self.tapped
+        self._hist.append(self._store(x, dn))
+        self.tapped += 1
+
+    def take(self) -> _Slot:
+        """the slot that belongs to the output of accepted frame number `taken`"""
+        if self.taken >= self.tapped:
+            raise RuntimeError("MatteLine.take: no tapped frame is waiting for its output")
+        k = self.taken
+        self.taken += 1
+        idx = max(k - (self.n - 1), self._first) - self._first
+        self._last_id = self._hist[idx]
+        self.last = self.slots[self._last_id]
+        keep_from = self.taken - (self.n - 1)               # what the next take may still ask for
+        while self._first < keep_from and len(self._hist) > 1:
+            self._hist.popleft()
+            self._first += 1
+        return self.last
+
+
+# ----------------------------------------------------------------------------- the device side
+class HipMatte:
+    """Static output buffers and the launch of one `(H, W)` stream: `composite` is `HipFrameIO.egress` with a source frame and a
+    depth plane beside the image.  Everything runs on `torch.cuda.current_stream()`."""
+
+    def __init__(self, height: int, width: int, device="cuda:0"):
+        if width % 8 or (height * width) % 16:
+            raise ValueError(f"HipMatte: width {width} must be a multiple of 8 and height * width a multiple of 16")
+        self.height, self.width, self.device = int(height), int(width), torch.device(device)
+        self.dev = torch.empty(1, self.height, self.width, 3, dtype=torch.uint8, device=self.device)
+        self.host = None if ops.DRY_RUN else torch.empty(1, self.height, self.width, 3, dtype=torch.uint8).pin_memory()
+
+    def composite(self, image: torch.Tensor, slot: _Slot, settings: dict, to_host: bool = True):
+        """fp16 [3,H,W] on the device + a `MatteLine` slot -> uint8 [H,W,3]: a numpy view of the pinned buffer (valid until the next
+        call), or with `to_host=False` the static device tensor"""
+        H, W = self.height, self.width
+        if image.dtype != torch.float16 or tuple(image.shape) != (3, H, W):
+            raise ValueError(f"composite: expected fp16 [3,{H},{W}], got {image.dtype} {tuple(image.shape)}")
+        if not image.is_contiguous():
+            image = image.contiguous()
+        lo32, inv32, hard = matte_params(settings["lo"], settings["hi"])
+        op, keep = ops.frame_matte(image, slot.source, slot.depth, self.dev, B=1, H=H, W=W, lo32=lo32, inv32=inv32, hard=hard,
+                                   far=settings["keep"] == "far", show=settings["show"], r=settings["feather"])
+        pl = _lib.OpList()
+        pl.append(op, *keep)
+        pl.run()
+        if not to_host:
+            return self.dev[0]
+        self.host.copy_(self.dev, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        return self.host.numpy()[0]

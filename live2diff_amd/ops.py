@@ -1420,3 +1420,27 @@ def weight_blend(table_dev, table_host, weights, *, nt=None):
     for k, a in enumerate(list(weights)[:4]):
         op.f[k] = float(a)
     return op, (table_dev, table_host)
+
+
+# ----------------------------------------------------------------------------- depth matte (matte.hip, matte.py)
+MATTE_HARD, MATTE_FAR, MATTE_SHOW = 1, 2, 4      # l2d.h L2D_MATTE_*
+MATTE_MAX_R = 8                                  # l2d.h L2D_MATTE_MAX_R
+
+
+def frame_matte(styled, source, depth, dst, *, B, H, W, lo32, inv32, hard, far=False, show=False, r=0, depth_stride=None):
+    """fp16 [B,3,H,W] styled / source + fp16 depth planes ([B,H,W], or channel 0 of a [B,3,H,W] tensor with `depth_stride=3 H W`)
+    -> uint8 [B,H,W,3]: the egress bytes of `styled` over those of `source` by the depth matte (matte.composite_ref);
+    `lo32, inv32, hard` as `matte.matte_params` returns them."""
+    assert styled.dtype == source.dtype == depth.dtype == torch.float16 and dst.dtype == torch.uint8
+    stride = H * W if depth_stride is None else int(depth_stride)
+    assert styled.numel() >= B * 3 * H * W and source.numel() >= B * 3 * H * W and dst.numel() >= B * H * W * 3
+    assert depth.numel() >= (B - 1) * stride + H * W
+    op = L2dOp()
+    op.kind = _lib.OP_FRAME_MATTE
+    op.p[0], op.p[1], op.p[2], op.p[3] = _ptr(styled), _ptr(source), _ptr(depth), _ptr(dst)
+    flags = (MATTE_HARD if hard else 0) | (MATTE_FAR if far else 0) | (MATTE_SHOW if show else 0)
+    for j, v in enumerate([B, H, W, r, flags]):
+        op.i[j] = int(v)
+    op.l[0] = stride
+    op.f[0], op.f[1] = float(lo32), float(inv32)
+    return op, (styled, source, depth, dst)

@@ -150,6 +150,9 @@ class StreamAnimateDiffusionDepth:
         self.mask_shift = 1
         self.is_tensorrt = False
         self.unet_warmup = None
+        # Optional tap on the depth path (matte.MatteLine): `tap(x, dn)` is called with every frame that enters the stream batch
+        # and its normalised depth, `tap.prime(x, dn)` with the warm-up frames of `prepare`.  None: nothing changes.
+        self.matte_tap = None
 
     @property
     def depth_glue(self):
@@ -270,7 +273,7 @@ class StreamAnimateDiffusionDepth:
         xs = [self.image_processor.preprocess(f, self.height, self.width).to(**to) for f in warmup_frames]
         warmup_x = torch.cat(xs, dim=0)
         x_t_latent = self.encode_image(warmup_x).transpose(0, 1)[None]           # [1,4,F,h,w]
-        depth_latent = self.encode_depth(warmup_x).transpose(0, 1)[None]
+        depth_latent = self.encode_depth(warmup_x, tap=getattr(getattr(self, "matte_tap", None), "prime", None)).transpose(0, 1)[None]
         warm = self.unet_warmup if self.unet_warmup is not None else self.unet
         for idx, t in enumerate(self.sub_timesteps_tensor):
             if hasattr(warm, "warmup"):
@@ -322,11 +325,12 @@ class StreamAnimateDiffusionDepth:
         out = self.vae.decode(x_0_pred_out / self.vae.config.scaling_factor, return_dict=False)[0]
         return out.clip(-1, 1)
 
-    def encode_depth(self, image_tensors):
+    def encode_depth(self, image_tensors, tap=None):
         """reference :544-571.  On the device the arithmetic around the (caller-owned) depth detector -- the 384x384 bilinear
         resize, the min-max normalisation over the batch, x3 channels, [-1,1], the resize back -- runs as HIP ops without the
         reference's two host-visible reductions (`self.depth_glue`, vae_hip.HipDepthGlue); CPU tensors (host-logic tests)
-        and `depth_glue = None` take the reference's torch expressions."""
+        and `depth_glue = None` take the reference's torch expressions.  `tap(image_tensors, dn)`, when given, sees the frame and
+        its normalised depth map ([B,3,h,w] in [-1, 1]) before the map is encoded and dropped."""
         image_tensors = image_tensors.to(device=self.device, dtype=self.depth_detector.dtype)
         h, w = image_tensors.shape[2], image_tensors.shape[3]
         glue = self.depth_glue
@@ -342,6 +346,8 @@ class StreamAnimateDiffusionDepth:
             dn = (depth_map - depth_map.min()) / (depth_map.max() - depth_map.min())
             dn = dn[:, None].repeat(1, 3, 1, 1) * 2 - 1
             dn = F.interpolate(dn, (h, w), mode="bilinear", align_corners=False)
+        if tap is not None:
+            tap(image_tensors, dn)
         return retrieve_latents(self.vae.encode(dn.to(dtype=self.vae.dtype)), self.generator) * self.vae.config.scaling_factor
 
     def enable_device_step(self, use_graph: bool = False, seed: int = 0):
@@ -385,7 +391,7 @@ class StreamAnimateDiffusionDepth:
         self._pre_stream.wait_stream(cur)                     # the frame is ready; earlier consumers of the side buffers are done
         with torch.cuda.stream(self._pre_stream):
             x_t_latent = self.encode_image(x)
-            depth_latent = self.encode_depth(x)
+            depth_latent = self.encode_depth(x, tap=getattr(self, "matte_tap", None))       # (the tap's copies: in front of the event)
             ev = torch.cuda.Event()
             ev.record(self._pre_stream)
         if x.is_cuda:
@@ -465,7 +471,7 @@ class StreamAnimateDiffusionDepth:
         x_t_latent = self.encode_image(x)
         sd, ed = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         sd.record()
-        depth_latent = self.encode_depth(x)
+        depth_latent = self.encode_depth(x, tap=getattr(self, "matte_tap", None))
         ed.record()
         x_0 = self.predict_x0_batch(x_t_latent.unsqueeze(2), depth_latent.unsqueeze(2))      # [1,4,1,h,w]
         x_output = self.decode_image(x_0[:, :, 0]).detach().clone()

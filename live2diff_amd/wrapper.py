@@ -15,6 +15,7 @@ backend cannot honour raise ValueError at construction, `"u8"` is a fifth output
 the frame leaves the device as the JPEG file the reference's demo makes of it on the host (jpeg_io.HipJpegEncoder).  A frame may
 also ARRIVE as a JPEG file (`bytes`, what the reference's demo receives from the browser, demo/util.py:22): it is decoded on the
 device (jpeg_io.HipJpegDecoder) and ingested there like a uint8 frame (`jpeg_decode="host"` decodes with Pillow instead).
+`set_matte` composites the output over the stream's own source frame by a matte of the frame's depth map (matte.py).
 """
 import os
 from pathlib import Path
@@ -253,6 +254,10 @@ class StreamAnimateDiffusionDepthWrapper:
     jpeg_decode = "device"                  # where a JPEG input frame is decoded ("device" | "host"); `_setup` sets the instance's
     jpeg_dec = None                         # jpeg_io.HipJpegDecoder, made by the first JPEG input frame on the device
     jpeg_host_decodes = 0                   # JPEG input frames Pillow decoded on the host (no device, "host", or an unsupported file)
+    _matte = None                           # the depth matte's settings (set_matte), None: off
+    _matte_line = None                      # matte.MatteLine: the delayed source frames and depth planes, while a matte is set
+    _matte_dev = None                       # matte.HipMatte, made by the first composited frame on the device
+    _matte_skip = 0                         # frames pushed before the matte was set: their outputs leave as they are
 
     def __init__(self, config_path: str, few_step_model_type: str, num_inference_steps: int,
                  t_index_list: Optional[List[int]] = None, strength: Optional[float] = None,
@@ -359,6 +364,72 @@ class StreamAnimateDiffusionDepthWrapper:
             self.stream.image_processor = FrameProcessor(self.io)
         self._init_styles(pipe)
 
+    # ------------------------------------------------------------------ depth matte (matte.py)
+    @property
+    def matte(self) -> Optional[dict]:
+        """the current matte as {lo, hi, keep, feather, show}, or None"""
+        return None if self._matte is None else dict(self._matte)
+
+    def set_matte(self, lo: float, hi: float, *, keep: str = "near", feather: int = 0, show: bool = False) -> None:
+        """Stylise one side of a depth ramp only: the output frame becomes `source + m (styled - source)` with m a smoothstep of
+        the frame's own normalised inverse depth (0 = the farthest point of the frame, 1 = the nearest) from `lo` to `hi`;
+        `keep="near"` stylises the near side and keeps the real far side, `keep="far"` the other way round; `feather` (0..8) is
+        the radius of a box blur of the matte in pixels; `show=True` returns the matte itself as a grey frame (to choose `lo`
+        and `hi` by eye).  One launch on the device in place of the egress launch ("u8", "pil"), or in front of the JPEG
+        encoder ("jpeg"); the float output types are not served.  May be called before or after `prepare` and between any two
+        frames: settings change with the next output; turning the matte on mid-stream starts the delay line (matte.MatteLine)
+        with the next frame, and outputs of frames it has not seen are composited with the oldest frame it has.  The frames
+        `prepare` returns are not composited."""
+        from .matte import SERVED_OUTPUT_TYPES, MatteLine, check_settings
+        if self.output_type not in SERVED_OUTPUT_TYPES:
+            raise ValueError(f"set_matte: output_type={self.output_type!r} is not composited: use one of "
+                             + ", ".join(repr(t) for t in SERVED_OUTPUT_TYPES))
+        settings = check_settings(lo, hi, keep=keep, feather=feather, show=show)
+        if self._matte_line is None:
+            self._matte_line = MatteLine(self.batch_size, self.height, self.width, device=self.stream.device)
+            self.stream.matte_tap = self._matte_line
+            self._matte_skip = len(getattr(self.stream, "_pending", None) or ())
+        self._matte = settings
+
+    def clear_matte(self) -> None:
+        """Back to the plain output route: no launch, copy or buffer of the matte is left in the frame's path."""
+        self._matte = self._matte_line = None
+        self._matte_skip = 0
+        self.stream.matte_tap = None
+
+    def _composite(self, image_tensor, slot):
+        """`postprocess_image` of a frame under the matte: op 43 in place of the egress op.  `slot` None (the line has seen no
+        frame yet): the plain route."""
+        from .matte import SERVED_OUTPUT_TYPES, composite_ref
+        ot = self.output_type
+        if ot not in SERVED_OUTPUT_TYPES:
+            raise ValueError(f"a matte is set and output_type={ot!r} is not composited: use one of "
+                             + ", ".join(repr(t) for t in SERVED_OUTPUT_TYPES) + ", or clear_matte()")
+        if slot is None or not torch.is_tensor(image_tensor):
+            return self.postprocess_image(image_tensor, output_type=ot)
+        if self.io is not None and image_tensor.is_cuda:
+            if self._matte_dev is None:
+                from .matte import HipMatte
+                self._matte_dev = HipMatte(self.height, self.width, device=image_tensor.device)
+            if ot == "jpeg":
+                if self.jpeg is None:
+                    from .jpeg_io import HipJpegEncoder
+                    self.jpeg = HipJpegEncoder(self.height, self.width, self.jpeg_quality, device=image_tensor.device)
+                out = self.jpeg.encode(self._matte_dev.composite(image_tensor[0], slot, self._matte, to_host=False))
+                self._check_jpeg()
+                return out
+            u8 = self._matte_dev.composite(image_tensor[0], slot, self._matte).copy()      # (the pinned buffer is overwritten by the next frame)
+        else:
+            u8 = composite_ref(image_tensor[:1], slot.source[None], slot.depth[None], **self._matte)[0]
+        self._check_jpeg()
+        if ot == "jpeg":
+            from .jpeg import encode_ref
+            return encode_ref(u8, self.jpeg_quality)
+        if ot == "u8":
+            return u8
+        from PIL import Image
+        return Image.fromarray(u8)
+
     # ------------------------------------------------------------------ styles (style_bank.py, DESIGN.md section 8.z3)
     def _init_styles(self, pipe) -> None:
         """The style the wrapper was built with becomes "default", as a copy: the active weights are scratch that the next switch
@@ -459,6 +530,7 @@ class StreamAnimateDiffusionDepthWrapper:
         Returns the generated warm-up frames, [F,H,W,3] in [0, 1] (wrapper.py:197-199)."""
         kw = dict(prompt=prompt, negative_prompt=negative_prompt, guidance_scale=guidance_scale, delta=delta, seed=self.seed)
         self._prompt = prompt
+        self._matte_skip = 0               # (`stream.prepare` primes the matte's delay line through the tap, when one is set)
         if isinstance(warmup_frames, (list, tuple)) and warmup_frames and all(_is_jpeg(f) for f in warmup_frames):
             # (a device frame is a view of one of the decoder's two static slots: it is copied before the slot's next turn)
             decoded = [d.clone() if torch.is_tensor(d) else torch.from_numpy(d).to(self.io.device) if self.io is not None else d
@@ -499,7 +571,13 @@ class StreamAnimateDiffusionDepthWrapper:
         [3,H,W] tensor in [0, 1] (the reference's input)."""
         if prompt is not None:
             self._update_prompt(prompt)
-        return self.postprocess_image(self.stream(self.preprocess_image(image)), output_type=self.output_type)
+        line = self._matte_line
+        if line is None:
+            return self.postprocess_image(self.stream(self.preprocess_image(image)), output_type=self.output_type)
+        seen = line.tapped
+        out = self.stream(self.preprocess_image(image))
+        # a frame the near-duplicate filter dropped never reached the tap: the repeated output keeps its slot
+        return self._composite(out, line.take() if line.tapped > seen else line.last)
 
     def push(self, image, prompt: Optional[str] = None) -> None:
         """pipelined mode (`frame_pipelining=True`): start a frame's encode / depth path; `pop()` returns the oldest frame's output"""
@@ -512,7 +590,13 @@ class StreamAnimateDiffusionDepthWrapper:
             self.io.release(self.io.last_view, self.stream._pending[-1][2])
 
     def pop(self):
-        return self.postprocess_image(self.stream.pop(), output_type=self.output_type)
+        out = self.stream.pop()
+        if self._matte_line is None:
+            return self.postprocess_image(out, output_type=self.output_type)
+        if self._matte_skip:
+            self._matte_skip -= 1
+            return self.postprocess_image(out, output_type=self.output_type)
+        return self._composite(out, self._matte_line.take())
 
     def _update_prompt(self, prompt: str) -> None:
         self.stream.update_prompt(prompt)

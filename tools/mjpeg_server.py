@@ -19,7 +19,12 @@ is dropped and counted.
 `--style NAME=DREAMBOOTH[,LORA:ALPHA...]` (repeatable) registers further styles beside the config's own (`"default"`); their packed
 weights stay resident on the device.  `POST /style` with a JSON body `{name: weight}` (up to four names, weights summing to 1)
 switches or blends the running stream: the producer thread applies it between two frames (`wrapper.set_style`), without a
-re-warm.  `GET /style` answers `{"styles": [...], "current": {...}}`."""
+re-warm.  `GET /style` answers `{"styles": [...], "current": {...}}`.
+
+`--matte LO,HI[,FEATHER[,far]]` stylises only the near side (`far`: the far side) of a ramp over the frame's own depth map and
+keeps the real picture elsewhere (`wrapper.set_matte`: composited on the device, in front of the JPEG encoder).  `POST /matte`
+with the same text as its body, or `off`, changes it while the stream runs; the producer applies it between two frames.
+`GET /matte` answers the current settings as JSON (`null`: off)."""
 import argparse
 import json
 import os
@@ -121,6 +126,54 @@ class StyleBox:
             self.failed += 1
 
 
+def parse_matte_arg(text: str):
+    """`LO,HI[,FEATHER[,far]]` -> the keywords of `wrapper.set_matte`, `off` -> None; ValueError otherwise (the wrapper checks the
+    ranges once more)"""
+    from live2diff_amd.matte import check_settings
+    text = text.strip()
+    if text == "off":
+        return None
+    parts = [t.strip() for t in text.split(",")]
+    if not 2 <= len(parts) <= 4 or (len(parts) == 4 and parts[3] not in ("far", "near")):
+        raise ValueError(f"matte {text!r}: use LO,HI[,FEATHER[,far]] or off")
+    try:
+        lo, hi = float(parts[0]), float(parts[1])
+        feather = int(parts[2]) if len(parts) > 2 else 0
+    except ValueError:
+        raise ValueError(f"matte {text!r}: LO and HI are numbers in [0, 1], FEATHER an integer from 0 to 8") from None
+    s = check_settings(lo, hi, keep=parts[3] if len(parts) == 4 else "near", feather=feather)
+    return dict(lo=s["lo"], hi=s["hi"], keep=s["keep"], feather=s["feather"])
+
+
+class MatteBox:
+    """What `POST /matte` delivers: the newest requested matte (a dict of `set_matte` keywords, or None for `off`), applied by the
+    producer between two frames.  `current` is what was last applied; `failed` counts requests the wrapper refused."""
+    _NOTHING = object()
+
+    def __init__(self, current=None):
+        self._lock = threading.Lock()
+        self.current, self._want, self.failed = current, self._NOTHING, 0
+
+    def put(self, settings) -> None:
+        with self._lock:
+            self._want = settings
+
+    def apply(self, wrapper) -> None:
+        """(producer thread, between frames)"""
+        with self._lock:
+            want, self._want = self._want, self._NOTHING
+        if want is self._NOTHING:
+            return
+        try:
+            if want is None:
+                wrapper.clear_matte()
+            else:
+                wrapper.set_matte(want["lo"], want["hi"], keep=want["keep"], feather=want["feather"])
+            self.current = wrapper.matte
+        except ValueError:
+            self.failed += 1
+
+
 def parse_style_arg(text: str):
     """`NAME=DREAMBOOTH[,LORA:ALPHA...]` -> (name, dreambooth path or None, {lora path: alpha})"""
     name, eq, rest = text.partition("=")
@@ -162,7 +215,7 @@ class Latest:
             return (self._seq, self._part) if self._seq > seen else None
 
 
-def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = None):
+def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = None, mattes: "MatteBox" = None):
     page = PAGE if inbox is None else CAMERA_PAGE
 
     class Handler(BaseHTTPRequestHandler):
@@ -201,8 +254,33 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
                 self.send_header("Content-Length", str(len(body)))
                 self.end_headers()
                 self.wfile.write(body)
+            elif self.path == "/matte" and mattes is not None:
+                body = json.dumps(mattes.current).encode()
+                self.send_response(200)
+                self.send_header("Content-Type", "application/json")
+                self.send_header("Content-Length", str(len(body)))
+                self.end_headers()
+                self.wfile.write(body)
             else:
                 self.send_error(404)
+
+        def do_matte(self):
+            try:
+                n = int(self.headers.get("Content-Length", ""))
+            except ValueError:
+                self.send_error(411)
+                return
+            if not 1 <= n <= 256:
+                self.send_error(413 if n > 256 else 400)
+                return
+            try:
+                want = parse_matte_arg(self.rfile.read(n).decode())
+            except ValueError as e:                       # (UnicodeDecodeError is a ValueError)
+                self.send_error(400, str(e.args[0] if e.args else e)[:200])
+                return
+            mattes.put(want)
+            self.send_response(204)
+            self.end_headers()
 
         def do_style(self):
             from live2diff_amd.style_bank import parse_style
@@ -227,6 +305,9 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
             if self.path == "/style" and styles is not None:
                 self.do_style()
                 return
+            if self.path == "/matte" and mattes is not None:
+                self.do_matte()
+                return
             if inbox is None or self.path != "/frame":
                 self.send_error(404)
                 return
@@ -249,21 +330,24 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
     return Handler
 
 
-def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: StyleBox = None) -> None:
-    """the producer: loops `frames` through the wrapper until `stop` is set; a posted style is applied between two frames"""
+def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: StyleBox = None, mattes: MatteBox = None) -> None:
+    """the producer: loops `frames` through the wrapper until `stop` is set; a posted style or matte is applied between two frames"""
     from live2diff_amd.jpeg import mjpeg_part
     try:
         i = 0
         while not stop.is_set():
             if styles is not None:
                 styles.apply(wrapper)
+            if mattes is not None:
+                mattes.apply(wrapper)
             latest.put(mjpeg_part(wrapper(frames[i % len(frames)])))
             i += 1
     finally:
         latest.close()
 
 
-def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: threading.Event, styles: StyleBox = None) -> None:
+def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: threading.Event, styles: StyleBox = None,
+                   mattes: MatteBox = None) -> None:
     """the producer of `--input post`: the first frames posted warm the stream up, then the newest posted frame goes through the
     wrapper, for ever; a frame the wrapper refuses (ValueError: a damaged file) is dropped and counted in `inbox.failed`"""
     from live2diff_amd.jpeg import mjpeg_part
@@ -278,6 +362,8 @@ def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: thr
                 continue
             if styles is not None:
                 styles.apply(wrapper)
+            if mattes is not None:
+                mattes.apply(wrapper)
             try:
                 latest.put(mjpeg_part(wrapper(frame)))
             except ValueError:
@@ -301,8 +387,12 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--style", action="append", default=[], metavar="NAME=DREAMBOOTH[,LORA:ALPHA...]",
                     help="register a further style (repeatable); POST /style {name: weight} switches or blends between frames")
+    ap.add_argument("--matte", default=None, metavar="LO,HI[,FEATHER[,far]]",
+                    help="stylise only the near (`far`: the far) side of a depth ramp from LO to HI in [0, 1], 1 = nearest; POST /matte "
+                         "with the same text, or `off`, changes it between frames")
     args = ap.parse_args(argv)
     style_args = [parse_style_arg(t) for t in args.style]
+    matte = parse_matte_arg(args.matte) if args.matte else None
 
     from stream_frames import read_frames
 
@@ -320,15 +410,18 @@ def main(argv=None):
     for name, db, loras in style_args:
         w.add_style(name, dreambooth_path=db, lora_dict=loras or None)
     styles = StyleBox(w.styles, w.style)
+    if matte is not None:
+        w.set_matte(matte["lo"], matte["hi"], keep=matte["keep"], feather=matte["feather"])      # (before `prepare`: the line is primed)
+    mattes = MatteBox(w.matte)
     prompt = args.prompt if args.prompt is not None else str(cfg.get("prompt", ""))
     latest, stop = Latest(), threading.Event()
     inbox = Inbox(sink) if post else None
     if post:
-        producer = threading.Thread(target=produce_posted, args=(w, prompt, inbox, latest, stop, styles), name="producer", daemon=True)
+        producer = threading.Thread(target=produce_posted, args=(w, prompt, inbox, latest, stop, styles, mattes), name="producer", daemon=True)
     else:
         w.prepare(frames[:sink], prompt)
-        producer = threading.Thread(target=produce, args=(w, frames, latest, stop, styles), name="producer", daemon=True)
-    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest, inbox, styles))
+        producer = threading.Thread(target=produce, args=(w, frames, latest, stop, styles, mattes), name="producer", daemon=True)
+    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest, inbox, styles, mattes))
     server.daemon_threads = True
     producer.start()
     print(f"http://{args.host}:{args.port}/  ({args.height}x{args.width}, quality {args.quality}; Ctrl-C stops)")
