@@ -3,9 +3,15 @@ in fp32 on the same fp16-rounded inputs: every block geometry (channel tiles x K
 NaN-poisoned, channel concat of two inputs, zero padding at all four image borders, the nearest-x2 up-sampling of Upsample3D folded
 into the gather (reference resnet.py:94-127), bias + per-sample time-embedding bias + residual, GroupNorm statistics of the
 output, bit-repeatability.  Tolerance: rel-L2 <= 2e-3 (fp16 storage, fp32 accumulate), SURVEY.md section 8c."""
+import os
+import sys
+
 import pytest
 import torch
 import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import norm_cases  # noqa: E402  (per-group accumulator bounds)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -164,6 +170,8 @@ def test_cconv_agrees_with_igemm_and_feeds_groupnorm(L):
         t1, t2 = full.view(B, T, G, 2 * cpg).sum((1, 3)), (full ** 2).view(B, T, G, 2 * cpg).sum((1, 3))
         assert (a0[1, :, :, 0] / 2 ** 20 - t1).abs().max() <= 1e-3 * max(1.0, t1.abs().max().item())
         assert (a0[1, :, :, 1] / 2 ** 12 - t2).abs().max() <= 1e-3 * t2.abs().max().item()
+        norm_cases.check_acc(accs[0][0], out.cpu().view(B, T, N), G, cpg, 0, what=f"cconv {sched} consumer 1")    # every group on its own
+        norm_cases.check_acc(accs[0][1], out.cpu().view(B, T, N), G, 2 * cpg, N, what=f"cconv {sched} consumer 2")
         gm, bt = (1 + 0.1 * rnd(N, seed=15).float()).half(), (0.1 * rnd(N, seed=16).float()).half()
         y = torch.empty(M, N, dtype=torch.float16, device=DEV)
         L.run(L.gn_apply(out, None, gm.to(DEV), bt.to(DEV), y, B=B, T=T, C1=N, ld1=N, G=G, nchunk=0, eps=1e-5, silu=True, acc_ptr=acc[0].data_ptr()))

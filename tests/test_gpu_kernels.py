@@ -4,11 +4,16 @@ Tolerances (fp16 storage, fp32 accumulate): per-op rel-L2 <= 2e-3 against the fp
 SAME fp16-rounded inputs.  Nothing here reads /root/reference.
 """
 import math
+import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import norm_cases  # noqa: E402  (per-group accumulator bounds)
 
 pytestmark = pytest.mark.gpu
 
@@ -333,6 +338,9 @@ def test_igemm_groupnorm_statistics_from_the_producer(L, B, T, K, C, tile, split
     t2 = (full ** 2).view(B, T, G, cpg2).sum((1, 3))
     assert (a0[1, :, :, 0] / 2 ** 20 - t1).abs().max() <= 1e-3 * max(1.0, t1.abs().max().item())
     assert (a0[1, :, :, 1] / 2 ** 12 - t2).abs().max() <= 1e-3 * t2.abs().max().item()
+    # ... and every group on its own, against the bounds of the arithmetic (the two lines above see the largest group only)
+    norm_cases.check_acc(accs[0][0], out.cpu().view(B, T, C), G, cpg1, 0, what="igemm consumer 1")
+    norm_cases.check_acc(accs[0][1], out.cpu().view(B, T, C), G, cpg2, choff2, what="igemm consumer 2")
     # gn_apply from the accumulators == GroupNorm of the stored tensor
     gm, bt = (1 + 0.1 * rnd(C, seed=5).float()).half(), (0.1 * rnd(C, seed=6).float()).half()
     y = torch.empty(M, C, dtype=torch.float16, device=DEV)

@@ -5,9 +5,15 @@ residual, LayerNorm, GEGLU feed-forward + residual, proj_out + block residual) a
 Tolerance: rel-L2 <= 3e-3 against fp32 (four chained fp16 GEMMs with their fp16 rounding points); BIT-IDENTICAL to the unfused HIP
 path (same rounding points, the same fp32 sums in the same k order: measured 0.00e+00 on every case, profiles/round5_n_rowchain_ab.txt,
 asserted with torch.equal since round 6)."""
+import os
+import sys
+
 import pytest
 import torch
 import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import norm_cases  # noqa: E402  (per-group accumulator bounds)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -90,6 +96,8 @@ def test_rowchain_against_fp32_and_the_unfused_path(L, layers, B, T):
     t1, t2 = full.view(B, T, G, 2 * C // G).sum((1, 3)), (full ** 2).view(B, T, G, 2 * C // G).sum((1, 3))
     assert (a0[1, :, :, 0] / 2 ** 20 - t1).abs().max() <= 1e-3 * max(1.0, t1.abs().max().item())
     assert (a0[1, :, :, 1] / 2 ** 12 - t2).abs().max() <= 1e-3 * max(1.0, t2.abs().max().item())
+    norm_cases.check_acc(a1[0], out.cpu().view(B, T, C), G, C // G, 0, what="rowchain consumer 1")              # every group on its own
+    norm_cases.check_acc(a1[1], out.cpu().view(B, T, C), G, 2 * C // G, C, what="rowchain consumer 2")
     # the four launches it replaces: row GEMM (+ residual), row GEMM with LayerNorm prologue + GEGLU, implicit GEMM (+ residual),
     # row GEMM (+ residual)
     h2 = torch.empty(M, C, dtype=torch.float16, device=DEV); hid = torch.empty(M, 4 * C, dtype=torch.float16, device=DEV)

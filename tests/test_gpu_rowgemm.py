@@ -4,9 +4,15 @@ the transposed (V^T) part, GroupNorm statistics of the output, every (NW, NT, MT
 
 Tolerance: per-op rel-L2 <= 2e-3 (3e-3 behind a fused norm: the normalised activations are rounded to fp16 before the affine
 map instead of after it), SURVEY.md section 8c."""
+import os
+import sys
+
 import pytest
 import torch
 import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import norm_cases  # noqa: E402  (per-group accumulator bounds)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -211,6 +217,8 @@ def test_rowgemm_groupnorm_statistics_of_the_output(L, B, T, K, C, choff2, Ccat)
     t1, t2 = full.view(B, T, G, cpg2).sum((1, 3)), (full ** 2).view(B, T, G, cpg2).sum((1, 3))
     assert (a0[1, :, :, 0] / 2 ** 20 - t1).abs().max() <= 1e-3 * max(1.0, t1.abs().max().item())
     assert (a0[1, :, :, 1] / 2 ** 12 - t2).abs().max() <= 1e-3 * t2.abs().max().item()
+    norm_cases.check_acc(accs[0][0], out.cpu().view(B, T, C), G, cpg1, 0, what="rowgemm consumer 1")            # every group on its own
+    norm_cases.check_acc(accs[0][1], out.cpu().view(B, T, C), G, cpg2, choff2, what="rowgemm consumer 2")
     gm, bt = (1 + 0.1 * rnd(C, seed=65).float()).half(), (0.1 * rnd(C, seed=66).float()).half()
     y = torch.empty(M, C, dtype=torch.float16, device=DEV)
     L.run(L.gn_apply(out, None, gm.to(DEV), bt.to(DEV), y, B=B, T=T, C1=C, ld1=C, G=G, nchunk=0, eps=1e-5, silu=True, acc_ptr=acc[0].data_ptr()))

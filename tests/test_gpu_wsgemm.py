@@ -4,9 +4,15 @@ normalisation), GEGLU, the transposed (V^T) part, 3x3 convolutions (padding, con
 than a tile), split-K with the fused reduction (bit-repeatable), GroupNorm statistics of the output, every block geometry.
 
 Tolerance: per-op rel-L2 <= 2e-3 (3e-3 behind the LayerNorm fold), SURVEY.md section 8c."""
+import os
+import sys
+
 import pytest
 import torch
 import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import norm_cases  # noqa: E402  (per-group accumulator bounds)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -288,6 +294,8 @@ def test_wsgemm_groupnorm_statistics_of_the_output(L, B, T, K, C, choff2, Ccat, 
         t1, t2 = fullc.view(B, T, G, cpg2).sum((1, 3)), (fullc ** 2).view(B, T, G, cpg2).sum((1, 3))
         assert (a0[1, :, :, 0] / 2 ** 20 - t1).abs().max() <= 1e-3 * max(1.0, t1.abs().max().item()), sched
         assert (a0[1, :, :, 1] / 2 ** 12 - t2).abs().max() <= 1e-3 * t2.abs().max().item(), sched
+        norm_cases.check_acc(accs[0][0], out.cpu().view(B, T, C), G, cpg1, 0, what=f"wsgemm {sched} consumer 1")    # every group on its own
+        norm_cases.check_acc(accs[0][1], out.cpu().view(B, T, C), G, cpg2, choff2, what=f"wsgemm {sched} consumer 2")
 
 
 def test_wsgemm_matches_rowgemm_and_igemm_on_frame_shapes(L):
