@@ -335,6 +335,26 @@ enum {
  *   v = clamp(fp16(fp16(x / 2) + 0.5), 0, 1) on styled and source (L2D_OP_FRAME_EGRESS' chain); o = v_c + m (v_s - v_c);
  *   byte = rint(255 o), half to even.  SHOW writes rint(255 m) to all three channels and reads neither frame.  m == 1 gives
  *   L2D_OP_FRAME_EGRESS(styled) and m == 0 L2D_OP_FRAME_EGRESS(source) byte for byte.  Refused: B H W 3 >= 2^31, B > 65535.
+ *
+ * Colour lock (colorlock.hip; no counterpart in the reference).  The per-channel mean and variance of the BYTES a frame leaves as
+ *   (b = L2D_OP_FRAME_EGRESS' byte of a pixel) are measured in exact integers and held to a target by one gain and one offset per
+ *   channel; the result is an fp16 frame in the decoder's convention that every outlet consumes unchanged.  Both ops: i0 H i1 W
+ *   (W % 8 == 0, H W % 16 == 0, H W <= L2D_COLOR_LOCK_MAX_PIXELS) i3 nblk = ceil(H W / L2D_COLOR_LOCK_BLOCK_PIXELS).
+ * L2D_OP_FRAME_MOMENTS  p0 half [3][H][W] p1 a second such tensor, or null p2 partials uint32 [i2][nblk][6] (all 16-byte aligned)
+ *   ; i2 number of tensors (1 | 2).  partials[t][k][0..2] = sum of b, partials[t][k][3..5] = sum of b^2 over pixels
+ *   [k BLOCK_PIXELS, (k + 1) BLOCK_PIXELS) of channel 0, 1, 2 of tensor t.  Every entry is written by a plain store on every
+ *   launch: nothing has to be zeroed, there are no atomics, and integer sums do not depend on any order.
+ * L2D_OP_COLOR_LOCK  p0 styled half [3][H][W] p1 out half [3][H][W] (not overlapping p0) p2 partials as above, tensor 0 = p0's (and
+ *   tensor 1 = the target frame's with L2D_COLOR_LOCK_SOURCE) p3 state_in double [3][2] = (mean, var) per channel p4 state_out
+ *   likewise (not overlapping p3: block 0 writes it while other blocks read p3) p5 coefficient record float [3][3] = (g, s, t) per
+ *   channel ; i2 flags ; l0, l1 the BITS of two doubles: the rate beta in (0, 1] and the strength a in [0, 1].  Arithmetic, every step
+ *   one correctly rounded operation and no fma, so that numpy restates it bit for bit (live2diff_amd/color_lock.py): with S1, S2 the
+ *   sums over the frame and n = H W, mean = double(S1) / double(n), var = double(n S2 - S1^2) / double(n n) (int64, exact); the new
+ *   state is the moments of tensor 1 (SOURCE), state_in (FREEZE), else the styled frame's moments c (INIT) or t + beta (c - t) in
+ *   three operations per value; per channel g = sqrt(var_t / var_s), 1 where either variance is 0, clamped to [1/4, 4], then
+ *   g = 1 + a (g - 1); m = mean_s + a (mean_t - mean_s); g32 = float(g), s32 = float(2 mean_s / 255 - 1), t32 = float(2 m / 255 - 1);
+ *   per pixel o = ((float(x) - s32) g32) + t32 in three fp32 operations, out = half(clamp(o, -1, 1)), round to nearest even.
+ *   Inputs are finite.
  */
 enum {
     L2D_OP_IGEMM = 1,
@@ -380,6 +400,8 @@ enum {
     L2D_OP_JPEG_RGB = 41,
     L2D_OP_WEIGHT_BLEND = 42,
     L2D_OP_FRAME_MATTE = 43,
+    L2D_OP_FRAME_MOMENTS = 44,
+    L2D_OP_COLOR_LOCK = 45,
 };
 
 /* flag bits of L2D_OP_FRAME_MATTE (i4) */
@@ -387,6 +409,13 @@ enum {
 #define L2D_MATTE_FAR 2
 #define L2D_MATTE_SHOW 4
 #define L2D_MATTE_MAX_R 8
+
+/* flag bits of L2D_OP_COLOR_LOCK (i2), and the sizes both colour-lock ops share */
+#define L2D_COLOR_LOCK_INIT 1
+#define L2D_COLOR_LOCK_SOURCE 2
+#define L2D_COLOR_LOCK_FREEZE 4
+#define L2D_COLOR_LOCK_BLOCK_PIXELS 4096 /* x 255^2 < 2^32: a block's sum of squares fits uint32 */
+#define L2D_COLOR_LOCK_MAX_PIXELS 4194304 /* 2^22: n S2 - S1^2 stays inside int64 */
 
 typedef struct l2d_op {
     int32_t kind;

@@ -1444,3 +1444,61 @@ def frame_matte(styled, source, depth, dst, *, B, H, W, lo32, inv32, hard, far=F
     op.l[0] = stride
     op.f[0], op.f[1] = float(lo32), float(inv32)
     return op, (styled, source, depth, dst)
+
+
+# ----------------------------------------------------------------------------- colour lock (colorlock.hip, color_lock.py)
+COLOR_LOCK_INIT, COLOR_LOCK_SOURCE, COLOR_LOCK_FREEZE = 1, 2, 4      # l2d.h L2D_COLOR_LOCK_*
+COLOR_LOCK_BLOCK_PIXELS = 4096                                       # l2d.h L2D_COLOR_LOCK_BLOCK_PIXELS
+COLOR_LOCK_MAX_PIXELS = 1 << 22                                      # l2d.h L2D_COLOR_LOCK_MAX_PIXELS
+
+
+def color_lock_blocks(H, W):
+    """the number of partial records one tensor of H x W pixels has"""
+    return -(-(int(H) * int(W)) // COLOR_LOCK_BLOCK_PIXELS)
+
+
+def _lock_frame(name, t, H, W):
+    if t.dtype != torch.float16 or tuple(t.shape[-3:]) != (3, H, W) or t.numel() != 3 * H * W or not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous fp16 [3,{H},{W}] frame, got {t.dtype} {tuple(t.shape)}")
+
+
+def frame_moments(frame, second, partials, *, H, W):
+    """fp16 [3,H,W] `frame` (and `second`, or None) -> uint32 (as int32) partials [1 or 2][blocks][6]: per block of
+    COLOR_LOCK_BLOCK_PIXELS pixels and per channel the sum and the sum of squares of the egress bytes (color_lock.sums_ref)"""
+    nt, nblk = (1 if second is None else 2), color_lock_blocks(H, W)
+    _lock_frame("frame_moments: frame", frame, H, W)
+    if second is not None:
+        _lock_frame("frame_moments: second", second, H, W)
+    if partials.dtype != torch.int32 or partials.numel() < nt * nblk * 6:
+        raise ValueError(f"frame_moments: partials must be int32 with at least {nt * nblk * 6} elements, got {partials.dtype} {tuple(partials.shape)}")
+    op = L2dOp()
+    op.kind = _lib.OP_FRAME_MOMENTS
+    op.p[0], op.p[1], op.p[2] = _ptr(frame), (None if second is None else _ptr(second)), _ptr(partials)
+    for j, v in enumerate([H, W, nt, nblk]):
+        op.i[j] = int(v)
+    return op, (frame, second, partials)
+
+
+def color_lock(styled, out, partials, state_in, state_out, coef, *, H, W, strength, rate, init=False, source=False, freeze=False):
+    """fp16 [3,H,W] `styled` + the partials `frame_moments` wrote (of `styled`, and with `source` of the target frame behind them)
+    + float64 [3,2] `state_in` -> fp16 [3,H,W] `out`, float64 [3,2] `state_out`, float32 [3,3] `coef`: color_lock.lock_ref"""
+    nblk = color_lock_blocks(H, W)
+    _lock_frame("color_lock: styled", styled, H, W)
+    _lock_frame("color_lock: out", out, H, W)
+    if partials.dtype != torch.int32 or partials.numel() < (2 if source else 1) * nblk * 6:
+        raise ValueError(f"color_lock: partials must be int32 with at least {(2 if source else 1) * nblk * 6} elements")
+    for name, t in (("state_in", state_in), ("state_out", state_out)):
+        if t.dtype != torch.float64 or t.numel() != 6 or not t.is_contiguous():
+            raise ValueError(f"color_lock: {name} must be a contiguous float64 [3,2] record, got {t.dtype} {tuple(t.shape)}")
+    if coef.dtype != torch.float32 or coef.numel() != 9 or not coef.is_contiguous():
+        raise ValueError(f"color_lock: coef must be a contiguous float32 [3,3] record, got {coef.dtype} {tuple(coef.shape)}")
+    op = L2dOp()
+    op.kind = _lib.OP_COLOR_LOCK
+    keep = (styled, out, partials, state_in, state_out, coef)
+    for j, t in enumerate(keep):
+        op.p[j] = _ptr(t)
+    flags = (COLOR_LOCK_INIT if init else 0) | (COLOR_LOCK_SOURCE if source else 0) | (COLOR_LOCK_FREEZE if freeze else 0)
+    for j, v in enumerate([H, W, flags, nblk]):
+        op.i[j] = int(v)
+    op.l[0], op.l[1] = (int(np.float64(v).view(np.int64)) for v in (rate, strength))         # the bits of the two doubles
+    return op, keep

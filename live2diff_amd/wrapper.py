@@ -15,7 +15,9 @@ backend cannot honour raise ValueError at construction, `"u8"` is a fifth output
 the frame leaves the device as the JPEG file the reference's demo makes of it on the host (jpeg_io.HipJpegEncoder).  A frame may
 also ARRIVE as a JPEG file (`bytes`, what the reference's demo receives from the browser, demo/util.py:22): it is decoded on the
 device (jpeg_io.HipJpegDecoder) and ingested there like a uint8 frame (`jpeg_decode="host"` decodes with Pillow instead).
-`set_matte` composites the output over the stream's own source frame by a matte of the frame's depth map (matte.py).
+`set_matte` composites the output over the stream's own source frame by a matte of the frame's depth map (matte.py);
+`set_color_lock` holds the output's per-channel colour statistics to the source's, a running average's or a reference image's
+(color_lock.py).
 """
 import os
 from pathlib import Path
@@ -257,7 +259,14 @@ class StreamAnimateDiffusionDepthWrapper:
     _matte = None                           # the depth matte's settings (set_matte), None: off
     _matte_line = None                      # matte.MatteLine: the delayed source frames and depth planes, while a matte is set
     _matte_dev = None                       # matte.HipMatte, made by the first composited frame on the device
-    _matte_skip = 0                         # frames pushed before the matte was set: their outputs leave as they are
+    _matte_skip = 0                         # frames pushed before the delay line existed: their outputs have no slot
+    _lock = None                            # the colour lock's settings (set_color_lock), None: off
+    _lock_dev = None                        # color_lock.HipColorLock, made by the first locked frame on the device
+    _lock_state = None                      # the target state on the host route (float64 [3,2]); on the device it stays there
+    _lock_ref = None                        # the moments of the reference image (mode "image")
+    _lock_load = None                       # a state the device record has yet to be loaded with
+    _lock_init = True                       # the next "ema" frame copies its own moments
+    _lock_last = None                       # the last locked frame: what a dropped frame's repeated output reuses
 
     def __init__(self, config_path: str, few_step_model_type: str, num_inference_steps: int,
                  t_index_list: Optional[List[int]] = None, strength: Optional[float] = None,
@@ -380,22 +389,35 @@ class StreamAnimateDiffusionDepthWrapper:
         frames: settings change with the next output; turning the matte on mid-stream starts the delay line (matte.MatteLine)
         with the next frame, and outputs of frames it has not seen are composited with the oldest frame it has.  The frames
         `prepare` returns are not composited."""
-        from .matte import SERVED_OUTPUT_TYPES, MatteLine, check_settings
+        from .matte import SERVED_OUTPUT_TYPES, check_settings
         if self.output_type not in SERVED_OUTPUT_TYPES:
             raise ValueError(f"set_matte: output_type={self.output_type!r} is not composited: use one of "
                              + ", ".join(repr(t) for t in SERVED_OUTPUT_TYPES))
         settings = check_settings(lo, hi, keep=keep, feather=feather, show=show)
-        if self._matte_line is None:
-            self._matte_line = MatteLine(self.batch_size, self.height, self.width, device=self.stream.device)
-            self.stream.matte_tap = self._matte_line
-            self._matte_skip = len(getattr(self.stream, "_pending", None) or ())
+        self._need_line()
         self._matte = settings
 
     def clear_matte(self) -> None:
-        """Back to the plain output route: no launch, copy or buffer of the matte is left in the frame's path."""
-        self._matte = self._matte_line = None
-        self._matte_skip = 0
-        self.stream.matte_tap = None
+        """Back to the plain output route: no launch, copy or buffer of the matte is left in the frame's path.  (A colour lock
+        to "source" keeps the delay line it shares with the matte.)"""
+        self._matte = None
+        self._release_line()
+
+    def _need_line(self) -> None:
+        """The delay line of source frames and depth planes, shared by the matte and the colour lock to "source": made by
+        whichever needs it first.  Outputs of frames pushed before it existed have no slot (`_matte_skip`)."""
+        if self._matte_line is None:
+            from .matte import MatteLine
+            self._matte_line = MatteLine(self.batch_size, self.height, self.width, device=self.stream.device)
+            self.stream.matte_tap = self._matte_line
+            self._matte_skip = len(getattr(self.stream, "_pending", None) or ())
+
+    def _release_line(self) -> None:
+        """drop the delay line when neither the matte nor a colour lock to "source" needs it"""
+        if self._matte is None and (self._lock is None or self._lock["mode"] != "source"):
+            self._matte_line = None
+            self._matte_skip = 0
+            self.stream.matte_tap = None
 
     def _composite(self, image_tensor, slot):
         """`postprocess_image` of a frame under the matte: op 43 in place of the egress op.  `slot` None (the line has seen no
@@ -429,6 +451,99 @@ class StreamAnimateDiffusionDepthWrapper:
             return u8
         from PIL import Image
         return Image.fromarray(u8)
+
+    # ------------------------------------------------------------------ colour lock (color_lock.py)
+    @property
+    def color_lock(self) -> Optional[dict]:
+        """the current colour lock as {to, strength, rate} (`to`: "source", "ema" or "image"), or None"""
+        return None if self._lock is None else dict(to=self._lock["mode"], strength=self._lock["strength"], rate=self._lock["rate"])
+
+    def set_color_lock(self, to="source", strength: float = 1.0, rate: float = 0.1) -> None:
+        """Hold the output's colour statistics: per channel, the mean and the standard deviation of the bytes the frame leaves
+        as are moved to a target by one gain (kept inside [1/4, 4]) and one offset.  `to="source"`: the frame's own source frame,
+        so the stream follows the room's lighting; `to="ema"`: a running average of the styled frames themselves,
+        t <- t + rate (c - t), so brightness and colour cast stop wandering (`prepare`, and this call, restart it from the next
+        frame); `to=` an image (a path, a PIL image, a uint8 frame, a JPEG file, a float [3,H,W] tensor in [0, 1]): that
+        image's statistics, measured once through the wrapper's own preprocessing and then frozen.  `strength` in [0, 1]
+        scales the correction (0: the frame as it is), `rate` in (0, 1] is the average's step.  Two small launches on the
+        device in front of the egress launch, the matte or the JPEG encoder; under a matte the styled frame is locked before
+        the composite, so the real part of the picture stays untouched.  Every output type but "latent" is served.  May be
+        called before or after `prepare` and between any two frames; the frames `prepare` returns are not locked, and a frame
+        the near-duplicate filter dropped repeats the last locked frame without moving the average."""
+        from .color_lock import SERVED_OUTPUT_TYPES, check_settings
+        if self.output_type not in SERVED_OUTPUT_TYPES:
+            raise ValueError(f"set_color_lock: output_type={self.output_type!r} is not locked: use one of "
+                             + ", ".join(repr(t) for t in SERVED_OUTPUT_TYPES))
+        settings = check_settings(to, strength, rate)
+        ref = self._reference_moments(to) if settings["mode"] == "image" else None
+        self._lock = settings
+        self._lock_ref = self._lock_state = self._lock_load = ref
+        self._lock_init, self._lock_last = True, None
+        if settings["mode"] == "source":
+            self._need_line()
+        else:
+            self._release_line()
+
+    def clear_color_lock(self) -> None:
+        """Back to the unlocked output: no launch, copy or buffer of the lock is left in the frame's path.  (A matte keeps the
+        delay line it shares with a lock to "source".)"""
+        self._lock = self._lock_ref = self._lock_state = self._lock_load = self._lock_last = None
+        self._lock_init = True
+        self._release_line()
+
+    def _reference_moments(self, image) -> np.ndarray:
+        """the moments of a reference image, through the preprocessing a frame of the stream gets"""
+        from .color_lock import moments_ref
+        x = self.preprocess_image(image)
+        dt = getattr(x, "dtype", None)
+        if self.io is not None and (dt == torch.uint8 or dt == np.uint8):
+            from .frame_io import HipFrameIO              # (an instance of its own: the stream's ingest slots are not disturbed)
+            x = HipFrameIO(self.height, self.width, device=self.io.device).ingest(x)
+            self._check_jpeg()
+        else:
+            x = self.stream.image_processor.preprocess(x, self.height, self.width)
+        return moments_ref(x[-1] if x.ndim == 4 else x)
+
+    def _locked(self, image_tensor: torch.Tensor, slot, repeated: bool) -> torch.Tensor:
+        """the frame under the colour lock, fp16 [1,3,H,W]: ops 44 + 45 on the device, `lock_ref` without one.  `repeated`: the
+        near-duplicate filter dropped the frame and `image_tensor` is the output of the one before; its locked frame is reused."""
+        lock = self._lock
+        if repeated and self._lock_last is not None:
+            return self._lock_last
+        source = None
+        if lock["mode"] == "source":
+            if slot is None:               # (an output of a frame the delay line has not seen)
+                return image_tensor
+            source = slot.source
+        if self.io is not None and image_tensor.is_cuda:
+            if self._lock_dev is None:
+                from .color_lock import HipColorLock
+                self._lock_dev = HipColorLock(self.height, self.width, device=image_tensor.device)
+            if self._lock_load is not None:
+                self._lock_dev.load_state(self._lock_load)
+                self._lock_load = None
+            out = self._lock_dev.lock(image_tensor[0], source, lock, init=self._lock_init)
+        else:
+            from .color_lock import lock_ref
+            out, self._lock_state = lock_ref(image_tensor[:1], self._lock_state, mode=lock["mode"], strength=lock["strength"],
+                                             rate=lock["rate"], init=self._lock_init, source=source)
+            out = torch.from_numpy(out)
+        self._lock_init = False
+        self._lock_last = out
+        return out
+
+    def _finish(self, image_tensor, slot, repeated: bool = False):
+        """`postprocess_image` of a frame while a colour lock or a matte is set: the lock first, then the matte's composite (or
+        the plain route) on the locked frame"""
+        if self._lock is not None and torch.is_tensor(image_tensor):
+            from .color_lock import SERVED_OUTPUT_TYPES
+            if self.output_type not in SERVED_OUTPUT_TYPES:
+                raise ValueError(f"a colour lock is set and output_type={self.output_type!r} is not locked: use one of "
+                                 + ", ".join(repr(t) for t in SERVED_OUTPUT_TYPES) + ", or clear_color_lock()")
+            image_tensor = self._locked(image_tensor, slot, repeated)
+        if self._matte is not None:
+            return self._composite(image_tensor, slot)
+        return self.postprocess_image(image_tensor, output_type=self.output_type)
 
     # ------------------------------------------------------------------ styles (style_bank.py, DESIGN.md section 8.z3)
     def _init_styles(self, pipe) -> None:
@@ -531,6 +646,9 @@ class StreamAnimateDiffusionDepthWrapper:
         kw = dict(prompt=prompt, negative_prompt=negative_prompt, guidance_scale=guidance_scale, delta=delta, seed=self.seed)
         self._prompt = prompt
         self._matte_skip = 0               # (`stream.prepare` primes the matte's delay line through the tap, when one is set)
+        self._lock_init, self._lock_last = True, None      # an "ema" colour lock starts again; a reference image's state stays
+        if self._lock is not None and self._lock["mode"] != "image":
+            self._lock_state = None
         if isinstance(warmup_frames, (list, tuple)) and warmup_frames and all(_is_jpeg(f) for f in warmup_frames):
             # (a device frame is a view of one of the decoder's two static slots: it is copied before the slot's next turn)
             decoded = [d.clone() if torch.is_tensor(d) else torch.from_numpy(d).to(self.io.device) if self.io is not None else d
@@ -572,12 +690,18 @@ class StreamAnimateDiffusionDepthWrapper:
         if prompt is not None:
             self._update_prompt(prompt)
         line = self._matte_line
-        if line is None:
+        if line is None and self._lock is None:
             return self.postprocess_image(self.stream(self.preprocess_image(image)), output_type=self.output_type)
+        if line is None:
+            # a frame the near-duplicate filter dropped comes back as the very tensor of the output before
+            before = getattr(self.stream, "prev_image_result", None)
+            out = self.stream(self.preprocess_image(image))
+            return self._finish(out, None, repeated=before is not None and out is before)
         seen = line.tapped
         out = self.stream(self.preprocess_image(image))
         # a frame the near-duplicate filter dropped never reached the tap: the repeated output keeps its slot
-        return self._composite(out, line.take() if line.tapped > seen else line.last)
+        fresh = line.tapped > seen
+        return self._finish(out, line.take() if fresh else line.last, repeated=not fresh)
 
     def push(self, image, prompt: Optional[str] = None) -> None:
         """pipelined mode (`frame_pipelining=True`): start a frame's encode / depth path; `pop()` returns the oldest frame's output"""
@@ -591,12 +715,15 @@ class StreamAnimateDiffusionDepthWrapper:
 
     def pop(self):
         out = self.stream.pop()
-        if self._matte_line is None:
+        if self._matte_line is None and self._lock is None:
             return self.postprocess_image(out, output_type=self.output_type)
-        if self._matte_skip:
-            self._matte_skip -= 1
-            return self.postprocess_image(out, output_type=self.output_type)
-        return self._composite(out, self._matte_line.take())
+        slot = None
+        if self._matte_line is not None:
+            if self._matte_skip:
+                self._matte_skip -= 1
+            else:
+                slot = self._matte_line.take()
+        return self._finish(out, slot)
 
     def _update_prompt(self, prompt: str) -> None:
         self.stream.update_prompt(prompt)

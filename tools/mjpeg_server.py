@@ -24,7 +24,12 @@ re-warm.  `GET /style` answers `{"styles": [...], "current": {...}}`.
 `--matte LO,HI[,FEATHER[,far]]` stylises only the near side (`far`: the far side) of a ramp over the frame's own depth map and
 keeps the real picture elsewhere (`wrapper.set_matte`: composited on the device, in front of the JPEG encoder).  `POST /matte`
 with the same text as its body, or `off`, changes it while the stream runs; the producer applies it between two frames.
-`GET /matte` answers the current settings as JSON (`null`: off)."""
+`GET /matte` answers the current settings as JSON (`null`: off).
+
+`--color-lock source|ema[,STRENGTH[,RATE]]` holds the output's per-channel brightness and contrast to the source frame's or to a
+running average of the stream's own (`wrapper.set_color_lock`: two small launches on the device in front of the JPEG encoder).
+`POST /color` with the same text as its body, or `off`, changes it while the stream runs; `GET /color` answers the current
+settings as JSON (`null`: off)."""
 import argparse
 import json
 import os
@@ -174,6 +179,53 @@ class MatteBox:
             self.failed += 1
 
 
+def parse_color_arg(text: str):
+    """`source|ema[,STRENGTH[,RATE]]` -> the keywords of `wrapper.set_color_lock`, `off` -> None; ValueError otherwise"""
+    from live2diff_amd.color_lock import check_settings
+    text = text.strip()
+    if text == "off":
+        return None
+    parts = [t.strip() for t in text.split(",")]
+    if not 1 <= len(parts) <= 3 or parts[0] not in ("source", "ema"):
+        raise ValueError(f"color lock {text!r}: use source|ema[,STRENGTH[,RATE]] or off")
+    try:
+        strength = float(parts[1]) if len(parts) > 1 else 1.0
+        rate = float(parts[2]) if len(parts) > 2 else 0.1
+    except ValueError:
+        raise ValueError(f"color lock {text!r}: STRENGTH is a number in [0, 1], RATE a number in (0, 1]") from None
+    s = check_settings(parts[0], strength, rate)
+    return dict(to=s["mode"], strength=s["strength"], rate=s["rate"])
+
+
+class ColorBox:
+    """What `POST /color` delivers: the newest requested colour lock (a dict of `set_color_lock` keywords, or None for `off`),
+    applied by the producer between two frames.  `current` is what was last applied; `failed` counts requests the wrapper refused."""
+    _NOTHING = object()
+
+    def __init__(self, current=None):
+        self._lock = threading.Lock()
+        self.current, self._want, self.failed = current, self._NOTHING, 0
+
+    def put(self, settings) -> None:
+        with self._lock:
+            self._want = settings
+
+    def apply(self, wrapper) -> None:
+        """(producer thread, between frames)"""
+        with self._lock:
+            want, self._want = self._want, self._NOTHING
+        if want is self._NOTHING:
+            return
+        try:
+            if want is None:
+                wrapper.clear_color_lock()
+            else:
+                wrapper.set_color_lock(want["to"], strength=want["strength"], rate=want["rate"])
+            self.current = wrapper.color_lock
+        except ValueError:
+            self.failed += 1
+
+
 def parse_style_arg(text: str):
     """`NAME=DREAMBOOTH[,LORA:ALPHA...]` -> (name, dreambooth path or None, {lora path: alpha})"""
     name, eq, rest = text.partition("=")
@@ -215,7 +267,7 @@ class Latest:
             return (self._seq, self._part) if self._seq > seen else None
 
 
-def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = None, mattes: "MatteBox" = None):
+def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = None, mattes: "MatteBox" = None, colors: "ColorBox" = None):
     page = PAGE if inbox is None else CAMERA_PAGE
 
     class Handler(BaseHTTPRequestHandler):
@@ -254,8 +306,8 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
                 self.send_header("Content-Length", str(len(body)))
                 self.end_headers()
                 self.wfile.write(body)
-            elif self.path == "/matte" and mattes is not None:
-                body = json.dumps(mattes.current).encode()
+            elif (self.path == "/matte" and mattes is not None) or (self.path == "/color" and colors is not None):
+                body = json.dumps((mattes if self.path == "/matte" else colors).current).encode()
                 self.send_response(200)
                 self.send_header("Content-Type", "application/json")
                 self.send_header("Content-Length", str(len(body)))
@@ -264,7 +316,8 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
             else:
                 self.send_error(404)
 
-        def do_matte(self):
+        def do_matte(self, box=None, parse=parse_matte_arg):
+            box = mattes if box is None else box
             try:
                 n = int(self.headers.get("Content-Length", ""))
             except ValueError:
@@ -274,11 +327,11 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
                 self.send_error(413 if n > 256 else 400)
                 return
             try:
-                want = parse_matte_arg(self.rfile.read(n).decode())
+                want = parse(self.rfile.read(n).decode())
             except ValueError as e:                       # (UnicodeDecodeError is a ValueError)
                 self.send_error(400, str(e.args[0] if e.args else e)[:200])
                 return
-            mattes.put(want)
+            box.put(want)
             self.send_response(204)
             self.end_headers()
 
@@ -308,6 +361,9 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
             if self.path == "/matte" and mattes is not None:
                 self.do_matte()
                 return
+            if self.path == "/color" and colors is not None:
+                self.do_matte(colors, parse_color_arg)
+                return
             if inbox is None or self.path != "/frame":
                 self.send_error(404)
                 return
@@ -330,8 +386,10 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
     return Handler
 
 
-def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: StyleBox = None, mattes: MatteBox = None) -> None:
-    """the producer: loops `frames` through the wrapper until `stop` is set; a posted style or matte is applied between two frames"""
+def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: StyleBox = None, mattes: MatteBox = None,
+            colors: ColorBox = None) -> None:
+    """the producer: loops `frames` through the wrapper until `stop` is set; a posted style, matte or colour lock is applied between
+    two frames"""
     from live2diff_amd.jpeg import mjpeg_part
     try:
         i = 0
@@ -340,6 +398,8 @@ def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: Styl
                 styles.apply(wrapper)
             if mattes is not None:
                 mattes.apply(wrapper)
+            if colors is not None:
+                colors.apply(wrapper)
             latest.put(mjpeg_part(wrapper(frames[i % len(frames)])))
             i += 1
     finally:
@@ -347,7 +407,7 @@ def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: Styl
 
 
 def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: threading.Event, styles: StyleBox = None,
-                   mattes: MatteBox = None) -> None:
+                   mattes: MatteBox = None, colors: ColorBox = None) -> None:
     """the producer of `--input post`: the first frames posted warm the stream up, then the newest posted frame goes through the
     wrapper, for ever; a frame the wrapper refuses (ValueError: a damaged file) is dropped and counted in `inbox.failed`"""
     from live2diff_amd.jpeg import mjpeg_part
@@ -364,6 +424,8 @@ def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: thr
                 styles.apply(wrapper)
             if mattes is not None:
                 mattes.apply(wrapper)
+            if colors is not None:
+                colors.apply(wrapper)
             try:
                 latest.put(mjpeg_part(wrapper(frame)))
             except ValueError:
@@ -390,9 +452,13 @@ def main(argv=None):
     ap.add_argument("--matte", default=None, metavar="LO,HI[,FEATHER[,far]]",
                     help="stylise only the near (`far`: the far) side of a depth ramp from LO to HI in [0, 1], 1 = nearest; POST /matte "
                          "with the same text, or `off`, changes it between frames")
+    ap.add_argument("--color-lock", default=None, metavar="source|ema[,STRENGTH[,RATE]]",
+                    help="hold the output's per-channel brightness and contrast to the source frame's (`source`) or to a running average "
+                         "of the stream's own (`ema`); POST /color with the same text, or `off`, changes it between frames")
     args = ap.parse_args(argv)
     style_args = [parse_style_arg(t) for t in args.style]
     matte = parse_matte_arg(args.matte) if args.matte else None
+    color = parse_color_arg(args.color_lock) if args.color_lock else None
 
     from stream_frames import read_frames
 
@@ -413,15 +479,18 @@ def main(argv=None):
     if matte is not None:
         w.set_matte(matte["lo"], matte["hi"], keep=matte["keep"], feather=matte["feather"])      # (before `prepare`: the line is primed)
     mattes = MatteBox(w.matte)
+    if color is not None:
+        w.set_color_lock(color["to"], strength=color["strength"], rate=color["rate"])        # (before `prepare`, like the matte)
+    colors = ColorBox(w.color_lock)
     prompt = args.prompt if args.prompt is not None else str(cfg.get("prompt", ""))
     latest, stop = Latest(), threading.Event()
     inbox = Inbox(sink) if post else None
     if post:
-        producer = threading.Thread(target=produce_posted, args=(w, prompt, inbox, latest, stop, styles, mattes), name="producer", daemon=True)
+        producer = threading.Thread(target=produce_posted, args=(w, prompt, inbox, latest, stop, styles, mattes, colors), name="producer", daemon=True)
     else:
         w.prepare(frames[:sink], prompt)
-        producer = threading.Thread(target=produce, args=(w, frames, latest, stop, styles, mattes), name="producer", daemon=True)
-    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest, inbox, styles, mattes))
+        producer = threading.Thread(target=produce, args=(w, frames, latest, stop, styles, mattes, colors), name="producer", daemon=True)
+    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest, inbox, styles, mattes, colors))
     server.daemon_threads = True
     producer.start()
     print(f"http://{args.host}:{args.port}/  ({args.height}x{args.width}, quality {args.quality}; Ctrl-C stops)")
