@@ -355,6 +355,21 @@ enum {
  *   g = 1 + a (g - 1); m = mean_s + a (mean_t - mean_s); g32 = float(g), s32 = float(2 mean_s / 255 - 1), t32 = float(2 m / 255 - 1);
  *   per pixel o = ((float(x) - s32) g32) + t32 in three fp32 operations, out = half(clamp(o, -1, 1)), round to nearest even.
  *   Inputs are finite.
+ *
+ * Output size (resize.hip; the reference's callers resize the PIL image they get on the host).  Pillow's `Image.resize` on 8-bit
+ *   images, integer arithmetic throughout -- the frame equals live2diff_amd/resize.py `resize_ref` (and Pillow) byte for byte.
+ * L2D_OP_FRAME_RESIZE  source patch to bytes, horizontal pass, vertical pass, one launch:  p0 src, either half [B][3][H][W] in
+ *   [-1, 1] (4-byte aligned; mapped to bytes with L2D_OP_FRAME_EGRESS' expression first) or uint8 [B][H][W][3] p1 dst uint8
+ *   [B][Ho][Wo][3] (any alignment) p2 table of the x axis p3 table of the y axis (int32, 4-byte aligned; for an axis of n_out
+ *   outputs: xmin [n_out], count [n_out], k [n_out][KS] behind one another, as resize.coefficients builds them: output xx reads
+ *   inputs xmin[xx] .. xmin[xx] + count[xx] - 1 with the weights k[xx][0 .. count[xx]), 22 fractional bits) ; i0 B i1 H i2 W
+ *   i3 Ho i4 Wo i5 source kind (0 half, 1 uint8) i6 KS of the x table i7 KS of the y table (1..L2D_RESIZE_MAX_KS).  One pass:
+ *   out = clip((2^21 + sum_x in[xmin + x] k[xx][x]) >> 22, 0, 255), arithmetic shift, in 32-bit integers (the host asserts
+ *   255 sum |k| + 2^21 < 2^31 for every row); x first, rounded to a uint8 image, then y.  An axis that keeps its size carries
+ *   the identity table (KS 1, k = 2^22).  What the kernel reads from a table is clamped to the image and to KS.  Only bytes of
+ *   [dst, dst + B Ho Wo 3) are written, by plain stores (whole dwords where the address allows, bytes at the ends of a row).
+ *   Refused: Ho, Wo outside 1..L2D_RESIZE_MAX_SIZE or outside [n_in / 2, 8 n_in], KS outside 1..L2D_RESIZE_MAX_KS,
+ *   B Ho Wo 3 >= 2^31, B > 65535, a null or misaligned table, an fp16 source that is not 4-byte aligned.
  */
 enum {
     L2D_OP_IGEMM = 1,
@@ -402,6 +417,7 @@ enum {
     L2D_OP_FRAME_MATTE = 43,
     L2D_OP_FRAME_MOMENTS = 44,
     L2D_OP_COLOR_LOCK = 45,
+    L2D_OP_FRAME_RESIZE = 46,
 };
 
 /* flag bits of L2D_OP_FRAME_MATTE (i4) */
@@ -416,6 +432,10 @@ enum {
 #define L2D_COLOR_LOCK_FREEZE 4
 #define L2D_COLOR_LOCK_BLOCK_PIXELS 4096 /* x 255^2 < 2^32: a block's sum of squares fits uint32 */
 #define L2D_COLOR_LOCK_MAX_PIXELS 4194304 /* 2^22: n S2 - S1^2 stays inside int64 */
+
+/* sizes of L2D_OP_FRAME_RESIZE */
+#define L2D_RESIZE_MAX_KS 13 /* taps per output: Lanczos (support 3) at a 2x down-scale, 2 * 6 + 1 */
+#define L2D_RESIZE_MAX_SIZE 4096
 
 typedef struct l2d_op {
     int32_t kind;

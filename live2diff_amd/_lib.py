@@ -28,6 +28,7 @@ OP_JPEG_ENTROPY_DEC, OP_JPEG_IDCT, OP_JPEG_RGB = 39, 40, 41
 OP_WEIGHT_BLEND = 42
 OP_FRAME_MATTE = 43
 OP_FRAME_MOMENTS, OP_COLOR_LOCK = 44, 45
+OP_FRAME_RESIZE = 46
 ABI_VERSION = 6
 
 

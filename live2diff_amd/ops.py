@@ -1502,3 +1502,30 @@ def color_lock(styled, out, partials, state_in, state_out, coef, *, H, W, streng
         op.i[j] = int(v)
     op.l[0], op.l[1] = (int(np.float64(v).view(np.int64)) for v in (rate, strength))         # the bits of the two doubles
     return op, keep
+
+
+# ----------------------------------------------------------------------------- output size (resize.hip, resize.py)
+RESIZE_MAX_KS = 13              # l2d.h L2D_RESIZE_MAX_KS
+RESIZE_MAX_SIZE = 4096          # l2d.h L2D_RESIZE_MAX_SIZE
+RESIZE_TILE = 32                # resize.hip RS_TW = RS_TH: a tile reads at most 2 * RESIZE_TILE + RESIZE_MAX_KS source pixels per axis
+
+
+def _resize_table(name, t, n_out):
+    if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() % n_out or t.numel() // n_out < 3:
+        raise ValueError(f"frame_resize: {name} must be a contiguous int32 table of {n_out} x (2 + KS) elements, got {t.dtype} "
+                         f"{tuple(t.shape)}")
+    return t.numel() // n_out - 2
+
+
+def frame_resize(src, dst, tx, ty, *, B, H, W, Ho, Wo):
+    """fp16 [B,3,H,W] in [-1, 1] (the egress op's bytes first) or uint8 [B,H,W,3] -> uint8 [B,Ho,Wo,3], Pillow's resampling
+    (resize.resize_ref); `tx`, `ty`: the int32 tables of the two axes as `resize.axis_table` lays them out"""
+    assert src.dtype in (torch.float16, torch.uint8) and dst.dtype == torch.uint8
+    assert src.numel() >= B * H * W * 3 and dst.numel() >= B * Ho * Wo * 3
+    ksx, ksy = _resize_table("tx", tx, Wo), _resize_table("ty", ty, Ho)
+    op = L2dOp()
+    op.kind = _lib.OP_FRAME_RESIZE
+    op.p[0], op.p[1], op.p[2], op.p[3] = _ptr(src), _ptr(dst), _ptr(tx), _ptr(ty)
+    for j, v in enumerate([B, H, W, Ho, Wo, int(src.dtype == torch.uint8), ksx, ksy]):
+        op.i[j] = int(v)
+    return op, (src, dst, tx, ty)

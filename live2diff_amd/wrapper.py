@@ -17,12 +17,13 @@ also ARRIVE as a JPEG file (`bytes`, what the reference's demo receives from the
 device (jpeg_io.HipJpegDecoder) and ingested there like a uint8 frame (`jpeg_decode="host"` decodes with Pillow instead).
 `set_matte` composites the output over the stream's own source frame by a matte of the frame's depth map (matte.py);
 `set_color_lock` holds the output's per-channel colour statistics to the source's, a running average's or a reference image's
-(color_lock.py).
+(color_lock.py).  `set_output_size` (or the `output_size` keyword) resamples the uint8 frame to a size of the caller's choice
+with Pillow's arithmetic, behind both and in front of the JPEG encoder or the copy to the host (resize.py).
 """
 import os
 from pathlib import Path
 from types import SimpleNamespace
-from typing import Dict, List, Optional, Union
+from typing import Dict, List, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -267,6 +268,9 @@ class StreamAnimateDiffusionDepthWrapper:
     _lock_load = None                       # a state the device record has yet to be loaded with
     _lock_init = True                       # the next "ema" frame copies its own moments
     _lock_last = None                       # the last locked frame: what a dropped frame's repeated output reuses
+    _size = None                            # the output size's settings (set_output_size), None: the UNet's geometry
+    _size_dev = None                        # resize.HipResize of the current size, made by the first resized frame on the device
+    _size_jpeg = None                       # {(height, width): jpeg_io.HipJpegEncoder}, one per output size "jpeg" frames left at
 
     def __init__(self, config_path: str, few_step_model_type: str, num_inference_steps: int,
                  t_index_list: Optional[List[int]] = None, strength: Optional[float] = None,
@@ -277,7 +281,8 @@ class StreamAnimateDiffusionDepthWrapper:
                  similar_image_filter_threshold: float = 0.98, similar_image_filter_max_skip_frame: int = 10,
                  use_denoising_batch: bool = True, cfg_type: str = "none", seed: int = 42,
                  engine_dir: Optional[Union[str, Path]] = "engines", opt_unet: bool = False, frame_pipelining: bool = False,
-                 jpeg_quality: int = 75, jpeg_decode: str = "device"):
+                 jpeg_quality: int = 75, jpeg_decode: str = "device", output_size: Optional[Tuple[int, int]] = None,
+                 output_resample: str = "lanczos"):
         self._check_keywords(few_step_model_type=few_step_model_type, acceleration=acceleration, cfg_type=cfg_type,
                              use_denoising_batch=use_denoising_batch, frame_buffer_size=frame_buffer_size, device_ids=device_ids,
                              opt_unet=opt_unet, output_type=output_type, dtype=dtype, jpeg_quality=jpeg_quality, jpeg_decode=jpeg_decode)
@@ -296,13 +301,13 @@ class StreamAnimateDiffusionDepthWrapper:
                     window_size=window, frame_pipelining=frame_pipelining, enable_similar_image_filter=enable_similar_image_filter,
                     similar_image_filter_threshold=similar_image_filter_threshold,
                     similar_image_filter_max_skip_frame=similar_image_filter_max_skip_frame, jpeg_quality=jpeg_quality,
-                    jpeg_decode=jpeg_decode)
+                    jpeg_decode=jpeg_decode, output_size=output_size, output_resample=output_resample)
 
     @classmethod
     def from_components(cls, pipe, *, num_inference_steps: int, t_index_list: Optional[List[int]] = None,
                         strength: Optional[float] = None, **kw):
         """The wrapper around an already assembled `pipe` namespace (tests, synthetic weights).  Keywords: those of the
-        constructor that do not name files (`jpeg_quality` and `jpeg_decode` among them), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
+        constructor that do not name files (`jpeg_quality`, `jpeg_decode`, `output_size` and `output_resample` among them), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
         self = cls.__new__(cls)
         cls._check_keywords(**{k: kw.pop(k) for k in ("acceleration", "cfg_type", "use_denoising_batch", "frame_buffer_size",
                                                       "device_ids", "opt_unet", "few_step_model_type") if k in kw},
@@ -341,7 +346,8 @@ class StreamAnimateDiffusionDepthWrapper:
     def _setup(self, pipe, *, num_inference_steps, t_index_list, strength, output_type="pil", device=None, dtype=torch.float16,
                width=512, height=512, do_add_noise=True, seed=42, clip_skip=1, warmup_frames=8, window_size=16,
                scheduler_kwargs=None, frame_pipelining=False, enable_similar_image_filter=False,
-               similar_image_filter_threshold=0.98, similar_image_filter_max_skip_frame=10, jpeg_quality=75, jpeg_decode="device"):
+               similar_image_filter_threshold=0.98, similar_image_filter_max_skip_frame=10, jpeg_quality=75, jpeg_decode="device",
+               output_size=None, output_resample="lanczos"):
         self.sd_turbo = False
         self.device = pipe.device if device is None else device
         self.dtype, self.width, self.height = dtype, width, height
@@ -352,6 +358,10 @@ class StreamAnimateDiffusionDepthWrapper:
         if output_type == "jpeg":
             from . import jpeg
             jpeg._check(height, width, jpeg_quality)       # a size that is no multiple of 16 is refused here, not at the first frame
+        if output_size is not None:                        # (and an output size nobody serves, likewise)
+            if not isinstance(output_size, (tuple, list)) or len(output_size) != 2:
+                raise ValueError(f"output_size={output_size!r}: use (height, width) or None")
+            self.set_output_size(*output_size, resample=output_resample)
         self.frame_buffer_size = 1
         self.use_denoising_batch = True
         self.seed = seed
@@ -533,17 +543,102 @@ class StreamAnimateDiffusionDepthWrapper:
         return out
 
     def _finish(self, image_tensor, slot, repeated: bool = False):
-        """`postprocess_image` of a frame while a colour lock or a matte is set: the lock first, then the matte's composite (or
-        the plain route) on the locked frame"""
+        """`postprocess_image` of a frame while a colour lock, a matte or an output size is set: the lock first, then the matte's
+        composite (or the plain route) on the locked frame, resampled when an output size is set"""
         if self._lock is not None and torch.is_tensor(image_tensor):
             from .color_lock import SERVED_OUTPUT_TYPES
             if self.output_type not in SERVED_OUTPUT_TYPES:
                 raise ValueError(f"a colour lock is set and output_type={self.output_type!r} is not locked: use one of "
                                  + ", ".join(repr(t) for t in SERVED_OUTPUT_TYPES) + ", or clear_color_lock()")
             image_tensor = self._locked(image_tensor, slot, repeated)
+        if self._size is not None:
+            return self._sized(image_tensor, slot)
         if self._matte is not None:
             return self._composite(image_tensor, slot)
         return self.postprocess_image(image_tensor, output_type=self.output_type)
+
+    # ------------------------------------------------------------------ output size (resize.py, DESIGN.md section 8.z6)
+    @property
+    def output_size(self) -> Optional[dict]:
+        """the current output size as {height, width, resample}, or None: frames leave at the UNet's size"""
+        return None if self._size is None else dict(self._size)
+
+    def set_output_size(self, height: int, width: int, resample: str = "lanczos") -> None:
+        """Give frames back at `height` x `width` instead of the UNet's size: Pillow's `Image.resize` on the uint8 frame
+        (`resample`: "lanczos", "bicubic" or "bilinear"), byte for byte, in one launch on the device.  Per axis the size may lie
+        between half and 8 times the UNet's, up to 4096; for "jpeg" it must also be a multiple of 16 and no wider than 1920, which
+        is checked here.  The order on a frame is colour lock, matte, resize, then the JPEG encoder ("jpeg", one encoder per
+        size; no raw frame reaches the host) or the copy to the host ("u8", "pil"); the float output types are not served.
+        Without a matte the launch takes the fp16 frame and replaces the egress launch; with one it takes the matte's uint8
+        frame.  Resampling the composite is the whole feature: under a matte the kept real part of the picture is the
+        UNet-sized source frame scaled up, not the camera's own pixels, and nothing is sharpened.  May be called before or after
+        `prepare` and between any two frames: the change applies from the next output.  The frames `prepare` returns are not
+        resized; a frame the near-duplicate filter dropped yields the bytes of the frame before it."""
+        from .resize import SERVED_OUTPUT_TYPES, check_filter, check_jpeg_size, check_size
+        if self.output_type not in SERVED_OUTPUT_TYPES:
+            raise ValueError(f"set_output_size: output_type={self.output_type!r} is not resampled: use one of "
+                             + ", ".join(repr(t) for t in SERVED_OUTPUT_TYPES))
+        ho, wo = check_size(self.height, self.width, height, width)
+        check_filter(resample)
+        if self.output_type == "jpeg":
+            check_jpeg_size(ho, wo)
+        self._size = dict(height=ho, width=wo, resample=resample)
+
+    def clear_output_size(self) -> None:
+        """Back to the UNet's size: no launch, copy or buffer of the resize is left in the frame's path."""
+        self._size = self._size_dev = self._size_jpeg = None
+
+    def _sized(self, image_tensor, slot):
+        """`postprocess_image` of a frame while an output size is set: the matte's composite (or the egress bytes) resampled,
+        then the encoder or the copy to the host.  On the device op 46 takes the fp16 frame in place of the egress launch, or
+        the matte's uint8 buffer."""
+        from .resize import SERVED_OUTPUT_TYPES, check_jpeg_size, resize_ref
+        ot, size = self.output_type, self._size
+        if ot not in SERVED_OUTPUT_TYPES:
+            raise ValueError(f"an output size is set and output_type={ot!r} is not resampled: use one of "
+                             + ", ".join(repr(t) for t in SERVED_OUTPUT_TYPES) + ", or clear_output_size()")
+        if not torch.is_tensor(image_tensor):
+            return self.postprocess_image(image_tensor, output_type=ot)
+        ho, wo = size["height"], size["width"]
+        if ot == "jpeg":
+            check_jpeg_size(ho, wo)
+        matte = self._matte is not None and slot is not None           # (slot None: the delay line has seen no frame yet)
+        if self.io is not None and image_tensor.is_cuda:
+            rs = self._size_dev
+            if rs is None or (rs.out_height, rs.out_width, rs.resample) != (ho, wo, size["resample"]):
+                from .resize import HipResize
+                rs = self._size_dev = HipResize(self.height, self.width, ho, wo, size["resample"], device=image_tensor.device)
+            src = image_tensor[0]
+            if matte:
+                if self._matte_dev is None:
+                    from .matte import HipMatte
+                    self._matte_dev = HipMatte(self.height, self.width, device=image_tensor.device)
+                src = self._matte_dev.composite(src, slot, self._matte, to_host=False)
+            if ot == "jpeg":
+                encoders = self._size_jpeg = self._size_jpeg or {}
+                if (ho, wo) not in encoders:
+                    from .jpeg_io import HipJpegEncoder
+                    encoders[ho, wo] = HipJpegEncoder(ho, wo, self.jpeg_quality, device=image_tensor.device)
+                out = encoders[ho, wo].encode(rs.resize(src, to_host=False))
+                self._check_jpeg()
+                return out
+            u8 = rs.resize(src).copy()                                 # (the pinned buffer is overwritten by the next frame)
+        else:
+            if matte:
+                from .matte import composite_ref
+                u8 = composite_ref(image_tensor[:1], slot.source[None], slot.depth[None], **self._matte)[0]
+            else:
+                from .frame_io import egress_ref
+                u8 = egress_ref(image_tensor)[0].numpy()
+            u8 = resize_ref(u8, ho, wo, size["resample"])
+        self._check_jpeg()
+        if ot == "jpeg":
+            from .jpeg import encode_ref
+            return encode_ref(u8, self.jpeg_quality)
+        if ot == "u8":
+            return u8
+        from PIL import Image
+        return Image.fromarray(u8)
 
     # ------------------------------------------------------------------ styles (style_bank.py, DESIGN.md section 8.z3)
     def _init_styles(self, pipe) -> None:
@@ -690,7 +785,7 @@ class StreamAnimateDiffusionDepthWrapper:
         if prompt is not None:
             self._update_prompt(prompt)
         line = self._matte_line
-        if line is None and self._lock is None:
+        if line is None and self._lock is None and self._size is None:
             return self.postprocess_image(self.stream(self.preprocess_image(image)), output_type=self.output_type)
         if line is None:
             # a frame the near-duplicate filter dropped comes back as the very tensor of the output before
@@ -715,7 +810,7 @@ class StreamAnimateDiffusionDepthWrapper:
 
     def pop(self):
         out = self.stream.pop()
-        if self._matte_line is None and self._lock is None:
+        if self._matte_line is None and self._lock is None and self._size is None:
             return self.postprocess_image(out, output_type=self.output_type)
         slot = None
         if self._matte_line is not None:

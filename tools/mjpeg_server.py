@@ -29,7 +29,12 @@ with the same text as its body, or `off`, changes it while the stream runs; the 
 `--color-lock source|ema[,STRENGTH[,RATE]]` holds the output's per-channel brightness and contrast to the source frame's or to a
 running average of the stream's own (`wrapper.set_color_lock`: two small launches on the device in front of the JPEG encoder).
 `POST /color` with the same text as its body, or `off`, changes it while the stream runs; `GET /color` answers the current
-settings as JSON (`null`: off)."""
+settings as JSON (`null`: off).
+
+`--output-size WxH[,FILTER]` serves frames of W x H pixels instead of the UNet's size (`wrapper.set_output_size`: Pillow's
+resampling in one launch on the device, in front of a JPEG encoder of that size; FILTER is lanczos, bicubic or bilinear; both
+sizes are multiples of 16 and W is at most 1920).  `POST /size` with the same text as its body, or `off`, changes it while the
+stream runs; `GET /size` answers the current settings as JSON (`null`: off)."""
 import argparse
 import json
 import os
@@ -226,6 +231,56 @@ class ColorBox:
             self.failed += 1
 
 
+def parse_size_arg(text: str):
+    """`WxH[,FILTER]` -> the keywords of `wrapper.set_output_size`, `off` -> None; ValueError otherwise (the wrapper, which knows
+    the stream's size, checks the ratio once more)"""
+    from live2diff_amd.resize import MAX_SIZE, check_filter, check_jpeg_size
+    text = text.strip()
+    if text == "off":
+        return None
+    size, comma, resample = text.partition(",")
+    w, x, h = size.strip().lower().partition("x")
+    try:
+        if not x or (comma and not resample.strip()):
+            raise ValueError
+        width, height = int(w), int(h)
+    except ValueError:
+        raise ValueError(f"output size {text!r}: use WxH[,FILTER] (two integers, then lanczos, bicubic or bilinear) or off") from None
+    if not (1 <= width <= MAX_SIZE and 1 <= height <= MAX_SIZE):
+        raise ValueError(f"output size {text!r}: W and H lie in 1..{MAX_SIZE}")
+    check_jpeg_size(height, width)
+    return dict(height=height, width=width, resample=check_filter(resample.strip() if comma else "lanczos"))
+
+
+class SizeBox:
+    """What `POST /size` delivers: the newest requested output size (a dict of `set_output_size` keywords, or None for `off`),
+    applied by the producer between two frames.  `current` is what was last applied; `failed` counts requests the wrapper refused."""
+    _NOTHING = object()
+
+    def __init__(self, current=None):
+        self._lock = threading.Lock()
+        self.current, self._want, self.failed = current, self._NOTHING, 0
+
+    def put(self, settings) -> None:
+        with self._lock:
+            self._want = settings
+
+    def apply(self, wrapper) -> None:
+        """(producer thread, between frames)"""
+        with self._lock:
+            want, self._want = self._want, self._NOTHING
+        if want is self._NOTHING:
+            return
+        try:
+            if want is None:
+                wrapper.clear_output_size()
+            else:
+                wrapper.set_output_size(want["height"], want["width"], resample=want["resample"])
+            self.current = wrapper.output_size
+        except ValueError:
+            self.failed += 1
+
+
 def parse_style_arg(text: str):
     """`NAME=DREAMBOOTH[,LORA:ALPHA...]` -> (name, dreambooth path or None, {lora path: alpha})"""
     name, eq, rest = text.partition("=")
@@ -267,7 +322,9 @@ class Latest:
             return (self._seq, self._part) if self._seq > seen else None
 
 
-def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = None, mattes: "MatteBox" = None, colors: "ColorBox" = None):
+def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = None, mattes: "MatteBox" = None, colors: "ColorBox" = None,
+                 sizes: "SizeBox" = None):
+    boxes = {"/matte": mattes, "/color": colors, "/size": sizes}
     page = PAGE if inbox is None else CAMERA_PAGE
 
     class Handler(BaseHTTPRequestHandler):
@@ -306,8 +363,8 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
                 self.send_header("Content-Length", str(len(body)))
                 self.end_headers()
                 self.wfile.write(body)
-            elif (self.path == "/matte" and mattes is not None) or (self.path == "/color" and colors is not None):
-                body = json.dumps((mattes if self.path == "/matte" else colors).current).encode()
+            elif boxes.get(self.path) is not None:
+                body = json.dumps(boxes[self.path].current).encode()
                 self.send_response(200)
                 self.send_header("Content-Type", "application/json")
                 self.send_header("Content-Length", str(len(body)))
@@ -364,6 +421,9 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
             if self.path == "/color" and colors is not None:
                 self.do_matte(colors, parse_color_arg)
                 return
+            if self.path == "/size" and sizes is not None:
+                self.do_matte(sizes, parse_size_arg)
+                return
             if inbox is None or self.path != "/frame":
                 self.send_error(404)
                 return
@@ -387,9 +447,9 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
 
 
 def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: StyleBox = None, mattes: MatteBox = None,
-            colors: ColorBox = None) -> None:
-    """the producer: loops `frames` through the wrapper until `stop` is set; a posted style, matte or colour lock is applied between
-    two frames"""
+            colors: ColorBox = None, sizes: SizeBox = None) -> None:
+    """the producer: loops `frames` through the wrapper until `stop` is set; a posted style, matte, colour lock or output size is
+    applied between two frames"""
     from live2diff_amd.jpeg import mjpeg_part
     try:
         i = 0
@@ -400,6 +460,8 @@ def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: Styl
                 mattes.apply(wrapper)
             if colors is not None:
                 colors.apply(wrapper)
+            if sizes is not None:
+                sizes.apply(wrapper)
             latest.put(mjpeg_part(wrapper(frames[i % len(frames)])))
             i += 1
     finally:
@@ -407,7 +469,7 @@ def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: Styl
 
 
 def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: threading.Event, styles: StyleBox = None,
-                   mattes: MatteBox = None, colors: ColorBox = None) -> None:
+                   mattes: MatteBox = None, colors: ColorBox = None, sizes: SizeBox = None) -> None:
     """the producer of `--input post`: the first frames posted warm the stream up, then the newest posted frame goes through the
     wrapper, for ever; a frame the wrapper refuses (ValueError: a damaged file) is dropped and counted in `inbox.failed`"""
     from live2diff_amd.jpeg import mjpeg_part
@@ -426,6 +488,8 @@ def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: thr
                 mattes.apply(wrapper)
             if colors is not None:
                 colors.apply(wrapper)
+            if sizes is not None:
+                sizes.apply(wrapper)
             try:
                 latest.put(mjpeg_part(wrapper(frame)))
             except ValueError:
@@ -455,10 +519,14 @@ def main(argv=None):
     ap.add_argument("--color-lock", default=None, metavar="source|ema[,STRENGTH[,RATE]]",
                     help="hold the output's per-channel brightness and contrast to the source frame's (`source`) or to a running average "
                          "of the stream's own (`ema`); POST /color with the same text, or `off`, changes it between frames")
+    ap.add_argument("--output-size", default=None, metavar="WxH[,FILTER]",
+                    help="serve frames of W x H pixels (multiples of 16, W <= 1920) resampled on the device with lanczos (default), "
+                         "bicubic or bilinear; POST /size with the same text, or `off`, changes it between frames")
     args = ap.parse_args(argv)
     style_args = [parse_style_arg(t) for t in args.style]
     matte = parse_matte_arg(args.matte) if args.matte else None
     color = parse_color_arg(args.color_lock) if args.color_lock else None
+    size = parse_size_arg(args.output_size) if args.output_size else None
 
     from stream_frames import read_frames
 
@@ -472,7 +540,8 @@ def main(argv=None):
     w = StreamAnimateDiffusionDepthWrapper(args.config, few_step_model_type="lcm", num_inference_steps=cfg.get("num_inference_steps", 50),
                                            t_index_list=cfg.get("t_index_list"), strength=cfg.get("strength"), output_type="jpeg",
                                            jpeg_quality=args.quality, height=args.height, width=args.width, seed=args.seed,
-                                           engine_dir=args.engine_dir)
+                                           engine_dir=args.engine_dir, output_size=size and (size["height"], size["width"]),
+                                           output_resample=size["resample"] if size else "lanczos")
     for name, db, loras in style_args:
         w.add_style(name, dreambooth_path=db, lora_dict=loras or None)
     styles = StyleBox(w.styles, w.style)
@@ -482,15 +551,16 @@ def main(argv=None):
     if color is not None:
         w.set_color_lock(color["to"], strength=color["strength"], rate=color["rate"])        # (before `prepare`, like the matte)
     colors = ColorBox(w.color_lock)
+    sizes = SizeBox(w.output_size)
     prompt = args.prompt if args.prompt is not None else str(cfg.get("prompt", ""))
     latest, stop = Latest(), threading.Event()
     inbox = Inbox(sink) if post else None
     if post:
-        producer = threading.Thread(target=produce_posted, args=(w, prompt, inbox, latest, stop, styles, mattes, colors), name="producer", daemon=True)
+        producer = threading.Thread(target=produce_posted, args=(w, prompt, inbox, latest, stop, styles, mattes, colors, sizes), name="producer", daemon=True)
     else:
         w.prepare(frames[:sink], prompt)
-        producer = threading.Thread(target=produce, args=(w, frames, latest, stop, styles, mattes, colors), name="producer", daemon=True)
-    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest, inbox, styles, mattes, colors))
+        producer = threading.Thread(target=produce, args=(w, frames, latest, stop, styles, mattes, colors, sizes), name="producer", daemon=True)
+    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest, inbox, styles, mattes, colors, sizes))
     server.daemon_threads = True
     producer.start()
     print(f"http://{args.host}:{args.port}/  ({args.height}x{args.width}, quality {args.quality}; Ctrl-C stops)")
