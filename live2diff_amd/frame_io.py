@@ -91,6 +91,14 @@ def egress_ref(x: torch.Tensor) -> torch.Tensor:
 
 
 # ----------------------------------------------------------------------------- the device side
+def to_pinned(dev: torch.Tensor, host: torch.Tensor) -> np.ndarray:
+    """a static device buffer copied into its pinned twin on the current stream and waited for: the numpy view of the pinned
+    buffer, valid until the next copy into it (the end of `HipFrameIO.egress`, `HipMatte.composite` and `HipResize.resize`)"""
+    host.copy_(dev, non_blocking=True)
+    torch.cuda.current_stream().synchronize()
+    return host.numpy()
+
+
 class _Slot:
     def __init__(self, Hs, Ws, H, W, device):
         self.staging = torch.empty(Hs, Ws, 3, dtype=torch.uint8).pin_memory()
@@ -226,9 +234,7 @@ class HipFrameIO:
         pl.run()
         if not to_host:
             return dev[0] if single else dev
-        host.copy_(dev, non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-        arr = host.numpy()
+        arr = to_pinned(dev, host)
         return arr[0] if single else arr
 
 

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .frame_io import to_pinned
 
 MAX_FEATHER = ops.MATTE_MAX_R
 SERVED_OUTPUT_TYPES = ("u8", "pil", "jpeg")
@@ -233,6 +234,4 @@ class HipMatte:
         pl.run()
         if not to_host:
             return self.dev[0]
-        self.host.copy_(self.dev, non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-        return self.host.numpy()[0]
+        return to_pinned(self.dev, self.host)[0]

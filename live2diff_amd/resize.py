@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .frame_io import to_pinned
 
 SERVED_OUTPUT_TYPES = ("u8", "pil", "jpeg")
 PRECISION_BITS = 22                      # 32 - 8 - 2: a byte times a coefficient of up to 2 in a signed 32-bit accumulator
@@ -211,6 +212,4 @@ class HipResize:
         self._plan(image).run()
         if not to_host:
             return self.dev[0]
-        self.host.copy_(self.dev, non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-        return self.host.numpy()[0]
+        return to_pinned(self.dev, self.host)[0]

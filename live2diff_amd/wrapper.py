@@ -19,7 +19,12 @@ device (jpeg_io.HipJpegDecoder) and ingested there like a uint8 frame (`jpeg_dec
 `set_color_lock` holds the output's per-channel colour statistics to the source's, a running average's or a reference image's
 (color_lock.py).  `set_output_size` (or the `output_size` keyword) resamples the uint8 frame to a size of the caller's choice
 with Pillow's arithmetic, behind both and in front of the JPEG encoder or the copy to the host (resize.py).
+
+Every frame leaves through one chain, `_route`: colour lock (`_finish`, in front of it) -> matte composite, or egress -> resize
+-> JPEG encoder, or copy to the host.  A stage that is not set is not in the chain; on the device each stage is one launch that
+hands its static buffer to the next, and only the last one copies to the host.
 """
+import functools
 import os
 from pathlib import Path
 from types import SimpleNamespace
@@ -400,9 +405,7 @@ class StreamAnimateDiffusionDepthWrapper:
         with the next frame, and outputs of frames it has not seen are composited with the oldest frame it has.  The frames
         `prepare` returns are not composited."""
         from .matte import SERVED_OUTPUT_TYPES, check_settings
-        if self.output_type not in SERVED_OUTPUT_TYPES:
-            raise ValueError(f"set_matte: output_type={self.output_type!r} is not composited: use one of "
-                             + ", ".join(repr(t) for t in SERVED_OUTPUT_TYPES))
+        self._check_served(SERVED_OUTPUT_TYPES, "composited", "clear_matte")
         settings = check_settings(lo, hi, keep=keep, feather=feather, show=show)
         self._need_line()
         self._matte = settings
@@ -429,39 +432,6 @@ class StreamAnimateDiffusionDepthWrapper:
             self._matte_skip = 0
             self.stream.matte_tap = None
 
-    def _composite(self, image_tensor, slot):
-        """`postprocess_image` of a frame under the matte: op 43 in place of the egress op.  `slot` None (the line has seen no
-        frame yet): the plain route."""
-        from .matte import SERVED_OUTPUT_TYPES, composite_ref
-        ot = self.output_type
-        if ot not in SERVED_OUTPUT_TYPES:
-            raise ValueError(f"a matte is set and output_type={ot!r} is not composited: use one of "
-                             + ", ".join(repr(t) for t in SERVED_OUTPUT_TYPES) + ", or clear_matte()")
-        if slot is None or not torch.is_tensor(image_tensor):
-            return self.postprocess_image(image_tensor, output_type=ot)
-        if self.io is not None and image_tensor.is_cuda:
-            if self._matte_dev is None:
-                from .matte import HipMatte
-                self._matte_dev = HipMatte(self.height, self.width, device=image_tensor.device)
-            if ot == "jpeg":
-                if self.jpeg is None:
-                    from .jpeg_io import HipJpegEncoder
-                    self.jpeg = HipJpegEncoder(self.height, self.width, self.jpeg_quality, device=image_tensor.device)
-                out = self.jpeg.encode(self._matte_dev.composite(image_tensor[0], slot, self._matte, to_host=False))
-                self._check_jpeg()
-                return out
-            u8 = self._matte_dev.composite(image_tensor[0], slot, self._matte).copy()      # (the pinned buffer is overwritten by the next frame)
-        else:
-            u8 = composite_ref(image_tensor[:1], slot.source[None], slot.depth[None], **self._matte)[0]
-        self._check_jpeg()
-        if ot == "jpeg":
-            from .jpeg import encode_ref
-            return encode_ref(u8, self.jpeg_quality)
-        if ot == "u8":
-            return u8
-        from PIL import Image
-        return Image.fromarray(u8)
-
     # ------------------------------------------------------------------ colour lock (color_lock.py, DESIGN.md section 8.z5)
     @property
     def color_lock(self) -> Optional[dict]:
@@ -481,9 +451,7 @@ class StreamAnimateDiffusionDepthWrapper:
         called before or after `prepare` and between any two frames; the frames `prepare` returns are not locked, and a frame
         the near-duplicate filter dropped repeats the last locked frame without moving the average."""
         from .color_lock import SERVED_OUTPUT_TYPES, check_settings
-        if self.output_type not in SERVED_OUTPUT_TYPES:
-            raise ValueError(f"set_color_lock: output_type={self.output_type!r} is not locked: use one of "
-                             + ", ".join(repr(t) for t in SERVED_OUTPUT_TYPES))
+        self._check_served(SERVED_OUTPUT_TYPES, "locked", "clear_color_lock")
         settings = check_settings(to, strength, rate)
         ref = self._reference_moments(to) if settings["mode"] == "image" else None
         self._lock = settings
@@ -542,20 +510,31 @@ class StreamAnimateDiffusionDepthWrapper:
         self._lock_last = out
         return out
 
+    def _check_served(self, served, noun: str, clear: str, what: Optional[str] = None) -> None:
+        """ValueError where `output_type` is none a feature serves.  `noun`: what the feature does to a frame ("composited");
+        `clear`: the method that turns it off; `what` ("a matte"): the check of a frame, while the feature is set -- without it
+        the check of the feature's `set_...` call"""
+        if self.output_type not in served:
+            head, tail = (f"set_{clear[len('clear_'):]}:", "") if what is None else (f"{what} is set and", f", or {clear}()")
+            raise ValueError(f"{head} output_type={self.output_type!r} is not {noun}: use one of "
+                             + ", ".join(repr(t) for t in served) + tail)
+
     def _finish(self, image_tensor, slot, repeated: bool = False):
-        """`postprocess_image` of a frame while a colour lock, a matte or an output size is set: the lock first, then the matte's
-        composite (or the plain route) on the locked frame, resampled when an output size is set"""
+        """`postprocess_image` of a frame while a colour lock, a matte or an output size is set: the lock first, then the rest
+        of the chain (`_route`) on the locked frame.  A frame that is no tensor is not locked and raises there."""
+        from . import color_lock, matte, resize
         if self._lock is not None and torch.is_tensor(image_tensor):
-            from .color_lock import SERVED_OUTPUT_TYPES
-            if self.output_type not in SERVED_OUTPUT_TYPES:
-                raise ValueError(f"a colour lock is set and output_type={self.output_type!r} is not locked: use one of "
-                                 + ", ".join(repr(t) for t in SERVED_OUTPUT_TYPES) + ", or clear_color_lock()")
+            self._check_served(color_lock.SERVED_OUTPUT_TYPES, "locked", "clear_color_lock", "a colour lock")
             image_tensor = self._locked(image_tensor, slot, repeated)
         if self._size is not None:
-            return self._sized(image_tensor, slot)
+            self._check_served(resize.SERVED_OUTPUT_TYPES, "resampled", "clear_output_size", "an output size")
         if self._matte is not None:
-            return self._composite(image_tensor, slot)
-        return self.postprocess_image(image_tensor, output_type=self.output_type)
+            self._check_served(matte.SERVED_OUTPUT_TYPES, "composited", "clear_matte", "a matte")
+        if not torch.is_tensor(image_tensor):
+            return self.postprocess_image(image_tensor, output_type=self.output_type)
+        if self._size is not None and self.output_type == "jpeg":      # (callers assign `output_type` between frames)
+            resize.check_jpeg_size(self._size["height"], self._size["width"])
+        return self._route(image_tensor, self.output_type, slot if self._matte is not None else None, self._size)
 
     # ------------------------------------------------------------------ output size (resize.py, DESIGN.md section 8.z6)
     @property
@@ -575,9 +554,7 @@ class StreamAnimateDiffusionDepthWrapper:
         `prepare` and between any two frames: the change applies from the next output.  The frames `prepare` returns are not
         resized; a frame the near-duplicate filter dropped yields the bytes of the frame before it."""
         from .resize import SERVED_OUTPUT_TYPES, check_filter, check_jpeg_size, check_size
-        if self.output_type not in SERVED_OUTPUT_TYPES:
-            raise ValueError(f"set_output_size: output_type={self.output_type!r} is not resampled: use one of "
-                             + ", ".join(repr(t) for t in SERVED_OUTPUT_TYPES))
+        self._check_served(SERVED_OUTPUT_TYPES, "resampled", "clear_output_size")
         ho, wo = check_size(self.height, self.width, height, width)
         check_filter(resample)
         if self.output_type == "jpeg":
@@ -587,58 +564,6 @@ class StreamAnimateDiffusionDepthWrapper:
     def clear_output_size(self) -> None:
         """Back to the UNet's size: no launch, copy or buffer of the resize is left in the frame's path."""
         self._size = self._size_dev = self._size_jpeg = None
-
-    def _sized(self, image_tensor, slot):
-        """`postprocess_image` of a frame while an output size is set: the matte's composite (or the egress bytes) resampled,
-        then the encoder or the copy to the host.  On the device op 46 takes the fp16 frame in place of the egress launch, or
-        the matte's uint8 buffer."""
-        from .resize import SERVED_OUTPUT_TYPES, check_jpeg_size, resize_ref
-        ot, size = self.output_type, self._size
-        if ot not in SERVED_OUTPUT_TYPES:
-            raise ValueError(f"an output size is set and output_type={ot!r} is not resampled: use one of "
-                             + ", ".join(repr(t) for t in SERVED_OUTPUT_TYPES) + ", or clear_output_size()")
-        if not torch.is_tensor(image_tensor):
-            return self.postprocess_image(image_tensor, output_type=ot)
-        ho, wo = size["height"], size["width"]
-        if ot == "jpeg":
-            check_jpeg_size(ho, wo)
-        matte = self._matte is not None and slot is not None           # (slot None: the delay line has seen no frame yet)
-        if self.io is not None and image_tensor.is_cuda:
-            rs = self._size_dev
-            if rs is None or (rs.out_height, rs.out_width, rs.resample) != (ho, wo, size["resample"]):
-                from .resize import HipResize
-                rs = self._size_dev = HipResize(self.height, self.width, ho, wo, size["resample"], device=image_tensor.device)
-            src = image_tensor[0]
-            if matte:
-                if self._matte_dev is None:
-                    from .matte import HipMatte
-                    self._matte_dev = HipMatte(self.height, self.width, device=image_tensor.device)
-                src = self._matte_dev.composite(src, slot, self._matte, to_host=False)
-            if ot == "jpeg":
-                encoders = self._size_jpeg = self._size_jpeg or {}
-                if (ho, wo) not in encoders:
-                    from .jpeg_io import HipJpegEncoder
-                    encoders[ho, wo] = HipJpegEncoder(ho, wo, self.jpeg_quality, device=image_tensor.device)
-                out = encoders[ho, wo].encode(rs.resize(src, to_host=False))
-                self._check_jpeg()
-                return out
-            u8 = rs.resize(src).copy()                                 # (the pinned buffer is overwritten by the next frame)
-        else:
-            if matte:
-                from .matte import composite_ref
-                u8 = composite_ref(image_tensor[:1], slot.source[None], slot.depth[None], **self._matte)[0]
-            else:
-                from .frame_io import egress_ref
-                u8 = egress_ref(image_tensor)[0].numpy()
-            u8 = resize_ref(u8, ho, wo, size["resample"])
-        self._check_jpeg()
-        if ot == "jpeg":
-            from .jpeg import encode_ref
-            return encode_ref(u8, self.jpeg_quality)
-        if ot == "u8":
-            return u8
-        from PIL import Image
-        return Image.fromarray(u8)
 
     # ------------------------------------------------------------------ styles (style_bank.py, DESIGN.md section 8.z3)
     def _init_styles(self, pipe) -> None:
@@ -866,40 +791,97 @@ class StreamAnimateDiffusionDepthWrapper:
     def postprocess_image(self, image_tensor: torch.Tensor, output_type: str = "pil"):
         """`image_utils.postprocess_image(x, output_type)[0]` (+ `.cpu()` for "pt" / "latent", wrapper.py:289-297); "u8" and "pil"
         through the egress kernel when the tensor is on the device; "jpeg" through the device-side encoder (no egress launch, no raw
-        frame on the host), the file of `encode_ref(egress_ref(x))` either way"""
+        frame on the host), the file of `encode_ref(egress_ref(x))` either way.  A matte, a colour lock and an output size are
+        not applied: this is `_route` with neither."""
         if not torch.is_tensor(image_tensor):
             raise ValueError(f"Input for postprocessing is in incorrect format: {type(image_tensor)}. We only support pytorch tensor")
-        out = self._postprocess(image_tensor, output_type)
-        self._check_jpeg()                 # behind the copy to the host every output type ends in: the status words are there too
-        return out
+        return self._route(image_tensor, output_type)
 
-    def _postprocess(self, image_tensor: torch.Tensor, output_type: str):
+    def _route(self, image_tensor: torch.Tensor, output_type: str, slot=None, size: Optional[dict] = None):
+        """The one way out for a frame (fp16 [1,3,H,W] in [-1, 1], behind the colour lock when one is set): the matte's composite
+        with `slot` (a `MatteLine` slot; None: no matte, or its line has seen no frame yet) or the egress bytes, resampled to
+        `size` (the setting of `set_output_size`, or None), then the JPEG encoder or the copy to the host.  On the device every
+        stage is one launch that hands its static device buffer to the next and only the last one copies to the host; the
+        resize takes the fp16 frame itself, and so does the encoder, so neither has an egress launch in front of it.  The float
+        output types leave as the reference's do."""
+        u8 = out = None
         if output_type == "latent":
-            return image_tensor[0].cpu()
-        if output_type == "pt":
-            return (image_tensor / 2 + 0.5).clamp(0, 1)[0].cpu()
-        if output_type == "np":
-            return (image_tensor / 2 + 0.5).clamp(0, 1).cpu().permute(0, 2, 3, 1).float().numpy()[0]
-        if output_type == "jpeg":
-            if self.io is not None and image_tensor.is_cuda:
-                if self.jpeg is None:
-                    from .jpeg_io import HipJpegEncoder
-                    self.jpeg = HipJpegEncoder(self.height, self.width, self.jpeg_quality, device=image_tensor.device)
-                return self.jpeg.encode(image_tensor[0])
-            from .frame_io import egress_ref
-            from .jpeg import encode_ref
-            return encode_ref(egress_ref(image_tensor)[0].numpy(), self.jpeg_quality)
-        if output_type not in ("pil", "u8"):
+            out = image_tensor[0].cpu()
+        elif output_type == "pt":
+            out = (image_tensor / 2 + 0.5).clamp(0, 1)[0].cpu()
+        elif output_type == "np":
+            out = (image_tensor / 2 + 0.5).clamp(0, 1).cpu().permute(0, 2, 3, 1).float().numpy()[0]
+        elif output_type not in ("pil", "u8", "jpeg"):
             raise ValueError(f"output_type={output_type!r}: use one of {OUTPUT_TYPES}")
-        if self.io is not None and image_tensor.is_cuda:
-            u8 = self.io.egress(image_tensor[0]).copy()          # (the pinned buffer is overwritten by the next frame)
+        elif self.io is not None and image_tensor.is_cuda:
+            dev, to_host = image_tensor.device, output_type != "jpeg"
+            stages = []
+            if slot is not None:
+                stages.append(functools.partial(self._matte_op(dev).composite, slot=slot, settings=self._matte))
+            if size is not None:
+                stages.append(self._size_op(size, dev).resize)
+            if not stages and to_host:
+                stages.append(self.io.egress)
+            x = image_tensor[0]
+            for i, stage in enumerate(stages):
+                x = stage(x, to_host=to_host and i + 1 == len(stages))
+            if to_host:
+                u8 = x.copy()              # (the pinned buffer is overwritten by the next frame)
+            else:
+                out = self._encoder(size, dev).encode(x)
         else:
-            from .frame_io import egress_ref
-            u8 = egress_ref(image_tensor)[0].numpy()
+            if slot is not None:
+                from .matte import composite_ref
+                u8 = composite_ref(image_tensor[:1], slot.source[None], slot.depth[None], **self._matte)[0]
+            else:
+                from .frame_io import egress_ref
+                u8 = egress_ref(image_tensor)[0].numpy()
+            if size is not None:
+                from .resize import resize_ref
+                u8 = resize_ref(u8, size["height"], size["width"], size["resample"])
+        self._check_jpeg()                 # behind the copy to the host every output type ends in: the status words are there too
+        if u8 is None:
+            return out
+        if output_type == "jpeg":
+            from .jpeg import encode_ref
+            return encode_ref(u8, self.jpeg_quality)
         if output_type == "u8":
             return u8
         from PIL import Image
         return Image.fromarray(u8)
+
+    def _matte_op(self, device):
+        """`matte.HipMatte` of the stream's size, made on first use"""
+        if self._matte_dev is None:
+            from .matte import HipMatte
+            self._matte_dev = HipMatte(self.height, self.width, device=device)
+        return self._matte_dev
+
+    def _size_op(self, size: dict, device):
+        """`resize.HipResize` of an output size: rebuilt when the size or the filter changes, kept otherwise"""
+        ho, wo, resample = size["height"], size["width"], size["resample"]
+        rs = self._size_dev
+        if rs is None or (rs.out_height, rs.out_width, rs.resample) != (ho, wo, resample):
+            from .resize import HipResize
+            rs = self._size_dev = HipResize(self.height, self.width, ho, wo, resample, device=device)
+        return rs
+
+    def _encoder(self, size: Optional[dict], device):
+        """`jpeg_io.HipJpegEncoder` of the size a frame leaves at, made on first use: `self.jpeg` for the UNet's own size (`size`
+        None), one per output size in `_size_jpeg` (which `clear_output_size` drops)"""
+        if size is None:
+            hw, enc = (self.height, self.width), self.jpeg
+        else:
+            hw, self._size_jpeg = (size["height"], size["width"]), self._size_jpeg or {}
+            enc = self._size_jpeg.get(hw)
+        if enc is None:
+            from .jpeg_io import HipJpegEncoder
+            enc = HipJpegEncoder(*hw, self.jpeg_quality, device=device)
+            if size is None:
+                self.jpeg = enc
+            else:
+                self._size_jpeg[hw] = enc
+        return enc
 
     @staticmethod
     def get_model_prefix(config_path: str, few_step_model_type: str, use_tiny_vae: bool, num_denoising_steps: int, height: int,

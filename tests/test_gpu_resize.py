@@ -1,6 +1,7 @@
 """-m gpu: L2D_OP_FRAME_RESIZE (csrc/resize.hip) against `resize.resize_ref` -- Pillow's `Image.resize`, pinned in
 tests/test_resize_cpu.py -- on every byte, from both source forms, behind guard bytes; and `set_output_size` on the wrapper with
-small native components against a twin wrapper's unresized output."""
+small native components against a twin wrapper's unresized output; and the launches the wrapper's output route makes under every
+combination of matte, colour lock and output size."""
 import functools
 
 import numpy as np
@@ -217,3 +218,105 @@ def test_wrapper_output_size_on_device():
     torch.cuda.synchronize()
     for i, (got, p) in enumerate(zip(out, plain)):
         same(("u8", "jpeg", "pil")[i % 3], got, p, tag=f"push / pop {i}")
+
+
+# the launches of the output route, as the parent of the commit that made the route one chain recorded them on the device: the
+# colour lock, then the matte, then the resize; the egress launch only where neither of the two takes its place; "jpeg" ends
+# in the encoder's three launches and never has an egress launch in front of them
+LOCK, MATTE, RESIZE, EGRESS = ("OP_FRAME_MOMENTS", "OP_COLOR_LOCK"), ("OP_FRAME_MATTE",), ("OP_FRAME_RESIZE",), ("OP_FRAME_EGRESS",)
+JPEG = ("OP_JPEG_DCT", "OP_JPEG_HUFF", "OP_JPEG_PACK")
+ROUTE_LAUNCHES = {                               # (output type, matte, colour lock, output size): the first and every later call
+    ("u8", False, False, False): EGRESS,
+    ("u8", False, False, True): RESIZE,
+    ("u8", False, True, False): LOCK + EGRESS,
+    ("u8", False, True, True): LOCK + RESIZE,
+    ("u8", True, False, False): MATTE,
+    ("u8", True, False, True): MATTE + RESIZE,
+    ("u8", True, True, False): LOCK + MATTE,
+    ("u8", True, True, True): LOCK + MATTE + RESIZE,
+    ("jpeg", False, False, False): JPEG,
+    ("jpeg", False, False, True): RESIZE + JPEG,
+    ("jpeg", False, True, False): LOCK + JPEG,
+    ("jpeg", False, True, True): LOCK + RESIZE + JPEG,
+    ("jpeg", True, False, False): MATTE + JPEG,
+    ("jpeg", True, False, True): MATTE + RESIZE + JPEG,
+    ("jpeg", True, True, False): LOCK + MATTE + JPEG,
+    ("jpeg", True, True, True): LOCK + MATTE + RESIZE + JPEG,
+}
+
+
+def test_output_route_launch_sequences(monkeypatch):
+    """The route alone (`_finish`, or `postprocess_image` with nothing set) on frames the stream made, under the eight
+    combinations of matte, colour lock and output size, as "u8" and as "jpeg", twice each (the second call meets the objects the
+    first one made): the op kinds of every list that runs equal ROUTE_LAUNCHES, and the bytes equal the host composition
+    lock_ref -> composite_ref | egress_ref -> resize_ref -> encode_ref of the same frame."""
+    from test_gpu_wrapper import PROMPT, SEED, Parts, u8_frames
+
+    from live2diff_amd import _lib, jpeg
+    from live2diff_amd.clip_hip import tiny_clip_config
+    from live2diff_amd.color_lock import lock_ref
+    from live2diff_amd.config import tiny_config
+    from live2diff_amd.frame_io import egress_ref
+    from live2diff_amd.matte import composite_ref
+    from live2diff_amd.resize import resize_ref
+    from live2diff_amd.wrapper import StreamAnimateDiffusionDepthWrapper as Wrapper
+    ccfg = tiny_clip_config()
+    ucfg = tiny_config(channels=(64, 128, 256, 256), cross_attention_dim=ccfg.hidden_size)
+    H = W = 64
+    N = 2
+    Ho, Wo = 80, 112
+    torch.manual_seed(0)
+    w = Wrapper.from_components(Parts(ucfg, ccfg, H, W, N).pipe(), output_type="u8", seed=SEED, device=DEV, num_inference_steps=50,
+                                t_index_list=[30, 40], width=W, height=H, warmup_frames=ucfg.sink_size, window_size=ucfg.window_size)
+    w.set_matte(0.3, 0.7, feather=2)
+    w.prepare(u8_frames(8, 96, 128, seed=1), PROMPT)
+    xs = []
+    for f in u8_frames(N + 1, 96, 128, seed=2):
+        w(f)
+        xs.append(w.stream.prev_image_result.clone())
+    xs = [xs[-2], w.stream.prev_image_result]                    # the first and the second call of every case
+    slot, settings = w._matte_line.last, w.matte
+    assert slot is not None and not torch.equal(xs[0], xs[1])
+
+    kinds = {v: k for k, v in vars(_lib).items() if k.startswith("OP_")}
+    ran, run = [], _lib.OpList.run
+
+    def recording(self, *a, **kw):
+        ran.extend(kinds[op.kind] for op in self._ops)
+        return run(self, *a, **kw)
+
+    monkeypatch.setattr(_lib.OpList, "run", recording)
+    bad = []
+    for (ot, matte, lock, size), launches in ROUTE_LAUNCHES.items():
+        w.clear_matte()
+        w.clear_color_lock()
+        w.clear_output_size()
+        w.output_type = ot
+        if matte:
+            w.set_matte(**settings)
+        if lock:
+            w.set_color_lock("ema", 0.8, 0.3)
+        if size:
+            w.set_output_size(Ho, Wo)
+        state = None
+        for call, x in enumerate(xs):
+            del ran[:]
+            got = w._finish(x, slot) if matte or lock or size else w.postprocess_image(x, ot)
+            seen = tuple(ran)
+            print(f"{ot:4s} matte={matte:d} lock={lock:d} size={size:d} call {call}: {' '.join(seen)}")
+            if seen != launches:
+                bad.append((ot, matte, lock, size, call, seen))
+            want = x
+            if lock:
+                want, state = lock_ref(x, state, mode="ema", strength=0.8, rate=0.3, init=call == 0)
+                want = torch.from_numpy(want)
+                assert call == 0 or not torch.equal(want, x.cpu())               # (the lock does something)
+            want = composite_ref(want, slot.source[None], slot.depth[None], **settings)[0] if matte else egress_ref(want)[0].numpy()
+            if size:
+                want = resize_ref(want, Ho, Wo, "lanczos")
+            tag = f"{ot} matte={matte:d} lock={lock:d} size={size:d} call {call}"
+            if ot == "u8":
+                assert got.dtype == np.uint8 and got.shape == want.shape and report(tag, got, want) == 0
+            else:
+                assert isinstance(got, bytes) and got == jpeg.encode_ref(want, 75), tag
+    assert not bad, bad
