@@ -363,13 +363,32 @@ enum {
  *   [B][Ho][Wo][3] (any alignment) p2 table of the x axis p3 table of the y axis (int32, 4-byte aligned; for an axis of n_out
  *   outputs: xmin [n_out], count [n_out], k [n_out][KS] behind one another, as resize.coefficients builds them: output xx reads
  *   inputs xmin[xx] .. xmin[xx] + count[xx] - 1 with the weights k[xx][0 .. count[xx]), 22 fractional bits) ; i0 B i1 H i2 W
- *   i3 Ho i4 Wo i5 source kind (0 half, 1 uint8) i6 KS of the x table i7 KS of the y table (1..L2D_RESIZE_MAX_KS).  One pass:
+ *   i3 Ho i4 Wo i5 source kind (0 half, 1 uint8) i6 KS of the x table i7 KS of the y table (1..L2D_RESIZE_MAX_KS) i8 the source's
+ *   row pitch in pixels (0: W; uint8 sources with B == 1 only: p0 is then the first pixel of an H x W window of a wider frame, at
+ *   any byte).  One pass:
  *   out = clip((2^21 + sum_x in[xmin + x] k[xx][x]) >> 22, 0, 255), arithmetic shift, in 32-bit integers (the host asserts
  *   255 sum |k| + 2^21 < 2^31 for every row); x first, rounded to a uint8 image, then y.  An axis that keeps its size carries
  *   the identity table (KS 1, k = 2^22).  What the kernel reads from a table is clamped to the image and to KS.  Only bytes of
  *   [dst, dst + B Ho Wo 3) are written, by plain stores (whole dwords where the address allows, bytes at the ends of a row).
  *   Refused: Ho, Wo outside 1..L2D_RESIZE_MAX_SIZE or outside [n_in / 2, 8 n_in], KS outside 1..L2D_RESIZE_MAX_KS,
- *   B Ho Wo 3 >= 2^31, B > 65535, a null or misaligned table, an fp16 source that is not 4-byte aligned.
+ *   B Ho Wo 3 >= 2^31, B > 65535, a null or misaligned table, an fp16 source that is not 4-byte aligned, a pitch below W or one
+ *   beside an fp16 source or B > 1.
+ *
+ * Matte at the output size (matte.hip; no counterpart in the reference).
+ * L2D_OP_FRAME_MATTE_UP  the styled frame at the output size composited over the camera's own pixels at that size by the matte of
+ *   the stream-sized depth plane, one launch:  p0 styled uint8 [B][Ho][Wo][3] p1 camera uint8 [B][Ho][Wo][3] p2 depth half, plane
+ *   b at p2 + b l0 elements, [H][W] p3 dst uint8 [B][Ho][Wo][3] (any alignment, as are p0 and p1) p4 table of the x axis p5 table
+ *   of the y axis (int32, 4-byte aligned; for an axis of n_out outputs: i0 [n_out], i1 [n_out], the bits of the fp32 weight f
+ *   [n_out] behind one another, as matte.up_table builds them: half-pixel bilinear taps) ; i0 B i1 H i2 W i3 Ho i4 Wo i5 r i6 flags
+ *   (both as L2D_OP_FRAME_MATTE's) ; l0 depth plane stride in elements (>= H W) ; f0 lo f1 inv (as L2D_OP_FRAME_MATTE's).
+ *   Arithmetic, every step one fp32 operation with one rounding and no fma (live2diff_amd/matte.py composite_up_ref): m as
+ *   L2D_OP_FRAME_MATTE forms it at H x W, box filter included; a_y = m[y][x0] + fx (m[y][x1] - m[y][x0]) on rows y0 and y1;
+ *   M = a_y0 + fy (a_y1 - a_y0); o = C + M (S - C) on the bytes; byte = rint(o), half to even.  SHOW writes rint(255 M) to all
+ *   three channels and reads neither frame.  M == 1 gives p0's bytes, M == 0 p1's.  What the kernel reads from a table is
+ *   clamped to the image, to the tile's patch and to [0, 1].  Only bytes of [dst, dst + B Ho Wo 3) are written, by plain stores
+ *   (whole dwords where the address allows, bytes at the ends of a row).  Refused: a null pointer, Ho, Wo outside
+ *   1..L2D_RESIZE_MAX_SIZE or outside [n_in / 2, 8 n_in], B Ho Wo 3 >= 2^31, B > 65535, r outside 0..L2D_MATTE_MAX_R, unknown
+ *   flags, a depth stride below H W, a misaligned table, lo / inv as L2D_OP_FRAME_MATTE refuses them.
  */
 enum {
     L2D_OP_IGEMM = 1,
@@ -418,6 +437,7 @@ enum {
     L2D_OP_FRAME_MOMENTS = 44,
     L2D_OP_COLOR_LOCK = 45,
     L2D_OP_FRAME_RESIZE = 46,
+    L2D_OP_FRAME_MATTE_UP = 47,
 };
 
 /* flag bits of L2D_OP_FRAME_MATTE (i4) */

@@ -29,6 +29,7 @@ OP_WEIGHT_BLEND = 42
 OP_FRAME_MATTE = 43
 OP_FRAME_MOMENTS, OP_COLOR_LOCK = 44, 45
 OP_FRAME_RESIZE = 46
+OP_FRAME_MATTE_UP = 47
 ABI_VERSION = 6
 
 

@@ -267,3 +267,224 @@ int l2d_launch_frame_matte(const l2d_op *op, hipStream_t s) {
     }
     return l2d_check_launch("frame_matte", op->tag);
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Matte at the output size: the styled frame, already resampled to the output size by
+// L2D_OP_FRAME_RESIZE, composited over the CAMERA's own pixels at that size by the matte of the stream-sized depth plane, sampled
+// bilinearly (half-pixel centres).  live2diff_amd/matte.py `composite_up_ref` restates it bit for bit:
+//
+//   m        the matte of L2D_OP_FRAME_MATTE at the stream's size, feather applied there (mt_matte + the two box passes)
+//   a_top = m[y0][x0] + fx (m[y0][x1] - m[y0][x0])     a_bot likewise on row y1     M = a_top + fy (a_bot - a_top)
+//   o = C + M (S - C) on the bytes as fp32             byte = rint(o)               (show: rint(255 M) in all three channels)
+//
+// each subtraction, multiplication and addition rounded once.  One work-group per MU_T x MU_T output tile and frame: the depth
+// patch the tile's taps reach plus the feather halo becomes m in LDS (coordinates clamped to the image: edge replication), the
+// box filter runs as a horizontal and a vertical pass there, the tile's M is formed from the four taps, then the bytes.
+#define MU_T 32                                   // output tile, pixels (both axes)
+#define MU_THREADS 256
+#define MU_SPAN (2 * MU_T)                        // source pixels a tile's taps reach along an axis at the 1/2 limit: see below
+#define MU_PATCH (MU_SPAN + 2 * MT_MAX_R)         // ... plus the halo: 80
+#define MU_STRIDE MU_PATCH                        // floats per LDS row; 80 % 32 == 16 keeps two short rows of one half-wave apart
+#define MU_ITEMS 32                               // stores per output row of a tile: <= 3 head bytes + 24 dwords + 3 tail bytes
+// The taps of output o lie at k = floor((o + 0.5) s - 0.5) and k + 1 with s = n_in / n_out <= 2.  Over a tile the first k and
+// the last differ by at most ceil((T - 1) s) <= 2 T - 2, so first k .. last k + 1 are at most 2 T source pixels.
+static_assert(MU_SPAN >= 2 * (MU_T - 1) + 2, "a tile's taps fit the span at a ratio of 1/2");
+static_assert(MU_T * 3 / 4 + 6 <= MU_ITEMS, "a tile row is stored by MU_ITEMS lanes");
+#define MU_LDS_BYTES (2 * MU_PATCH * MU_STRIDE * 4 + MU_T * MU_T * 4 + MU_T * MU_T * 3 + 6 * MU_T * 4)
+static_assert(MU_LDS_BYTES == 59136, "the LDS size DESIGN.md section 8.z7 states");
+static_assert(2 * MU_LDS_BYTES <= 160 * 1024, "two work-groups per CU");
+
+__device__ __forceinline__ int mu_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// One axis of the tile: the span [s0, s0 + n) of source coordinates its taps reach.  Everything read from a table is clamped
+// to the image and to the span, so a wrong table gives a wrong picture and never an access outside a buffer.
+__device__ __forceinline__ void mu_span(const int *__restrict__ tab, int n_out, int n_in, int o0, int t, int &s0, int &n) {
+    s0 = mu_clampi(tab[o0], 0, n_in - 1);
+    const int s1 = mu_clampi(tab[n_out + o0 + t - 1], s0, n_in - 1);
+    n = s1 - s0 + 1 > MU_SPAN ? MU_SPAN : s1 - s0 + 1;
+}
+
+__device__ __forceinline__ void mu_stage(const int *__restrict__ tab, int n_out, int n_in, int o0, int t, int s0, int n, int lane,
+                                         int *i0, int *i1, float *f) {
+    int a = 0, b = 0;
+    float w = 0.0f;
+    if (lane < t) {
+        a = mu_clampi(mu_clampi(tab[o0 + lane], 0, n_in - 1) - s0, 0, n - 1);
+        b = mu_clampi(mu_clampi(tab[n_out + o0 + lane], 0, n_in - 1) - s0, 0, n - 1);
+        w = __int_as_float(tab[2 * n_out + o0 + lane]);
+        w = fminf(fmaxf(w, 0.0f), 1.0f);          // (a weight of `up_table` lies in [0, 1]: this changes none of them)
+    }
+    i0[lane] = a;
+    i1[lane] = b;
+    f[lane] = w;
+}
+
+__global__ __launch_bounds__(MU_THREADS) void frame_matte_up_kernel(const uint8_t *__restrict__ styled, const uint8_t *__restrict__ camera,
+                                                                    const h16 *__restrict__ depth, uint8_t *__restrict__ dst,
+                                                                    const int *__restrict__ tx, const int *__restrict__ ty, int H, int W,
+                                                                    int Ho, int Wo, long long dstride, mt_params p) {
+    __shared__ __attribute__((aligned(16))) float mm[MU_PATCH * MU_STRIDE];       // m of the patch; later the filtered m
+    __shared__ __attribute__((aligned(16))) float hh[MU_PATCH * MU_STRIDE];       // the horizontal pass' rows
+    __shared__ float mt[MU_T * MU_T];                                             // M of the tile
+    __shared__ __attribute__((aligned(16))) unsigned char ob[MU_T * MU_T * 3];    // the tile's bytes
+    __shared__ int x0s[MU_T], x1s[MU_T], y0s[MU_T], y1s[MU_T];
+    __shared__ float fxs[MU_T], fys[MU_T];
+    const int tid = threadIdx.x;
+    const int ox0 = blockIdx.x * MU_T, oy0 = blockIdx.y * MU_T, b = blockIdx.z;
+    const int tw = Wo - ox0 < MU_T ? Wo - ox0 : MU_T, th = Ho - oy0 < MU_T ? Ho - oy0 : MU_T;
+    const int r = p.r, taps = 2 * r + 1;
+    int sx0, nx, sy0, ny;
+    mu_span(tx, Wo, W, ox0, tw, sx0, nx);
+    mu_span(ty, Ho, H, oy0, th, sy0, ny);
+    if (tid < MU_T) {
+        mu_stage(tx, Wo, W, ox0, tw, sx0, nx, tid, x0s, x1s, fxs);
+    } else if (tid >= 64 && tid < 64 + MU_T) {
+        mu_stage(ty, Ho, H, oy0, th, sy0, ny, tid - 64, y0s, y1s, fys);
+    }
+
+    // m of the patch and its halo: mm[j][c] = m(clamp(sy0 - r + j), clamp(sx0 - r + c))
+    const int rows = ny + 2 * r, cols = nx + 2 * r;
+    const h16 *dp = depth + (long long)b * dstride;
+    for (int i = tid; i < rows * cols; i += MU_THREADS) {
+        const int j = i / cols, c = i - j * cols;
+        const int yy = mu_clampi(sy0 - r + j, 0, H - 1), xx = mu_clampi(sx0 - r + c, 0, W - 1);
+        mm[j * MU_STRIDE + c] = mt_matte(dp[(long long)yy * W + xx], p);
+    }
+    __syncthreads();
+
+    if (r > 0) {
+        const float n = (float)taps;
+        // horizontal: hh[j][c] = (mm[j][c] + ... + mm[j][c + 2 r]) / n
+        for (int i = tid; i < rows * nx; i += MU_THREADS) {
+            const int j = i / nx, c = i - j * nx;
+            const float *src = mm + j * MU_STRIDE + c;
+            float acc = src[0];
+            for (int k = 1; k < taps; ++k) acc = __fadd_rn(acc, src[k]);
+            hh[j * MU_STRIDE + c] = __fdiv_rn(acc, n);
+        }
+        __syncthreads();
+        // vertical, into the patch buffer (nobody reads the patch any more): mm[y][c] = (hh[y][c] + ... + hh[y + 2 r][c]) / n
+        for (int i = tid; i < ny * nx; i += MU_THREADS) {
+            const int y = i / nx, c = i - y * nx;
+            const float *src = hh + y * MU_STRIDE + c;
+            float acc = src[0];
+            for (int k = 1; k < taps; ++k) acc = __fadd_rn(acc, src[k * MU_STRIDE]);
+            mm[y * MU_STRIDE + c] = __fdiv_rn(acc, n);
+        }
+        __syncthreads();
+    }
+
+    // M of the tile from the four taps
+    for (int i = tid; i < th * tw; i += MU_THREADS) {
+        const int yy = i / tw, xx = i - yy * tw;
+        const float *t0 = mm + y0s[yy] * MU_STRIDE, *t1 = mm + y1s[yy] * MU_STRIDE;
+        const int a = x0s[xx], c = x1s[xx];
+        const float fx = fxs[xx], fy = fys[yy];
+        const float top = __fadd_rn(t0[a], __fmul_rn(fx, __fsub_rn(t0[c], t0[a])));
+        const float bot = __fadd_rn(t1[a], __fmul_rn(fx, __fsub_rn(t1[c], t1[a])));
+        mt[yy * MU_T + xx] = __fadd_rn(top, __fmul_rn(fy, __fsub_rn(bot, top)));
+    }
+    __syncthreads();
+
+    // the bytes: one lane per byte of a tile row, consecutive lanes consecutive addresses of both frames
+    const int nb = tw * 3;
+    const int show = p.flags & MT_SHOW;
+    for (int i = tid; i < th * nb; i += MU_THREADS) {
+        const int yy = i / nb, e = i - yy * nb;
+        const float M = mt[yy * MU_T + e / 3];
+        float o;
+        if (show) {
+            o = __fmul_rn(M, 255.0f);
+        } else {
+            const long long g = (((long long)b * Ho + oy0 + yy) * Wo + ox0) * 3 + e;
+            const float S = (float)styled[g], C = (float)camera[g];
+            o = __fadd_rn(C, __fmul_rn(M, __fsub_rn(S, C)));
+        }
+        ob[yy * MU_T * 3 + e] = (unsigned char)(unsigned)rintf(o);
+    }
+    __syncthreads();
+
+    // the tile's rows: tw * 3 bytes each at an address of any alignment -- bytes up to the first dword boundary, whole dwords,
+    // bytes behind the last one; MU_ITEMS lanes per row, one store each (resize.hip's stores).  Every byte lies inside row
+    // oy0 + yy < Ho, columns ox0 .. ox0 + tw - 1 < Wo.
+    for (int i = tid; i < th * MU_ITEMS; i += MU_THREADS) {
+        const int yy = i / MU_ITEMS, it = i % MU_ITEMS;
+        uint8_t *g = dst + (((long long)b * Ho + oy0 + yy) * Wo + ox0) * 3;
+        const unsigned char *o = ob + yy * MU_T * 3;
+        int head = (int)((0 - (uintptr_t)g) & 3);
+        head = head > nb ? nb : head;
+        const int ndw = (nb - head) >> 2;
+        const int tail = nb - head - ndw * 4;
+        if (it < head) {
+            g[it] = o[it];
+        } else if (it < head + ndw) {
+            const int e = head + (it - head) * 4;
+            *reinterpret_cast<unsigned *>(g + e) =
+                (unsigned)o[e] | ((unsigned)o[e + 1] << 8) | ((unsigned)o[e + 2] << 16) | ((unsigned)o[e + 3] << 24);
+        } else if (it < head + ndw + tail) {
+            const int e = head + ndw * 4 + (it - head - ndw);
+            g[e] = o[e];
+        }
+    }
+}
+
+static bool mu_axis_ok(int n_in, int n_out) {
+    return n_out >= 1 && n_out <= L2D_RESIZE_MAX_SIZE && 2ll * n_out >= n_in && n_out <= 8ll * n_in;
+}
+
+int l2d_launch_frame_matte_up(const l2d_op *op, hipStream_t s) {
+    const int B = op->i[0], H = op->i[1], W = op->i[2], Ho = op->i[3], Wo = op->i[4], r = op->i[5], flags = op->i[6];
+    const long long dstride = op->l[0];
+    for (int k = 0; k < 6; ++k) {
+        if (!op->p[k]) {
+            l2d_set_error("frame_matte_up(tag %d): pointer %d is null", op->tag, k);
+            return L2D_EINVAL;
+        }
+    }
+    if (B <= 0 || H <= 0 || W <= 0) {
+        l2d_set_error("frame_matte_up(tag %d): non-positive size (B %d, H %d, W %d)", op->tag, B, H, W);
+        return L2D_EINVAL;
+    }
+    if (!mu_axis_ok(H, Ho) || !mu_axis_ok(W, Wo)) {
+        l2d_set_error("frame_matte_up(tag %d): %d x %d -> %d x %d: an output size must lie in 1..%d and between half and 8 times the "
+                      "matte's size", op->tag, H, W, Ho, Wo, L2D_RESIZE_MAX_SIZE);
+        return L2D_EINVAL;
+    }
+    if ((long long)B * Ho * Wo * 3 >= (1ll << 31) || B > 65535) {
+        l2d_set_error("frame_matte_up(tag %d): B Ho Wo 3 must stay below 2^31 and B below 65536", op->tag);
+        return L2D_EINVAL;
+    }
+    if (r < 0 || r > MT_MAX_R) {
+        l2d_set_error("frame_matte_up(tag %d): feather radius %d, need 0..%d", op->tag, r, MT_MAX_R);
+        return L2D_EINVAL;
+    }
+    if (flags & ~(MT_HARD | MT_FAR | MT_SHOW)) {
+        l2d_set_error("frame_matte_up(tag %d): unknown flag bits 0x%x (1 hard, 2 far, 4 show)", op->tag, flags);
+        return L2D_EINVAL;
+    }
+    const long long HW = (long long)H * W;
+    if (dstride < HW || (((uintptr_t)op->p[2]) & 1)) {
+        l2d_set_error("frame_matte_up(tag %d): depth plane stride %lld, need at least H W = %lld, and a 2-byte aligned plane", op->tag,
+                      dstride, HW);
+        return L2D_EINVAL;
+    }
+    for (int k = 4; k < 6; ++k) {
+        if (((uintptr_t)op->p[k]) & 3) {
+            l2d_set_error("frame_matte_up(tag %d): table pointer %d is not 4-byte aligned", op->tag, k);
+            return L2D_EINVAL;
+        }
+    }
+    const float lo = op->f[0], inv = op->f[1];
+    if (!(lo >= -1.0f && lo <= 1.0f) || !(inv >= 0.0f) || inv > 3.0e38f || ((flags & MT_HARD) != 0) != (inv == 0.0f)) {
+        l2d_set_error("frame_matte_up(tag %d): lo = %g must lie in [-1, 1], inv = %g be finite, and 0 exactly when the hard flag is set",
+                      op->tag, lo, inv);
+        return L2D_EINVAL;
+    }
+    L2D_DRY_RETURN();
+    mt_params p;
+    p.lo = lo; p.inv = inv; p.flags = flags; p.r = r;
+    hipLaunchKernelGGL(frame_matte_up_kernel, dim3((Wo + MU_T - 1) / MU_T, (Ho + MU_T - 1) / MU_T, B), dim3(MU_THREADS), 0, s,
+                       (const uint8_t *)op->p[0], (const uint8_t *)op->p[1], (const h16 *)op->p[2], (uint8_t *)op->p[3],
+                       (const int *)op->p[4], (const int *)op->p[5], H, W, Ho, Wo, dstride, p);
+    return l2d_check_launch("frame_matte_up", op->tag);
+}

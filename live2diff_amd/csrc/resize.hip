@@ -81,7 +81,7 @@ __device__ __forceinline__ void rs_stage(const int *__restrict__ tab, int n_out,
 template <bool U8>
 __global__ __launch_bounds__(RS_THREADS) void frame_resize_kernel(const void *__restrict__ src, uint8_t *__restrict__ dst,
                                                                   const int *__restrict__ tx, const int *__restrict__ ty, int H, int W,
-                                                                  int Ho, int Wo, int ksx, int ksy) {
+                                                                  int Ho, int Wo, int ksx, int ksy, int pitch) {
     __shared__ __attribute__((aligned(16))) unsigned char patch[RS_SPAN * RS_PSTRIDE];      // source bytes; later the output tile
     __shared__ __attribute__((aligned(16))) unsigned char hbuf[RS_SPAN * RS_TW * 3];        // the horizontal pass' rows
     __shared__ int kx[RS_TW * RS_MAX_KS], ky[RS_TH * RS_MAX_KS];
@@ -101,10 +101,11 @@ __global__ __launch_bounds__(RS_THREADS) void frame_resize_kernel(const void *__
     // the source patch as bytes, pixel-interleaved: patch[j][x * 3 + c]
     if (U8) {
         const int rowb = ax.n * 3;
-        const uint8_t *s8 = (const uint8_t *)src + (((long long)b * H + ay.s0) * W + ax.s0) * 3;
+        // (`pitch`: the source's row pitch in pixels, W unless the source is a window of a wider frame)
+        const uint8_t *s8 = (const uint8_t *)src + (((long long)b * H + ay.s0) * pitch + ax.s0) * 3;
         for (int i = tid; i < ay.n * rowb; i += RS_THREADS) {
             const int j = i / rowb, e = i - j * rowb;
-            patch[j * RS_PSTRIDE + e] = s8[(long long)j * W * 3 + e];
+            patch[j * RS_PSTRIDE + e] = s8[(long long)j * pitch * 3 + e];
         }
     } else {
         const int plane = ay.n * ax.n;
@@ -215,14 +216,21 @@ int l2d_launch_frame_resize(const l2d_op *op, hipStream_t s) {
         l2d_set_error("frame_resize(tag %d): the fp16 source is not 4-byte aligned", op->tag);
         return L2D_EINVAL;
     }
+    const int pitch = op->i[8];                   // 0: W
+    if (pitch != 0 && (pitch < W || kind != 1 || B != 1)) {
+        l2d_set_error("frame_resize(tag %d): a source row pitch (%d pixels) must be at least W = %d and goes with a uint8 source and "
+                      "B = 1 only", op->tag, pitch, W);
+        return L2D_EINVAL;
+    }
     L2D_DRY_RETURN();
     const dim3 grid((Wo + RS_TW - 1) / RS_TW, (Ho + RS_TH - 1) / RS_TH, B);
     uint8_t *dst = (uint8_t *)op->p[1];
     const int *tx = (const int *)op->p[2], *ty = (const int *)op->p[3];
     if (kind == 1) {
-        hipLaunchKernelGGL(frame_resize_kernel<true>, grid, dim3(RS_THREADS), 0, s, op->p[0], dst, tx, ty, H, W, Ho, Wo, ksx, ksy);
+        hipLaunchKernelGGL(frame_resize_kernel<true>, grid, dim3(RS_THREADS), 0, s, op->p[0], dst, tx, ty, H, W, Ho, Wo, ksx, ksy,
+                           pitch ? pitch : W);
     } else {
-        hipLaunchKernelGGL(frame_resize_kernel<false>, grid, dim3(RS_THREADS), 0, s, op->p[0], dst, tx, ty, H, W, Ho, Wo, ksx, ksy);
+        hipLaunchKernelGGL(frame_resize_kernel<false>, grid, dim3(RS_THREADS), 0, s, op->p[0], dst, tx, ty, H, W, Ho, Wo, ksx, ksy, W);
     }
     return l2d_check_launch("frame_resize", op->tag);
 }

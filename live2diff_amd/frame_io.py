@@ -128,6 +128,10 @@ class HipFrameIO:
         self.last_view = None              # what the last single-frame ingest returned (for release())
         self._device_plans = {}            # (source pointer, slot) -> plan: device frames out of static buffers (jpeg_io.HipJpegDecoder)
         self._device_seen = ()             # the last four source pointers of device frames (integers: nothing is kept alive)
+        # Optional hook (resize.CameraTap), single frames only: `camera_tap.prepare(Hs, Ws)` in front of everything a frame
+        # launches (it may refuse the geometry), `camera_tap(src)` behind the ingest launch on the same stream, with the device
+        # uint8 [1,Hs,Ws,3] source that was just ingested.  None: nothing changes.
+        self.camera_tap = None
 
     # ------------------------------------------------------------------ ingest
     def _plan_source(self, Hs: int, Ws: int):
@@ -165,6 +169,8 @@ class HipFrameIO:
             out = torch.empty(B, 3, self.height, self.width, dtype=torch.float16, device=self.device)
             self._ingest_op(src, out, B).run()
             return out
+        if self.camera_tap is not None:
+            self.camera_tap.prepare(Hs, Ws)
         slot = self._slots[self._turn]
         self._turn ^= 1
         cur = torch.cuda.current_stream()
@@ -198,6 +204,8 @@ class HipFrameIO:
                     self._device_plans[key] = plan
                 self._device_seen = (self._device_seen + (ptr,))[-4:]
         plan.run()
+        if self.camera_tap is not None:
+            self.camera_tap(src)
         self.last_view = slot.out
         return slot.out
 

@@ -9,7 +9,10 @@ the stream's output over the stream's own source frame, on the device, in the la
   * `MatteLine`       the delay line: with N denoising steps the frame that leaves the stream at call t entered it at call
                       t - (N - 1), the ingested frame lives in a two-slot buffer, and in push / pop mode the depth path runs on
                       a side stream -- so source frames and depth planes are kept, delayed and consumed on the device;
-  * `HipMatte`        the static output buffers and the one-op launch of one stream.
+  * `HipMatte`        the static output buffers and the one-op launch of one stream;
+  * `up_table`, `matte_up_ref`, `composite_up_ref`, `HipMatteUp`   the matte at the output size: the
+                      arithmetic of L2D_OP_FRAME_MATTE_UP -- the matte sampled bilinearly at the output size, the styled bytes
+                      over the camera's own -- and its launch.
 """
 import collections
 from typing import Optional, Tuple
@@ -106,6 +109,74 @@ def composite_ref(styled, source, depth, lo: float, hi: float, feather: int = 0,
     return np.rint(o * scale).astype(np.uint8)
 
 
+def up_table(n_in: int, n_out: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(i0 int32 [n_out], i1 int32 [n_out], f float32 [n_out]): half-pixel bilinear sampling of one axis.  In Python floats
+    s = (o + 0.5) n_in / n_out - 0.5, k = floor(s), f = float32(s - k), i0 = clamp(k, 0, n_in - 1), i1 = clamp(k + 1, 0, n_in - 1)."""
+    import math
+    n_in, n_out = int(n_in), int(n_out)
+    i0, i1, f = np.empty(n_out, np.int32), np.empty(n_out, np.int32), np.empty(n_out, np.float32)
+    for o in range(n_out):
+        s = (o + 0.5) * n_in / n_out - 0.5
+        k = math.floor(s)
+        f[o] = np.float32(s - k)
+        i0[o], i1[o] = min(max(k, 0), n_in - 1), min(max(k + 1, 0), n_in - 1)
+    return i0, i1, f
+
+
+def table_words(n_in: int, n_out: int) -> np.ndarray:
+    """`up_table` as the kernel reads it: int32 [3, n_out] -- i0, i1 and the bits of f"""
+    i0, i1, f = up_table(n_in, n_out)
+    return np.ascontiguousarray(np.stack([i0, i1, f.view(np.int32)]))
+
+
+def matte_up_ref(m: np.ndarray, out_height: int, out_width: int) -> np.ndarray:
+    """fp32 [B,H,W] matte of `matte_ref` (the feather already applied) -> fp32 [B,Ho,Wo]: per row a = m[x0] + fx (m[x1] - m[x0])
+    on rows y0 and y1, then M = top + fy (bot - top); each subtraction, multiplication and addition rounds once.  M is exactly 1
+    or 0 where its four taps are, and `m` itself bit for bit where the size does not change."""
+    m = np.asarray(m, dtype=np.float32)
+    if m.ndim == 2:
+        m = m[None]
+    x0, x1, fx = up_table(m.shape[2], out_width)
+    y0, y1, fy = up_table(m.shape[1], out_height)
+    fy = fy[None, :, None]
+
+    def rows(y):
+        a = m[:, y]
+        left = a[:, :, x0]
+        return left + fx * (a[:, :, x1] - left)
+
+    top, bot = rows(y0), rows(y1)
+    out = top + fy * (bot - top)
+    assert out.dtype == np.float32
+    return out
+
+
+def composite_up_ref(styled_u8, camera_u8, depth, lo: float, hi: float, feather: int = 0, keep: str = "near",
+                     show: bool = False) -> np.ndarray:
+    """L2D_OP_FRAME_MATTE_UP on the host: uint8 [B,Ho,Wo,3] `styled_u8` (the styled frame at the output size) and `camera_u8` (the
+    camera's own pixels at that size) + fp16 [B,H,W] `depth` -> uint8 [B,Ho,Wo,3].  M = matte_up_ref(matte_ref(depth, ...)),
+    o = C + M (S - C) on the bytes as fp32 -- S - C is exact, then one multiplication and one addition --, byte =
+    round_half_even(o); `show` writes round_half_even(255 M) to all three channels.  Rounding is monotone and 0 <= M <= 1, so o
+    lies between C and S and nothing is clamped (asserted); M == 1 gives S and M == 0 gives C exactly."""
+    def u8(x):
+        x = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+        if x.dtype != np.uint8 or x.ndim not in (3, 4) or x.shape[-1] != 3:
+            raise ValueError(f"composite_up_ref: expected uint8 [B,Ho,Wo,3], got {x.dtype} {x.shape}")
+        return x[None] if x.ndim == 3 else x
+
+    S, C = u8(styled_u8), u8(camera_u8)
+    if S.shape != C.shape:
+        raise ValueError(f"composite_up_ref: the styled frame is {S.shape}, the camera frame {C.shape}")
+    M = matte_up_ref(matte_ref(depth, lo, hi, feather, keep), S.shape[1], S.shape[2])[..., None]
+    assert M.shape[0] == S.shape[0] and float(M.min()) >= 0.0 and float(M.max()) <= 1.0
+    if show:
+        return np.rint(np.repeat(M, 3, axis=-1) * np.float32(255.0)).astype(np.uint8)
+    S, C = S.astype(np.float32), C.astype(np.float32)
+    o = C + M * (S - C)
+    assert o.dtype == np.float32 and np.all(o >= np.minimum(S, C)) and np.all(o <= np.maximum(S, C))
+    return np.rint(o).astype(np.uint8)
+
+
 def check_settings(lo, hi, *, keep="near", feather=0, show=False) -> dict:
     """the settings as a dict, or ValueError: lo > hi, values outside [0, 1], `feather` no integer in 0..8, `keep` not near / far"""
     for name, v in (("lo", lo), ("hi", hi)):
@@ -125,6 +196,7 @@ class _Slot:
     def __init__(self, height, width, device):
         self.source = torch.empty(3, height, width, dtype=torch.float16, device=device)
         self.depth = torch.empty(height, width, dtype=torch.float16, device=device)
+        self.camera = None                     # the frame's own pixels at the output size (resize.CameraBuffer), or None
 
 
 class MatteLine:
@@ -144,11 +216,21 @@ class MatteLine:
     it has.
 
     Slots in use: the N - 1 frames behind the newest taken one, the one taken last, and the tapped-but-not-taken frames of
-    push / pop mode.  The ring grows when a caller pushes deeper than before; in steady state nothing is allocated."""
+    push / pop mode.  The ring grows when a caller pushes deeper than before; in steady state nothing is allocated.
+
+    The camera frame.  While `camera_source` is set (a `resize.CameraTap`, or anything with `pending`
+    and `give_back`), a slot also takes the buffer the source holds as `pending` -- the frame's own pixels at the output size,
+    resampled inside `HipFrameIO.ingest` -- as `slot.camera`, and gives the slot's previous buffer back to the source's pool.
+    That is a move of a reference, not a copy: the tap may run on the side stream of `push` and launches nothing there for the
+    camera frame.  The rule that makes the buffers safe without events of their own: EVERY launch that writes or reads a camera
+    buffer runs on the caller's stream -- the resample inside `ingest`, the composite inside the wrapper's `_finish` -- so a
+    buffer that went back to the pool is overwritten only behind its last reader.  A frame that was not ingested on the device
+    (a float tensor, a batch) leaves `slot.camera` None; `last` keeps its buffer as it keeps its slot."""
 
     def __init__(self, n_steps: int, height: int, width: int, device="cpu"):
         self.n, self.height, self.width, self.device = int(n_steps), int(height), int(width), torch.device(device)
         self.slots = []
+        self.camera_source = None
         self.clear()
 
     def clear(self) -> None:
@@ -173,7 +255,18 @@ class MatteLine:
         s = self.slots[i]
         s.source.copy_(x[-1], non_blocking=True)
         s.depth.copy_(dn[-1, 0] if dn.ndim == 4 else dn[-1], non_blocking=True)
+        src, camera = self.camera_source, None
+        if src is not None and src.pending is not None:
+            camera, src.pending = src.pending, None
+        old, s.camera = s.camera, camera
+        if old is not None and src is not None:
+            src.give_back(old)
         return i
+
+    def drop_cameras(self) -> None:
+        """forget every camera buffer (the output size or the filter changed, or the feature was turned off)"""
+        for s in self.slots:
+            s.camera = None
 
     def prime(self, x: torch.Tensor, dn: torch.Tensor) -> None:
         """`x` [F,3,H,W], `dn` [F,3,H,W]: the warm-up frames of `prepare` and their normalised depth; the last one is kept"""
@@ -229,6 +322,40 @@ class HipMatte:
         lo32, inv32, hard = matte_params(settings["lo"], settings["hi"])
         op, keep = ops.frame_matte(image, slot.source, slot.depth, self.dev, B=1, H=H, W=W, lo32=lo32, inv32=inv32, hard=hard,
                                    far=settings["keep"] == "far", show=settings["show"], r=settings["feather"])
+        pl = _lib.OpList()
+        pl.append(op, *keep)
+        pl.run()
+        if not to_host:
+            return self.dev[0]
+        return to_pinned(self.dev, self.host)[0]
+
+
+class HipMatteUp:
+    """Device tables, static output buffers and the launch of one `(H, W) -> (Ho, Wo)` geometry: `composite` is
+    `HipMatte.composite` at the output size, on the bytes `HipResize.resize` made of the styled frame and the slot's camera
+    buffer.  Everything runs on `torch.cuda.current_stream()`."""
+
+    def __init__(self, height: int, width: int, out_height: int, out_width: int, device="cuda:0"):
+        from .resize import check_size
+        self.height, self.width, self.device = int(height), int(width), torch.device(device)
+        self.out_height, self.out_width = check_size(height, width, out_height, out_width)
+        self.tx, self.ty = (torch.from_numpy(table_words(n_in, n_out)).to(self.device)
+                            for n_in, n_out in ((self.width, self.out_width), (self.height, self.out_height)))
+        self.dev = torch.empty(1, self.out_height, self.out_width, 3, dtype=torch.uint8, device=self.device)
+        self.host = None if ops.DRY_RUN else torch.empty(1, self.out_height, self.out_width, 3, dtype=torch.uint8).pin_memory()
+
+    def composite(self, styled_u8: torch.Tensor, slot: _Slot, settings: dict, to_host: bool = True):
+        """uint8 [Ho,Wo,3] on the device + a `MatteLine` slot that carries a camera buffer -> uint8 [Ho,Wo,3]: a numpy view of the
+        pinned buffer (valid until the next call), or with `to_host=False` the static device tensor"""
+        Ho, Wo = self.out_height, self.out_width
+        camera = slot.camera.data
+        for name, t in (("styled", styled_u8), ("camera", camera)):
+            if t.dtype != torch.uint8 or tuple(t.shape) != (Ho, Wo, 3) or not t.is_contiguous():
+                raise ValueError(f"composite: expected a contiguous uint8 [{Ho},{Wo},3] {name} frame, got {t.dtype} {tuple(t.shape)}")
+        lo32, inv32, hard = matte_params(settings["lo"], settings["hi"])
+        op, keep = ops.frame_matte_up(styled_u8, camera, slot.depth, self.dev, self.tx, self.ty, B=1, H=self.height, W=self.width,
+                                      Ho=Ho, Wo=Wo, lo32=lo32, inv32=inv32, hard=hard, far=settings["keep"] == "far",
+                                      show=settings["show"], r=settings["feather"])
         pl = _lib.OpList()
         pl.append(op, *keep)
         pl.run()

@@ -1517,15 +1517,51 @@ def _resize_table(name, t, n_out):
     return t.numel() // n_out - 2
 
 
-def frame_resize(src, dst, tx, ty, *, B, H, W, Ho, Wo):
+def frame_resize(src, dst, tx, ty, *, B, H, W, Ho, Wo, src_pitch=None):
     """fp16 [B,3,H,W] in [-1, 1] (the egress op's bytes first) or uint8 [B,H,W,3] -> uint8 [B,Ho,Wo,3], Pillow's resampling
-    (resize.resize_ref); `tx`, `ty`: the int32 tables of the two axes as `resize.axis_table` lays them out"""
+    (resize.resize_ref); `tx`, `ty`: the int32 tables of the two axes as `resize.axis_table` lays them out.  `src_pitch` (uint8,
+    B == 1): `src` begins at the first pixel of an H x W window of a frame whose rows are `src_pitch` pixels apart -- a view of the
+    frame from that pixel on; None or 0: W."""
     assert src.dtype in (torch.float16, torch.uint8) and dst.dtype == torch.uint8
-    assert src.numel() >= B * H * W * 3 and dst.numel() >= B * Ho * Wo * 3
+    pitch = int(src_pitch or 0)
+    if pitch:
+        avail = src.untyped_storage().nbytes() - src.storage_offset()         # (uint8: bytes from the window's first pixel on)
+        assert avail >= ((H - 1) * pitch + W) * 3, (avail, H, W, pitch)
+    else:
+        assert src.numel() >= B * H * W * 3
+    assert dst.numel() >= B * Ho * Wo * 3
     ksx, ksy = _resize_table("tx", tx, Wo), _resize_table("ty", ty, Ho)
     op = L2dOp()
     op.kind = _lib.OP_FRAME_RESIZE
     op.p[0], op.p[1], op.p[2], op.p[3] = _ptr(src), _ptr(dst), _ptr(tx), _ptr(ty)
     for j, v in enumerate([B, H, W, Ho, Wo, int(src.dtype == torch.uint8), ksx, ksy]):
         op.i[j] = int(v)
+    op.i[8] = pitch
     return op, (src, dst, tx, ty)
+
+
+def frame_matte_up(styled, camera, depth, dst, tx, ty, *, B, H, W, Ho, Wo, lo32, inv32, hard, far=False, show=False, r=0,
+                   depth_stride=None):
+    """uint8 [B,Ho,Wo,3] styled / camera + fp16 depth planes [B,H,W] (`depth_stride` as `frame_matte`'s) -> uint8 [B,Ho,Wo,3]: the
+    styled bytes over the camera's by the depth matte sampled at the output size (matte.composite_up_ref); `tx`, `ty`: int32
+    [3, n_out] tables of the two axes as `matte.up_table` returns them (i0, i1, the bits of f)"""
+    assert styled.dtype == camera.dtype == dst.dtype == torch.uint8 and depth.dtype == torch.float16
+    stride = H * W if depth_stride is None else int(depth_stride)
+    n = B * Ho * Wo * 3
+    assert styled.numel() >= n and camera.numel() >= n and dst.numel() >= n
+    assert depth.numel() >= (B - 1) * stride + H * W
+    for name, t, n_out in (("tx", tx, Wo), ("ty", ty, Ho)):
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != 3 * n_out:
+            raise ValueError(f"frame_matte_up: {name} must be a contiguous int32 table of 3 x {n_out} elements, got {t.dtype} "
+                             f"{tuple(t.shape)}")
+    op = L2dOp()
+    op.kind = _lib.OP_FRAME_MATTE_UP
+    keep = (styled, camera, depth, dst, tx, ty)
+    for j, t in enumerate(keep):
+        op.p[j] = _ptr(t)
+    flags = (MATTE_HARD if hard else 0) | (MATTE_FAR if far else 0) | (MATTE_SHOW if show else 0)
+    for j, v in enumerate([B, H, W, Ho, Wo, r, flags]):
+        op.i[j] = int(v)
+    op.l[0] = stride
+    op.f[0], op.f[1] = float(lo32), float(inv32)
+    return op, keep

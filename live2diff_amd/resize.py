@@ -6,7 +6,9 @@ vertical pass in 32-bit integers, each rounded and clipped to a uint8 image of i
   * `coefficients`, `resize_pass`, `resize_ref`   the arithmetic of L2D_OP_FRAME_RESIZE in numpy integers -- the kernel's oracle,
                       as `matte.composite_ref` and `jpeg.encode_ref` are; `resize_ref` equals Pillow byte for byte;
   * `check_size`, `check_filter`   the served geometries and the argument checks of `set_output_size`;
-  * `HipResize`       the device tables, the static output buffers and the one-op plans of one geometry.
+  * `HipResize`       the device tables, the static output buffers and the one-op plans of one geometry;
+  * `camera_box`, `CameraTap`   the matte at the output size: the window of the camera frame the ingest
+                      looks at, and the hook of `HipFrameIO.ingest` that resamples it to the output size as the frame comes in.
 """
 import math
 from typing import Tuple
@@ -15,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .frame_io import to_pinned
+from .frame_io import geometry, to_pinned
 
 SERVED_OUTPUT_TYPES = ("u8", "pil", "jpeg")
 PRECISION_BITS = 22                      # 32 - 8 - 2: a byte times a coefficient of up to 2 in a signed 32-bit accumulator
@@ -141,6 +143,22 @@ def check_size(height: int, width: int, out_height, out_width, batch: int = 1) -
     return int(out_height), int(out_width)
 
 
+def camera_box(Hs: int, Ws: int, H: int, W: int) -> Tuple[int, int, int, int]:
+    """(y0, x0, bh, bw): the integer window of an Hs x Ws camera frame that the ingest's resize + centre crop to H x W looks at.
+    From `frame_io.geometry`'s (nh, nw, top, left), per axis in Python floats: b = clamp(floor(size n_src / n_res + 0.5), 1, n_src),
+    o = clamp(floor(first n_src / n_res + 0.5), 0, n_src - b).  The window is rounded to whole source pixels, so it can sit up to
+    half a source pixel off the frame the stream stylises."""
+    nh, nw, top, left = geometry(Hs, Ws, H, W)
+
+    def axis(size, first, n_src, n_res):
+        b = min(max(int(math.floor(size * n_src / n_res + 0.5)), 1), n_src)
+        o = min(max(int(math.floor(first * n_src / n_res + 0.5)), 0), n_src - b)
+        return o, b
+
+    (y0, bh), (x0, bw) = axis(H, top, Hs, nh), axis(W, left, Ws, nw)
+    return y0, x0, bh, bw
+
+
 def check_jpeg_size(out_height: int, out_width: int) -> None:
     """the JPEG encoder's own rules on an output size: multiples of 16, no wider than `ops.JPEG_MAX_W`"""
     if out_height % 16 or out_width % 16:
@@ -213,3 +231,84 @@ class HipResize:
         if not to_host:
             return self.dev[0]
         return to_pinned(self.dev, self.host)[0]
+
+
+class CameraBuffer:
+    """one camera frame at an output size: uint8 [Ho,Wo,3] on the device, and the (Ho, Wo, resample) it was resampled for"""
+
+    def __init__(self, data: torch.Tensor, key):
+        self.data, self.key = data, key
+
+
+class CameraTap:
+    """The hook of `HipFrameIO.ingest` (`camera_tap`) while the matte is composited at the output size: every single frame that
+    is ingested also leaves its own pixels -- `camera_box` of the uint8 frame on the device -- resampled to the output size
+    (`resize_ref` of the window, one launch of L2D_OP_FRAME_RESIZE with the frame's row pitch) in a buffer out of a pool, as
+    `pending`.  `MatteLine._store` moves `pending` into the frame's slot and gives the slot's previous buffer back
+    (`give_back`); `begin` (the wrapper, in front of every frame) takes back a `pending` nobody claimed, e.g. that of a frame
+    the near-duplicate filter dropped.
+
+    For one `(Hs, Ws)` it holds the box, the two `axis_table`s and one kept plan per (source, buffer) pair, by the rule of
+    `HipResize._plan`; a frame of another size rebuilds them (the pool's buffers are at the output size and stay).  `prepare(Hs, Ws)` runs in front of the ingest
+    launch and raises `check_size`'s ValueError for a window the resize does not serve.  The pool grows with the delay line's
+    ring and allocates nothing in steady state.  Launches on `torch.cuda.current_stream()` only, from inside `ingest`."""
+
+    MAX_PLANS = 16
+
+    def __init__(self, height: int, width: int, out_height: int, out_width: int, resample: str = "lanczos", device="cuda:0"):
+        self.height, self.width, self.device = int(height), int(width), torch.device(device)
+        self.out_height, self.out_width, self.resample = int(out_height), int(out_width), check_filter(resample)
+        self.key = (self.out_height, self.out_width, self.resample)
+        self.pending = None
+        self.free = []
+        self.allocated = 0
+        self._src = self.box = None
+
+    def prepare(self, Hs: int, Ws: int) -> None:
+        if self._src == (Hs, Ws):
+            return
+        y0, x0, bh, bw = box = camera_box(Hs, Ws, self.height, self.width)
+        check_size(bh, bw, self.out_height, self.out_width)
+        tx, ty = axis_table(bw, self.out_width, self.resample), axis_table(bh, self.out_height, self.resample)
+        self.tx, self.ty = torch.from_numpy(tx).to(self.device), torch.from_numpy(ty).to(self.device)
+        self._src, self.box = (Hs, Ws), box
+        self._plans, self._seen = {}, ()
+
+    def begin(self) -> None:
+        """in front of a frame: a `pending` buffer nobody claimed goes back to the pool"""
+        if self.pending is not None:
+            self.free.append(self.pending)
+            self.pending = None
+
+    def give_back(self, buf) -> None:
+        if buf is not None and buf.key == self.key:
+            self.free.append(buf)
+
+    def _buffer(self) -> CameraBuffer:
+        if self.free:
+            return self.free.pop()
+        self.allocated += 1
+        return CameraBuffer(torch.empty(self.out_height, self.out_width, 3, dtype=torch.uint8, device=self.device), self.key)
+
+    def __call__(self, src: torch.Tensor) -> None:
+        """`src`: the device uint8 [1,Hs,Ws,3] frame the ingest launch just read, on the stream it ran on"""
+        Hs, Ws = src.shape[-3], src.shape[-2]
+        self.prepare(Hs, Ws)
+        self.begin()
+        buf = self._buffer()
+        y0, x0, bh, bw = self.box
+        key = (src.data_ptr(), buf.data.data_ptr())
+        pl = self._plans.get(key)
+        if pl is None:
+            window = src.reshape(-1)[(y0 * Ws + x0) * 3:]
+            op, keep = ops.frame_resize(window, buf.data, self.tx, self.ty, B=1, H=bh, W=bw, Ho=self.out_height, Wo=self.out_width,
+                                        src_pitch=Ws)
+            pl = _lib.OpList()
+            pl.append(op, *keep)
+            if key in self._seen:
+                if len(self._plans) >= self.MAX_PLANS:
+                    self._plans.clear()
+                self._plans[key] = pl
+            self._seen = (self._seen + (key,))[-self.MAX_PLANS:]
+        pl.run()
+        self.pending = buf

@@ -19,6 +19,7 @@ device (jpeg_io.HipJpegDecoder) and ingested there like a uint8 frame (`jpeg_dec
 `set_color_lock` holds the output's per-channel colour statistics to the source's, a running average's or a reference image's
 (color_lock.py).  `set_output_size` (or the `output_size` keyword) resamples the uint8 frame to a size of the caller's choice
 with Pillow's arithmetic, behind both and in front of the JPEG encoder or the copy to the host (resize.py).
+`set_matte_source("camera")` composites the matte at the output size over the camera's own pixels (matte.HipMatteUp).
 
 Every frame leaves through one chain, `_route`: colour lock (`_finish`, in front of it) -> matte composite, or egress -> resize
 -> JPEG encoder, or copy to the host.  A stage that is not set is not in the chain; on the device each stage is one launch that
@@ -276,6 +277,9 @@ class StreamAnimateDiffusionDepthWrapper:
     _size = None                            # the output size's settings (set_output_size), None: the UNet's geometry
     _size_dev = None                        # resize.HipResize of the current size, made by the first resized frame on the device
     _size_jpeg = None                       # {(height, width): jpeg_io.HipJpegEncoder}, one per output size "jpeg" frames left at
+    _matte_source = "stream"                # what the kept real part of a matted, resized frame is made of (set_matte_source)
+    _camera = None                          # resize.CameraTap, while "camera", a matte and an output size are all set on the device
+    _matte_up = None                        # matte.HipMatteUp of the current output size, made by the first frame that needs it
 
     def __init__(self, config_path: str, few_step_model_type: str, num_inference_steps: int,
                  t_index_list: Optional[List[int]] = None, strength: Optional[float] = None,
@@ -287,7 +291,7 @@ class StreamAnimateDiffusionDepthWrapper:
                  use_denoising_batch: bool = True, cfg_type: str = "none", seed: int = 42,
                  engine_dir: Optional[Union[str, Path]] = "engines", opt_unet: bool = False, frame_pipelining: bool = False,
                  jpeg_quality: int = 75, jpeg_decode: str = "device", output_size: Optional[Tuple[int, int]] = None,
-                 output_resample: str = "lanczos"):
+                 output_resample: str = "lanczos", matte_source: str = "stream"):
         self._check_keywords(few_step_model_type=few_step_model_type, acceleration=acceleration, cfg_type=cfg_type,
                              use_denoising_batch=use_denoising_batch, frame_buffer_size=frame_buffer_size, device_ids=device_ids,
                              opt_unet=opt_unet, output_type=output_type, dtype=dtype, jpeg_quality=jpeg_quality, jpeg_decode=jpeg_decode)
@@ -306,13 +310,13 @@ class StreamAnimateDiffusionDepthWrapper:
                     window_size=window, frame_pipelining=frame_pipelining, enable_similar_image_filter=enable_similar_image_filter,
                     similar_image_filter_threshold=similar_image_filter_threshold,
                     similar_image_filter_max_skip_frame=similar_image_filter_max_skip_frame, jpeg_quality=jpeg_quality,
-                    jpeg_decode=jpeg_decode, output_size=output_size, output_resample=output_resample)
+                    jpeg_decode=jpeg_decode, output_size=output_size, output_resample=output_resample, matte_source=matte_source)
 
     @classmethod
     def from_components(cls, pipe, *, num_inference_steps: int, t_index_list: Optional[List[int]] = None,
                         strength: Optional[float] = None, **kw):
         """The wrapper around an already assembled `pipe` namespace (tests, synthetic weights).  Keywords: those of the
-        constructor that do not name files (`jpeg_quality`, `jpeg_decode`, `output_size` and `output_resample` among them), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
+        constructor that do not name files (`jpeg_quality`, `jpeg_decode`, `output_size`, `output_resample` and `matte_source` among them), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
         self = cls.__new__(cls)
         cls._check_keywords(**{k: kw.pop(k) for k in ("acceleration", "cfg_type", "use_denoising_batch", "frame_buffer_size",
                                                       "device_ids", "opt_unet", "few_step_model_type") if k in kw},
@@ -352,7 +356,8 @@ class StreamAnimateDiffusionDepthWrapper:
                width=512, height=512, do_add_noise=True, seed=42, clip_skip=1, warmup_frames=8, window_size=16,
                scheduler_kwargs=None, frame_pipelining=False, enable_similar_image_filter=False,
                similar_image_filter_threshold=0.98, similar_image_filter_max_skip_frame=10, jpeg_quality=75, jpeg_decode="device",
-               output_size=None, output_resample="lanczos"):
+               output_size=None, output_resample="lanczos", matte_source="stream"):
+        self._check_matte_source(matte_source)
         self.sd_turbo = False
         self.device = pipe.device if device is None else device
         self.dtype, self.width, self.height = dtype, width, height
@@ -387,6 +392,7 @@ class StreamAnimateDiffusionDepthWrapper:
             self.io = HipFrameIO(height, width, device=pipe.device)
             self.stream.image_processor = FrameProcessor(self.io)
         self._init_styles(pipe)
+        self.set_matte_source(matte_source)
 
     # ------------------------------------------------------------------ depth matte (matte.py)
     @property
@@ -403,18 +409,82 @@ class StreamAnimateDiffusionDepthWrapper:
         encoder ("jpeg"); the float output types are not served.  May be called before or after `prepare` and between any two
         frames: settings change with the next output; turning the matte on mid-stream starts the delay line (matte.MatteLine)
         with the next frame, and outputs of frames it has not seen are composited with the oldest frame it has.  The frames
-        `prepare` returns are not composited."""
+        `prepare` returns are not composited.  The kept real part is the stream-sized source frame, also under an output size;
+        `set_matte_source("camera")` keeps the camera's own pixels there instead."""
         from .matte import SERVED_OUTPUT_TYPES, check_settings
         self._check_served(SERVED_OUTPUT_TYPES, "composited", "clear_matte")
         settings = check_settings(lo, hi, keep=keep, feather=feather, show=show)
         self._need_line()
         self._matte = settings
+        self._sync_camera()
 
     def clear_matte(self) -> None:
-        """Back to the plain output route: no launch, copy or buffer of the matte is left in the frame's path.  (A colour lock
-        to "source" keeps the delay line it shares with the matte.)"""
+        """Back to the plain output route: no launch, copy or buffer of the matte is left in the frame's path, the camera
+        buffers of `set_matte_source("camera")` included.  (A colour lock to "source" keeps the delay line it shares with the
+        matte.)"""
         self._matte = None
         self._release_line()
+        self._sync_camera()
+
+    # ------------------------------------------------------------------ matte at the output size (DESIGN.md section 8.z7)
+    @property
+    def matte_source(self) -> str:
+        """"stream" or "camera": what the kept real part of a matted frame is made of under an output size"""
+        return self._matte_source
+
+    @staticmethod
+    def _check_matte_source(source) -> None:
+        if source not in ("stream", "camera"):
+            raise ValueError(f"matte_source={source!r}: use 'stream' or 'camera'")
+
+    def set_matte_source(self, source: str) -> None:
+        """What a matte keeps real when an output size is set.  "stream" (the default): the stream-sized source frame, composited
+        at the stream's size and resampled with the rest of the picture.  "camera": the camera frame's own pixels -- the window
+        of the uint8 frame the ingest looks at (`resize.camera_box`, rounded to whole source pixels), resampled to the output
+        size with the output size's filter as the frame is ingested, and composited there with the matte sampled bilinearly
+        (`matte.composite_up_ref`); with `keep="far"` and a 1080-line camera the person is the camera's person, not 512 lines
+        scaled up.  The order on a frame stays colour lock, matte, size: the two stages become the resize of the styled frame and
+        one composite launch at the output size.
+
+        "camera" acts on an output frame only when a matte and an output size are both set, the frame runs on the device
+        route, and the frame it is paired with came in as a uint8 frame or a JPEG file while all that held (the delay line's
+        slot then carries its pixels).  Every other frame takes the "stream" route unchanged -- float tensors, PIL images and
+        paths (they reach the stream at its own size: there is no camera frame), frames that entered before the mode, the matte
+        or the current output size was set, and the host route without a device.  That is the behaviour, not an error.  A camera
+        geometry whose window the output size does not serve (a ratio outside 1/2 .. 8) raises ValueError from the frame that
+        first meets it.  May be called before or after `prepare` and between any two frames."""
+        self._check_matte_source(source)
+        self._matte_source = source
+        self._sync_camera()
+
+    def _sync_camera(self) -> None:
+        """Install the camera tap (`HipFrameIO.camera_tap`, `MatteLine.camera_source`) while "camera", a matte and an output
+        size are all set on the device route, rebuilt when the size or the filter changed; otherwise take it out and drop every
+        camera buffer, so that nothing of the feature stays in the frame's path."""
+        io, line, size = getattr(self, "io", None), self._matte_line, self._size
+        want = self._matte_source == "camera" and self._matte is not None and size is not None and io is not None and line is not None
+        key = (size["height"], size["width"], size["resample"]) if want else None
+        if want and self._camera is not None and self._camera.key == key:
+            tap = self._camera
+        else:
+            if line is not None:
+                line.drop_cameras()
+            self._matte_up = None
+            tap = None
+            if want:
+                from .resize import CameraTap
+                tap = CameraTap(self.height, self.width, *key, device=io.device)
+            self._camera = tap
+        if io is not None:
+            io.camera_tap = tap
+        if line is not None:
+            line.camera_source = tap
+
+    def _camera_slot(self, slot, image_tensor) -> bool:
+        """does this output frame take the composite at the output size?"""
+        tap = self._camera
+        return (tap is not None and slot is not None and slot.camera is not None and slot.camera.key == tap.key
+                and self.io is not None and torch.is_tensor(image_tensor) and image_tensor.is_cuda)
 
     def _need_line(self) -> None:
         """The delay line of source frames and depth planes, shared by the matte and the colour lock to "source": made by
@@ -534,7 +604,8 @@ class StreamAnimateDiffusionDepthWrapper:
             return self.postprocess_image(image_tensor, output_type=self.output_type)
         if self._size is not None and self.output_type == "jpeg":      # (callers assign `output_type` between frames)
             resize.check_jpeg_size(self._size["height"], self._size["width"])
-        return self._route(image_tensor, self.output_type, slot if self._matte is not None else None, self._size)
+        slot = slot if self._matte is not None else None
+        return self._route(image_tensor, self.output_type, slot, self._size, camera=self._camera_slot(slot, image_tensor))
 
     # ------------------------------------------------------------------ output size (resize.py)
     @property
@@ -550,7 +621,8 @@ class StreamAnimateDiffusionDepthWrapper:
         size; no raw frame reaches the host) or the copy to the host ("u8", "pil"); the float output types are not served.
         Without a matte the launch takes the fp16 frame and replaces the egress launch; with one it takes the matte's uint8
         frame.  Resampling the composite is the whole feature: under a matte the kept real part of the picture is the
-        UNet-sized source frame scaled up, not the camera's own pixels, and nothing is sharpened.  May be called before or after
+        UNet-sized source frame scaled up, not the camera's own pixels (`set_matte_source("camera")` keeps those instead), and
+        nothing is sharpened.  May be called before or after
         `prepare` and between any two frames: the change applies from the next output.  The frames `prepare` returns are not
         resized; a frame the near-duplicate filter dropped yields the bytes of the frame before it."""
         from .resize import SERVED_OUTPUT_TYPES, check_filter, check_jpeg_size, check_size
@@ -560,10 +632,13 @@ class StreamAnimateDiffusionDepthWrapper:
         if self.output_type == "jpeg":
             check_jpeg_size(ho, wo)
         self._size = dict(height=ho, width=wo, resample=resample)
+        self._sync_camera()
 
     def clear_output_size(self) -> None:
-        """Back to the UNet's size: no launch, copy or buffer of the resize is left in the frame's path."""
+        """Back to the UNet's size: no launch, copy or buffer of the resize is left in the frame's path, the camera buffers of
+        `set_matte_source("camera")` included."""
         self._size = self._size_dev = self._size_jpeg = None
+        self._sync_camera()
 
     # ------------------------------------------------------------------ styles (style_bank.py, DESIGN.md section 8.z3)
     def _init_styles(self, pipe) -> None:
@@ -709,6 +784,8 @@ class StreamAnimateDiffusionDepthWrapper:
         [3,H,W] tensor in [0, 1] (the reference's input)."""
         if prompt is not None:
             self._update_prompt(prompt)
+        if self._camera is not None:
+            self._camera.begin()           # (a camera buffer nobody claimed belongs to no later frame)
         line = self._matte_line
         if line is None and self._lock is None and self._size is None:
             return self.postprocess_image(self.stream(self.preprocess_image(image)), output_type=self.output_type)
@@ -727,6 +804,8 @@ class StreamAnimateDiffusionDepthWrapper:
         """pipelined mode (`frame_pipelining=True`): start a frame's encode / depth path; `pop()` returns the oldest frame's output"""
         if prompt is not None:
             self._update_prompt(prompt)
+        if self._camera is not None:
+            self._camera.begin()
         self.stream.push(self.preprocess_image(image))
         if self.io is not None and self.io.last_view is not None:
             # push() ran the ingest on this stream before ordering the side stream behind it; the side stream reads the slot
@@ -797,10 +876,12 @@ class StreamAnimateDiffusionDepthWrapper:
             raise ValueError(f"Input for postprocessing is in incorrect format: {type(image_tensor)}. We only support pytorch tensor")
         return self._route(image_tensor, output_type)
 
-    def _route(self, image_tensor: torch.Tensor, output_type: str, slot=None, size: Optional[dict] = None):
+    def _route(self, image_tensor: torch.Tensor, output_type: str, slot=None, size: Optional[dict] = None, camera: bool = False):
         """The one way out for a frame (fp16 [1,3,H,W] in [-1, 1], behind the colour lock when one is set): the matte's composite
         with `slot` (a `MatteLine` slot; None: no matte, or its line has seen no frame yet) or the egress bytes, resampled to
-        `size` (the setting of `set_output_size`, or None), then the JPEG encoder or the copy to the host.  On the device every
+        `size` (the setting of `set_output_size`, or None), then the JPEG encoder or the copy to the host.  `camera` (the slot
+        carries the camera's pixels at `size`, `_camera_slot`): the resize of the styled frame first, then the composite at the
+        output size, in place of those two stages.  On the device every
         stage is one launch that hands its static device buffer to the next and only the last one copies to the host; the
         resize takes the fp16 frame itself, and so does the encoder, so neither has an egress launch in front of it.  The float
         output types leave as the reference's do."""
@@ -816,9 +897,12 @@ class StreamAnimateDiffusionDepthWrapper:
         elif self.io is not None and image_tensor.is_cuda:
             dev, to_host = image_tensor.device, output_type != "jpeg"
             stages = []
-            if slot is not None:
+            if camera:
+                stages.append(self._size_op(size, dev).resize)
+                stages.append(functools.partial(self._matte_up_op(size, dev).composite, slot=slot, settings=self._matte))
+            elif slot is not None:
                 stages.append(functools.partial(self._matte_op(dev).composite, slot=slot, settings=self._matte))
-            if size is not None:
+            if size is not None and not camera:
                 stages.append(self._size_op(size, dev).resize)
             if not stages and to_host:
                 stages.append(self.io.egress)
@@ -856,6 +940,15 @@ class StreamAnimateDiffusionDepthWrapper:
             from .matte import HipMatte
             self._matte_dev = HipMatte(self.height, self.width, device=device)
         return self._matte_dev
+
+    def _matte_up_op(self, size: dict, device):
+        """`matte.HipMatteUp` of an output size: rebuilt when the size changes, kept otherwise"""
+        ho, wo = size["height"], size["width"]
+        mu = self._matte_up
+        if mu is None or (mu.out_height, mu.out_width) != (ho, wo):
+            from .matte import HipMatteUp
+            mu = self._matte_up = HipMatteUp(self.height, self.width, ho, wo, device=device)
+        return mu
 
     def _size_op(self, size: dict, device):
         """`resize.HipResize` of an output size: rebuilt when the size or the filter changes, kept otherwise"""

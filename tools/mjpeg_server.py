@@ -34,7 +34,12 @@ settings as JSON (`null`: off).
 `--output-size WxH[,FILTER]` serves frames of W x H pixels instead of the UNet's size (`wrapper.set_output_size`: Pillow's
 resampling in one launch on the device, in front of a JPEG encoder of that size; FILTER is lanczos, bicubic or bilinear; both
 sizes are multiples of 16 and W is at most 1920).  `POST /size` with the same text as its body, or `off`, changes it while the
-stream runs; `GET /size` answers the current settings as JSON (`null`: off)."""
+stream runs; `GET /size` answers the current settings as JSON (`null`: off).
+
+`--matte-source stream|camera` chooses what a matte keeps real under an output size (`wrapper.set_matte_source`): `stream`, the
+UNet-sized source frame resampled with the rest of the picture, or `camera`, the posted frame's own pixels resampled to the output
+size and composited there.  `POST /matte-source` with one of the two words changes it while the stream runs; `GET /matte-source`
+answers the current one as a JSON string."""
 import argparse
 import json
 import os
@@ -281,6 +286,40 @@ class SizeBox:
             self.failed += 1
 
 
+def parse_matte_source_arg(text: str) -> str:
+    """`stream` or `camera` -> the argument of `wrapper.set_matte_source`; ValueError otherwise"""
+    text = text.strip()
+    if text not in ("stream", "camera"):
+        raise ValueError(f"matte source {text!r}: use stream or camera")
+    return text
+
+
+class MatteSourceBox:
+    """What `POST /matte-source` delivers: the newest requested source (`stream` or `camera`), applied by the producer between two
+    frames.  `current` is what was last applied; `failed` counts requests the wrapper refused."""
+    _NOTHING = object()
+
+    def __init__(self, current="stream"):
+        self._lock = threading.Lock()
+        self.current, self._want, self.failed = current, self._NOTHING, 0
+
+    def put(self, source) -> None:
+        with self._lock:
+            self._want = source
+
+    def apply(self, wrapper) -> None:
+        """(producer thread, between frames)"""
+        with self._lock:
+            want, self._want = self._want, self._NOTHING
+        if want is self._NOTHING:
+            return
+        try:
+            wrapper.set_matte_source(want)
+            self.current = wrapper.matte_source
+        except ValueError:
+            self.failed += 1
+
+
 def parse_style_arg(text: str):
     """`NAME=DREAMBOOTH[,LORA:ALPHA...]` -> (name, dreambooth path or None, {lora path: alpha})"""
     name, eq, rest = text.partition("=")
@@ -323,8 +362,8 @@ class Latest:
 
 
 def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = None, mattes: "MatteBox" = None, colors: "ColorBox" = None,
-                 sizes: "SizeBox" = None):
-    boxes = {"/matte": mattes, "/color": colors, "/size": sizes}
+                 sizes: "SizeBox" = None, sources: "MatteSourceBox" = None):
+    boxes = {"/matte": mattes, "/color": colors, "/size": sizes, "/matte-source": sources}
     page = PAGE if inbox is None else CAMERA_PAGE
 
     class Handler(BaseHTTPRequestHandler):
@@ -424,6 +463,9 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
             if self.path == "/size" and sizes is not None:
                 self.do_matte(sizes, parse_size_arg)
                 return
+            if self.path == "/matte-source" and sources is not None:
+                self.do_matte(sources, parse_matte_source_arg)
+                return
             if inbox is None or self.path != "/frame":
                 self.send_error(404)
                 return
@@ -447,9 +489,9 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
 
 
 def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: StyleBox = None, mattes: MatteBox = None,
-            colors: ColorBox = None, sizes: SizeBox = None) -> None:
-    """the producer: loops `frames` through the wrapper until `stop` is set; a posted style, matte, colour lock or output size is
-    applied between two frames"""
+            colors: ColorBox = None, sizes: SizeBox = None, sources: MatteSourceBox = None) -> None:
+    """the producer: loops `frames` through the wrapper until `stop` is set; a posted style, matte, colour lock, output size or
+    matte source is applied between two frames"""
     from live2diff_amd.jpeg import mjpeg_part
     try:
         i = 0
@@ -462,6 +504,8 @@ def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: Styl
                 colors.apply(wrapper)
             if sizes is not None:
                 sizes.apply(wrapper)
+            if sources is not None:
+                sources.apply(wrapper)
             latest.put(mjpeg_part(wrapper(frames[i % len(frames)])))
             i += 1
     finally:
@@ -469,7 +513,7 @@ def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: Styl
 
 
 def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: threading.Event, styles: StyleBox = None,
-                   mattes: MatteBox = None, colors: ColorBox = None, sizes: SizeBox = None) -> None:
+                   mattes: MatteBox = None, colors: ColorBox = None, sizes: SizeBox = None, sources: MatteSourceBox = None) -> None:
     """the producer of `--input post`: the first frames posted warm the stream up, then the newest posted frame goes through the
     wrapper, for ever; a frame the wrapper refuses (ValueError: a damaged file) is dropped and counted in `inbox.failed`"""
     from live2diff_amd.jpeg import mjpeg_part
@@ -490,6 +534,8 @@ def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: thr
                 colors.apply(wrapper)
             if sizes is not None:
                 sizes.apply(wrapper)
+            if sources is not None:
+                sources.apply(wrapper)
             try:
                 latest.put(mjpeg_part(wrapper(frame)))
             except ValueError:
@@ -522,6 +568,9 @@ def main(argv=None):
     ap.add_argument("--output-size", default=None, metavar="WxH[,FILTER]",
                     help="serve frames of W x H pixels (multiples of 16, W <= 1920) resampled on the device with lanczos (default), "
                          "bicubic or bilinear; POST /size with the same text, or `off`, changes it between frames")
+    ap.add_argument("--matte-source", default="stream", type=parse_matte_source_arg, metavar="stream|camera",
+                    help="what a matte keeps real under an output size: the UNet-sized source frame (`stream`) or the input frame's own "
+                         "pixels at the output size (`camera`); POST /matte-source with one of the two words changes it between frames")
     args = ap.parse_args(argv)
     style_args = [parse_style_arg(t) for t in args.style]
     matte = parse_matte_arg(args.matte) if args.matte else None
@@ -541,7 +590,7 @@ def main(argv=None):
                                            t_index_list=cfg.get("t_index_list"), strength=cfg.get("strength"), output_type="jpeg",
                                            jpeg_quality=args.quality, height=args.height, width=args.width, seed=args.seed,
                                            engine_dir=args.engine_dir, output_size=size and (size["height"], size["width"]),
-                                           output_resample=size["resample"] if size else "lanczos")
+                                           output_resample=size["resample"] if size else "lanczos", matte_source=args.matte_source)
     for name, db, loras in style_args:
         w.add_style(name, dreambooth_path=db, lora_dict=loras or None)
     styles = StyleBox(w.styles, w.style)
@@ -552,15 +601,16 @@ def main(argv=None):
         w.set_color_lock(color["to"], strength=color["strength"], rate=color["rate"])        # (before `prepare`, like the matte)
     colors = ColorBox(w.color_lock)
     sizes = SizeBox(w.output_size)
+    sources = MatteSourceBox(w.matte_source)
     prompt = args.prompt if args.prompt is not None else str(cfg.get("prompt", ""))
     latest, stop = Latest(), threading.Event()
     inbox = Inbox(sink) if post else None
     if post:
-        producer = threading.Thread(target=produce_posted, args=(w, prompt, inbox, latest, stop, styles, mattes, colors, sizes), name="producer", daemon=True)
+        producer = threading.Thread(target=produce_posted, args=(w, prompt, inbox, latest, stop, styles, mattes, colors, sizes, sources), name="producer", daemon=True)
     else:
         w.prepare(frames[:sink], prompt)
-        producer = threading.Thread(target=produce, args=(w, frames, latest, stop, styles, mattes, colors, sizes), name="producer", daemon=True)
-    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest, inbox, styles, mattes, colors, sizes))
+        producer = threading.Thread(target=produce, args=(w, frames, latest, stop, styles, mattes, colors, sizes, sources), name="producer", daemon=True)
+    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest, inbox, styles, mattes, colors, sizes, sources))
     server.daemon_threads = True
     producer.start()
     print(f"http://{args.host}:{args.port}/  ({args.height}x{args.width}, quality {args.quality}; Ctrl-C stops)")
