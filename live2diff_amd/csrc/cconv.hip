@@ -610,7 +610,7 @@ __global__ __launch_bounds__(64 * (CG * KG + NLD), 2) void cconv_kernel(CConvArg
             const int cidx = it * NTHR + tid, row = cidx / CPRN, cc = cidx - row * CPRN;
             h16x8 v = l2d_ld8(ot + row * pitch + cc * 8);
             if (a.res) v = v + resv[it];
-            l2d_st8(a.out + mrow(row) * a.ldo + n0 + cc * 8, v);
+            l2d_st8_out<L2D_WT_CCONV>(a.out + mrow(row) * a.ldo + n0 + cc * 8, v);
             if (gn) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {

@@ -97,6 +97,32 @@ __device__ __forceinline__ float l2d_gelu(float x) {
 
 __device__ __forceinline__ h16x8 l2d_ld8(const h16 *p) { return *reinterpret_cast<const h16x8 *>(p); }
 __device__ __forceinline__ void l2d_st8(h16 *p, h16x8 v) { *reinterpret_cast<h16x8 *>(p) = v; }
+// Write-through form of l2d_st8 for a kernel's OUTPUT rows (global_store_dwordx4 ... sc1): the line goes to memory as it is
+// written and leaves the producing XCD's L2, so it is not among the dirty lines the end-of-kernel release has to write back
+// before the next launch may start.  Only for 16-byte stores to 16-byte aligned addresses: narrower sc1 stores are one fabric
+// write each (2.7x - 12x the time per byte), so every 4- / 8-byte epilogue path (igemm's direct epilogue, the flash kernel's O
+// rows) stays a plain store.  Measured per kernel family in the frame (DESIGN.md section 3.10, table in section 9): every family
+// below got faster and none of their successors slower, so all of them use it.  L2D_WT_MASK, one bit per family, rebuilds the
+// A/B libraries (tools/wt_libs.sh); a cleared bit gives that family plain stores.
+typedef unsigned int __attribute__((ext_vector_type(4))) l2d_u32x4;
+__device__ __forceinline__ void l2d_st8_wt(h16 *p, h16x8 v) {
+    __builtin_amdgcn_global_store_b128((l2d_u32x4 __attribute__((address_space(1))) *)p, __builtin_bit_cast(l2d_u32x4, v), "agent");
+}
+#define L2D_WT_ROWCHAIN 1
+#define L2D_WT_ROWGEMM 2
+#define L2D_WT_WSGEMM 4
+#define L2D_WT_IGEMM 8      // igemm's staged epilogue and pconv's copy of it
+#define L2D_WT_CCONV 16
+#define L2D_WT_TATTN 32
+#define L2D_WT_NORM 64
+#ifndef L2D_WT_MASK
+#define L2D_WT_MASK 127
+#endif
+template <int FAM>
+__device__ __forceinline__ void l2d_st8_out(h16 *p, h16x8 v) {
+    if constexpr ((L2D_WT_MASK & FAM) != 0) l2d_st8_wt(p, v);
+    else l2d_st8(p, v);
+}
 __device__ __forceinline__ h16x8 l2d_zero8() {
     h16x8 z;
 #pragma unroll

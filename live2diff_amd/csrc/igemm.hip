@@ -612,7 +612,7 @@ __global__ __launch_bounds__(256, (TN == 128 && BK == 32) ? (NS == 2 ? 4 : 3) : 
             h16x8 v = l2d_ld8(ot + row * pitch + cc * 8);
             if (resp) v = v + (RES_EARLY ? resv[RES_EARLY ? it : 0] : rlate[RES_EARLY ? 0 : it]);
             if (a.epi == 4) v = __builtin_elementwise_max(v, l2d_zero8());          // relu(conv + skip), TAESD blocks
-            l2d_st8(outp + (long long)m * a.ldo + n, v);
+            l2d_st8_out<L2D_WT_IGEMM>(outp + (long long)m * a.ldo + n, v);
             if (gn) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {

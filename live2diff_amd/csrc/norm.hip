@@ -185,7 +185,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(GNArgs a, int pix_per_blo
                 else if (a.silu == 3) y = fmaxf((float)(h16)y + (float)rr[e], 0.f);   // relu(norm(x) + shortcut): ResNetV2 bottleneck
                 o[e] = (h16)y;
             }
-            l2d_st8(a.out + oidx, o);
+            l2d_st8_out<L2D_WT_NORM>(a.out + oidx, o);
         }
     }
 }
@@ -273,7 +273,7 @@ __global__ __launch_bounds__(256) void gn_self_kernel(GNArgs a, int band) {
             else if (a.silu == 3) y = fmaxf((float)(h16)y + (float)rr[e], 0.f);
             o[e] = (h16)y;
         }
-        l2d_st8(a.out + oidx, o);
+        l2d_st8_out<L2D_WT_NORM>(a.out + oidx, o);
     }
 }
 

@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256, 2) void pconv_kernel(PConvArgs a) {
         h16x8 v = l2d_ld8(ot + row * pitch + cc * 8);
         if (a.res) v = v + resv[it];
         if (a.epi == 4) v = __builtin_elementwise_max(v, l2d_zero8());          // relu(conv + skip), TAESD blocks
-        l2d_st8(a.out + mrow(row) * a.ldo + n0 + cc * 8, v);
+        l2d_st8_out<L2D_WT_IGEMM>(a.out + mrow(row) * a.ldo + n0 + cc * 8, v);
         if (gn) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {

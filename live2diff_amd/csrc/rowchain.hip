@@ -293,7 +293,7 @@ __global__ __launch_bounds__(C * 2 / NT) void rowchain_tail_kernel(RowChainArgs 
     for (int i = 0; i < LPT; ++i) {
         const int row = r0 + RSTEP * i;
         const h16x8 v = l2d_ld8(Hh + ((slot * BM) + (row ^ (2 * (slot & 7)))) * 8) + vx[i];
-        l2d_st8(a.out + (long long)(m0 + row) * a.ldo + slot * 8, v);
+        l2d_st8_out<L2D_WT_ROWCHAIN>(a.out + (long long)(m0 + row) * a.ldo + slot * 8, v);
         if (gn) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -453,7 +453,7 @@ __global__ __launch_bounds__(C * 2 / NT) void rowchain_head_kernel(RowHeadArgs a
 #pragma unroll
         for (int i = 0; i < NS8; ++i) {
             v[i] = l2d_ld8(Hh + (((j + 8 * i) * BM) + (r ^ (2 * j))) * 8);
-            l2d_st8(a.hout + (long long)(m0 + r) * a.ldh + (j + 8 * i) * 8, v[i]);
+            l2d_st8_out<L2D_WT_ROWCHAIN>(a.hout + (long long)(m0 + r) * a.ldh + (j + 8 * i) * 8, v[i]);
 #pragma unroll
             for (int e = 0; e < 8; ++e) t += (float)v[i][e];
         }
@@ -506,13 +506,13 @@ __global__ __launch_bounds__(C * 2 / NT) void rowchain_head_kernel(RowHeadArgs a
             constexpr int CPT = BM / 8;
             for (int idx = tid; idx < C * CPT; idx += NTHR) {
                 const int ch = idx / CPT, cq = idx - ch * CPT;
-                l2d_st8(ob + (long long)ch * a.ldt + cq * 8, l2d_ld8(St + ch * PT + cq * 8));
+                l2d_st8_out<L2D_WT_ROWCHAIN>(ob + (long long)ch * a.ldt + cq * 8, l2d_ld8(St + ch * PT + cq * 8));
             }
         } else {
 #pragma unroll
             for (int i = 0; i < LPT; ++i) {
                 const int row = r0 + RSTEP * i;
-                l2d_st8(a.out + (long long)(m0 + row) * a.ldo + p * C + slot * 8, l2d_ld8(St + ((slot * BM) + (row ^ (2 * (slot & 7)))) * 8));
+                l2d_st8_out<L2D_WT_ROWCHAIN>(a.out + (long long)(m0 + row) * a.ldo + p * C + slot * 8, l2d_ld8(St + ((slot * BM) + (row ^ (2 * (slot & 7)))) * 8));
             }
         }
     }

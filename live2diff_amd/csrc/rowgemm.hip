@@ -224,7 +224,7 @@ __device__ __forceinline__ void rowgemm_body(const RowGemmArgs &a, h16 *smem, h1
         constexpr int CPT = BM / 8;                           // 16-byte chunks per channel row
         for (int idx = tid; idx < BNp * CPT; idx += nthr) {
             const int ch = idx / CPT, c = idx - ch * CPT;
-            l2d_st8(ob + (long long)ch * a.ldt + c * 8, l2d_ld8(os + ch * pt + c * 8));
+            l2d_st8_out<L2D_WT_ROWGEMM>(ob + (long long)ch * a.ldt + c * 8, l2d_ld8(os + ch * pt + c * 8));
         }
         return;
     }
@@ -282,7 +282,7 @@ __device__ __forceinline__ void rowgemm_body(const RowGemmArgs &a, h16 *smem, h1
             if constexpr (RES_PRE) v = v + resv[it];
             else v = v + l2d_ld8(a.res + (long long)(m0 + row) * a.ldr + nb_o + cc * 8);
         }
-        l2d_st8(a.out + (long long)(m0 + row) * a.ldo + nb_o + cc * 8, v);
+        l2d_st8_out<L2D_WT_ROWGEMM>(a.out + (long long)(m0 + row) * a.ldo + nb_o + cc * 8, v);
         if (gn) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {

@@ -209,7 +209,7 @@ __global__ __launch_bounds__(40 * PB) void tattn_stream_ring_kernel(TAttnArgs a,
                 for (int r = 0; r < R; ++r) {
                     const int l = s * R + r;
                     h16x8 kk = l2d_ld8(st + r * NT * 8);         // masked slots hold zeros
-                    if (l == u) l2d_st8(ku + coff, kk);          // cache keeps the pre-PE projections (:117-119)
+                    if (l == u) l2d_st8_out<L2D_WT_TATTN>(ku + coff, kk);          // cache keeps the pre-PE projections (:117-119)
                     kk = kk + l2d_ld8(kpt + l * 320);            // fp16 rounding of K+pe as in the reference (:140)
                     sc[l] = ring_dot8(q8, kk);
                 }
@@ -251,7 +251,7 @@ __global__ __launch_bounds__(40 * PB) void tattn_stream_ring_kernel(TAttnArgs a,
                 for (int r = 0; r < R; ++r) {
                     const int l = (s - NSTG / 2) * R + r;
                     h16x8 vv = l2d_ld8(st + r * NT * 8);
-                    if (l == u) l2d_st8(ku + slab + coff, vv);
+                    if (l == u) l2d_st8_out<L2D_WT_TATTN>(ku + slab + coff, vv);
                     vv = vv + l2d_ld8(vpt + l * 320);            // (:141)
                     ring_axpy8(o, sc[l], vv);
                 }
@@ -263,7 +263,7 @@ __global__ __launch_bounds__(40 * PB) void tattn_stream_ring_kernel(TAttnArgs a,
         h16x8 ov;
 #pragma unroll
         for (int e = 0; e < 8; ++e) ov[e] = (h16)o[e];
-        l2d_st8(out_b + (long long)gi * (PB * C) + ooff, ov);
+        l2d_st8_out<L2D_WT_TATTN>(out_b + (long long)gi * (PB * C) + ooff, ov);
     }
 }
 #endif
@@ -427,7 +427,7 @@ __global__ __launch_bounds__(384) void tattn_stream_ringlw_kernel(TAttnArgs a, c
             for (int r = 0; r < R; ++r) {
                 const int l = s * R + r;
                 h16x8 kk = l2d_ld8(st + r * NT * 8);
-                if (l == u) l2d_st8(ku + coff, kk);
+                if (l == u) l2d_st8_out<L2D_WT_TATTN>(ku + coff, kk);
                 kk = kk + l2d_ld8(kpt + l * 320);
                 d[r] = ring_dot8(q8, kk);
             }
@@ -493,7 +493,7 @@ __global__ __launch_bounds__(384) void tattn_stream_ringlw_kernel(TAttnArgs a, c
             for (int r = 0; r < R; ++r) {
                 const int l = s * R + r;
                 h16x8 vv = l2d_ld8(st + r * NT * 8);
-                if (l == u) l2d_st8(ku + slab + coff, vv);
+                if (l == u) l2d_st8_out<L2D_WT_TATTN>(ku + slab + coff, vv);
                 vv = vv + l2d_ld8(vpt + l * 320);
                 ring_axpy8(o, pr[r], vv);
             }
@@ -503,7 +503,7 @@ __global__ __launch_bounds__(384) void tattn_stream_ringlw_kernel(TAttnArgs a, c
         h16x8 ov;
 #pragma unroll
         for (int e = 0; e < 8; ++e) ov[e] = (h16)o[e];
-        l2d_st8(out_b + (long long)gi * (PB * C) + ooff, ov);
+        l2d_st8_out<L2D_WT_TATTN>(out_b + (long long)gi * (PB * C) + ooff, ov);
     }
 }
 

@@ -614,7 +614,7 @@ __global__ __launch_bounds__(64 * MAXW) void wsgemm_kernel(WsArgs a) {
             constexpr int CPT = BM / 8;
             for (int idx = tid; idx < BNp * CPT; idx += nthr) {
                 const int ch = idx / CPT, c = idx - ch * CPT;
-                l2d_st8(ob + (long long)ch * a.ldt + c * 8, l2d_ld8(os + ch * pt + c * 8));
+                l2d_st8_out<L2D_WT_WSGEMM>(ob + (long long)ch * a.ldt + c * 8, l2d_ld8(os + ch * pt + c * 8));
             }
         }
         return;
@@ -699,7 +699,7 @@ __global__ __launch_bounds__(64 * MAXW) void wsgemm_kernel(WsArgs a) {
                     if (k < PF) v = v + resp[k < PF ? k : 0];
                     else v = v + l2d_ld8(a.res + (long long)(m0 + row) * a.ldr + nb_o + cc * 8);
                 }
-                l2d_st8(a.out + (long long)(m0 + row) * a.ldo + nb_o + cc * 8, v);
+                l2d_st8_out<L2D_WT_WSGEMM>(a.out + (long long)(m0 + row) * a.ldo + nb_o + cc * 8, v);
                 if (gn) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
