@@ -389,6 +389,28 @@ enum {
  *   (whole dwords where the address allows, bytes at the ends of a row).  Refused: a null pointer, Ho, Wo outside
  *   1..L2D_RESIZE_MAX_SIZE or outside [n_in / 2, 8 n_in], B Ho Wo 3 >= 2^31, B > 65535, r outside 0..L2D_MATTE_MAX_R, unknown
  *   flags, a depth stride below H W, a misaligned table, lo / inv as L2D_OP_FRAME_MATTE refuses them.
+ *
+ * Steady (steady.hip; no counterpart in the reference).  Where the frame's source did not move since the source of the output
+ *   before, the previous output pixel is held (a per-pixel EMA); where it moved, the styled pixel passes untouched.  The result is
+ *   an fp16 frame in the decoder's convention that every outlet consumes unchanged, like L2D_OP_COLOR_LOCK's.
+ * L2D_OP_FRAME_STEADY  one launch:  p0 styled half [3][H][W] p1 source half [3][H][W] p2 prev_out half [3][H][W] p3 prev_bytes uint8
+ *   [3][H][W] (PLANAR: the bytes of the previous output's source, channel by channel) p4 out half [3][H][W] p5 next_bytes uint8
+ *   [3][H][W] p6 picture half [3][H][W] (read as a pointer only with L2D_STEADY_SHOW; the half frames 16-byte aligned, the byte
+ *   planes 8) ; i0 H i1 W (W % 8 == 0, 3 H W < 2^31) i2 r (0..L2D_STEADY_MAX_R) i3 flags (L2D_STEADY_HARD | _SHOW | _INIT) ; f0 lo
+ *   f1 inv (1 / (hi - lo), both in byte levels; finite, not negative) f2 s (the strength, in [0, 1]).  Arithmetic, the motion in
+ *   exact integers and every floating-point step one fp32 operation with one rounding and no fma, so that numpy restates it bit
+ *   for bit (live2diff_amd/steady.py steady_ref): b = L2D_OP_FRAME_EGRESS' byte of p1; d = max over the channels of |b - p3|;
+ *   D = the sum of d over the (2r+1) x (2r+1) window, coordinates clamped to the image; dbar = float(D) / float((2r+1)^2), one
+ *   correctly rounded division; t = clamp((dbar - lo) inv, 0, 1) (HARD: dbar >= lo ? 1 : 0); w = (t t) (3 - 2 t) (1 moving,
+ *   0 still); a = 1 - s (1 - w); o = half(P + a (S - P)), round to nearest even, and S's own bits where a == 1.  p4 = o and
+ *   p5 = b are the next launch's p2 and p3: (p4, p5) ping-pong against (p2, p3), because a tile's halo reads its neighbours'
+ *   previous bytes.  Every element of p4 and p5 is written by a plain store on every launch: nothing has to be zeroed.  SHOW
+ *   also writes half(2 w - 1) to all three channels of p6 (the state p4 stays the blend).  INIT (the first frame of a sequence):
+ *   o = S (p6 too), p5 = b, and p2 / p3 are not read -- they may be null or hold anything.  Inputs are finite.  r == 0 and INIT:
+ *   one lane per 8 pixels; r > 0: one work-group per 16 x 64 tile, d of the tile and its halo, then the row sums, in LDS.
+ *   Refused: a null pointer (p2 / p3 only with INIT, p6 only without SHOW), a misaligned one, W % 8 != 0, 3 H W >= 2^31, r
+ *   outside 0..L2D_STEADY_MAX_R, unknown flags, p4 (or p6) overlapping p0, p1, p2 or one another, p5 overlapping p3, a
+ *   non-finite or negative lo / inv, s outside [0, 1].
  */
 enum {
     L2D_OP_IGEMM = 1,
@@ -438,6 +460,7 @@ enum {
     L2D_OP_COLOR_LOCK = 45,
     L2D_OP_FRAME_RESIZE = 46,
     L2D_OP_FRAME_MATTE_UP = 47,
+    L2D_OP_FRAME_STEADY = 48,
 };
 
 /* flag bits of L2D_OP_FRAME_MATTE (i4) */
@@ -452,6 +475,12 @@ enum {
 #define L2D_COLOR_LOCK_FREEZE 4
 #define L2D_COLOR_LOCK_BLOCK_PIXELS 4096 /* x 255^2 < 2^32: a block's sum of squares fits uint32 */
 #define L2D_COLOR_LOCK_MAX_PIXELS 4194304 /* 2^22: n S2 - S1^2 stays inside int64 */
+
+/* flag bits of L2D_OP_FRAME_STEADY (i3), and its largest radius */
+#define L2D_STEADY_HARD 1
+#define L2D_STEADY_SHOW 2
+#define L2D_STEADY_INIT 4
+#define L2D_STEADY_MAX_R 8
 
 /* sizes of L2D_OP_FRAME_RESIZE */
 #define L2D_RESIZE_MAX_KS 13 /* taps per output: Lanczos (support 3) at a 2x down-scale, 2 * 6 + 1 */

@@ -1565,3 +1565,42 @@ def frame_matte_up(styled, camera, depth, dst, tx, ty, *, B, H, W, Ho, Wo, lo32,
     op.l[0] = stride
     op.f[0], op.f[1] = float(lo32), float(inv32)
     return op, keep
+
+
+# ----------------------------------------------------------------------------- steady (steady.hip, steady.py)
+STEADY_HARD, STEADY_SHOW, STEADY_INIT = 1, 2, 4      # l2d.h L2D_STEADY_*
+STEADY_MAX_R = 8                                     # l2d.h L2D_STEADY_MAX_R
+
+
+def frame_steady(styled, source, prev_out, prev_bytes, out, next_bytes, *, H, W, lo32, inv32, s32, r=0, hard=False, show=False,
+                 init=False, picture=None):
+    """fp16 [3,H,W] `styled`, `source`, `prev_out` + planar uint8 [3,H,W] `prev_bytes` -> fp16 [3,H,W] `out`, uint8 [3,H,W]
+    `next_bytes` (steady.steady_ref): the previous output held where the source's bytes did not move.  `lo32, inv32, hard` as
+    `steady.steady_params` returns them, `s32` the strength; `show` also writes the picture of the weight to `picture`; with
+    `init` the two `prev_*` operands are not read and may be None."""
+    _lock_frame("frame_steady: styled", styled, H, W)
+    _lock_frame("frame_steady: source", source, H, W)
+    _lock_frame("frame_steady: out", out, H, W)
+    if prev_out is not None or not init:
+        _lock_frame("frame_steady: prev_out", prev_out, H, W)
+    for name, t in (("prev_bytes", prev_bytes), ("next_bytes", next_bytes)):
+        if t is None and init and name == "prev_bytes":
+            continue
+        if t.dtype != torch.uint8 or tuple(t.shape[-3:]) != (3, H, W) or t.numel() != 3 * H * W or not t.is_contiguous():
+            raise ValueError(f"frame_steady: {name}: expected a contiguous planar uint8 [3,{H},{W}] record, got {t.dtype} {tuple(t.shape)}")
+    if bool(show) != (picture is not None):
+        raise ValueError("frame_steady: a picture buffer goes with show=True, and with nothing else")
+    if picture is not None:
+        _lock_frame("frame_steady: picture", picture, H, W)
+    if isinstance(r, bool) or int(r) != r or not 0 <= int(r) <= STEADY_MAX_R:
+        raise ValueError(f"frame_steady: r={r!r}: use an integer from 0 to {STEADY_MAX_R}")
+    op = L2dOp()
+    op.kind = _lib.OP_FRAME_STEADY
+    keep = (styled, source, prev_out, prev_bytes, out, next_bytes, picture)
+    for j, t in enumerate(keep):
+        op.p[j] = _ptr(t)
+    flags = (STEADY_HARD if hard else 0) | (STEADY_SHOW if show else 0) | (STEADY_INIT if init else 0)
+    for j, v in enumerate([H, W, r, flags]):
+        op.i[j] = int(v)
+    op.f[0], op.f[1], op.f[2] = float(lo32), float(inv32), float(s32)
+    return op, keep

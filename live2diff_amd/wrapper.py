@@ -20,8 +20,9 @@ device (jpeg_io.HipJpegDecoder) and ingested there like a uint8 frame (`jpeg_dec
 (color_lock.py).  `set_output_size` (or the `output_size` keyword) resamples the uint8 frame to a size of the caller's choice
 with Pillow's arithmetic, behind both and in front of the JPEG encoder or the copy to the host (resize.py).
 `set_matte_source("camera")` composites the matte at the output size over the camera's own pixels (matte.HipMatteUp).
+`set_steady` holds the previous output pixel where the frame's source did not move (steady.py), behind the colour lock.
 
-Every frame leaves through one chain, `_route`: colour lock (`_finish`, in front of it) -> matte composite, or egress -> resize
+Every frame leaves through one chain, `_route`: colour lock, then steady (`_finish`, in front of it) -> matte composite, or egress -> resize
 -> JPEG encoder, or copy to the host.  A stage that is not set is not in the chain; on the device each stage is one launch that
 hands its static buffer to the next, and only the last one copies to the host.
 """
@@ -274,6 +275,11 @@ class StreamAnimateDiffusionDepthWrapper:
     _lock_load = None                       # a state the device record has yet to be loaded with
     _lock_init = True                       # the next "ema" frame copies its own moments
     _lock_last = None                       # the last locked frame: what a dropped frame's repeated output reuses
+    _steady = None                          # the steady mode's settings (set_steady), None: off
+    _steady_dev = None                      # steady.HipSteady, made by the first steadied frame on the device
+    _steady_state = None                    # (previous output, previous source bytes) on the host route; on the device it stays there
+    _steady_init = True                     # the next steadied frame starts the sequence: it passes as it is
+    _steady_last = None                     # the last steadied frame: what a dropped frame's repeated output reuses
     _size = None                            # the output size's settings (set_output_size), None: the UNet's geometry
     _size_dev = None                        # resize.HipResize of the current size, made by the first resized frame on the device
     _size_jpeg = None                       # {(height, width): jpeg_io.HipJpegEncoder}, one per output size "jpeg" frames left at
@@ -291,7 +297,7 @@ class StreamAnimateDiffusionDepthWrapper:
                  use_denoising_batch: bool = True, cfg_type: str = "none", seed: int = 42,
                  engine_dir: Optional[Union[str, Path]] = "engines", opt_unet: bool = False, frame_pipelining: bool = False,
                  jpeg_quality: int = 75, jpeg_decode: str = "device", output_size: Optional[Tuple[int, int]] = None,
-                 output_resample: str = "lanczos", matte_source: str = "stream"):
+                 output_resample: str = "lanczos", matte_source: str = "stream", steady: Optional[dict] = None):
         self._check_keywords(few_step_model_type=few_step_model_type, acceleration=acceleration, cfg_type=cfg_type,
                              use_denoising_batch=use_denoising_batch, frame_buffer_size=frame_buffer_size, device_ids=device_ids,
                              opt_unet=opt_unet, output_type=output_type, dtype=dtype, jpeg_quality=jpeg_quality, jpeg_decode=jpeg_decode)
@@ -310,13 +316,14 @@ class StreamAnimateDiffusionDepthWrapper:
                     window_size=window, frame_pipelining=frame_pipelining, enable_similar_image_filter=enable_similar_image_filter,
                     similar_image_filter_threshold=similar_image_filter_threshold,
                     similar_image_filter_max_skip_frame=similar_image_filter_max_skip_frame, jpeg_quality=jpeg_quality,
-                    jpeg_decode=jpeg_decode, output_size=output_size, output_resample=output_resample, matte_source=matte_source)
+                    jpeg_decode=jpeg_decode, output_size=output_size, output_resample=output_resample, matte_source=matte_source,
+                    steady=steady)
 
     @classmethod
     def from_components(cls, pipe, *, num_inference_steps: int, t_index_list: Optional[List[int]] = None,
                         strength: Optional[float] = None, **kw):
         """The wrapper around an already assembled `pipe` namespace (tests, synthetic weights).  Keywords: those of the
-        constructor that do not name files (`jpeg_quality`, `jpeg_decode`, `output_size`, `output_resample` and `matte_source` among them), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
+        constructor that do not name files (`jpeg_quality`, `jpeg_decode`, `output_size`, `output_resample`, `matte_source` and `steady` among them), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
         self = cls.__new__(cls)
         cls._check_keywords(**{k: kw.pop(k) for k in ("acceleration", "cfg_type", "use_denoising_batch", "frame_buffer_size",
                                                       "device_ids", "opt_unet", "few_step_model_type") if k in kw},
@@ -356,8 +363,10 @@ class StreamAnimateDiffusionDepthWrapper:
                width=512, height=512, do_add_noise=True, seed=42, clip_skip=1, warmup_frames=8, window_size=16,
                scheduler_kwargs=None, frame_pipelining=False, enable_similar_image_filter=False,
                similar_image_filter_threshold=0.98, similar_image_filter_max_skip_frame=10, jpeg_quality=75, jpeg_decode="device",
-               output_size=None, output_resample="lanczos", matte_source="stream"):
+               output_size=None, output_resample="lanczos", matte_source="stream", steady=None):
         self._check_matte_source(matte_source)
+        if steady is not None and not isinstance(steady, dict):
+            raise ValueError(f"steady={steady!r}: use a dict of set_steady's keywords, or None")
         self.sd_turbo = False
         self.device = pipe.device if device is None else device
         self.dtype, self.width, self.height = dtype, width, height
@@ -393,6 +402,8 @@ class StreamAnimateDiffusionDepthWrapper:
             self.stream.image_processor = FrameProcessor(self.io)
         self._init_styles(pipe)
         self.set_matte_source(matte_source)
+        if steady is not None:
+            self.set_steady(**steady)
 
     # ------------------------------------------------------------------ depth matte (matte.py)
     @property
@@ -487,8 +498,8 @@ class StreamAnimateDiffusionDepthWrapper:
                 and self.io is not None and torch.is_tensor(image_tensor) and image_tensor.is_cuda)
 
     def _need_line(self) -> None:
-        """The delay line of source frames and depth planes, shared by the matte and the colour lock to "source": made by
-        whichever needs it first.  Outputs of frames pushed before it existed have no slot (`_matte_skip`)."""
+        """The delay line of source frames and depth planes, shared by the matte, the colour lock to "source" and the steady
+        mode: made by whichever needs it first.  Outputs of frames pushed before it existed have no slot (`_matte_skip`)."""
         if self._matte_line is None:
             from .matte import MatteLine
             self._matte_line = MatteLine(self.batch_size, self.height, self.width, device=self.stream.device)
@@ -496,8 +507,8 @@ class StreamAnimateDiffusionDepthWrapper:
             self._matte_skip = len(getattr(self.stream, "_pending", None) or ())
 
     def _release_line(self) -> None:
-        """drop the delay line when neither the matte nor a colour lock to "source" needs it"""
-        if self._matte is None and (self._lock is None or self._lock["mode"] != "source"):
+        """drop the delay line when neither the matte, a colour lock to "source" nor the steady mode needs it"""
+        if self._matte is None and self._steady is None and (self._lock is None or self._lock["mode"] != "source"):
             self._matte_line = None
             self._matte_skip = 0
             self.stream.matte_tap = None
@@ -580,6 +591,67 @@ class StreamAnimateDiffusionDepthWrapper:
         self._lock_last = out
         return out
 
+    # ------------------------------------------------------------------ steady (steady.py)
+    @property
+    def steady(self) -> Optional[dict]:
+        """the current steady mode as {lo, hi, strength, radius, show}, or None"""
+        return None if self._steady is None else dict(self._steady)
+
+    def set_steady(self, lo: float = 2.0, hi: float = 10.0, *, strength: float = 0.8, radius: int = 2, show: bool = False) -> None:
+        """Hold still what the camera holds still.  Per pixel the motion of the frame's SOURCE since the source of the output
+        before is measured on the bytes a viewer would see (the largest change over the three channels, averaged over a
+        (2 radius + 1)^2 window, `radius` 0..8): at or below `lo` byte levels a pixel counts as still and the previous output
+        pixel is held, `out = prev + (1 - strength) (styled - prev)`; at or above `hi` it counts as moving and the new styled
+        pixel passes untouched, bit for bit; a smoothstep in between.  A hard cut moves everything and passes by itself.
+        `strength` in [0, 1] is how firmly a still pixel is held (0: the frame as it is, 1: frozen).  `show=True` returns the
+        weight itself as a grey frame (white = moving), to choose `lo` and `hi` by eye.  The defaults are a starting point
+        chosen for a sensor noise of about one byte level; they are not tuned on footage.  One small launch on the device
+        behind the colour lock and in front of the egress launch, the matte, the resize or the JPEG encoder; under a matte
+        the styled frame is steadied before the composite, so the real part of the picture stays untouched.  Every output
+        type but "latent" is served.  May be called before or after `prepare` and between any two frames; this call and
+        `prepare` restart the sequence (the next frame passes as it is), the frames `prepare` returns are not touched, a frame
+        the near-duplicate filter dropped repeats the last steadied frame without moving the state, and the output of a
+        frame that entered the stream before the delay line existed passes unchanged."""
+        from .steady import SERVED_OUTPUT_TYPES, check_settings
+        self._check_served(SERVED_OUTPUT_TYPES, "held steady", "clear_steady")
+        settings = check_settings(lo, hi, strength, radius, show)
+        self._need_line()
+        self._steady = settings
+        self._steady_state = self._steady_last = None
+        self._steady_init = True
+
+    def clear_steady(self) -> None:
+        """Back to the plain output: no launch, copy or buffer of the steady mode is left in the frame's path.  (A matte and a
+        colour lock to "source" keep the delay line they share with it.)"""
+        self._steady = self._steady_dev = self._steady_state = self._steady_last = None
+        self._steady_init = True
+        self._release_line()
+
+    def _steadied(self, image_tensor: torch.Tensor, slot, repeated: bool) -> torch.Tensor:
+        """the frame under the steady mode, fp16 [1,3,H,W]: op 48 on the device, `steady_ref` without one.  `repeated`: the
+        near-duplicate filter dropped the frame and `image_tensor` is the output of the one before; its steadied frame is
+        reused and the state does not move."""
+        st = self._steady
+        if repeated and self._steady_last is not None:
+            return self._steady_last
+        if slot is None:                   # (an output of a frame the delay line has not seen: the sequence starts behind it)
+            self._steady_init, self._steady_last = True, None
+            return image_tensor
+        if self.io is not None and image_tensor.is_cuda:
+            if self._steady_dev is None:
+                from .steady import HipSteady
+                self._steady_dev = HipSteady(self.height, self.width, device=image_tensor.device)
+            out = self._steady_dev.steady(image_tensor[0], slot.source, st, init=self._steady_init)
+        else:
+            from .steady import steady_ref
+            out, self._steady_state = steady_ref(image_tensor[:1], slot.source, self._steady_state, lo=st["lo"], hi=st["hi"],
+                                                 strength=st["strength"], radius=st["radius"], show=st["show"],
+                                                 init=self._steady_init)
+            out = torch.from_numpy(out)
+        self._steady_init = False
+        self._steady_last = out
+        return out
+
     def _check_served(self, served, noun: str, clear: str, what: Optional[str] = None) -> None:
         """ValueError where `output_type` is none a feature serves.  `noun`: what the feature does to a frame ("composited");
         `clear`: the method that turns it off; `what` ("a matte"): the check of a frame, while the feature is set -- without it
@@ -590,12 +662,16 @@ class StreamAnimateDiffusionDepthWrapper:
                              + ", ".join(repr(t) for t in served) + tail)
 
     def _finish(self, image_tensor, slot, repeated: bool = False):
-        """`postprocess_image` of a frame while a colour lock, a matte or an output size is set: the lock first, then the rest
-        of the chain (`_route`) on the locked frame.  A frame that is no tensor is not locked and raises there."""
-        from . import color_lock, matte, resize
+        """`postprocess_image` of a frame while a colour lock, the steady mode, a matte or an output size is set: the lock
+        first, then steady, then the rest of the chain (`_route`) on that frame.  A frame that is no tensor is neither locked
+        nor steadied and raises there."""
+        from . import color_lock, matte, resize, steady
         if self._lock is not None and torch.is_tensor(image_tensor):
             self._check_served(color_lock.SERVED_OUTPUT_TYPES, "locked", "clear_color_lock", "a colour lock")
             image_tensor = self._locked(image_tensor, slot, repeated)
+        if self._steady is not None and torch.is_tensor(image_tensor):
+            self._check_served(steady.SERVED_OUTPUT_TYPES, "held steady", "clear_steady", "the steady mode")
+            image_tensor = self._steadied(image_tensor, slot, repeated)
         if self._size is not None:
             self._check_served(resize.SERVED_OUTPUT_TYPES, "resampled", "clear_output_size", "an output size")
         if self._matte is not None:
@@ -744,6 +820,7 @@ class StreamAnimateDiffusionDepthWrapper:
         self._lock_init, self._lock_last = True, None      # an "ema" colour lock starts again; a reference image's state stays
         if self._lock is not None and self._lock["mode"] != "image":
             self._lock_state = None
+        self._steady_init, self._steady_last, self._steady_state = True, None, None      # the steady mode starts again too
         if isinstance(warmup_frames, (list, tuple)) and warmup_frames and all(_is_jpeg(f) for f in warmup_frames):
             # (a device frame is a view of one of the decoder's two static slots: it is copied before the slot's next turn)
             decoded = [d.clone() if torch.is_tensor(d) else torch.from_numpy(d).to(self.io.device) if self.io is not None else d
@@ -877,7 +954,7 @@ class StreamAnimateDiffusionDepthWrapper:
         return self._route(image_tensor, output_type)
 
     def _route(self, image_tensor: torch.Tensor, output_type: str, slot=None, size: Optional[dict] = None, camera: bool = False):
-        """The one way out for a frame (fp16 [1,3,H,W] in [-1, 1], behind the colour lock when one is set): the matte's composite
+        """The one way out for a frame (fp16 [1,3,H,W] in [-1, 1], behind the colour lock and the steady mode when set): the matte's composite
         with `slot` (a `MatteLine` slot; None: no matte, or its line has seen no frame yet) or the egress bytes, resampled to
         `size` (the setting of `set_output_size`, or None), then the JPEG encoder or the copy to the host.  `camera` (the slot
         carries the camera's pixels at `size`, `_camera_slot`): the resize of the styled frame first, then the composite at the

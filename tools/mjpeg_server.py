@@ -39,7 +39,12 @@ stream runs; `GET /size` answers the current settings as JSON (`null`: off).
 `--matte-source stream|camera` chooses what a matte keeps real under an output size (`wrapper.set_matte_source`): `stream`, the
 UNet-sized source frame resampled with the rest of the picture, or `camera`, the posted frame's own pixels resampled to the output
 size and composited there.  `POST /matte-source` with one of the two words changes it while the stream runs; `GET /matte-source`
-answers the current one as a JSON string."""
+answers the current one as a JSON string.
+
+`--steady LO,HI[,STRENGTH[,RADIUS]]` holds the previous output pixel where the frame's source did not move
+(`wrapper.set_steady`: one small launch on the device behind the colour lock; LO and HI are byte levels of the locally averaged
+motion).  `POST /steady` with the same text as its body, or `off`, changes it while the stream runs; `GET /steady` answers the
+current settings as JSON (`null`: off)."""
 import argparse
 import json
 import os
@@ -236,6 +241,55 @@ class ColorBox:
             self.failed += 1
 
 
+def parse_steady_arg(text: str):
+    """`LO,HI[,STRENGTH[,RADIUS]]` -> the keywords of `wrapper.set_steady`, `off` -> None; ValueError otherwise"""
+    from live2diff_amd.steady import check_settings
+    text = text.strip()
+    if text == "off":
+        return None
+    parts = [t.strip() for t in text.split(",")]
+    if not 2 <= len(parts) <= 4:
+        raise ValueError(f"steady {text!r}: use LO,HI[,STRENGTH[,RADIUS]] or off")
+    try:
+        lo, hi = float(parts[0]), float(parts[1])
+        strength = float(parts[2]) if len(parts) > 2 else 0.8
+        radius = int(parts[3]) if len(parts) > 3 else 2
+    except ValueError:
+        raise ValueError(f"steady {text!r}: LO and HI are numbers in [0, 255], STRENGTH a number in [0, 1], RADIUS an integer "
+                         "from 0 to 8") from None
+    s = check_settings(lo, hi, strength, radius)
+    return dict(lo=s["lo"], hi=s["hi"], strength=s["strength"], radius=s["radius"])
+
+
+class SteadyBox:
+    """What `POST /steady` delivers: the newest requested steady mode (a dict of `set_steady` keywords, or None for `off`),
+    applied by the producer between two frames.  `current` is what was last applied; `failed` counts requests the wrapper refused."""
+    _NOTHING = object()
+
+    def __init__(self, current=None):
+        self._lock = threading.Lock()
+        self.current, self._want, self.failed = current, self._NOTHING, 0
+
+    def put(self, settings) -> None:
+        with self._lock:
+            self._want = settings
+
+    def apply(self, wrapper) -> None:
+        """(producer thread, between frames)"""
+        with self._lock:
+            want, self._want = self._want, self._NOTHING
+        if want is self._NOTHING:
+            return
+        try:
+            if want is None:
+                wrapper.clear_steady()
+            else:
+                wrapper.set_steady(want["lo"], want["hi"], strength=want["strength"], radius=want["radius"])
+            self.current = wrapper.steady
+        except ValueError:
+            self.failed += 1
+
+
 def parse_size_arg(text: str):
     """`WxH[,FILTER]` -> the keywords of `wrapper.set_output_size`, `off` -> None; ValueError otherwise (the wrapper, which knows
     the stream's size, checks the ratio once more)"""
@@ -362,8 +416,8 @@ class Latest:
 
 
 def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = None, mattes: "MatteBox" = None, colors: "ColorBox" = None,
-                 sizes: "SizeBox" = None, sources: "MatteSourceBox" = None):
-    boxes = {"/matte": mattes, "/color": colors, "/size": sizes, "/matte-source": sources}
+                 sizes: "SizeBox" = None, sources: "MatteSourceBox" = None, steadies: "SteadyBox" = None):
+    boxes = {"/matte": mattes, "/color": colors, "/size": sizes, "/matte-source": sources, "/steady": steadies}
     page = PAGE if inbox is None else CAMERA_PAGE
 
     class Handler(BaseHTTPRequestHandler):
@@ -466,6 +520,9 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
             if self.path == "/matte-source" and sources is not None:
                 self.do_matte(sources, parse_matte_source_arg)
                 return
+            if self.path == "/steady" and steadies is not None:
+                self.do_matte(steadies, parse_steady_arg)
+                return
             if inbox is None or self.path != "/frame":
                 self.send_error(404)
                 return
@@ -489,9 +546,9 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
 
 
 def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: StyleBox = None, mattes: MatteBox = None,
-            colors: ColorBox = None, sizes: SizeBox = None, sources: MatteSourceBox = None) -> None:
-    """the producer: loops `frames` through the wrapper until `stop` is set; a posted style, matte, colour lock, output size or
-    matte source is applied between two frames"""
+            colors: ColorBox = None, sizes: SizeBox = None, sources: MatteSourceBox = None, steadies: SteadyBox = None) -> None:
+    """the producer: loops `frames` through the wrapper until `stop` is set; a posted style, matte, colour lock, output size,
+    matte source or steady mode is applied between two frames"""
     from live2diff_amd.jpeg import mjpeg_part
     try:
         i = 0
@@ -506,6 +563,8 @@ def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: Styl
                 sizes.apply(wrapper)
             if sources is not None:
                 sources.apply(wrapper)
+            if steadies is not None:
+                steadies.apply(wrapper)
             latest.put(mjpeg_part(wrapper(frames[i % len(frames)])))
             i += 1
     finally:
@@ -513,7 +572,8 @@ def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: Styl
 
 
 def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: threading.Event, styles: StyleBox = None,
-                   mattes: MatteBox = None, colors: ColorBox = None, sizes: SizeBox = None, sources: MatteSourceBox = None) -> None:
+                   mattes: MatteBox = None, colors: ColorBox = None, sizes: SizeBox = None, sources: MatteSourceBox = None,
+                   steadies: SteadyBox = None) -> None:
     """the producer of `--input post`: the first frames posted warm the stream up, then the newest posted frame goes through the
     wrapper, for ever; a frame the wrapper refuses (ValueError: a damaged file) is dropped and counted in `inbox.failed`"""
     from live2diff_amd.jpeg import mjpeg_part
@@ -536,6 +596,8 @@ def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: thr
                 sizes.apply(wrapper)
             if sources is not None:
                 sources.apply(wrapper)
+            if steadies is not None:
+                steadies.apply(wrapper)
             try:
                 latest.put(mjpeg_part(wrapper(frame)))
             except ValueError:
@@ -571,11 +633,16 @@ def main(argv=None):
     ap.add_argument("--matte-source", default="stream", type=parse_matte_source_arg, metavar="stream|camera",
                     help="what a matte keeps real under an output size: the UNet-sized source frame (`stream`) or the input frame's own "
                          "pixels at the output size (`camera`); POST /matte-source with one of the two words changes it between frames")
+    ap.add_argument("--steady", default=None, metavar="LO,HI[,STRENGTH[,RADIUS]]",
+                    help="hold the previous output pixel where the source moved by LO byte levels or less (moving from HI on), by "
+                         "STRENGTH (default 0.8), the motion averaged over a radius of RADIUS pixels (default 2); POST /steady with "
+                         "the same text, or `off`, changes it between frames")
     args = ap.parse_args(argv)
     style_args = [parse_style_arg(t) for t in args.style]
     matte = parse_matte_arg(args.matte) if args.matte else None
     color = parse_color_arg(args.color_lock) if args.color_lock else None
     size = parse_size_arg(args.output_size) if args.output_size else None
+    steady = parse_steady_arg(args.steady) if args.steady else None
 
     from stream_frames import read_frames
 
@@ -602,15 +669,18 @@ def main(argv=None):
     colors = ColorBox(w.color_lock)
     sizes = SizeBox(w.output_size)
     sources = MatteSourceBox(w.matte_source)
+    if steady is not None:
+        w.set_steady(steady["lo"], steady["hi"], strength=steady["strength"], radius=steady["radius"])      # (before `prepare` too)
+    steadies = SteadyBox(w.steady)
     prompt = args.prompt if args.prompt is not None else str(cfg.get("prompt", ""))
     latest, stop = Latest(), threading.Event()
     inbox = Inbox(sink) if post else None
     if post:
-        producer = threading.Thread(target=produce_posted, args=(w, prompt, inbox, latest, stop, styles, mattes, colors, sizes, sources), name="producer", daemon=True)
+        producer = threading.Thread(target=produce_posted, args=(w, prompt, inbox, latest, stop, styles, mattes, colors, sizes, sources, steadies), name="producer", daemon=True)
     else:
         w.prepare(frames[:sink], prompt)
-        producer = threading.Thread(target=produce, args=(w, frames, latest, stop, styles, mattes, colors, sizes, sources), name="producer", daemon=True)
-    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest, inbox, styles, mattes, colors, sizes, sources))
+        producer = threading.Thread(target=produce, args=(w, frames, latest, stop, styles, mattes, colors, sizes, sources, steadies), name="producer", daemon=True)
+    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest, inbox, styles, mattes, colors, sizes, sources, steadies))
     server.daemon_threads = True
     producer.start()
     print(f"http://{args.host}:{args.port}/  ({args.height}x{args.width}, quality {args.quality}; Ctrl-C stops)")
