@@ -335,6 +335,10 @@ enum {
  *   v = clamp(fp16(fp16(x / 2) + 0.5), 0, 1) on styled and source (L2D_OP_FRAME_EGRESS' chain); o = v_c + m (v_s - v_c);
  *   byte = rint(255 o), half to even.  SHOW writes rint(255 m) to all three channels and reads neither frame.  m == 1 gives
  *   L2D_OP_FRAME_EGRESS(styled) and m == 0 L2D_OP_FRAME_EGRESS(source) byte for byte.  Refused: B H W 3 >= 2^31, B > 65535.
+ *   L2D_MATTE_PLANE (this op and L2D_OP_FRAME_MATTE_UP): p2 is a float plane [H][W] of ready matte values in [0, 1] (plane b at
+ *   p2 + b l0 floats; L2D_OP_FRAME_MATTE_EDGE writes one), 16-byte aligned here and 4-byte aligned there.  The ramp, HARD and FAR
+ *   are skipped -- f0, f1 and those two bits are not read --, the feather, the blend and SHOW work on the plane's values as on m.
+ *   A compile-time variant of the kernels: with the flag clear nothing of the paths above changes.
  *
  * Colour lock (colorlock.hip; no counterpart in the reference).  The per-channel mean and variance of the BYTES a frame leaves as
  *   (b = L2D_OP_FRAME_EGRESS' byte of a pixel) are measured in exact integers and held to a target by one gain and one offset per
@@ -389,6 +393,22 @@ enum {
  *   (whole dwords where the address allows, bytes at the ends of a row).  Refused: a null pointer, Ho, Wo outside
  *   1..L2D_RESIZE_MAX_SIZE or outside [n_in / 2, 8 n_in], B Ho Wo 3 >= 2^31, B > 65535, r outside 0..L2D_MATTE_MAX_R, unknown
  *   flags, a depth stride below H W, a misaligned table, lo / inv as L2D_OP_FRAME_MATTE refuses them.
+ *
+ * Edge-aware matte (matte_edge.hip; no counterpart in the reference): the matte re-fitted locally as a linear function of the
+ *   frame it cuts (a guided filter, He et al.), so that its edges land on the frame's own edges.
+ * L2D_OP_FRAME_MATTE_EDGE  one launch:  p0 source half [3][H][W] p1 depth half [H][W] p2 out float [H][W] (all 16-byte aligned) ;
+ *   i0 H i1 W (W % 8 == 0, 3 H W < 2^31) i2 r (1..L2D_MATTE_EDGE_MAX_R) i3 flags (L2D_MATTE_HARD | _FAR) ; l0 the BITS of the
+ *   double E = double(n n) eps eps with n = (2r+1)^2 and eps >= 1 in byte levels (so E >= n n) ; f0 lo f1 inv (as
+ *   L2D_OP_FRAME_MATTE's).  Arithmetic, exact integers and a few individually rounded fp64 operations, no fma, so that numpy
+ *   restates it bit for bit (live2diff_amd/matte.py edge_ref): P = rint(255 m) with m as L2D_OP_FRAME_MATTE forms it in front
+ *   of the feather; b = L2D_OP_FRAME_EGRESS' bytes of p0; Y = (77 R + 150 G + 29 B + 128) >> 8; S_I, S_P, S_II, S_IP the sums of
+ *   Y, P, Y Y, Y P over the (2r+1) x (2r+1) window, coordinates clamped to the image; cov = n S_IP - S_I S_P and var = n S_II -
+ *   S_I S_I in int64; a = double(cov) / (double(var) + E); A = rint(4096 a); bc = (double(S_P) - a double(S_I)) / double(n);
+ *   B = rint(4096 bc) (both fit int32: |a| <= 127.5 / (2 eps)); Q = window_sum(A) Y + window_sum(B) in int64; q = double(Q) /
+ *   double(n 4096 255); out = float(min(max(q, 0), 1)).  One work-group per 16 x 64 tile; Y and P of the tile and a halo of 2r as
+ *   bytes in LDS, the sums separably.  Every element of p2 is written by a plain store on every launch: nothing has to be zeroed.
+ *   Refused: a null or misaligned pointer, W % 8 != 0, 3 H W >= 2^31, r outside 1..L2D_MATTE_EDGE_MAX_R, unknown flags, an E
+ *   that is not finite or below n n, lo / inv as L2D_OP_FRAME_MATTE refuses them.
  *
  * Steady (steady.hip; no counterpart in the reference).  Where the frame's source did not move since the source of the output
  *   before, the previous output pixel is held (a per-pixel EMA); where it moved, the styled pixel passes untouched.  The result is
@@ -461,13 +481,16 @@ enum {
     L2D_OP_FRAME_RESIZE = 46,
     L2D_OP_FRAME_MATTE_UP = 47,
     L2D_OP_FRAME_STEADY = 48,
+    L2D_OP_FRAME_MATTE_EDGE = 49,
 };
 
-/* flag bits of L2D_OP_FRAME_MATTE (i4) */
+/* flag bits of L2D_OP_FRAME_MATTE (i4) and L2D_OP_FRAME_MATTE_UP (i6); HARD and FAR also of L2D_OP_FRAME_MATTE_EDGE (i3) */
 #define L2D_MATTE_HARD 1
 #define L2D_MATTE_FAR 2
 #define L2D_MATTE_SHOW 4
+#define L2D_MATTE_PLANE 16 /* p2 is a float plane of ready matte values (8 is not assigned) */
 #define L2D_MATTE_MAX_R 8
+#define L2D_MATTE_EDGE_MAX_R 8 /* the largest radius of L2D_OP_FRAME_MATTE_EDGE */
 
 /* flag bits of L2D_OP_COLOR_LOCK (i2), and the sizes both colour-lock ops share */
 #define L2D_COLOR_LOCK_INIT 1

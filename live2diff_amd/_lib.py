@@ -31,6 +31,7 @@ OP_FRAME_MOMENTS, OP_COLOR_LOCK = 44, 45
 OP_FRAME_RESIZE = 46
 OP_FRAME_MATTE_UP = 47
 OP_FRAME_STEADY = 48
+OP_FRAME_MATTE_EDGE = 49
 ABI_VERSION = 6
 
 

@@ -24,6 +24,7 @@
 #define MT_HARD L2D_MATTE_HARD
 #define MT_FAR L2D_MATTE_FAR
 #define MT_SHOW L2D_MATTE_SHOW
+#define MT_PLANE L2D_MATTE_PLANE
 
 struct mt_params {
     float lo, inv;
@@ -41,6 +42,30 @@ __device__ __forceinline__ float mt_matte(h16 depth, const mt_params &p) {
     }
     const float m = __fmul_rn(__fmul_rn(t, t), __fsub_rn(3.0f, __fmul_rn(2.0f, t)));
     return (p.flags & MT_FAR) ? __fsub_rn(1.0f, m) : m;
+}
+
+// L2D_MATTE_PLANE: the `depth` operand is an fp32 plane of ready matte values (L2D_OP_FRAME_MATTE_EDGE
+// writes one) and the ramp is skipped.  PLANE is a template parameter of the three kernel bodies, so the kernels of the flag-clear
+// path (frame_matte_point_kernel, frame_matte_box_kernel, frame_matte_up_kernel) hold no trace of it; frame_plane_* are its.
+template <bool PLANE>
+__device__ __forceinline__ float mt_value(const void *depth, long long i, const mt_params &p) {
+    if constexpr (PLANE) return reinterpret_cast<const float *>(depth)[i];
+    else return mt_matte(reinterpret_cast<const h16 *>(depth)[i], p);
+}
+
+// eight consecutive values from element i (a multiple of 8) on
+template <bool PLANE>
+__device__ __forceinline__ void mt_value8(const void *depth, long long i, const mt_params &p, float *v) {
+    if constexpr (PLANE) {
+        const f32x4 *src = reinterpret_cast<const f32x4 *>(reinterpret_cast<const float *>(depth) + i);
+        const f32x4 a = src[0], b = src[1];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { v[e] = a[e]; v[e + 4] = b[e]; }
+    } else {
+        const h16x8 d = l2d_ld8(reinterpret_cast<const h16 *>(depth) + i);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = mt_matte(d[e], p);
+    }
 }
 
 // the egress op's fp16 chain (frame_io.hip fio_u8), widened to fp32
@@ -75,9 +100,9 @@ __device__ __forceinline__ void mt_blend(const h16 (&s)[3][N], const h16 (&c)[3]
 
 // r = 0: every pixel on its own.  One lane = 16 consecutive pixels of the [H W] plane = 48 bytes, three 16-byte stores (the
 // egress kernel's shape).
-__global__ __launch_bounds__(256) void frame_matte_point_kernel(const h16 *__restrict__ styled, const h16 *__restrict__ source,
-                                                                const h16 *__restrict__ depth, uint8_t *__restrict__ dst, int B, int HW,
-                                                                long long dstride, mt_params p) {
+template <bool PLANE>
+__device__ __forceinline__ void mt_point_body(const h16 *__restrict__ styled, const h16 *__restrict__ source, const void *__restrict__ depth,
+                                              uint8_t *__restrict__ dst, int B, int HW, long long dstride, const mt_params &p) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     const int per = HW >> 4;
     if (idx >= (long long)B * per) return;
@@ -86,13 +111,8 @@ __global__ __launch_bounds__(256) void frame_matte_point_kernel(const h16 *__res
     const int show = p.flags & MT_SHOW;
     h16 s[3][16], c[3][16];
     float m[16];
-    const h16 *dp = depth + (long long)b * dstride + p0;
-    const h16x8 d0 = l2d_ld8(dp), d1 = l2d_ld8(dp + 8);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        m[e] = mt_matte(d0[e], p);
-        m[e + 8] = mt_matte(d1[e], p);
-    }
+    mt_value8<PLANE>(depth, (long long)b * dstride + p0, p, m);
+    mt_value8<PLANE>(depth, (long long)b * dstride + p0 + 8, p, m + 8);
     if (!show) {
         const long long off = (long long)b * 3 * HW + p0;
 #pragma unroll
@@ -118,13 +138,25 @@ __global__ __launch_bounds__(256) void frame_matte_point_kernel(const h16 *__res
     for (int v = 0; v < 3; ++v) out[v] = make_uint4(wd[v * 4], wd[v * 4 + 1], wd[v * 4 + 2], wd[v * 4 + 3]);
 }
 
+__global__ __launch_bounds__(256) void frame_matte_point_kernel(const h16 *__restrict__ styled, const h16 *__restrict__ source,
+                                                                const h16 *__restrict__ depth, uint8_t *__restrict__ dst, int B, int HW,
+                                                                long long dstride, mt_params p) {
+    mt_point_body<false>(styled, source, depth, dst, B, HW, dstride, p);
+}
+
+__global__ __launch_bounds__(256) void frame_plane_point_kernel(const h16 *__restrict__ styled, const h16 *__restrict__ source,
+                                                                const float *__restrict__ plane, uint8_t *__restrict__ dst, int B, int HW,
+                                                                long long dstride, mt_params p) {
+    mt_point_body<true>(styled, source, plane, dst, B, HW, dstride, p);
+}
+
 // r > 0: one work-group per MT_TH x MT_TW tile.  Stage 1 writes m of the tile and its halo into LDS (rows clamped to the image;
 // an 8-pixel group lies wholly inside or wholly outside it because W % 8 == 0, and one outside holds the edge pixel's value);
 // stage 2 is the horizontal pass, one lane per column (conflict-free 4-byte reads); stage 3 the vertical pass in the blend
 // stage's layout (16-byte reads), then the blend and 8 pixels = 24 bytes per lane as three 8-byte stores.
-__global__ __launch_bounds__(MT_THREADS) void frame_matte_box_kernel(const h16 *__restrict__ styled, const h16 *__restrict__ source,
-                                                                     const h16 *__restrict__ depth, uint8_t *__restrict__ dst, int H, int W,
-                                                                     long long dstride, mt_params p) {
+template <bool PLANE>
+__device__ __forceinline__ void mt_box_body(const h16 *__restrict__ styled, const h16 *__restrict__ source, const void *__restrict__ depth,
+                                            uint8_t *__restrict__ dst, int H, int W, long long dstride, const mt_params &p) {
     __shared__ __attribute__((aligned(16))) float mm[MT_MH][MT_MW];
     __shared__ __attribute__((aligned(16))) float hh[MT_MH][MT_TW];
     const int tid = threadIdx.x;
@@ -151,22 +183,20 @@ __global__ __launch_bounds__(MT_THREADS) void frame_matte_box_kernel(const h16 *
         for (int e = 0; e < 8; ++e) { s[ch][e] = sv[e]; c[ch][e] = cv[e]; }
     }
 
-    const h16 *dp = depth + (long long)b * dstride;
+    const long long dp = (long long)b * dstride;
     for (int g = tid; g < rows * (MT_MW / 8); g += MT_THREADS) {
         const int j = g / (MT_MW / 8), cg = g % (MT_MW / 8);
         int yy = y0 - r + j;
         yy = yy < 0 ? 0 : (yy > H - 1 ? H - 1 : yy);
         const int gx = x0 - 8 + cg * 8;
-        const h16 *row = dp + (long long)yy * W;
+        const long long row = dp + (long long)yy * W;
         float v[8];
         if (gx < 0 || gx >= W) {
-            const float edge = mt_matte(row[gx < 0 ? 0 : W - 1], p);
+            const float edge = mt_value<PLANE>(depth, row + (gx < 0 ? 0 : W - 1), p);
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = edge;
         } else {
-            const h16x8 d = l2d_ld8(row + gx);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = mt_matte(d[e], p);
+            mt_value8<PLANE>(depth, row + gx, p, v);
         }
         f32x4 *o = reinterpret_cast<f32x4 *>(&mm[j][cg * 8]);
         o[0] = f32x4{v[0], v[1], v[2], v[3]};
@@ -212,6 +242,18 @@ __global__ __launch_bounds__(MT_THREADS) void frame_matte_box_kernel(const h16 *
     for (int v = 0; v < 3; ++v) out[v] = make_uint2(wd[v * 2], wd[v * 2 + 1]);
 }
 
+__global__ __launch_bounds__(MT_THREADS) void frame_matte_box_kernel(const h16 *__restrict__ styled, const h16 *__restrict__ source,
+                                                                     const h16 *__restrict__ depth, uint8_t *__restrict__ dst, int H, int W,
+                                                                     long long dstride, mt_params p) {
+    mt_box_body<false>(styled, source, depth, dst, H, W, dstride, p);
+}
+
+__global__ __launch_bounds__(MT_THREADS) void frame_plane_box_kernel(const h16 *__restrict__ styled, const h16 *__restrict__ source,
+                                                                     const float *__restrict__ plane, uint8_t *__restrict__ dst, int H, int W,
+                                                                     long long dstride, mt_params p) {
+    mt_box_body<true>(styled, source, plane, dst, H, W, dstride, p);
+}
+
 int l2d_launch_frame_matte(const l2d_op *op, hipStream_t s) {
     const int B = op->i[0], H = op->i[1], W = op->i[2], r = op->i[3], flags = op->i[4];
     const long long dstride = op->l[0];
@@ -228,10 +270,11 @@ int l2d_launch_frame_matte(const l2d_op *op, hipStream_t s) {
         l2d_set_error("frame_matte(tag %d): feather radius %d, need 0..%d", op->tag, r, MT_MAX_R);
         return L2D_EINVAL;
     }
-    if (flags & ~(MT_HARD | MT_FAR | MT_SHOW)) {
-        l2d_set_error("frame_matte(tag %d): unknown flag bits 0x%x (1 hard, 2 far, 4 show)", op->tag, flags);
+    if (flags & ~(MT_HARD | MT_FAR | MT_SHOW | MT_PLANE)) {
+        l2d_set_error("frame_matte(tag %d): unknown flag bits 0x%x (1 hard, 2 far, 4 show, 16 plane)", op->tag, flags);
         return L2D_EINVAL;
     }
+    const bool plane = (flags & MT_PLANE) != 0;
     if (dstride < HW || dstride % 8) {
         l2d_set_error("frame_matte(tag %d): depth plane stride %lld, need a multiple of 8 that is at least H W = %lld", op->tag, dstride, HW);
         return L2D_EINVAL;
@@ -246,8 +289,8 @@ int l2d_launch_frame_matte(const l2d_op *op, hipStream_t s) {
         l2d_set_error("frame_matte(tag %d): B H W 3 must stay below 2^31 and B below 65536", op->tag);
         return L2D_EINVAL;
     }
-    const float lo = op->f[0], inv = op->f[1];
-    if (!(lo >= -1.0f && lo <= 1.0f) || !(inv >= 0.0f) || inv > 3.0e38f || ((flags & MT_HARD) != 0) != (inv == 0.0f)) {
+    const float lo = plane ? 0.0f : op->f[0], inv = plane ? 0.0f : op->f[1];          // (a plane: the ramp is not read)
+    if (!plane && (!(lo >= -1.0f && lo <= 1.0f) || !(inv >= 0.0f) || inv > 3.0e38f || ((flags & MT_HARD) != 0) != (inv == 0.0f))) {
         l2d_set_error("frame_matte(tag %d): lo = %g must lie in [-1, 1], inv = %g be finite, and 0 exactly when the hard flag is set", op->tag,
                       lo, inv);
         return L2D_EINVAL;
@@ -256,14 +299,20 @@ int l2d_launch_frame_matte(const l2d_op *op, hipStream_t s) {
     mt_params p;
     p.lo = lo; p.inv = inv; p.flags = flags; p.r = r;
     const h16 *styled = (const h16 *)op->p[0], *source = (const h16 *)op->p[1], *depth = (const h16 *)op->p[2];
+    const float *mplane = (const float *)op->p[2];
     uint8_t *dst = (uint8_t *)op->p[3];
-    if (r == 0) {
-        const long long total = (long long)B * (HW / 16);
+    const dim3 tiles((W + MT_TW - 1) / MT_TW, (H + MT_TH - 1) / MT_TH, B);
+    const long long total = (long long)B * (HW / 16);
+    if (plane && r == 0) {
+        hipLaunchKernelGGL(frame_plane_point_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, styled, source, mplane, dst, B,
+                           (int)HW, dstride, p);
+    } else if (plane) {
+        hipLaunchKernelGGL(frame_plane_box_kernel, tiles, dim3(MT_THREADS), 0, s, styled, source, mplane, dst, H, W, dstride, p);
+    } else if (r == 0) {
         hipLaunchKernelGGL(frame_matte_point_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, styled, source, depth, dst, B,
                            (int)HW, dstride, p);
     } else {
-        hipLaunchKernelGGL(frame_matte_box_kernel, dim3((W + MT_TW - 1) / MT_TW, (H + MT_TH - 1) / MT_TH, B), dim3(MT_THREADS), 0, s, styled,
-                           source, depth, dst, H, W, dstride, p);
+        hipLaunchKernelGGL(frame_matte_box_kernel, tiles, dim3(MT_THREADS), 0, s, styled, source, depth, dst, H, W, dstride, p);
     }
     return l2d_check_launch("frame_matte", op->tag);
 }
@@ -319,10 +368,10 @@ __device__ __forceinline__ void mu_stage(const int *__restrict__ tab, int n_out,
     f[lane] = w;
 }
 
-__global__ __launch_bounds__(MU_THREADS) void frame_matte_up_kernel(const uint8_t *__restrict__ styled, const uint8_t *__restrict__ camera,
-                                                                    const h16 *__restrict__ depth, uint8_t *__restrict__ dst,
-                                                                    const int *__restrict__ tx, const int *__restrict__ ty, int H, int W,
-                                                                    int Ho, int Wo, long long dstride, mt_params p) {
+template <bool PLANE>
+__device__ __forceinline__ void mu_body(const uint8_t *__restrict__ styled, const uint8_t *__restrict__ camera, const void *__restrict__ depth,
+                                        uint8_t *__restrict__ dst, const int *__restrict__ tx, const int *__restrict__ ty, int H, int W, int Ho,
+                                        int Wo, long long dstride, const mt_params &p) {
     __shared__ __attribute__((aligned(16))) float mm[MU_PATCH * MU_STRIDE];       // m of the patch; later the filtered m
     __shared__ __attribute__((aligned(16))) float hh[MU_PATCH * MU_STRIDE];       // the horizontal pass' rows
     __shared__ float mt[MU_T * MU_T];                                             // M of the tile
@@ -344,11 +393,11 @@ __global__ __launch_bounds__(MU_THREADS) void frame_matte_up_kernel(const uint8_
 
     // m of the patch and its halo: mm[j][c] = m(clamp(sy0 - r + j), clamp(sx0 - r + c))
     const int rows = ny + 2 * r, cols = nx + 2 * r;
-    const h16 *dp = depth + (long long)b * dstride;
+    const long long dp = (long long)b * dstride;
     for (int i = tid; i < rows * cols; i += MU_THREADS) {
         const int j = i / cols, c = i - j * cols;
         const int yy = mu_clampi(sy0 - r + j, 0, H - 1), xx = mu_clampi(sx0 - r + c, 0, W - 1);
-        mm[j * MU_STRIDE + c] = mt_matte(dp[(long long)yy * W + xx], p);
+        mm[j * MU_STRIDE + c] = mt_value<PLANE>(depth, dp + (long long)yy * W + xx, p);
     }
     __syncthreads();
 
@@ -428,6 +477,21 @@ __global__ __launch_bounds__(MU_THREADS) void frame_matte_up_kernel(const uint8_
     }
 }
 
+__global__ __launch_bounds__(MU_THREADS) void frame_matte_up_kernel(const uint8_t *__restrict__ styled, const uint8_t *__restrict__ camera,
+                                                                    const h16 *__restrict__ depth, uint8_t *__restrict__ dst,
+                                                                    const int *__restrict__ tx, const int *__restrict__ ty, int H, int W,
+                                                                    int Ho, int Wo, long long dstride, mt_params p) {
+    mu_body<false>(styled, camera, depth, dst, tx, ty, H, W, Ho, Wo, dstride, p);
+}
+
+// (its name must not contain the name above: tests/test_matte_up_resources.py finds that kernel by it)
+__global__ __launch_bounds__(MU_THREADS) void frame_plane_up_kernel(const uint8_t *__restrict__ styled, const uint8_t *__restrict__ camera,
+                                                                    const float *__restrict__ plane, uint8_t *__restrict__ dst,
+                                                                    const int *__restrict__ tx, const int *__restrict__ ty, int H, int W,
+                                                                    int Ho, int Wo, long long dstride, mt_params p) {
+    mu_body<true>(styled, camera, plane, dst, tx, ty, H, W, Ho, Wo, dstride, p);
+}
+
 static bool mu_axis_ok(int n_in, int n_out) {
     return n_out >= 1 && n_out <= L2D_RESIZE_MAX_SIZE && 2ll * n_out >= n_in && n_out <= 8ll * n_in;
 }
@@ -458,14 +522,15 @@ int l2d_launch_frame_matte_up(const l2d_op *op, hipStream_t s) {
         l2d_set_error("frame_matte_up(tag %d): feather radius %d, need 0..%d", op->tag, r, MT_MAX_R);
         return L2D_EINVAL;
     }
-    if (flags & ~(MT_HARD | MT_FAR | MT_SHOW)) {
-        l2d_set_error("frame_matte_up(tag %d): unknown flag bits 0x%x (1 hard, 2 far, 4 show)", op->tag, flags);
+    if (flags & ~(MT_HARD | MT_FAR | MT_SHOW | MT_PLANE)) {
+        l2d_set_error("frame_matte_up(tag %d): unknown flag bits 0x%x (1 hard, 2 far, 4 show, 16 plane)", op->tag, flags);
         return L2D_EINVAL;
     }
+    const bool plane = (flags & MT_PLANE) != 0;
     const long long HW = (long long)H * W;
-    if (dstride < HW || (((uintptr_t)op->p[2]) & 1)) {
-        l2d_set_error("frame_matte_up(tag %d): depth plane stride %lld, need at least H W = %lld, and a 2-byte aligned plane", op->tag,
-                      dstride, HW);
+    if (dstride < HW || (((uintptr_t)op->p[2]) & (plane ? 3 : 1))) {
+        l2d_set_error("frame_matte_up(tag %d): depth plane stride %lld, need at least H W = %lld, and a 2-byte aligned plane (4-byte: a "
+                      "float plane)", op->tag, dstride, HW);
         return L2D_EINVAL;
     }
     for (int k = 4; k < 6; ++k) {
@@ -474,8 +539,8 @@ int l2d_launch_frame_matte_up(const l2d_op *op, hipStream_t s) {
             return L2D_EINVAL;
         }
     }
-    const float lo = op->f[0], inv = op->f[1];
-    if (!(lo >= -1.0f && lo <= 1.0f) || !(inv >= 0.0f) || inv > 3.0e38f || ((flags & MT_HARD) != 0) != (inv == 0.0f)) {
+    const float lo = plane ? 0.0f : op->f[0], inv = plane ? 0.0f : op->f[1];          // (a plane: the ramp is not read)
+    if (!plane && (!(lo >= -1.0f && lo <= 1.0f) || !(inv >= 0.0f) || inv > 3.0e38f || ((flags & MT_HARD) != 0) != (inv == 0.0f))) {
         l2d_set_error("frame_matte_up(tag %d): lo = %g must lie in [-1, 1], inv = %g be finite, and 0 exactly when the hard flag is set",
                       op->tag, lo, inv);
         return L2D_EINVAL;
@@ -483,8 +548,15 @@ int l2d_launch_frame_matte_up(const l2d_op *op, hipStream_t s) {
     L2D_DRY_RETURN();
     mt_params p;
     p.lo = lo; p.inv = inv; p.flags = flags; p.r = r;
-    hipLaunchKernelGGL(frame_matte_up_kernel, dim3((Wo + MU_T - 1) / MU_T, (Ho + MU_T - 1) / MU_T, B), dim3(MU_THREADS), 0, s,
-                       (const uint8_t *)op->p[0], (const uint8_t *)op->p[1], (const h16 *)op->p[2], (uint8_t *)op->p[3],
-                       (const int *)op->p[4], (const int *)op->p[5], H, W, Ho, Wo, dstride, p);
+    const dim3 tiles((Wo + MU_T - 1) / MU_T, (Ho + MU_T - 1) / MU_T, B);
+    if (plane) {
+        hipLaunchKernelGGL(frame_plane_up_kernel, tiles, dim3(MU_THREADS), 0, s, (const uint8_t *)op->p[0], (const uint8_t *)op->p[1],
+                           (const float *)op->p[2], (uint8_t *)op->p[3], (const int *)op->p[4], (const int *)op->p[5], H, W, Ho, Wo, dstride,
+                           p);
+    } else {
+        hipLaunchKernelGGL(frame_matte_up_kernel, tiles, dim3(MU_THREADS), 0, s, (const uint8_t *)op->p[0], (const uint8_t *)op->p[1],
+                           (const h16 *)op->p[2], (uint8_t *)op->p[3], (const int *)op->p[4], (const int *)op->p[5], H, W, Ho, Wo, dstride,
+                           p);
+    }
     return l2d_check_launch("frame_matte_up", op->tag);
 }

@@ -12,7 +12,10 @@ the stream's output over the stream's own source frame, on the device, in the la
   * `HipMatte`        the static output buffers and the one-op launch of one stream;
   * `up_table`, `matte_up_ref`, `composite_up_ref`, `HipMatteUp`   the matte at the output size: the
                       arithmetic of L2D_OP_FRAME_MATTE_UP -- the matte sampled bilinearly at the output size, the styled bytes
-                      over the camera's own -- and its launch.
+                      over the camera's own -- and its launch;
+  * `check_edge`, `guide_ref`, `edge_ref`, `HipMatteEdge`   the edge-aware matte: the matte re-fitted
+                      locally as a linear function of the source frame's luma (a guided filter), in exact integers and a few
+                      individually rounded fp64 steps -- the arithmetic of L2D_OP_FRAME_MATTE_EDGE -- and its launch.
 """
 import collections
 from typing import Optional, Tuple
@@ -24,6 +27,7 @@ from . import _lib, ops
 from .frame_io import to_pinned
 
 MAX_FEATHER = ops.MATTE_MAX_R
+MAX_EDGE_RADIUS = ops.MATTE_EDGE_MAX_R
 SERVED_OUTPUT_TYPES = ("u8", "pil", "jpeg")
 
 
@@ -63,10 +67,11 @@ def _box_pass(m: np.ndarray, r: int, axis: int) -> np.ndarray:
     return acc / np.float32(2 * r + 1)
 
 
-def matte_ref(depth, lo: float, hi: float, feather: int = 0, keep: str = "near") -> np.ndarray:
+def matte_ref(depth, lo: float, hi: float, feather: int = 0, keep: str = "near", *, edge: Optional[dict] = None, source=None) -> np.ndarray:
     """fp16 [B,H,W] depth planes (channel 0 of `encode_depth`'s `dn`: min-max normalised, in [-1, 1], at frame size) -> fp32
     [B,H,W] matte in [0, 1]: t = clamp((d - lo32) inv32, 0, 1) (hard: d >= lo32), m = (t t) (3 - 2 t), `keep="far"`: 1 - m, then
-    the (2r+1) x (2r+1) box filter as a horizontal and a vertical pass."""
+    the (2r+1) x (2r+1) box filter as a horizontal and a vertical pass.  `edge` ({radius, eps}, with the fp16 [B,3,H,W] `source`
+    frames as the guide): `edge_ref` refines m in front of the box filter."""
     check_settings(lo, hi, keep=keep, feather=feather)
     lo32, inv32, hard = matte_params(lo, hi)
     d = _np16(depth).astype(np.float32)
@@ -80,10 +85,90 @@ def matte_ref(depth, lo: float, hi: float, feather: int = 0, keep: str = "near")
     m = (t * t) * (np.float32(3.0) - np.float32(2.0) * t)
     if keep == "far":
         m = one - m
+    if edge is not None:
+        if source is None:
+            raise ValueError("matte_ref: an edge-aware matte needs the source frames as its guide")
+        src = _np16(source)
+        src = src[None] if src.ndim == 3 else src
+        if src.shape[0] != m.shape[0]:
+            raise ValueError(f"matte_ref: {m.shape[0]} depth planes, {src.shape[0]} source frames")
+        m = np.stack([edge_ref(m[b], src[b], edge["radius"], edge["eps"]) for b in range(m.shape[0])])
     if feather:
         m = _box_pass(_box_pass(m, feather, 2), feather, 1)
     assert m.dtype == np.float32
     return m
+
+
+# ----------------------------------------------------------------------------- edge-aware matte
+EDGE_SHIFT = 4096              # the fixed point of the coefficients A and B: 12 fractional bits
+
+
+def check_edge(radius=4, eps=10.0) -> dict:
+    """the edge setting as {radius, eps}, or ValueError: `radius` no integer in 1..8, `eps` no finite number >= 1 (byte levels:
+    the contrast of the guide below which a window counts as flat; from 1 on the coefficients fit 32 bits)"""
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= MAX_EDGE_RADIUS:
+        raise ValueError(f"matte edge: radius={radius!r}: use an integer from 1 to {MAX_EDGE_RADIUS}")
+    if (isinstance(eps, bool) or not isinstance(eps, (int, float, np.integer, np.floating)) or not np.isfinite(float(eps))
+            or not 1.0 <= float(eps) <= 1.0e100):
+        raise ValueError(f"matte edge: eps={eps!r}: use a finite number of byte levels, at least 1")
+    return dict(radius=int(radius), eps=float(eps))
+
+
+def edge_E(radius: int, eps: float) -> float:
+    """E = double(n n) eps eps with n = (2 radius + 1)^2, in Python doubles: what the op carries in place of eps"""
+    n = (2 * int(radius) + 1) ** 2
+    return float(n * n) * float(eps) * float(eps)
+
+
+def guide_ref(source) -> np.ndarray:
+    """int64 [H,W] in 0..255: the guide Y = (77 R + 150 G + 29 B + 128) >> 8 of the egress bytes of the fp16 [3,H,W] frame"""
+    from .steady import source_bytes
+    b = source_bytes(source).astype(np.int64)
+    return (77 * b[0] + 150 * b[1] + 29 * b[2] + 128) >> 8
+
+
+def edge_coefficients(P: np.ndarray, Y: np.ndarray, radius: int, eps: float) -> Tuple[np.ndarray, np.ndarray]:
+    """(A, B) int64 [H,W], both inside int32 (asserted): stage 1 of `edge_ref` on the integer planes P and Y in 0..255"""
+    from .steady import window_sum
+    r = int(radius)
+    n = (2 * r + 1) ** 2
+    P, Y = np.asarray(P).astype(np.int64), np.asarray(Y).astype(np.int64)
+    S_I, S_P, S_II, S_IP = (window_sum(v, r) for v in (Y, P, Y * Y, Y * P))
+    cov, var = n * S_IP - S_I * S_P, n * S_II - S_I * S_I
+    assert int(np.abs(cov).max()) < 1 << 33 and 0 <= int(var.min()) and int(var.max()) < 1 << 33
+    a = cov.astype(np.float64) / (var.astype(np.float64) + np.float64(edge_E(r, eps)))
+    A = np.rint(a * np.float64(EDGE_SHIFT))
+    prod = a * S_I.astype(np.float64)                       # (numpy: one multiplication, one subtraction, one division)
+    bc = (S_P.astype(np.float64) - prod) / np.float64(n)
+    B = np.rint(bc * np.float64(EDGE_SHIFT))
+    assert float(np.abs(A).max()) < 2.0 ** 31 and float(np.abs(B).max()) < 2.0 ** 31
+    return A.astype(np.int64), B.astype(np.int64)
+
+
+def edge_ref(m0, source, radius: int, eps: float) -> np.ndarray:
+    """L2D_OP_FRAME_MATTE_EDGE on the host: the fp32 [H,W] matte `m0` (`matte_ref` with feather 0: ramp and `keep` applied) and
+    the fp16 [3,H,W] `source` frame -> fp32 [H,W], the matte re-fitted by the frame (a guided filter with the frame's luma as
+    the guide).  P = rint(255 m0), Y = `guide_ref(source)`, n = (2r+1)^2; per pixel over the window (coordinates clamped)
+    cov = n S_IP - S_I S_P and var = n S_II - S_I S_I in exact integers, a = double(cov) / (double(var) + E), A = rint(4096 a),
+    bc = (double(S_P) - a double(S_I)) / double(n), B = rint(4096 bc); then Q = window_sum(A) Y + window_sum(B) in exact integers,
+    q = double(Q) / double(n 4096 255), m' = float32(min(max(q, 0), 1)).  A constant m0 comes back as float32(P / 255): an
+    all-near or all-far matte stays exactly 1 or 0."""
+    from .steady import window_sum
+    e = check_edge(radius, eps)
+    r = e["radius"]
+    n = (2 * r + 1) ** 2
+    m0 = np.asarray(m0, dtype=np.float32)
+    if m0.ndim != 2:
+        raise ValueError(f"edge_ref: expected one [H,W] matte, got {m0.shape}")
+    P = np.rint(m0 * np.float32(255.0)).astype(np.int64)
+    Y = guide_ref(source)
+    if Y.shape != P.shape:
+        raise ValueError(f"edge_ref: the matte is {P.shape}, the source frame {Y.shape}")
+    assert 0 <= int(P.min()) and int(P.max()) <= 255
+    A, B = edge_coefficients(P, Y, r, e["eps"])
+    Q = window_sum(A, r) * Y + window_sum(B, r)
+    q = Q.astype(np.float64) / np.float64(n * EDGE_SHIFT * 255)
+    return np.minimum(np.maximum(q, 0.0), 1.0).astype(np.float32)
 
 
 def _unit(x) -> np.ndarray:
@@ -94,12 +179,14 @@ def _unit(x) -> np.ndarray:
     return (x * 0.5 + 0.5).clamp(0, 1).permute(0, 2, 3, 1).float().numpy()
 
 
-def composite_ref(styled, source, depth, lo: float, hi: float, feather: int = 0, keep: str = "near", show: bool = False) -> np.ndarray:
+def composite_ref(styled, source, depth, lo: float, hi: float, feather: int = 0, keep: str = "near", show: bool = False, *,
+                  edge: Optional[dict] = None) -> np.ndarray:
     """L2D_OP_FRAME_MATTE on the host: fp16 [B,3,H,W] `styled` and `source` in [-1, 1] + fp16 [B,H,W] `depth` -> uint8 [B,H,W,3].
     o = v_c + m (v_s - v_c) in three fp32 operations, byte = round_half_even(255 o); `show` writes round_half_even(255 m) to all
     three channels.  Both v are multiples of 2^-24 in [0, 1], so v_s - v_c is exact: m == 1 gives the bytes of
-    `egress_ref(styled)` and m == 0 those of `egress_ref(source)`, whatever the feather radius."""
-    m = matte_ref(depth, lo, hi, feather, keep)[..., None]
+    `egress_ref(styled)` and m == 0 those of `egress_ref(source)`, whatever the feather radius.  `edge` ({radius, eps}): the matte
+    refined by `source` first (`edge_ref`)."""
+    m = matte_ref(depth, lo, hi, feather, keep, edge=edge, source=source if edge is not None else None)[..., None]
     scale = np.float32(255.0)
     if show:
         return np.rint(np.repeat(m, 3, axis=-1) * scale).astype(np.uint8)
@@ -152,12 +239,14 @@ def matte_up_ref(m: np.ndarray, out_height: int, out_width: int) -> np.ndarray:
 
 
 def composite_up_ref(styled_u8, camera_u8, depth, lo: float, hi: float, feather: int = 0, keep: str = "near",
-                     show: bool = False) -> np.ndarray:
+                     show: bool = False, *, edge: Optional[dict] = None, source=None) -> np.ndarray:
     """L2D_OP_FRAME_MATTE_UP on the host: uint8 [B,Ho,Wo,3] `styled_u8` (the styled frame at the output size) and `camera_u8` (the
     camera's own pixels at that size) + fp16 [B,H,W] `depth` -> uint8 [B,Ho,Wo,3].  M = matte_up_ref(matte_ref(depth, ...)),
     o = C + M (S - C) on the bytes as fp32 -- S - C is exact, then one multiplication and one addition --, byte =
     round_half_even(o); `show` writes round_half_even(255 M) to all three channels.  Rounding is monotone and 0 <= M <= 1, so o
-    lies between C and S and nothing is clamped (asserted); M == 1 gives S and M == 0 gives C exactly."""
+    lies between C and S and nothing is clamped (asserted); M == 1 gives S and M == 0 gives C exactly.  `edge` ({radius, eps},
+    with the stream-sized fp16 [B,3,H,W] `source` frames): the matte is refined at the stream's size (`edge_ref`) and sampled
+    as before."""
     def u8(x):
         x = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
         if x.dtype != np.uint8 or x.ndim not in (3, 4) or x.shape[-1] != 3:
@@ -167,7 +256,7 @@ def composite_up_ref(styled_u8, camera_u8, depth, lo: float, hi: float, feather:
     S, C = u8(styled_u8), u8(camera_u8)
     if S.shape != C.shape:
         raise ValueError(f"composite_up_ref: the styled frame is {S.shape}, the camera frame {C.shape}")
-    M = matte_up_ref(matte_ref(depth, lo, hi, feather, keep), S.shape[1], S.shape[2])[..., None]
+    M = matte_up_ref(matte_ref(depth, lo, hi, feather, keep, edge=edge, source=source), S.shape[1], S.shape[2])[..., None]
     assert M.shape[0] == S.shape[0] and float(M.min()) >= 0.0 and float(M.max()) <= 1.0
     if show:
         return np.rint(np.repeat(M, 3, axis=-1) * np.float32(255.0)).astype(np.uint8)
@@ -300,6 +389,25 @@ class MatteLine:
 
 
 # ----------------------------------------------------------------------------- the device side
+class HipMatteEdge:
+    """The static fp32 plane and the launch of the edge-aware matte of one `(H, W)` stream: `op` is the record of
+    L2D_OP_FRAME_MATTE_EDGE for a `MatteLine` slot, which the composites put in front of their own launch with the plane in place
+    of the depth plane.  Nothing is zeroed: every launch writes the whole plane."""
+
+    def __init__(self, height: int, width: int, device="cuda:0"):
+        if width % 8 or height < 1 or 3 * height * width >= 1 << 31:
+            raise ValueError(f"HipMatteEdge: width {width} must be a multiple of 8, height {height} at least 1 and 3 H W below 2^31")
+        self.height, self.width, self.device = int(height), int(width), torch.device(device)
+        self.plane = torch.empty(self.height, self.width, dtype=torch.float32, device=self.device)
+
+    def op(self, slot: "_Slot", settings: dict, edge: dict):
+        """(record, tensors to keep): `slot.source` and `slot.depth` under the matte `settings` and the `edge` setting -> `plane`"""
+        e = check_edge(edge["radius"], edge["eps"])
+        lo32, inv32, hard = matte_params(settings["lo"], settings["hi"])
+        return ops.frame_matte_edge(slot.source, slot.depth, self.plane, H=self.height, W=self.width, r=e["radius"],
+                                    E=edge_E(e["radius"], e["eps"]), lo32=lo32, inv32=inv32, hard=hard, far=settings["keep"] == "far")
+
+
 class HipMatte:
     """Static output buffers and the launch of one `(H, W)` stream: `composite` is `HipFrameIO.egress` with a source frame and a
     depth plane beside the image.  Everything runs on `torch.cuda.current_stream()`."""
@@ -310,19 +418,29 @@ class HipMatte:
         self.height, self.width, self.device = int(height), int(width), torch.device(device)
         self.dev = torch.empty(1, self.height, self.width, 3, dtype=torch.uint8, device=self.device)
         self.host = None if ops.DRY_RUN else torch.empty(1, self.height, self.width, 3, dtype=torch.uint8).pin_memory()
+        self.edge = None                       # HipMatteEdge, made by the first frame with an edge setting
 
-    def composite(self, image: torch.Tensor, slot: _Slot, settings: dict, to_host: bool = True):
+    def composite(self, image: torch.Tensor, slot: _Slot, settings: dict, to_host: bool = True, edge: Optional[dict] = None):
         """fp16 [3,H,W] on the device + a `MatteLine` slot -> uint8 [H,W,3]: a numpy view of the pinned buffer (valid until the next
-        call), or with `to_host=False` the static device tensor"""
+        call), or with `to_host=False` the static device tensor.  `edge` ({radius, eps}): the matte refined by the slot's source
+        frame first -- one more launch in front, and the composite reads its plane."""
         H, W = self.height, self.width
         if image.dtype != torch.float16 or tuple(image.shape) != (3, H, W):
             raise ValueError(f"composite: expected fp16 [3,{H},{W}], got {image.dtype} {tuple(image.shape)}")
         if not image.is_contiguous():
             image = image.contiguous()
-        lo32, inv32, hard = matte_params(settings["lo"], settings["hi"])
-        op, keep = ops.frame_matte(image, slot.source, slot.depth, self.dev, B=1, H=H, W=W, lo32=lo32, inv32=inv32, hard=hard,
-                                   far=settings["keep"] == "far", show=settings["show"], r=settings["feather"])
         pl = _lib.OpList()
+        if edge is not None:
+            if self.edge is None:
+                self.edge = HipMatteEdge(H, W, device=self.device)
+            op, keep = self.edge.op(slot, settings, edge)
+            pl.append(op, *keep)
+            op, keep = ops.frame_matte(image, slot.source, None, self.dev, B=1, H=H, W=W, show=settings["show"], r=settings["feather"],
+                                       plane=self.edge.plane)
+        else:
+            lo32, inv32, hard = matte_params(settings["lo"], settings["hi"])
+            op, keep = ops.frame_matte(image, slot.source, slot.depth, self.dev, B=1, H=H, W=W, lo32=lo32, inv32=inv32, hard=hard,
+                                       far=settings["keep"] == "far", show=settings["show"], r=settings["feather"])
         pl.append(op, *keep)
         pl.run()
         if not to_host:
@@ -343,20 +461,30 @@ class HipMatteUp:
                             for n_in, n_out in ((self.width, self.out_width), (self.height, self.out_height)))
         self.dev = torch.empty(1, self.out_height, self.out_width, 3, dtype=torch.uint8, device=self.device)
         self.host = None if ops.DRY_RUN else torch.empty(1, self.out_height, self.out_width, 3, dtype=torch.uint8).pin_memory()
+        self.edge = None                       # HipMatteEdge, made by the first frame with an edge setting
 
-    def composite(self, styled_u8: torch.Tensor, slot: _Slot, settings: dict, to_host: bool = True):
+    def composite(self, styled_u8: torch.Tensor, slot: _Slot, settings: dict, to_host: bool = True, edge: Optional[dict] = None):
         """uint8 [Ho,Wo,3] on the device + a `MatteLine` slot that carries a camera buffer -> uint8 [Ho,Wo,3]: a numpy view of the
-        pinned buffer (valid until the next call), or with `to_host=False` the static device tensor"""
+        pinned buffer (valid until the next call), or with `to_host=False` the static device tensor.  `edge` ({radius, eps}): the
+        matte refined at the stream's size by the slot's stream-sized source frame first, then sampled as before."""
         Ho, Wo = self.out_height, self.out_width
         camera = slot.camera.data
         for name, t in (("styled", styled_u8), ("camera", camera)):
             if t.dtype != torch.uint8 or tuple(t.shape) != (Ho, Wo, 3) or not t.is_contiguous():
                 raise ValueError(f"composite: expected a contiguous uint8 [{Ho},{Wo},3] {name} frame, got {t.dtype} {tuple(t.shape)}")
-        lo32, inv32, hard = matte_params(settings["lo"], settings["hi"])
-        op, keep = ops.frame_matte_up(styled_u8, camera, slot.depth, self.dev, self.tx, self.ty, B=1, H=self.height, W=self.width,
-                                      Ho=Ho, Wo=Wo, lo32=lo32, inv32=inv32, hard=hard, far=settings["keep"] == "far",
-                                      show=settings["show"], r=settings["feather"])
         pl = _lib.OpList()
+        if edge is not None:
+            if self.edge is None:
+                self.edge = HipMatteEdge(self.height, self.width, device=self.device)
+            op, keep = self.edge.op(slot, settings, edge)
+            pl.append(op, *keep)
+            op, keep = ops.frame_matte_up(styled_u8, camera, None, self.dev, self.tx, self.ty, B=1, H=self.height, W=self.width, Ho=Ho,
+                                          Wo=Wo, show=settings["show"], r=settings["feather"], plane=self.edge.plane)
+        else:
+            lo32, inv32, hard = matte_params(settings["lo"], settings["hi"])
+            op, keep = ops.frame_matte_up(styled_u8, camera, slot.depth, self.dev, self.tx, self.ty, B=1, H=self.height, W=self.width,
+                                          Ho=Ho, Wo=Wo, lo32=lo32, inv32=inv32, hard=hard, far=settings["keep"] == "far",
+                                          show=settings["show"], r=settings["feather"])
         pl.append(op, *keep)
         pl.run()
         if not to_host:

@@ -1425,25 +1425,67 @@ def weight_blend(table_dev, table_host, weights, *, nt=None):
 # ----------------------------------------------------------------------------- depth matte (matte.hip, matte.py)
 MATTE_HARD, MATTE_FAR, MATTE_SHOW = 1, 2, 4      # l2d.h L2D_MATTE_*
 MATTE_MAX_R = 8                                  # l2d.h L2D_MATTE_MAX_R
+MATTE_PLANE = 16                                 # l2d.h L2D_MATTE_PLANE
+MATTE_EDGE_MAX_R = 8                             # l2d.h L2D_MATTE_EDGE_MAX_R
 
 
-def frame_matte(styled, source, depth, dst, *, B, H, W, lo32, inv32, hard, far=False, show=False, r=0, depth_stride=None):
+def _matte_plane(name, plane, B, H, W, stride):
+    """the `plane=` operand of `frame_matte` / `frame_matte_up`: fp32 matte values in place of the depth planes"""
+    if plane.dtype != torch.float32 or not plane.is_contiguous() or plane.numel() < (B - 1) * stride + H * W:
+        raise ValueError(f"{name}: plane must be a contiguous float32 tensor of at least {(B - 1) * stride + H * W} elements, got "
+                         f"{plane.dtype} {tuple(plane.shape)}")
+
+
+def frame_matte(styled, source, depth, dst, *, B, H, W, lo32=0.0, inv32=0.0, hard=False, far=False, show=False, r=0, depth_stride=None,
+                plane=None):
     """fp16 [B,3,H,W] styled / source + fp16 depth planes ([B,H,W], or channel 0 of a [B,3,H,W] tensor with `depth_stride=3 H W`)
     -> uint8 [B,H,W,3]: the egress bytes of `styled` over those of `source` by the depth matte (matte.composite_ref);
-    `lo32, inv32, hard` as `matte.matte_params` returns them."""
-    assert styled.dtype == source.dtype == depth.dtype == torch.float16 and dst.dtype == torch.uint8
+    `lo32, inv32, hard` as `matte.matte_params` returns them.  `plane` (fp32 [B,H,W], with `depth=None`): ready matte values in
+    place of the depth planes, as `frame_matte_edge` writes them; the ramp, `hard` and `far` do not apply."""
+    assert styled.dtype == source.dtype == torch.float16 and dst.dtype == torch.uint8
     stride = H * W if depth_stride is None else int(depth_stride)
     assert styled.numel() >= B * 3 * H * W and source.numel() >= B * 3 * H * W and dst.numel() >= B * H * W * 3
-    assert depth.numel() >= (B - 1) * stride + H * W
+    if plane is not None:
+        if depth is not None or hard or far:
+            raise ValueError("frame_matte: plane= goes with depth=None, and without hard / far (the plane carries them)")
+        _matte_plane("frame_matte", plane, B, H, W, stride)
+        depth, lo32, inv32 = plane, 0.0, 0.0
+    else:
+        assert depth.dtype == torch.float16 and depth.numel() >= (B - 1) * stride + H * W
     op = L2dOp()
     op.kind = _lib.OP_FRAME_MATTE
     op.p[0], op.p[1], op.p[2], op.p[3] = _ptr(styled), _ptr(source), _ptr(depth), _ptr(dst)
-    flags = (MATTE_HARD if hard else 0) | (MATTE_FAR if far else 0) | (MATTE_SHOW if show else 0)
+    flags = ((MATTE_HARD if hard else 0) | (MATTE_FAR if far else 0) | (MATTE_SHOW if show else 0)
+             | (MATTE_PLANE if plane is not None else 0))
     for j, v in enumerate([B, H, W, r, flags]):
         op.i[j] = int(v)
     op.l[0] = stride
     op.f[0], op.f[1] = float(lo32), float(inv32)
     return op, (styled, source, depth, dst)
+
+
+def frame_matte_edge(source, depth, out, *, H, W, r, E, lo32, inv32, hard, far=False):
+    """fp16 [3,H,W] `source` + fp16 [H,W] `depth` -> fp32 [H,W] `out`: the matte of `frame_matte` in front of its feather, refined
+    by the source frame (matte.edge_ref).  `r`: the radius, 1..MATTE_EDGE_MAX_R; `E`: `matte.edge_E(r, eps)`, a Python float;
+    `lo32, inv32, hard` as `matte.matte_params` returns them."""
+    _lock_frame("frame_matte_edge: source", source, H, W)
+    if depth.dtype != torch.float16 or depth.numel() != H * W or not depth.is_contiguous():
+        raise ValueError(f"frame_matte_edge: depth: expected a contiguous fp16 [{H},{W}] plane, got {depth.dtype} {tuple(depth.shape)}")
+    if out.dtype != torch.float32 or out.numel() != H * W or not out.is_contiguous():
+        raise ValueError(f"frame_matte_edge: out: expected a contiguous float32 [{H},{W}] plane, got {out.dtype} {tuple(out.shape)}")
+    if isinstance(r, bool) or int(r) != r or not 1 <= int(r) <= MATTE_EDGE_MAX_R:
+        raise ValueError(f"frame_matte_edge: r={r!r}: use an integer from 1 to {MATTE_EDGE_MAX_R}")
+    op = L2dOp()
+    op.kind = _lib.OP_FRAME_MATTE_EDGE
+    keep = (source, depth, out)
+    for j, t in enumerate(keep):
+        op.p[j] = _ptr(t)
+    flags = (MATTE_HARD if hard else 0) | (MATTE_FAR if far else 0)
+    for j, v in enumerate([H, W, r, flags]):
+        op.i[j] = int(v)
+    op.l[0] = int(np.float64(E).view(np.int64))                                              # the bits of the double
+    op.f[0], op.f[1] = float(lo32), float(inv32)
+    return op, keep
 
 
 # ----------------------------------------------------------------------------- colour lock (colorlock.hip, color_lock.py)
@@ -1540,16 +1582,23 @@ def frame_resize(src, dst, tx, ty, *, B, H, W, Ho, Wo, src_pitch=None):
     return op, (src, dst, tx, ty)
 
 
-def frame_matte_up(styled, camera, depth, dst, tx, ty, *, B, H, W, Ho, Wo, lo32, inv32, hard, far=False, show=False, r=0,
-                   depth_stride=None):
+def frame_matte_up(styled, camera, depth, dst, tx, ty, *, B, H, W, Ho, Wo, lo32=0.0, inv32=0.0, hard=False, far=False, show=False, r=0,
+                   depth_stride=None, plane=None):
     """uint8 [B,Ho,Wo,3] styled / camera + fp16 depth planes [B,H,W] (`depth_stride` as `frame_matte`'s) -> uint8 [B,Ho,Wo,3]: the
     styled bytes over the camera's by the depth matte sampled at the output size (matte.composite_up_ref); `tx`, `ty`: int32
-    [3, n_out] tables of the two axes as `matte.up_table` returns them (i0, i1, the bits of f)"""
-    assert styled.dtype == camera.dtype == dst.dtype == torch.uint8 and depth.dtype == torch.float16
+    [3, n_out] tables of the two axes as `matte.up_table` returns them (i0, i1, the bits of f).  `plane` (fp32 [B,H,W], with
+    `depth=None`): as `frame_matte`'s."""
+    assert styled.dtype == camera.dtype == dst.dtype == torch.uint8
     stride = H * W if depth_stride is None else int(depth_stride)
     n = B * Ho * Wo * 3
     assert styled.numel() >= n and camera.numel() >= n and dst.numel() >= n
-    assert depth.numel() >= (B - 1) * stride + H * W
+    if plane is not None:
+        if depth is not None or hard or far:
+            raise ValueError("frame_matte_up: plane= goes with depth=None, and without hard / far (the plane carries them)")
+        _matte_plane("frame_matte_up", plane, B, H, W, stride)
+        depth, lo32, inv32 = plane, 0.0, 0.0
+    else:
+        assert depth.dtype == torch.float16 and depth.numel() >= (B - 1) * stride + H * W
     for name, t, n_out in (("tx", tx, Wo), ("ty", ty, Ho)):
         if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != 3 * n_out:
             raise ValueError(f"frame_matte_up: {name} must be a contiguous int32 table of 3 x {n_out} elements, got {t.dtype} "
@@ -1559,7 +1608,8 @@ def frame_matte_up(styled, camera, depth, dst, tx, ty, *, B, H, W, Ho, Wo, lo32,
     keep = (styled, camera, depth, dst, tx, ty)
     for j, t in enumerate(keep):
         op.p[j] = _ptr(t)
-    flags = (MATTE_HARD if hard else 0) | (MATTE_FAR if far else 0) | (MATTE_SHOW if show else 0)
+    flags = ((MATTE_HARD if hard else 0) | (MATTE_FAR if far else 0) | (MATTE_SHOW if show else 0)
+             | (MATTE_PLANE if plane is not None else 0))
     for j, v in enumerate([B, H, W, Ho, Wo, r, flags]):
         op.i[j] = int(v)
     op.l[0] = stride

@@ -21,6 +21,7 @@ device (jpeg_io.HipJpegDecoder) and ingested there like a uint8 frame (`jpeg_dec
 with Pillow's arithmetic, behind both and in front of the JPEG encoder or the copy to the host (resize.py).
 `set_matte_source("camera")` composites the matte at the output size over the camera's own pixels (matte.HipMatteUp).
 `set_steady` holds the previous output pixel where the frame's source did not move (steady.py), behind the colour lock.
+`set_matte_edge` refines the matte by the source frame, so that its edges land on the frame's own (matte.edge_ref).
 
 Every frame leaves through one chain, `_route`: colour lock, then steady (`_finish`, in front of it) -> matte composite, or egress -> resize
 -> JPEG encoder, or copy to the host.  A stage that is not set is not in the chain; on the device each stage is one launch that
@@ -286,6 +287,7 @@ class StreamAnimateDiffusionDepthWrapper:
     _matte_source = "stream"                # what the kept real part of a matted, resized frame is made of (set_matte_source)
     _camera = None                          # resize.CameraTap, while "camera", a matte and an output size are all set on the device
     _matte_up = None                        # matte.HipMatteUp of the current output size, made by the first frame that needs it
+    _matte_edge = None                      # the edge-aware matte's settings (set_matte_edge), None: off
 
     def __init__(self, config_path: str, few_step_model_type: str, num_inference_steps: int,
                  t_index_list: Optional[List[int]] = None, strength: Optional[float] = None,
@@ -297,7 +299,8 @@ class StreamAnimateDiffusionDepthWrapper:
                  use_denoising_batch: bool = True, cfg_type: str = "none", seed: int = 42,
                  engine_dir: Optional[Union[str, Path]] = "engines", opt_unet: bool = False, frame_pipelining: bool = False,
                  jpeg_quality: int = 75, jpeg_decode: str = "device", output_size: Optional[Tuple[int, int]] = None,
-                 output_resample: str = "lanczos", matte_source: str = "stream", steady: Optional[dict] = None):
+                 output_resample: str = "lanczos", matte_source: str = "stream", steady: Optional[dict] = None,
+                 matte_edge: Optional[dict] = None):
         self._check_keywords(few_step_model_type=few_step_model_type, acceleration=acceleration, cfg_type=cfg_type,
                              use_denoising_batch=use_denoising_batch, frame_buffer_size=frame_buffer_size, device_ids=device_ids,
                              opt_unet=opt_unet, output_type=output_type, dtype=dtype, jpeg_quality=jpeg_quality, jpeg_decode=jpeg_decode)
@@ -317,13 +320,13 @@ class StreamAnimateDiffusionDepthWrapper:
                     similar_image_filter_threshold=similar_image_filter_threshold,
                     similar_image_filter_max_skip_frame=similar_image_filter_max_skip_frame, jpeg_quality=jpeg_quality,
                     jpeg_decode=jpeg_decode, output_size=output_size, output_resample=output_resample, matte_source=matte_source,
-                    steady=steady)
+                    steady=steady, matte_edge=matte_edge)
 
     @classmethod
     def from_components(cls, pipe, *, num_inference_steps: int, t_index_list: Optional[List[int]] = None,
                         strength: Optional[float] = None, **kw):
         """The wrapper around an already assembled `pipe` namespace (tests, synthetic weights).  Keywords: those of the
-        constructor that do not name files (`jpeg_quality`, `jpeg_decode`, `output_size`, `output_resample`, `matte_source` and `steady` among them), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
+        constructor that do not name files (`jpeg_quality`, `jpeg_decode`, `output_size`, `output_resample`, `matte_source`, `steady` and `matte_edge` among them), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
         self = cls.__new__(cls)
         cls._check_keywords(**{k: kw.pop(k) for k in ("acceleration", "cfg_type", "use_denoising_batch", "frame_buffer_size",
                                                       "device_ids", "opt_unet", "few_step_model_type") if k in kw},
@@ -363,10 +366,12 @@ class StreamAnimateDiffusionDepthWrapper:
                width=512, height=512, do_add_noise=True, seed=42, clip_skip=1, warmup_frames=8, window_size=16,
                scheduler_kwargs=None, frame_pipelining=False, enable_similar_image_filter=False,
                similar_image_filter_threshold=0.98, similar_image_filter_max_skip_frame=10, jpeg_quality=75, jpeg_decode="device",
-               output_size=None, output_resample="lanczos", matte_source="stream", steady=None):
+               output_size=None, output_resample="lanczos", matte_source="stream", steady=None, matte_edge=None):
         self._check_matte_source(matte_source)
         if steady is not None and not isinstance(steady, dict):
             raise ValueError(f"steady={steady!r}: use a dict of set_steady's keywords, or None")
+        if matte_edge is not None and not isinstance(matte_edge, dict):
+            raise ValueError(f"matte_edge={matte_edge!r}: use a dict of set_matte_edge's keywords, or None")
         self.sd_turbo = False
         self.device = pipe.device if device is None else device
         self.dtype, self.width, self.height = dtype, width, height
@@ -404,6 +409,8 @@ class StreamAnimateDiffusionDepthWrapper:
         self.set_matte_source(matte_source)
         if steady is not None:
             self.set_steady(**steady)
+        if matte_edge is not None:
+            self.set_matte_edge(**matte_edge)
 
     # ------------------------------------------------------------------ depth matte (matte.py)
     @property
@@ -467,6 +474,34 @@ class StreamAnimateDiffusionDepthWrapper:
         self._check_matte_source(source)
         self._matte_source = source
         self._sync_camera()
+
+    # ------------------------------------------------------------------ edge-aware matte
+    @property
+    def matte_edge(self) -> Optional[dict]:
+        """the current edge setting as {radius, eps}, or None"""
+        return None if self._matte_edge is None else dict(self._matte_edge)
+
+    def set_matte_edge(self, radius: int = 4, eps: float = 10.0) -> None:
+        """Refine the matte by the frame it cuts.  The depth map is soft and its edges sit a few pixels beside the object's;
+        with this setting the matte (ramp and `keep` applied, in front of the feather) is re-fitted in every (2 radius + 1)^2
+        window as a linear function of the source frame's luma -- a guided filter, `matte.edge_ref` --, so that its edges land
+        where the frame's own edges are.  `radius` 1..8 pixels: how far an edge may move; `eps` >= 1 in byte levels: the
+        contrast of the frame below which a window counts as flat and the matte is only smoothed there.  An all-near or
+        all-far matte stays exactly that.  A setting beside the matte, like `set_matte_source`: it acts only while a matte is
+        set, on its output types, and `matte` keeps its five keys.  One more launch on the device in front of the composite's,
+        no synchronisation; `feather` and `show` apply to the refined matte; with `set_matte_source("camera")` the matte is
+        refined at the stream's size by the stream-sized source frame and then sampled at the output size as before.  A frame
+        the near-duplicate filter repeats is refined again from the same slot: the same bytes.  May be called before or after
+        `prepare` and between any two frames; the change applies from the next output."""
+        from .matte import check_edge
+        self._matte_edge = check_edge(radius, eps)
+
+    def clear_matte_edge(self) -> None:
+        """Back to the matte as the depth map gives it: no launch or buffer of the refinement is left in the frame's path."""
+        self._matte_edge = None
+        for dev in (self._matte_dev, self._matte_up):
+            if dev is not None:
+                dev.edge = None
 
     def _sync_camera(self) -> None:
         """Install the camera tap (`HipFrameIO.camera_tap`, `MatteLine.camera_source`) while "camera", a matte and an output
@@ -976,9 +1011,10 @@ class StreamAnimateDiffusionDepthWrapper:
             stages = []
             if camera:
                 stages.append(self._size_op(size, dev).resize)
-                stages.append(functools.partial(self._matte_up_op(size, dev).composite, slot=slot, settings=self._matte))
+                stages.append(functools.partial(self._matte_up_op(size, dev).composite, slot=slot, settings=self._matte,
+                                                edge=self._matte_edge))
             elif slot is not None:
-                stages.append(functools.partial(self._matte_op(dev).composite, slot=slot, settings=self._matte))
+                stages.append(functools.partial(self._matte_op(dev).composite, slot=slot, settings=self._matte, edge=self._matte_edge))
             if size is not None and not camera:
                 stages.append(self._size_op(size, dev).resize)
             if not stages and to_host:
@@ -993,7 +1029,7 @@ class StreamAnimateDiffusionDepthWrapper:
         else:
             if slot is not None:
                 from .matte import composite_ref
-                u8 = composite_ref(image_tensor[:1], slot.source[None], slot.depth[None], **self._matte)[0]
+                u8 = composite_ref(image_tensor[:1], slot.source[None], slot.depth[None], **self._matte, edge=self._matte_edge)[0]
             else:
                 from .frame_io import egress_ref
                 u8 = egress_ref(image_tensor)[0].numpy()

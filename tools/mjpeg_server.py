@@ -44,7 +44,13 @@ answers the current one as a JSON string.
 `--steady LO,HI[,STRENGTH[,RADIUS]]` holds the previous output pixel where the frame's source did not move
 (`wrapper.set_steady`: one small launch on the device behind the colour lock; LO and HI are byte levels of the locally averaged
 motion).  `POST /steady` with the same text as its body, or `off`, changes it while the stream runs; `GET /steady` answers the
-current settings as JSON (`null`: off)."""
+current settings as JSON (`null`: off).
+
+`--matte-edge R[,EPS]` refines the matte by the frame it cuts, so that its edges land on the frame's own edges
+(`wrapper.set_matte_edge`: a guided filter of radius R in 1..8 pixels, one more launch in front of the composite; EPS, default
+10, is the contrast in byte levels below which a window counts as flat).  It acts only while a matte is set.  `POST /matte-edge`
+with the same text as its body, or `off`, changes it while the stream runs; `GET /matte-edge` answers the current settings as
+JSON (`null`: off)."""
 import argparse
 import json
 import os
@@ -290,6 +296,54 @@ class SteadyBox:
             self.failed += 1
 
 
+def parse_matte_edge_arg(text: str):
+    """`R[,EPS]` -> the keywords of `wrapper.set_matte_edge`, `off` -> None; ValueError otherwise"""
+    from live2diff_amd.matte import MAX_EDGE_RADIUS, check_edge
+    text = text.strip()
+    if text == "off":
+        return None
+    parts = [t.strip() for t in text.split(",")]
+    if not 1 <= len(parts) <= 2:
+        raise ValueError(f"matte edge {text!r}: use R[,EPS] or off")
+    try:
+        radius = int(parts[0])
+        eps = float(parts[1]) if len(parts) > 1 else 10.0
+    except ValueError:
+        raise ValueError(f"matte edge {text!r}: R is an integer from 1 to {MAX_EDGE_RADIUS}, EPS a number of byte levels, at least "
+                         "1") from None
+    return check_edge(radius, eps)
+
+
+class MatteEdgeBox:
+    """What `POST /matte-edge` delivers: the newest requested edge setting (a dict of `set_matte_edge` keywords, or None for
+    `off`), applied by the producer between two frames.  `current` is what was last applied; `failed` counts requests the wrapper
+    refused."""
+    _NOTHING = object()
+
+    def __init__(self, current=None):
+        self._lock = threading.Lock()
+        self.current, self._want, self.failed = current, self._NOTHING, 0
+
+    def put(self, settings) -> None:
+        with self._lock:
+            self._want = settings
+
+    def apply(self, wrapper) -> None:
+        """(producer thread, between frames)"""
+        with self._lock:
+            want, self._want = self._want, self._NOTHING
+        if want is self._NOTHING:
+            return
+        try:
+            if want is None:
+                wrapper.clear_matte_edge()
+            else:
+                wrapper.set_matte_edge(want["radius"], want["eps"])
+            self.current = wrapper.matte_edge
+        except ValueError:
+            self.failed += 1
+
+
 def parse_size_arg(text: str):
     """`WxH[,FILTER]` -> the keywords of `wrapper.set_output_size`, `off` -> None; ValueError otherwise (the wrapper, which knows
     the stream's size, checks the ratio once more)"""
@@ -416,8 +470,8 @@ class Latest:
 
 
 def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = None, mattes: "MatteBox" = None, colors: "ColorBox" = None,
-                 sizes: "SizeBox" = None, sources: "MatteSourceBox" = None, steadies: "SteadyBox" = None):
-    boxes = {"/matte": mattes, "/color": colors, "/size": sizes, "/matte-source": sources, "/steady": steadies}
+                 sizes: "SizeBox" = None, sources: "MatteSourceBox" = None, steadies: "SteadyBox" = None, edges: "MatteEdgeBox" = None):
+    boxes = {"/matte": mattes, "/color": colors, "/size": sizes, "/matte-source": sources, "/steady": steadies, "/matte-edge": edges}
     page = PAGE if inbox is None else CAMERA_PAGE
 
     class Handler(BaseHTTPRequestHandler):
@@ -523,6 +577,9 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
             if self.path == "/steady" and steadies is not None:
                 self.do_matte(steadies, parse_steady_arg)
                 return
+            if self.path == "/matte-edge" and edges is not None:
+                self.do_matte(edges, parse_matte_edge_arg)
+                return
             if inbox is None or self.path != "/frame":
                 self.send_error(404)
                 return
@@ -546,9 +603,10 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
 
 
 def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: StyleBox = None, mattes: MatteBox = None,
-            colors: ColorBox = None, sizes: SizeBox = None, sources: MatteSourceBox = None, steadies: SteadyBox = None) -> None:
+            colors: ColorBox = None, sizes: SizeBox = None, sources: MatteSourceBox = None, steadies: SteadyBox = None,
+            edges: MatteEdgeBox = None) -> None:
     """the producer: loops `frames` through the wrapper until `stop` is set; a posted style, matte, colour lock, output size,
-    matte source or steady mode is applied between two frames"""
+    matte source, steady mode or matte edge is applied between two frames"""
     from live2diff_amd.jpeg import mjpeg_part
     try:
         i = 0
@@ -565,6 +623,8 @@ def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: Styl
                 sources.apply(wrapper)
             if steadies is not None:
                 steadies.apply(wrapper)
+            if edges is not None:
+                edges.apply(wrapper)
             latest.put(mjpeg_part(wrapper(frames[i % len(frames)])))
             i += 1
     finally:
@@ -573,7 +633,7 @@ def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: Styl
 
 def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: threading.Event, styles: StyleBox = None,
                    mattes: MatteBox = None, colors: ColorBox = None, sizes: SizeBox = None, sources: MatteSourceBox = None,
-                   steadies: SteadyBox = None) -> None:
+                   steadies: SteadyBox = None, edges: MatteEdgeBox = None) -> None:
     """the producer of `--input post`: the first frames posted warm the stream up, then the newest posted frame goes through the
     wrapper, for ever; a frame the wrapper refuses (ValueError: a damaged file) is dropped and counted in `inbox.failed`"""
     from live2diff_amd.jpeg import mjpeg_part
@@ -598,6 +658,8 @@ def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: thr
                 sources.apply(wrapper)
             if steadies is not None:
                 steadies.apply(wrapper)
+            if edges is not None:
+                edges.apply(wrapper)
             try:
                 latest.put(mjpeg_part(wrapper(frame)))
             except ValueError:
@@ -637,12 +699,17 @@ def main(argv=None):
                     help="hold the previous output pixel where the source moved by LO byte levels or less (moving from HI on), by "
                          "STRENGTH (default 0.8), the motion averaged over a radius of RADIUS pixels (default 2); POST /steady with "
                          "the same text, or `off`, changes it between frames")
+    ap.add_argument("--matte-edge", default=None, metavar="R[,EPS]",
+                    help="refine the matte by the frame it cuts (a guided filter of radius R, 1..8 pixels; EPS, default 10: the contrast in "
+                         "byte levels below which a window counts as flat); acts while a matte is set; POST /matte-edge with the same "
+                         "text, or `off`, changes it between frames")
     args = ap.parse_args(argv)
     style_args = [parse_style_arg(t) for t in args.style]
     matte = parse_matte_arg(args.matte) if args.matte else None
     color = parse_color_arg(args.color_lock) if args.color_lock else None
     size = parse_size_arg(args.output_size) if args.output_size else None
     steady = parse_steady_arg(args.steady) if args.steady else None
+    edge = parse_matte_edge_arg(args.matte_edge) if args.matte_edge else None
 
     from stream_frames import read_frames
 
@@ -672,15 +739,18 @@ def main(argv=None):
     if steady is not None:
         w.set_steady(steady["lo"], steady["hi"], strength=steady["strength"], radius=steady["radius"])      # (before `prepare` too)
     steadies = SteadyBox(w.steady)
+    if edge is not None:
+        w.set_matte_edge(edge["radius"], edge["eps"])
+    edges = MatteEdgeBox(w.matte_edge)
     prompt = args.prompt if args.prompt is not None else str(cfg.get("prompt", ""))
     latest, stop = Latest(), threading.Event()
     inbox = Inbox(sink) if post else None
     if post:
-        producer = threading.Thread(target=produce_posted, args=(w, prompt, inbox, latest, stop, styles, mattes, colors, sizes, sources, steadies), name="producer", daemon=True)
+        producer = threading.Thread(target=produce_posted, args=(w, prompt, inbox, latest, stop, styles, mattes, colors, sizes, sources, steadies, edges), name="producer", daemon=True)
     else:
         w.prepare(frames[:sink], prompt)
-        producer = threading.Thread(target=produce, args=(w, frames, latest, stop, styles, mattes, colors, sizes, sources, steadies), name="producer", daemon=True)
-    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest, inbox, styles, mattes, colors, sizes, sources, steadies))
+        producer = threading.Thread(target=produce, args=(w, frames, latest, stop, styles, mattes, colors, sizes, sources, steadies, edges), name="producer", daemon=True)
+    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest, inbox, styles, mattes, colors, sizes, sources, steadies, edges))
     server.daemon_threads = True
     producer.start()
     print(f"http://{args.host}:{args.port}/  ({args.height}x{args.width}, quality {args.quality}; Ctrl-C stops)")
