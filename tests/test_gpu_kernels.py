@@ -1,4 +1,7 @@
 """-m gpu: every HIP kernel, called through the C ABI (libl2d_hip.so), against fp32 references.
+(The igemm tests here launch pipeline variants 5 and 1, token-tile-major order and whichever epilogue the shape's alignment gives --
+the references round once whichever that is; every variant, both orders and both epilogues, each against its own rounding, per element:
+test_gpu_gemm_envelope.py.)
 
 Tolerances (fp16 storage, fp32 accumulate): per-op rel-L2 <= 2e-3 against the fp32 reference evaluated on the
 SAME fp16-rounded inputs.  Nothing here reads /root/reference.
@@ -117,7 +120,10 @@ def test_igemm_swapped_batched(L):
 @pytest.mark.parametrize("fused", [False, True])
 def test_igemm_splitk(L, M, K, N, S, tile, fused):
     """fused: the last-arriving block of a tile reduces the S partial tiles (fixed order) and runs the epilogue -- one launch;
-    otherwise the separate reduction launch of round 1.  Both must leave the same bits on repeated runs."""
+    otherwise the separate reduction launch of round 1.  Both must leave the same bits on repeated runs.
+    Which epilogue: ldr = round_up(N + 2, 4) is never a multiple of 8 for these N, so BOTH forms end in the direct epilogue
+    (igemm_epilogue(): residual added in fp32, one rounding) -- the kernel's `vec` condition needs ldr % 8 == 0.  The fused reduction in
+    front of the LDS-staged epilogue (what the plan launches) is run per element by test_gpu_gemm_envelope.py::test_igemm_splitk."""
     x = rnd(M, K, seed=1)
     w = rnd(N, K, seed=2, scale=K ** -0.5)
     b = rnd(N, seed=3).float()

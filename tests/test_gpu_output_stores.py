@@ -140,7 +140,8 @@ def test_rowgemm_transposed_v_stores(L):
 # ----------------------------------------------------------------------------------------------------- wsgemm.hip
 @pytest.mark.parametrize("S", [1, 2])
 def test_wsgemm_row_stores(L, S):
-    """M 128, N 64, K 128, whole-row stores behind the direct (S = 1) and the split-K (S = 2) epilogue"""
+    """M 128, N 64, K 128, whole-row stores of the unsplit launch (S = 1) and behind the split-K reduction (S = 2); wsgemm has one
+    epilogue, the LDS-staged one (fp16 tile, residual added in fp16)"""
     M, K, N = 128, 128, 64
     x, w, b, r = rnd(M, K, seed=1), rnd(N, K, seed=2, scale=K ** -0.5), rnd(N, seed=3).float(), rnd(M, N, seed=4)
     ref = (x.float() @ w.float().t() + b).half().float() + r.float()
@@ -245,7 +246,8 @@ def test_pconv_stores(L):
 
 @pytest.mark.parametrize("C,sched", [(64, (1, 4, 1, 1)), (128, (1, 4, 1, 2))])
 def test_cconv_stores(L, C, sched):
-    """B 1, H 8, W 16, N 64: the staged tile behind the direct and the split-K epilogue (S = 2 needs two 64-channel chunks: C 128)"""
+    """B 1, H 8, W 16, N 64: the staged tile of the unsplit launch and behind the split-K reduction (S = 2 needs two 64-channel chunks:
+    C 128); cconv has one epilogue, the LDS-staged one"""
     N = 64
     CG, KG, NLD, S = sched
     B, H, W, x, w, b, r, ref = _conv_case(C, N)
