@@ -431,6 +431,37 @@ enum {
  *   Refused: a null pointer (p2 / p3 only with INIT, p6 only without SHOW), a misaligned one, W % 8 != 0, 3 H W >= 2^31, r
  *   outside 0..L2D_STEADY_MAX_R, unknown flags, p4 (or p6) overlapping p0, p1, p2 or one another, p5 overlapping p3, a
  *   non-finite or negative lo / inv, s outside [0, 1].
+ *
+ * Detail mode (detail.hip; no counterpart in the reference): the camera's fine detail in the frame at the output size, by the
+ *   regression-based detail injection of pan-sharpening.  The styled frame is the low-resolution colour image, the camera's luma
+ *   at the output size the high-resolution band, the gain the local regression slope of each styled channel on the source
+ *   frame's luma (stage 1 of L2D_OP_FRAME_MATTE_EDGE's guided filter).  Exact integers and individually rounded operations, no
+ *   fma, so that numpy restates both ops bit for bit (live2diff_amd/detail.py gains_ref, inject_ref).
+ * L2D_OP_FRAME_DETAIL_GAIN  one launch:  p0 the frame L2D_OP_FRAME_RESIZE is about to read, half [3][H][W] (mapped to bytes with
+ *   L2D_OP_FRAME_EGRESS' expression first) or, with L2D_DETAIL_U8, uint8 [H][W][3] p1 source half [3][H][W] p2 out int32 [3][H][W]
+ *   (all 16-byte aligned) ; i0 H i1 W (W % 8 == 0, 3 H W < 2^31) i2 r (1..L2D_MATTE_EDGE_MAX_R) i3 flags (L2D_DETAIL_U8) ; l0 the
+ *   BITS of the double E = double(n n) eps eps, as L2D_OP_FRAME_MATTE_EDGE's.  P[c] = the bytes of channel c of p0; Y = (77 R +
+ *   150 G + 29 B + 128) >> 8 of L2D_OP_FRAME_EGRESS' bytes of p1; S_I, S_II, S_P, S_IP the sums of Y, Y Y, P, Y P over the
+ *   (2r+1) x (2r+1) window, coordinates clamped to the image; cov = n S_IP - S_I S_P and var = n S_II - S_I S_I in int64;
+ *   a = double(cov) / (double(var) + E); A = rint(4096 a) (|A| <= 261120); out[c] = the window sum of A, coordinates clamped:
+ *   n 4096 times the mean gain, |out| <= 261120 n < 2^31.  One work-group per 16 x 64 tile; Y and the three P planes of the tile
+ *   and a halo of 2r as bytes in LDS; S_I and S_II are formed once, S_P, S_IP, A and its sums channel by channel through one
+ *   set of row-sum buffers.  Every element of p2 is written by a plain store on every launch: nothing has to be zeroed.
+ *   Refused: a null or misaligned pointer, W % 8 != 0, 3 H W >= 2^31, r outside 1..L2D_MATTE_EDGE_MAX_R, unknown flags, an E
+ *   that is not finite or below n n.
+ * L2D_OP_FRAME_DETAIL  one launch:  p0 S, the styled frame at the output size p1 C, the camera's own pixels at that size p2 L, the
+ *   source frame through the resize S went through (all uint8 [Ho][Wo][3], any alignment) p3 G int32 [3][H][W], p2 of
+ *   L2D_OP_FRAME_DETAIL_GAIN p4 table of the x axis p5 table of the y axis (int32, 4-byte aligned, as L2D_OP_FRAME_MATTE_UP's) p6
+ *   dst uint8 [Ho][Wo][3] (any alignment; overlapping none of p0..p2) ; i0 H i1 W i2 Ho i3 Wo i4 flags (L2D_DETAIL_SHOW) ; f0
+ *   k = float(strength / (n 4096)) f1 limit (byte levels).  luma(x) = (77 R + 150 G + 29 B + 128) >> 8; d = luma(C) - luma(L);
+ *   g = the bilinear taps of float(G[c]): a_y = g[y][x0] + fx (g[y][x1] - g[y][x0]) on rows y0 and y1, a_y0 + fy (a_y1 - a_y0);
+ *   t = g float(d); u = t k; u = min(max(u, -limit), limit); o = min(max(float(S) + u, 0), 255); byte = rint(o), half to even,
+ *   every step one fp32 operation.  SHOW writes rint(min(max(128 + u, 0), 255)) per channel and does not read p0.  C == L, k == 0
+ *   and G == 0 each give p0's bytes; |byte - S| <= ceil(limit).  One work-group per 32 x 32 output tile, the gains its taps
+ *   reach staged in LDS as floats.  What the kernel reads from a table is clamped to the image, to the tile's patch and to
+ *   [0, 1].  Only bytes of [dst, dst + Ho Wo 3) are written, by plain stores (whole dwords where the address allows, bytes at
+ *   the ends of a row).  Refused: a null pointer, Ho, Wo outside 1..L2D_RESIZE_MAX_SIZE or outside [n_in / 2, 8 n_in], Ho Wo 3 or
+ *   3 H W >= 2^31, misaligned tables or G, unknown flags, a limit or k that is not finite or negative, dst overlapping an input.
  */
 enum {
     L2D_OP_IGEMM = 1,
@@ -482,6 +513,8 @@ enum {
     L2D_OP_FRAME_MATTE_UP = 47,
     L2D_OP_FRAME_STEADY = 48,
     L2D_OP_FRAME_MATTE_EDGE = 49,
+    L2D_OP_FRAME_DETAIL_GAIN = 50,
+    L2D_OP_FRAME_DETAIL = 51,
 };
 
 /* flag bits of L2D_OP_FRAME_MATTE (i4) and L2D_OP_FRAME_MATTE_UP (i6); HARD and FAR also of L2D_OP_FRAME_MATTE_EDGE (i3) */
@@ -504,6 +537,10 @@ enum {
 #define L2D_STEADY_SHOW 2
 #define L2D_STEADY_INIT 4
 #define L2D_STEADY_MAX_R 8
+
+/* flag bits of L2D_OP_FRAME_DETAIL_GAIN (i3: U8) and L2D_OP_FRAME_DETAIL (i4: SHOW) */
+#define L2D_DETAIL_U8 1 /* p0 is the uint8 [H][W][3] frame of the matte, not the half frame */
+#define L2D_DETAIL_SHOW 2
 
 /* sizes of L2D_OP_FRAME_RESIZE */
 #define L2D_RESIZE_MAX_KS 13 /* taps per output: Lanczos (support 3) at a 2x down-scale, 2 * 6 + 1 */

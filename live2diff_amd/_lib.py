@@ -32,6 +32,7 @@ OP_FRAME_RESIZE = 46
 OP_FRAME_MATTE_UP = 47
 OP_FRAME_STEADY = 48
 OP_FRAME_MATTE_EDGE = 49
+OP_FRAME_DETAIL_GAIN, OP_FRAME_DETAIL = 50, 51
 ABI_VERSION = 6
 
 

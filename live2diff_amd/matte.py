@@ -302,7 +302,7 @@ class MatteLine:
     `prime` (called by `prepare`) clears the line and fills the N - 1 positions behind the first frame with the last warm-up
     frame and its depth.  That is a definition, not parity: the reference's first N - 1 outputs come from zeroed latent rows and
     correspond to no frame at all.  A line that starts mid-stream has no such positions: `take` then returns the oldest entry
-    it has.
+    it has, and `last_own` is False -- the slot is another frame's, which the detail mode (detail.py) does not sharpen with.
 
     Slots in use: the N - 1 frames behind the newest taken one, the one taken last, and the tapped-but-not-taken frames of
     push / pop mode.  The ring grows when a caller pushes deeper than before; in steady state nothing is allocated.
@@ -328,6 +328,7 @@ class MatteLine:
         self.tapped = 0                        # accepted frames copied in
         self.taken = 0                         # outputs composited
         self.last: Optional[_Slot] = None
+        self.last_own = False                  # `last` is the slot of the output's own frame, not the oldest entry in its place
         self._last_id = None
 
     def _free_slot(self) -> int:
@@ -379,6 +380,7 @@ class MatteLine:
         k = self.taken
         self.taken += 1
         idx = max(k - (self.n - 1), self._first) - self._first
+        self.last_own = k - (self.n - 1) >= self._first
         self._last_id = self._hist[idx]
         self.last = self.slots[self._last_id]
         keep_from = self.taken - (self.n - 1)               # what the next take may still ask for

@@ -1654,3 +1654,66 @@ def frame_steady(styled, source, prev_out, prev_bytes, out, next_bytes, *, H, W,
         op.i[j] = int(v)
     op.f[0], op.f[1], op.f[2] = float(lo32), float(inv32), float(s32)
     return op, keep
+
+
+# ----------------------------------------------------------------------------- detail mode (detail.hip, detail.py)
+DETAIL_U8, DETAIL_SHOW = 1, 2                        # l2d.h L2D_DETAIL_*
+DETAIL_MAX_GAIN = 261120                             # |A| = |rint(4096 a)| with |a| <= 127.5 / 2 (eps >= 1): detail.hip states it
+
+
+def frame_detail_gain(frame, source, out, *, H, W, r, E):
+    """the frame the resize reads -- fp16 [3,H,W] (its egress bytes) or uint8 [H,W,3] (the matte's frame) -- + the fp16 [3,H,W]
+    `source` frame -> int32 [3,H,W] `out`: per channel n 4096 times the mean over the window of the regression slope of the
+    frame's bytes on the source frame's luma (detail.gains_ref).  `r`: the radius, 1..MATTE_EDGE_MAX_R; `E`:
+    `matte.edge_E(r, eps)`, a Python float."""
+    u8 = frame.dtype == torch.uint8
+    if u8:
+        if tuple(frame.shape[-3:]) != (H, W, 3) or frame.numel() != 3 * H * W or not frame.is_contiguous():
+            raise ValueError(f"frame_detail_gain: frame: expected a contiguous uint8 [{H},{W},3] frame, got {tuple(frame.shape)}")
+    else:
+        _lock_frame("frame_detail_gain: frame", frame, H, W)
+    _lock_frame("frame_detail_gain: source", source, H, W)
+    if out.dtype != torch.int32 or tuple(out.shape[-3:]) != (3, H, W) or out.numel() != 3 * H * W or not out.is_contiguous():
+        raise ValueError(f"frame_detail_gain: out: expected contiguous int32 [3,{H},{W}] planes, got {out.dtype} {tuple(out.shape)}")
+    if isinstance(r, bool) or int(r) != r or not 1 <= int(r) <= MATTE_EDGE_MAX_R:
+        raise ValueError(f"frame_detail_gain: r={r!r}: use an integer from 1 to {MATTE_EDGE_MAX_R}")
+    op = L2dOp()
+    op.kind = _lib.OP_FRAME_DETAIL_GAIN
+    keep = (frame, source, out)
+    for j, t in enumerate(keep):
+        op.p[j] = _ptr(t)
+    for j, v in enumerate([H, W, r, DETAIL_U8 if u8 else 0]):
+        op.i[j] = int(v)
+    op.l[0] = int(np.float64(E).view(np.int64))                                              # the bits of the double
+    return op, keep
+
+
+def frame_detail(styled, camera, low, gains, tx, ty, dst, *, H, W, Ho, Wo, k, limit, show=False):
+    """uint8 [Ho,Wo,3] `styled` (S), `camera` (C) and `low` (L: the source frame through S's resize) + the int32 [3,H,W] `gains`
+    of `frame_detail_gain` -> uint8 [Ho,Wo,3] `dst`: S + clamp(g (luma(C) - luma(L)) k, +-limit) with g the gains sampled
+    bilinearly (detail.inject_ref).  `tx`, `ty`: int32 [3, n_out] tables as `matte.table_words` builds them; `k`:
+    float32(strength / (n 4096)); `show` writes 128 + the injected term."""
+    for name, t in (("styled", styled), ("camera", camera), ("low", low), ("dst", dst)):
+        if t.dtype != torch.uint8 or tuple(t.shape[-3:]) != (Ho, Wo, 3) or t.numel() != Ho * Wo * 3 or not t.is_contiguous():
+            raise ValueError(f"frame_detail: {name}: expected a contiguous uint8 [{Ho},{Wo},3] frame, got {t.dtype} {tuple(t.shape)}")
+    if gains.dtype != torch.int32 or tuple(gains.shape[-3:]) != (3, H, W) or gains.numel() != 3 * H * W or not gains.is_contiguous():
+        raise ValueError(f"frame_detail: gains: expected contiguous int32 [3,{H},{W}] planes, got {gains.dtype} {tuple(gains.shape)}")
+    for name, t, n_out in (("tx", tx, Wo), ("ty", ty, Ho)):
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != 3 * n_out:
+            raise ValueError(f"frame_detail: {name} must be a contiguous int32 table of 3 x {n_out} elements, got {t.dtype} "
+                             f"{tuple(t.shape)}")
+    for name, t in (("styled", styled), ("camera", camera), ("low", low)):
+        if t.data_ptr() == dst.data_ptr():
+            raise ValueError(f"frame_detail: dst may not be the {name} frame")
+    k, limit = float(k), float(limit)
+    if not (np.isfinite(k) and k >= 0.0 and np.isfinite(limit) and limit >= 0.0):
+        raise ValueError(f"frame_detail: k={k!r} and limit={limit!r} must be finite and not negative")
+    op = L2dOp()
+    op.kind = _lib.OP_FRAME_DETAIL
+    keep = (styled, camera, low, gains, tx, ty, dst)
+    for j, t in enumerate(keep):
+        op.p[j] = _ptr(t)
+    for j, v in enumerate([H, W, Ho, Wo, DETAIL_SHOW if show else 0]):
+        op.i[j] = int(v)
+    op.f[0], op.f[1] = k, limit
+    return op, keep

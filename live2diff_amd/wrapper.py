@@ -22,9 +22,10 @@ with Pillow's arithmetic, behind both and in front of the JPEG encoder or the co
 `set_matte_source("camera")` composites the matte at the output size over the camera's own pixels (matte.HipMatteUp).
 `set_steady` holds the previous output pixel where the frame's source did not move (steady.py), behind the colour lock.
 `set_matte_edge` refines the matte by the source frame, so that its edges land on the frame's own (matte.edge_ref).
+`set_detail` brings the camera's fine detail into the frame at the output size, behind the resize (detail.py).
 
 Every frame leaves through one chain, `_route`: colour lock, then steady (`_finish`, in front of it) -> matte composite, or egress -> resize
--> JPEG encoder, or copy to the host.  A stage that is not set is not in the chain; on the device each stage is one launch that
+-> detail -> JPEG encoder, or copy to the host.  A stage that is not set is not in the chain; on the device each stage is one launch that
 hands its static buffer to the next, and only the last one copies to the host.
 """
 import functools
@@ -288,6 +289,8 @@ class StreamAnimateDiffusionDepthWrapper:
     _camera = None                          # resize.CameraTap, while "camera", a matte and an output size are all set on the device
     _matte_up = None                        # matte.HipMatteUp of the current output size, made by the first frame that needs it
     _matte_edge = None                      # the edge-aware matte's settings (set_matte_edge), None: off
+    _detail = None                          # the detail mode's settings (set_detail), None: off
+    _detail_dev = None                      # detail.HipDetail of the current output size, made by the first frame that needs it
 
     def __init__(self, config_path: str, few_step_model_type: str, num_inference_steps: int,
                  t_index_list: Optional[List[int]] = None, strength: Optional[float] = None,
@@ -300,7 +303,7 @@ class StreamAnimateDiffusionDepthWrapper:
                  engine_dir: Optional[Union[str, Path]] = "engines", opt_unet: bool = False, frame_pipelining: bool = False,
                  jpeg_quality: int = 75, jpeg_decode: str = "device", output_size: Optional[Tuple[int, int]] = None,
                  output_resample: str = "lanczos", matte_source: str = "stream", steady: Optional[dict] = None,
-                 matte_edge: Optional[dict] = None):
+                 matte_edge: Optional[dict] = None, detail: Optional[dict] = None):
         self._check_keywords(few_step_model_type=few_step_model_type, acceleration=acceleration, cfg_type=cfg_type,
                              use_denoising_batch=use_denoising_batch, frame_buffer_size=frame_buffer_size, device_ids=device_ids,
                              opt_unet=opt_unet, output_type=output_type, dtype=dtype, jpeg_quality=jpeg_quality, jpeg_decode=jpeg_decode)
@@ -320,13 +323,13 @@ class StreamAnimateDiffusionDepthWrapper:
                     similar_image_filter_threshold=similar_image_filter_threshold,
                     similar_image_filter_max_skip_frame=similar_image_filter_max_skip_frame, jpeg_quality=jpeg_quality,
                     jpeg_decode=jpeg_decode, output_size=output_size, output_resample=output_resample, matte_source=matte_source,
-                    steady=steady, matte_edge=matte_edge)
+                    steady=steady, matte_edge=matte_edge, detail=detail)
 
     @classmethod
     def from_components(cls, pipe, *, num_inference_steps: int, t_index_list: Optional[List[int]] = None,
                         strength: Optional[float] = None, **kw):
         """The wrapper around an already assembled `pipe` namespace (tests, synthetic weights).  Keywords: those of the
-        constructor that do not name files (`jpeg_quality`, `jpeg_decode`, `output_size`, `output_resample`, `matte_source`, `steady` and `matte_edge` among them), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
+        constructor that do not name files (`jpeg_quality`, `jpeg_decode`, `output_size`, `output_resample`, `matte_source`, `steady`, `matte_edge` and `detail` among them), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
         self = cls.__new__(cls)
         cls._check_keywords(**{k: kw.pop(k) for k in ("acceleration", "cfg_type", "use_denoising_batch", "frame_buffer_size",
                                                       "device_ids", "opt_unet", "few_step_model_type") if k in kw},
@@ -366,12 +369,14 @@ class StreamAnimateDiffusionDepthWrapper:
                width=512, height=512, do_add_noise=True, seed=42, clip_skip=1, warmup_frames=8, window_size=16,
                scheduler_kwargs=None, frame_pipelining=False, enable_similar_image_filter=False,
                similar_image_filter_threshold=0.98, similar_image_filter_max_skip_frame=10, jpeg_quality=75, jpeg_decode="device",
-               output_size=None, output_resample="lanczos", matte_source="stream", steady=None, matte_edge=None):
+               output_size=None, output_resample="lanczos", matte_source="stream", steady=None, matte_edge=None, detail=None):
         self._check_matte_source(matte_source)
         if steady is not None and not isinstance(steady, dict):
             raise ValueError(f"steady={steady!r}: use a dict of set_steady's keywords, or None")
         if matte_edge is not None and not isinstance(matte_edge, dict):
             raise ValueError(f"matte_edge={matte_edge!r}: use a dict of set_matte_edge's keywords, or None")
+        if detail is not None and not isinstance(detail, dict):
+            raise ValueError(f"detail={detail!r}: use a dict of set_detail's keywords, or None")
         self.sd_turbo = False
         self.device = pipe.device if device is None else device
         self.dtype, self.width, self.height = dtype, width, height
@@ -411,6 +416,8 @@ class StreamAnimateDiffusionDepthWrapper:
             self.set_steady(**steady)
         if matte_edge is not None:
             self.set_matte_edge(**matte_edge)
+        if detail is not None:
+            self.set_detail(**detail)
 
     # ------------------------------------------------------------------ depth matte (matte.py)
     @property
@@ -504,18 +511,19 @@ class StreamAnimateDiffusionDepthWrapper:
                 dev.edge = None
 
     def _sync_camera(self) -> None:
-        """Install the camera tap (`HipFrameIO.camera_tap`, `MatteLine.camera_source`) while "camera", a matte and an output
-        size are all set on the device route, rebuilt when the size or the filter changed; otherwise take it out and drop every
-        camera buffer, so that nothing of the feature stays in the frame's path."""
+        """Install the camera tap (`HipFrameIO.camera_tap`, `MatteLine.camera_source`) while an output size is set on the device
+        route and either "camera" with a matte or the detail mode wants it, rebuilt when the size or the filter changed;
+        otherwise take it out and drop every camera buffer, so that nothing of the two features stays in the frame's path."""
         io, line, size = getattr(self, "io", None), self._matte_line, self._size
-        want = self._matte_source == "camera" and self._matte is not None and size is not None and io is not None and line is not None
+        want = (((self._matte_source == "camera" and self._matte is not None) or self._detail is not None)
+                and size is not None and io is not None and line is not None)
         key = (size["height"], size["width"], size["resample"]) if want else None
         if want and self._camera is not None and self._camera.key == key:
             tap = self._camera
         else:
             if line is not None:
                 line.drop_cameras()
-            self._matte_up = None
+            self._matte_up = self._detail_dev = None
             tap = None
             if want:
                 from .resize import CameraTap
@@ -529,12 +537,13 @@ class StreamAnimateDiffusionDepthWrapper:
     def _camera_slot(self, slot, image_tensor) -> bool:
         """does this output frame take the composite at the output size?"""
         tap = self._camera
-        return (tap is not None and slot is not None and slot.camera is not None and slot.camera.key == tap.key
+        return (tap is not None and self._matte_source == "camera" and self._matte is not None and slot is not None
+                and slot.camera is not None and slot.camera.key == tap.key
                 and self.io is not None and torch.is_tensor(image_tensor) and image_tensor.is_cuda)
 
     def _need_line(self) -> None:
-        """The delay line of source frames and depth planes, shared by the matte, the colour lock to "source" and the steady
-        mode: made by whichever needs it first.  Outputs of frames pushed before it existed have no slot (`_matte_skip`)."""
+        """The delay line of source frames and depth planes, shared by the matte, the colour lock to "source", the steady mode
+        and the detail mode: made by whichever needs it first.  Outputs of frames pushed before it existed have no slot (`_matte_skip`)."""
         if self._matte_line is None:
             from .matte import MatteLine
             self._matte_line = MatteLine(self.batch_size, self.height, self.width, device=self.stream.device)
@@ -542,8 +551,9 @@ class StreamAnimateDiffusionDepthWrapper:
             self._matte_skip = len(getattr(self.stream, "_pending", None) or ())
 
     def _release_line(self) -> None:
-        """drop the delay line when neither the matte, a colour lock to "source" nor the steady mode needs it"""
-        if self._matte is None and self._steady is None and (self._lock is None or self._lock["mode"] != "source"):
+        """drop the delay line when neither the matte, a colour lock to "source", the steady mode nor the detail mode needs it"""
+        if (self._matte is None and self._steady is None and self._detail is None
+                and (self._lock is None or self._lock["mode"] != "source")):
             self._matte_line = None
             self._matte_skip = 0
             self.stream.matte_tap = None
@@ -700,7 +710,7 @@ class StreamAnimateDiffusionDepthWrapper:
         """`postprocess_image` of a frame while a colour lock, the steady mode, a matte or an output size is set: the lock
         first, then steady, then the rest of the chain (`_route`) on that frame.  A frame that is no tensor is neither locked
         nor steadied and raises there."""
-        from . import color_lock, matte, resize, steady
+        from . import color_lock, detail, matte, resize, steady
         if self._lock is not None and torch.is_tensor(image_tensor):
             self._check_served(color_lock.SERVED_OUTPUT_TYPES, "locked", "clear_color_lock", "a colour lock")
             image_tensor = self._locked(image_tensor, slot, repeated)
@@ -711,12 +721,64 @@ class StreamAnimateDiffusionDepthWrapper:
             self._check_served(resize.SERVED_OUTPUT_TYPES, "resampled", "clear_output_size", "an output size")
         if self._matte is not None:
             self._check_served(matte.SERVED_OUTPUT_TYPES, "composited", "clear_matte", "a matte")
+        if self._detail is not None:
+            self._check_served(detail.SERVED_OUTPUT_TYPES, "given detail", "clear_detail", "the detail mode")
         if not torch.is_tensor(image_tensor):
             return self.postprocess_image(image_tensor, output_type=self.output_type)
         if self._size is not None and self.output_type == "jpeg":      # (callers assign `output_type` between frames)
             resize.check_jpeg_size(self._size["height"], self._size["width"])
+        detail_slot = slot if self._detail_slot(slot, image_tensor) else None
         slot = slot if self._matte is not None else None
-        return self._route(image_tensor, self.output_type, slot, self._size, camera=self._camera_slot(slot, image_tensor))
+        return self._route(image_tensor, self.output_type, slot, self._size, camera=self._camera_slot(slot, image_tensor),
+                           detail_slot=detail_slot)
+
+    # ------------------------------------------------------------------ detail mode (detail.py)
+    @property
+    def detail(self) -> Optional[dict]:
+        """the current detail mode as {radius, eps, strength, limit, show}, or None"""
+        return None if self._detail is None else dict(self._detail)
+
+    def set_detail(self, radius: int = 2, eps: float = 2.0, strength: float = 1.0, limit: float = 64.0, show: bool = False) -> None:
+        """Bring the camera's fine detail into the frame at the output size.  The resize gives 1080 lines made of the stream's
+        512; the camera frame at the output size holds what the stream-size bottleneck lost: d = luma(camera) - luma(source
+        frame through the same resize).  Per channel, d is added to the resized styled frame times a gain: the local
+        regression slope of the styled frame on the source frame's luma in every (2 radius + 1)^2 window of the stream's frame
+        (`radius` 1..8; `eps` >= 1 in byte levels: the contrast of the source below which a window counts as flat), averaged
+        over the window and sampled bilinearly at the output size (`detail.detail_ref`).  Where the style follows the camera's
+        structure its sub-pixel edges and texture come back in the style's own colours and polarity; where the style is flat
+        nothing is added.  `strength` in [0, 4] scales the injected term (0: the frame as it is), `limit` in [0, 255] bounds it
+        in byte levels, `show=True` returns 128 + the injected term (to choose `eps` by eye).  Three small launches on the
+        device behind the resize: the order on a frame is colour lock, steady, matte on the "stream" route, resize, detail,
+        the matte composite at the output size on the "camera" route, then the JPEG encoder or the copy to the host -- the
+        gains are always fitted on the bytes the resize reads.
+
+        The mode acts on an output frame only when an output size is set, the frame runs on the device route, and the frame
+        it is paired with came in as a uint8 frame or a JPEG file while the mode and the current output size were set (the
+        delay line's slot then carries its pixels).  Every other frame leaves exactly as without the mode -- float tensors,
+        PIL images and paths, frames from before the mode or the size was set, the frames `prepare` returns, and the host
+        route without a device.  That is the behaviour, not an error.  A frame the near-duplicate filter repeats is computed
+        again from the same slot: the same bytes.  May be called before or after `prepare` and between any two frames."""
+        from .detail import SERVED_OUTPUT_TYPES, check_settings
+        self._check_served(SERVED_OUTPUT_TYPES, "given detail", "clear_detail")
+        settings = check_settings(radius, eps, strength, limit, show)
+        self._need_line()
+        self._detail = settings
+        self._sync_camera()
+
+    def clear_detail(self) -> None:
+        """Back to the plain resize: no launch, buffer or camera tap of the mode is left in the frame's path.  (A matte with
+        `set_matte_source("camera")` keeps the tap, and the other users of the delay line keep the line.)"""
+        self._detail = self._detail_dev = None
+        self._release_line()
+        self._sync_camera()
+
+    def _detail_slot(self, slot, image_tensor) -> bool:
+        """does this output frame get the camera's detail?"""
+        tap, line = self._camera, self._matte_line
+        return (self._detail is not None and self._size is not None and tap is not None and slot is not None
+                and line is not None and line.last is slot and line.last_own      # (the slot of the output's own frame)
+                and slot.camera is not None and slot.camera.key == tap.key
+                and self.io is not None and torch.is_tensor(image_tensor) and image_tensor.is_cuda)
 
     # ------------------------------------------------------------------ output size (resize.py, DESIGN.md section 8.z6)
     @property
@@ -733,7 +795,7 @@ class StreamAnimateDiffusionDepthWrapper:
         Without a matte the launch takes the fp16 frame and replaces the egress launch; with one it takes the matte's uint8
         frame.  Resampling the composite is the whole feature: under a matte the kept real part of the picture is the
         UNet-sized source frame scaled up, not the camera's own pixels (`set_matte_source("camera")` keeps those instead), and
-        nothing is sharpened.  May be called before or after
+        nothing is sharpened (`set_detail` brings the camera's fine detail into the resized frame).  May be called before or after
         `prepare` and between any two frames: the change applies from the next output.  The frames `prepare` returns are not
         resized; a frame the near-duplicate filter dropped yields the bytes of the frame before it."""
         from .resize import SERVED_OUTPUT_TYPES, check_filter, check_jpeg_size, check_size
@@ -988,12 +1050,14 @@ class StreamAnimateDiffusionDepthWrapper:
             raise ValueError(f"Input for postprocessing is in incorrect format: {type(image_tensor)}. We only support pytorch tensor")
         return self._route(image_tensor, output_type)
 
-    def _route(self, image_tensor: torch.Tensor, output_type: str, slot=None, size: Optional[dict] = None, camera: bool = False):
+    def _route(self, image_tensor: torch.Tensor, output_type: str, slot=None, size: Optional[dict] = None, camera: bool = False,
+               detail_slot=None):
         """The one way out for a frame (fp16 [1,3,H,W] in [-1, 1], behind the colour lock and the steady mode when set): the matte's composite
         with `slot` (a `MatteLine` slot; None: no matte, or its line has seen no frame yet) or the egress bytes, resampled to
         `size` (the setting of `set_output_size`, or None), then the JPEG encoder or the copy to the host.  `camera` (the slot
         carries the camera's pixels at `size`, `_camera_slot`): the resize of the styled frame first, then the composite at the
-        output size, in place of those two stages.  On the device every
+        output size, in place of those two stages.  `detail_slot` (the frame's slot where the detail mode acts on it,
+        `_detail_slot`): the detail launches behind the resize, on the frame the resize read.  On the device every
         stage is one launch that hands its static device buffer to the next and only the last one copies to the host; the
         resize takes the fp16 frame itself, and so does the encoder, so neither has an egress launch in front of it.  The float
         output types leave as the reference's do."""
@@ -1009,19 +1073,30 @@ class StreamAnimateDiffusionDepthWrapper:
         elif self.io is not None and image_tensor.is_cuda:
             dev, to_host = image_tensor.device, output_type != "jpeg"
             stages = []
+            give_detail = None
+            if detail_slot is not None and size is not None:
+                give_detail = functools.partial(self._detail_op(size, dev).apply, slot=detail_slot, settings=self._detail)
             if camera:
                 stages.append(self._size_op(size, dev).resize)
+                if give_detail is not None:
+                    stages.append(give_detail)
                 stages.append(functools.partial(self._matte_up_op(size, dev).composite, slot=slot, settings=self._matte,
                                                 edge=self._matte_edge))
             elif slot is not None:
                 stages.append(functools.partial(self._matte_op(dev).composite, slot=slot, settings=self._matte, edge=self._matte_edge))
             if size is not None and not camera:
                 stages.append(self._size_op(size, dev).resize)
+                if give_detail is not None:
+                    stages.append(give_detail)
             if not stages and to_host:
                 stages.append(self.io.egress)
-            x = image_tensor[0]
+            x = before = image_tensor[0]
             for i, stage in enumerate(stages):
-                x = stage(x, to_host=to_host and i + 1 == len(stages))
+                last = to_host and i + 1 == len(stages)
+                if stage is give_detail:   # (it also takes the frame the resize in front of it read)
+                    x = stage(x, before, to_host=last)
+                else:
+                    before, x = x, stage(x, to_host=last)
             if to_host:
                 u8 = x.copy()              # (the pinned buffer is overwritten by the next frame)
             else:
@@ -1062,6 +1137,15 @@ class StreamAnimateDiffusionDepthWrapper:
             from .matte import HipMatteUp
             mu = self._matte_up = HipMatteUp(self.height, self.width, ho, wo, device=device)
         return mu
+
+    def _detail_op(self, size: dict, device):
+        """`detail.HipDetail` of an output size: rebuilt when the size or the filter changes, kept otherwise"""
+        ho, wo, resample = size["height"], size["width"], size["resample"]
+        dt = self._detail_dev
+        if dt is None or (dt.out_height, dt.out_width, dt.resample) != (ho, wo, resample):
+            from .detail import HipDetail
+            dt = self._detail_dev = HipDetail(self.height, self.width, ho, wo, resample, device=device)
+        return dt
 
     def _size_op(self, size: dict, device):
         """`resize.HipResize` of an output size: rebuilt when the size or the filter changes, kept otherwise"""

@@ -50,7 +50,14 @@ current settings as JSON (`null`: off).
 (`wrapper.set_matte_edge`: a guided filter of radius R in 1..8 pixels, one more launch in front of the composite; EPS, default
 10, is the contrast in byte levels below which a window counts as flat).  It acts only while a matte is set.  `POST /matte-edge`
 with the same text as its body, or `off`, changes it while the stream runs; `GET /matte-edge` answers the current settings as
-JSON (`null`: off)."""
+JSON (`null`: off).
+
+`--detail R[,EPS[,STRENGTH[,LIMIT]]]` brings the camera's fine detail into the frame at the output size (`wrapper.set_detail`: the
+camera frame's high-pass at the output size, added with the local regression slope of the styled frame on the source frame over
+windows of radius R in 1..8 pixels; EPS, default 2, is the contrast in byte levels below which a window counts as flat,
+STRENGTH, default 1, scales the injected term and LIMIT, default 64, bounds it in byte levels).  It acts only while an output
+size is set.  `POST /detail` with the same text as its body, or `off`, changes it while the stream runs; `GET /detail` answers
+the current settings as JSON (`null`: off)."""
 import argparse
 import json
 import os
@@ -344,6 +351,54 @@ class MatteEdgeBox:
             self.failed += 1
 
 
+def parse_detail_arg(text: str):
+    """`R[,EPS[,STRENGTH[,LIMIT]]]` -> the keywords of `wrapper.set_detail`, `off` -> None; ValueError otherwise"""
+    from live2diff_amd.detail import MAX_RADIUS, check_settings
+    text = text.strip()
+    if text == "off":
+        return None
+    parts = [t.strip() for t in text.split(",")]
+    if not 1 <= len(parts) <= 4:
+        raise ValueError(f"detail {text!r}: use R[,EPS[,STRENGTH[,LIMIT]]] or off")
+    try:
+        radius = int(parts[0])
+        eps, strength, limit = (float(parts[i]) if len(parts) > i else d for i, d in ((1, 2.0), (2, 1.0), (3, 64.0)))
+    except ValueError:
+        raise ValueError(f"detail {text!r}: R is an integer from 1 to {MAX_RADIUS}, EPS (at least 1), STRENGTH (0..4) and LIMIT "
+                         "(0..255) are numbers") from None
+    return check_settings(radius, eps, strength, limit)
+
+
+class DetailBox:
+    """What `POST /detail` delivers: the newest requested detail setting (a dict of `set_detail` keywords, or None for `off`),
+    applied by the producer between two frames.  `current` is what was last applied; `failed` counts requests the wrapper
+    refused."""
+    _NOTHING = object()
+
+    def __init__(self, current=None):
+        self._lock = threading.Lock()
+        self.current, self._want, self.failed = current, self._NOTHING, 0
+
+    def put(self, settings) -> None:
+        with self._lock:
+            self._want = settings
+
+    def apply(self, wrapper) -> None:
+        """(producer thread, between frames)"""
+        with self._lock:
+            want, self._want = self._want, self._NOTHING
+        if want is self._NOTHING:
+            return
+        try:
+            if want is None:
+                wrapper.clear_detail()
+            else:
+                wrapper.set_detail(**want)
+            self.current = wrapper.detail
+        except ValueError:
+            self.failed += 1
+
+
 def parse_size_arg(text: str):
     """`WxH[,FILTER]` -> the keywords of `wrapper.set_output_size`, `off` -> None; ValueError otherwise (the wrapper, which knows
     the stream's size, checks the ratio once more)"""
@@ -470,8 +525,10 @@ class Latest:
 
 
 def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = None, mattes: "MatteBox" = None, colors: "ColorBox" = None,
-                 sizes: "SizeBox" = None, sources: "MatteSourceBox" = None, steadies: "SteadyBox" = None, edges: "MatteEdgeBox" = None):
-    boxes = {"/matte": mattes, "/color": colors, "/size": sizes, "/matte-source": sources, "/steady": steadies, "/matte-edge": edges}
+                 sizes: "SizeBox" = None, sources: "MatteSourceBox" = None, steadies: "SteadyBox" = None, details: "DetailBox" = None,
+                 edges: "MatteEdgeBox" = None):
+    boxes = {"/matte": mattes, "/color": colors, "/size": sizes, "/matte-source": sources, "/steady": steadies, "/matte-edge": edges,
+             "/detail": details}
     page = PAGE if inbox is None else CAMERA_PAGE
 
     class Handler(BaseHTTPRequestHandler):
@@ -580,6 +637,9 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
             if self.path == "/matte-edge" and edges is not None:
                 self.do_matte(edges, parse_matte_edge_arg)
                 return
+            if self.path == "/detail" and details is not None:
+                self.do_matte(details, parse_detail_arg)
+                return
             if inbox is None or self.path != "/frame":
                 self.send_error(404)
                 return
@@ -604,9 +664,9 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
 
 def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: StyleBox = None, mattes: MatteBox = None,
             colors: ColorBox = None, sizes: SizeBox = None, sources: MatteSourceBox = None, steadies: SteadyBox = None,
-            edges: MatteEdgeBox = None) -> None:
+            details: DetailBox = None, edges: MatteEdgeBox = None) -> None:
     """the producer: loops `frames` through the wrapper until `stop` is set; a posted style, matte, colour lock, output size,
-    matte source, steady mode or matte edge is applied between two frames"""
+    matte source, steady mode, matte edge or detail mode is applied between two frames"""
     from live2diff_amd.jpeg import mjpeg_part
     try:
         i = 0
@@ -625,6 +685,8 @@ def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: Styl
                 steadies.apply(wrapper)
             if edges is not None:
                 edges.apply(wrapper)
+            if details is not None:
+                details.apply(wrapper)
             latest.put(mjpeg_part(wrapper(frames[i % len(frames)])))
             i += 1
     finally:
@@ -633,7 +695,7 @@ def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: Styl
 
 def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: threading.Event, styles: StyleBox = None,
                    mattes: MatteBox = None, colors: ColorBox = None, sizes: SizeBox = None, sources: MatteSourceBox = None,
-                   steadies: SteadyBox = None, edges: MatteEdgeBox = None) -> None:
+                   steadies: SteadyBox = None, details: DetailBox = None, edges: MatteEdgeBox = None) -> None:
     """the producer of `--input post`: the first frames posted warm the stream up, then the newest posted frame goes through the
     wrapper, for ever; a frame the wrapper refuses (ValueError: a damaged file) is dropped and counted in `inbox.failed`"""
     from live2diff_amd.jpeg import mjpeg_part
@@ -660,6 +722,8 @@ def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: thr
                 steadies.apply(wrapper)
             if edges is not None:
                 edges.apply(wrapper)
+            if details is not None:
+                details.apply(wrapper)
             try:
                 latest.put(mjpeg_part(wrapper(frame)))
             except ValueError:
@@ -703,6 +767,10 @@ def main(argv=None):
                     help="refine the matte by the frame it cuts (a guided filter of radius R, 1..8 pixels; EPS, default 10: the contrast in "
                          "byte levels below which a window counts as flat); acts while a matte is set; POST /matte-edge with the same "
                          "text, or `off`, changes it between frames")
+    ap.add_argument("--detail", default=None, metavar="R[,EPS[,STRENGTH[,LIMIT]]]",
+                    help="bring the camera's fine detail into the frame at the output size (windows of radius R, 1..8 pixels; EPS, default "
+                         "2: the contrast in byte levels below which a window counts as flat; STRENGTH, default 1; LIMIT, default 64 byte "
+                         "levels); acts while an output size is set; POST /detail with the same text, or `off`, changes it between frames")
     args = ap.parse_args(argv)
     style_args = [parse_style_arg(t) for t in args.style]
     matte = parse_matte_arg(args.matte) if args.matte else None
@@ -710,6 +778,7 @@ def main(argv=None):
     size = parse_size_arg(args.output_size) if args.output_size else None
     steady = parse_steady_arg(args.steady) if args.steady else None
     edge = parse_matte_edge_arg(args.matte_edge) if args.matte_edge else None
+    detail = parse_detail_arg(args.detail) if args.detail else None
 
     from stream_frames import read_frames
 
@@ -742,15 +811,18 @@ def main(argv=None):
     if edge is not None:
         w.set_matte_edge(edge["radius"], edge["eps"])
     edges = MatteEdgeBox(w.matte_edge)
+    if detail is not None:
+        w.set_detail(**detail)               # (before `prepare`: the line is primed, the first frames carry their camera frame)
+    details = DetailBox(w.detail)
     prompt = args.prompt if args.prompt is not None else str(cfg.get("prompt", ""))
     latest, stop = Latest(), threading.Event()
     inbox = Inbox(sink) if post else None
     if post:
-        producer = threading.Thread(target=produce_posted, args=(w, prompt, inbox, latest, stop, styles, mattes, colors, sizes, sources, steadies, edges), name="producer", daemon=True)
+        producer = threading.Thread(target=produce_posted, args=(w, prompt, inbox, latest, stop, styles, mattes, colors, sizes, sources, steadies, details, edges), name="producer", daemon=True)
     else:
         w.prepare(frames[:sink], prompt)
-        producer = threading.Thread(target=produce, args=(w, frames, latest, stop, styles, mattes, colors, sizes, sources, steadies, edges), name="producer", daemon=True)
-    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest, inbox, styles, mattes, colors, sizes, sources, steadies, edges))
+        producer = threading.Thread(target=produce, args=(w, frames, latest, stop, styles, mattes, colors, sizes, sources, steadies, details, edges), name="producer", daemon=True)
+    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest, inbox, styles, mattes, colors, sizes, sources, steadies, details, edges))
     server.daemon_threads = True
     producer.start()
     print(f"http://{args.host}:{args.port}/  ({args.height}x{args.width}, quality {args.quality}; Ctrl-C stops)")
