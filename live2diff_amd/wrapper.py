@@ -447,7 +447,7 @@ class StreamAnimateDiffusionDepthWrapper:
         """Back to the plain output route: no launch, copy or buffer of the matte is left in the frame's path, the camera
         buffers of `set_matte_source("camera")` included.  (A colour lock to "source" keeps the delay line it shares with the
         matte.)"""
-        self._matte = None
+        self._matte = self._matte_dev = self._matte_up = None
         self._release_line()
         self._sync_camera()
 
@@ -534,6 +534,16 @@ class StreamAnimateDiffusionDepthWrapper:
         if line is not None:
             line.camera_source = tap
 
+    def _camera_begin(self, image) -> None:
+        """In front of every frame: a camera buffer nobody claimed belongs to no later frame, and the tap sits out the ingest
+        of a frame that has no camera frame -- a path or a PIL image is resized on the host and reaches the ingest at the
+        stream's own size, as a uint8 array that the tap would otherwise take for a camera's."""
+        tap = self._camera
+        if tap is not None:
+            tap.begin()
+            host_sized = isinstance(image, (str, os.PathLike)) or (hasattr(image, "convert") and hasattr(image, "resize"))
+            self.io.camera_tap = None if host_sized else tap
+
     def _camera_slot(self, slot, image_tensor) -> bool:
         """does this output frame take the composite at the output size?"""
         tap = self._camera
@@ -575,7 +585,11 @@ class StreamAnimateDiffusionDepthWrapper:
         device in front of the egress launch, the matte or the JPEG encoder; under a matte the styled frame is locked before
         the composite, so the real part of the picture stays untouched.  Every output type but "latent" is served.  May be
         called before or after `prepare` and between any two frames; the frames `prepare` returns are not locked, and a frame
-        the near-duplicate filter dropped repeats the last locked frame without moving the average."""
+        the near-duplicate filter dropped repeats the last locked frame without moving the average (with no locked frame to
+        repeat, a drop directly behind this call, the repeated frame is locked as a frame of its own).  With `to="source"` the
+        output of a frame that entered the stream before the delay line existed is locked to the oldest entry the line has, as
+        the matte composites it with that entry; the mode keeps no state, so no later frame inherits anything from it (an
+        output with no slot at all, in push / pop mode, passes unlocked)."""
         from .color_lock import SERVED_OUTPUT_TYPES, check_settings
         self._check_served(SERVED_OUTPUT_TYPES, "locked", "clear_color_lock")
         settings = check_settings(to, strength, rate)
@@ -591,7 +605,7 @@ class StreamAnimateDiffusionDepthWrapper:
     def clear_color_lock(self) -> None:
         """Back to the unlocked output: no launch, copy or buffer of the lock is left in the frame's path.  (A matte keeps the
         delay line it shares with a lock to "source".)"""
-        self._lock = self._lock_ref = self._lock_state = self._lock_load = self._lock_last = None
+        self._lock = self._lock_dev = self._lock_ref = self._lock_state = self._lock_load = self._lock_last = None
         self._lock_init = True
         self._release_line()
 
@@ -656,7 +670,11 @@ class StreamAnimateDiffusionDepthWrapper:
         type but "latent" is served.  May be called before or after `prepare` and between any two frames; this call and
         `prepare` restart the sequence (the next frame passes as it is), the frames `prepare` returns are not touched, a frame
         the near-duplicate filter dropped repeats the last steadied frame without moving the state, and the output of a
-        frame that entered the stream before the delay line existed passes unchanged."""
+        frame that entered the stream before the delay line existed passes unchanged: the delay line has no slot of its own
+        for it (the matte composites it with the oldest entry the line has, another frame's), so the sequence has not started
+        yet -- the first output with a slot of its own is the init frame, and the state never holds another frame's source.
+        (A repeated frame with no steadied frame to repeat, a drop directly behind this call, is treated as a frame of its
+        own with the slot of the output before.)"""
         from .steady import SERVED_OUTPUT_TYPES, check_settings
         self._check_served(SERVED_OUTPUT_TYPES, "held steady", "clear_steady")
         settings = check_settings(lo, hi, strength, radius, show)
@@ -679,7 +697,10 @@ class StreamAnimateDiffusionDepthWrapper:
         st = self._steady
         if repeated and self._steady_last is not None:
             return self._steady_last
-        if slot is None:                   # (an output of a frame the delay line has not seen: the sequence starts behind it)
+        line = self._matte_line
+        if slot is None or (line is not None and line.last is slot and not line.last_own):
+            # an output of a frame the delay line has not seen -- no slot, or the oldest entry in its place, another frame's:
+            # the sequence starts behind it, and the state never holds a source that is not the output's own
             self._steady_init, self._steady_last = True, None
             return image_tensor
         if self.io is not None and image_tensor.is_cuda:
@@ -958,8 +979,7 @@ class StreamAnimateDiffusionDepthWrapper:
         [3,H,W] tensor in [0, 1] (the reference's input)."""
         if prompt is not None:
             self._update_prompt(prompt)
-        if self._camera is not None:
-            self._camera.begin()           # (a camera buffer nobody claimed belongs to no later frame)
+        self._camera_begin(image)
         line = self._matte_line
         if line is None and self._lock is None and self._size is None:
             return self.postprocess_image(self.stream(self.preprocess_image(image)), output_type=self.output_type)
@@ -978,8 +998,7 @@ class StreamAnimateDiffusionDepthWrapper:
         """pipelined mode (`frame_pipelining=True`): start a frame's encode / depth path; `pop()` returns the oldest frame's output"""
         if prompt is not None:
             self._update_prompt(prompt)
-        if self._camera is not None:
-            self._camera.begin()
+        self._camera_begin(image)
         self.stream.push(self.preprocess_image(image))
         if self.io is not None and self.io.last_view is not None:
             # push() ran the ingest on this stream before ordering the side stream behind it; the side stream reads the slot

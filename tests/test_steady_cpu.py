@@ -520,7 +520,57 @@ def test_wrapper_without_steady_is_the_twin(monkeypatch):
     assert all(np.array_equal(a, b) for a, b in zip(got[4:], plain[4:]))
     assert w._steady is None and w._steady_dev is None and w._steady_state is None and w._steady_last is None
     assert w._matte_line is None and w.stream.matte_tap is None
-    # mid-stream: the line starts with the next frame, whose output passes as the first of a sequence
+    # mid-stream (N = 2): the line starts with the next frame, whose output belongs to a frame the line has not seen -- it passes,
+    # the sequence has not started and the state holds nothing of the foreign slot
     w.set_steady()
     got = w(frames[0])
-    assert np.array_equal(got, egress_ref(w.stream.prev_image_result)[0].numpy()) and not w._steady_init
+    assert np.array_equal(got, egress_ref(w.stream.prev_image_result)[0].numpy())
+    assert not w._matte_line.last_own and w._steady_init and w._steady_state is None and w._steady_last is None
+    # the first output with its own slot is the init frame: it passes, and the state is that frame and its own source's bytes
+    got = w(frames[1])
+    assert np.array_equal(got, egress_ref(w.stream.prev_image_result)[0].numpy())
+    assert w._matte_line.last_own and not w._steady_init
+    assert same(w._steady_state[0], w.stream.prev_image_result[0].to(torch.float16).numpy())
+    assert same(w._steady_state[1], SD.source_bytes(pre(frames[0])))
+    # ... and the one after it is the first that differs
+    got = w(frames[2])
+    assert not np.array_equal(got, egress_ref(w.stream.prev_image_result)[0].numpy())
+    assert same(w._steady_state[1], SD.source_bytes(pre(frames[1])))
+
+
+@pytest.mark.parametrize("n_steps", [1, 2, 3])
+@pytest.mark.parametrize("kind", ["unrelated", "moving"])
+def test_wrapper_mid_stream_start_never_holds_a_foreign_source(monkeypatch, n_steps, kind):
+    """`set_steady()` with its defaults after two plain frames.  The first N - 1 outputs behind it belong to frames that entered
+    before the delay line existed: `take()` hands out the oldest entry it has, another frame's, and steady must not start on
+    it.  On unrelated frames (everything moves between any two) every output equals the unsteadied bytes -- the largest byte
+    difference is 0 on calls 3 .. 7 for N = 1, 2 and 3; a sequence started on the foreign slot measured zero motion on the
+    first own slot and held it to the output before (on these frames 30 levels on call 4 at N = 2; 26 and 30 on calls 4 and 5 at
+    N = 3).  On moving-camera frames the first
+    output with its own slot passes as the init frame and the one after it is the first that differs."""
+    import pipeline_mocks as M
+    frames = frames_of(7, seed=21)
+    if kind == "moving":
+        frames = moving(frames)
+    torch.manual_seed(123)
+    w = build(monkeypatch, n_steps)
+    w.prepare(M.frames(8, seed=7), "a prompt")
+    for f in frames[:2]:
+        w(f)
+    w.set_steady()
+    own, diffs = [], []
+    for t, f in enumerate(frames[2:]):
+        got = w(f)
+        plain = egress_ref(w.stream.prev_image_result)[0].numpy()
+        own.append(w._matte_line.last_own)
+        diffs.append(int(np.abs(got.astype(int) - plain.astype(int)).max()))
+        if own[-1]:                              # the state is the output's own source, always
+            assert same(w._steady_state[1], SD.source_bytes(pre(frames[2 + t - (n_steps - 1)])))
+        else:
+            assert w._steady_init and w._steady_state is None and w._steady_last is None
+    print(f"N = {n_steps}, {kind}: last_own {own}, largest byte difference to the unsteadied frame {diffs}")
+    assert own == [False] * (n_steps - 1) + [True] * (5 - (n_steps - 1))
+    if kind == "unrelated":
+        assert diffs == [0] * 5
+    else:
+        assert diffs[:n_steps] == [0] * n_steps and all(d > 0 for d in diffs[n_steps:])
