@@ -462,6 +462,31 @@ enum {
  *   [0, 1].  Only bytes of [dst, dst + Ho Wo 3) are written, by plain stores (whole dwords where the address allows, bytes at
  *   the ends of a row).  Refused: a null pointer, Ho, Wo outside 1..L2D_RESIZE_MAX_SIZE or outside [n_in / 2, 8 n_in], Ho Wo 3 or
  *   3 H W >= 2^31, misaligned tables or G, unknown flags, a limit or k that is not finite or negative, dst overlapping an input.
+ *
+ * Depth from the caller (depth_in.hip; no counterpart in the reference): a depth frame in place of the detector's.  Individually
+ *   rounded fp32 operations, no fma, so that numpy restates both ops bit for bit (live2diff_amd/depth_io.py resample_ref,
+ *   normalize_ref).
+ * L2D_OP_DEPTH_INGEST  one launch:  p0 src uint16 or (L2D_DEPTH_F32) float [B][Hd][Wd] p1 R float [B][H][W] (16-byte aligned) p2
+ *   partials float [B tiles][3] p3 xmin int32 [W] p4 wx float [W][Kx] p5 ymin int32 [H] p6 wy float [H][Ky] (rows [left, left + W)
+ *   and [top, top + H) of frame_io.aa_weights(Wd, nw) / (Hd, nh); a tap past a row's own count has weight 0) ; i0 B i1 Hd i2 Wd i3 H
+ *   i4 W i5 nh i6 nw i7 top i8 left (L2D_OP_FRAME_INGEST's geometry, of the depth frame's own size) i9 Kx i10 Ky (1..
+ *   L2D_DEPTH_MAX_TAPS) i11 flags i12 the invalid uint16 value ; f0 the invalid fp32 value.  Per sample: valid when (uint16) z !=
+ *   invalid or (fp32) z finite and != invalid -- with L2D_DEPTH_HAS_INVALID, else no value is excluded --, and u finite and >= 0,
+ *   u = float(z) or (L2D_DEPTH_DISTANCE) 1 / float(z); u = 0, v = 0 where not valid, v = 1 where valid.  num = sum_y wy (sum_x wx
+ *   u), den = sum_y wy (sum_x wx v), taps ascending, every product and sum rounded to fp32; R = num / den where den > 0, else -1.
+ *   partials[(b tiles_y + ty) tiles_x + tx] = {min, max, any} of R over the valued pixels of tile (ty, tx) of L2D_DEPTH_TILE_H x
+ *   L2D_DEPTH_TILE_W pixels ({+inf, -1, 0} where there is none).  Every element of p1 and p2 is written by a plain store on
+ *   every launch: nothing has to be zeroed.  Table entries are clamped to the image.  Refused: a null or misaligned pointer, a
+ *   non-positive size, B Hd Wd or B H W >= 2^31, B > 65535, a window outside the resized image, a scale above 8, taps outside
+ *   1..L2D_DEPTH_MAX_TAPS, unknown flags, an invalid value that is no uint16.
+ * L2D_OP_DEPTH_NORMALIZE  one launch:  p0 R float [B][H][W] p1 partials (of all B frames) p2 out half [B][3][H][W] (p0, p2 16-byte
+ *   aligned) ; i0 B i1 H i2 W (H W % 8 == 0) i3 the number of partials (B tiles) i4 flags (L2D_DEPTH_FIXED_RANGE) ; f0 mn f1 mx of
+ *   the fixed range.  mn, mx = min, max over all partials (every block, in a fixed order), or f0, f1; n = min(max((R - mn) / (mx -
+ *   mn), 0), 1); out = half(2 n - 1) on the three planes; -1 where R < 0, and everywhere where the map is flat: with the partials,
+ *   no pixel has a value or float(mx - mn) <= float(mx 2^-14) (that holds mx <= mn and the rounding noise of the resampling of a
+ *   constant frame); with L2D_DEPTH_FIXED_RANGE, mx <= mn only.
+ *   Refused: a null or misaligned pointer, a non-positive size, H W % 8 != 0, 3 B H W >= 2^31, unknown flags, a partial count
+ *   that is not B tiles, a NaN in the fixed range.
  */
 enum {
     L2D_OP_IGEMM = 1,
@@ -515,6 +540,8 @@ enum {
     L2D_OP_FRAME_MATTE_EDGE = 49,
     L2D_OP_FRAME_DETAIL_GAIN = 50,
     L2D_OP_FRAME_DETAIL = 51,
+    L2D_OP_DEPTH_INGEST = 52,
+    L2D_OP_DEPTH_NORMALIZE = 53,
 };
 
 /* flag bits of L2D_OP_FRAME_MATTE (i4) and L2D_OP_FRAME_MATTE_UP (i6); HARD and FAR also of L2D_OP_FRAME_MATTE_EDGE (i3) */
@@ -541,6 +568,15 @@ enum {
 /* flag bits of L2D_OP_FRAME_DETAIL_GAIN (i3: U8) and L2D_OP_FRAME_DETAIL (i4: SHOW) */
 #define L2D_DETAIL_U8 1 /* p0 is the uint8 [H][W][3] frame of the matte, not the half frame */
 #define L2D_DETAIL_SHOW 2
+
+/* flag bits of L2D_OP_DEPTH_INGEST (i11: F32, DISTANCE, HAS_INVALID) and L2D_OP_DEPTH_NORMALIZE (i4: FIXED_RANGE), and their sizes */
+#define L2D_DEPTH_F32 1 /* p0 holds fp32 samples, not uint16 */
+#define L2D_DEPTH_DISTANCE 2 /* u = 1 / z (metric distance in), not z (inverse depth in) */
+#define L2D_DEPTH_HAS_INVALID 4 /* samples equal to i12 (uint16) / f0 (fp32) are holes */
+#define L2D_DEPTH_FIXED_RANGE 8 /* mn = f0, mx = f1 instead of the partials */
+#define L2D_DEPTH_TILE_H 16 /* the output tile of one work-group: one {min, max, any} partial each */
+#define L2D_DEPTH_TILE_W 32
+#define L2D_DEPTH_MAX_TAPS 17 /* per axis, at a down-scale of 8 */
 
 /* sizes of L2D_OP_FRAME_RESIZE */
 #define L2D_RESIZE_MAX_KS 13 /* taps per output: Lanczos (support 3) at a 2x down-scale, 2 * 6 + 1 */

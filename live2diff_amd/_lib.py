@@ -33,6 +33,7 @@ OP_FRAME_MATTE_UP = 47
 OP_FRAME_STEADY = 48
 OP_FRAME_MATTE_EDGE = 49
 OP_FRAME_DETAIL_GAIN, OP_FRAME_DETAIL = 50, 51
+OP_DEPTH_INGEST, OP_DEPTH_NORMALIZE = 52, 53
 ABI_VERSION = 6
 
 

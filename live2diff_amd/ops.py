@@ -1717,3 +1717,73 @@ def frame_detail(styled, camera, low, gains, tx, ty, dst, *, H, W, Ho, Wo, k, li
         op.i[j] = int(v)
     op.f[0], op.f[1] = k, limit
     return op, keep
+
+
+# ----------------------------------------------------------------------------- depth from the caller (depth_in.hip, depth_io.py)
+DEPTH_F32, DEPTH_DISTANCE, DEPTH_HAS_INVALID, DEPTH_FIXED_RANGE = 1, 2, 4, 8      # l2d.h L2D_DEPTH_*
+DEPTH_TILE_H, DEPTH_TILE_W, DEPTH_MAX_TAPS = 16, 32, 17
+
+
+def depth_tiles(H: int, W: int) -> int:
+    """work-groups (and {min, max, any} partials) of one frame of `depth_ingest`"""
+    return ((H + DEPTH_TILE_H - 1) // DEPTH_TILE_H) * ((W + DEPTH_TILE_W - 1) // DEPTH_TILE_W)
+
+
+def depth_ingest(src, R, partials, xmin, wx, ymin, wy, *, B, Hd, Wd, H, W, nh, nw, top, left, distance, invalid):
+    """uint16 / fp32 [B,Hd,Wd] `src` -> fp32 [B,H,W] `R` (the normalised convolution of u = z or 1 / z over the valid samples,
+    -1 where a pixel has no value) and fp32 [B tiles, 3] `partials` ({min, max, any} per tile): depth_io.resample_ref.
+    `xmin`, `wx`, `ymin`, `wy`: the tables of `depth_io.tables`; `invalid`: the value that marks a hole, or None."""
+    f32 = src.dtype == torch.float32
+    if not f32 and src.dtype not in (torch.uint16, torch.int16):          # (int16: the bits of uint16 samples)
+        raise ValueError(f"depth_ingest: src: expected uint16 or float32 samples, got {src.dtype}")
+    if src.numel() != B * Hd * Wd or not src.is_contiguous():
+        raise ValueError(f"depth_ingest: src: expected a contiguous [{B},{Hd},{Wd}] frame, got {tuple(src.shape)}")
+    if R.dtype != torch.float32 or R.numel() != B * H * W or not R.is_contiguous():
+        raise ValueError(f"depth_ingest: R: expected a contiguous fp32 [{B},{H},{W}] plane, got {R.dtype} {tuple(R.shape)}")
+    if partials.dtype != torch.float32 or partials.numel() != B * depth_tiles(H, W) * 3 or not partials.is_contiguous():
+        raise ValueError(f"depth_ingest: partials: expected contiguous fp32 [{B * depth_tiles(H, W)},3], got {partials.dtype} "
+                         f"{tuple(partials.shape)}")
+    for name, idx, w, n in (("x", xmin, wx, W), ("y", ymin, wy, H)):
+        if idx.dtype != torch.int32 or idx.numel() != n or w.dtype != torch.float32 or w.ndim != 2 or w.shape[0] != n \
+                or not idx.is_contiguous() or not w.is_contiguous():
+            raise ValueError(f"depth_ingest: the {name} tables must be contiguous int32 [{n}] and fp32 [{n}, taps]")
+    flags = (DEPTH_F32 if f32 else 0) | (DEPTH_DISTANCE if distance else 0)
+    inv_i, inv_f = 0, 0.0
+    if invalid is not None:
+        if f32:
+            flags |= DEPTH_HAS_INVALID
+            inv_f = float(np.float32(invalid))
+        elif float(invalid) == int(invalid) and 0 <= int(invalid) <= 65535:     # (no uint16 sample equals any other value)
+            flags |= DEPTH_HAS_INVALID
+            inv_i = int(invalid)
+    op = L2dOp()
+    op.kind = _lib.OP_DEPTH_INGEST
+    keep = (src, R, partials, xmin, wx, ymin, wy)
+    for j, t in enumerate(keep):
+        op.p[j] = _ptr(t)
+    for j, v in enumerate([B, Hd, Wd, H, W, nh, nw, top, left, wx.shape[1], wy.shape[1], flags, inv_i]):
+        op.i[j] = int(v)
+    op.f[0] = inv_f
+    return op, keep
+
+
+def depth_normalize(R, partials, out, *, B, H, W, fixed=None):
+    """fp32 [B,H,W] `R` + the partials of all B frames -> fp16 [B,3,H,W] `out` in [-1, 1]: depth_io.normalize_ref.  `fixed`:
+    (mn, mx) as float32 in units of u, or None: min and max over the partials"""
+    if R.dtype != torch.float32 or R.numel() != B * H * W or not R.is_contiguous():
+        raise ValueError(f"depth_normalize: R: expected a contiguous fp32 [{B},{H},{W}] plane, got {R.dtype} {tuple(R.shape)}")
+    if out.dtype != torch.float16 or out.numel() != B * 3 * H * W or not out.is_contiguous():
+        raise ValueError(f"depth_normalize: out: expected a contiguous fp16 [{B},3,{H},{W}] map, got {out.dtype} {tuple(out.shape)}")
+    npart = B * depth_tiles(H, W)
+    if partials.dtype != torch.float32 or partials.numel() != npart * 3 or not partials.is_contiguous():
+        raise ValueError(f"depth_normalize: partials: expected contiguous fp32 [{npart},3], got {partials.dtype} {tuple(partials.shape)}")
+    op = L2dOp()
+    op.kind = _lib.OP_DEPTH_NORMALIZE
+    keep = (R, partials, out)
+    for j, t in enumerate(keep):
+        op.p[j] = _ptr(t)
+    for j, v in enumerate([B, H, W, npart, DEPTH_FIXED_RANGE if fixed is not None else 0]):
+        op.i[j] = int(v)
+    if fixed is not None:
+        op.f[0], op.f[1] = float(fixed[0]), float(fixed[1])
+    return op, keep

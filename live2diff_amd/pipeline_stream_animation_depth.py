@@ -153,6 +153,10 @@ class StreamAnimateDiffusionDepth:
         # Optional tap on the depth path (matte.MatteLine): `tap(x, dn)` is called with every frame that enters the stream batch
         # and its normalised depth, `tap.prime(x, dn)` with the warm-up frames of `prepare`.  None: nothing changes.
         self.matte_tap = None
+        # Depth from the caller (depth_io.py): how a `depth=` frame is read -- `depth_io.check_settings`' keywords, applied from
+        # the next frame -- and the device-side ingest, created by the first such frame on the device.
+        self.depth_input = dict(kind="distance", invalid=0, range=None)
+        self._depth_ingest = None
 
     @property
     def depth_glue(self):
@@ -228,8 +232,10 @@ class StreamAnimateDiffusionDepth:
     @torch.no_grad()
     def prepare(self, warmup_frames, prompt: str = "", negative_prompt: str = "", guidance_scale: float = 1.2,
                 delta: float = 1.0, generator: Optional[torch.Generator] = None, seed: int = 2,
-                prompt_embeds: Optional[torch.Tensor] = None):
-        """Forward the warm-up frames ([F,3,H,W] in [0,1]) and fill the KV-cache (reference :171-344)."""
+                prompt_embeds: Optional[torch.Tensor] = None, warmup_depths=None):
+        """Forward the warm-up frames ([F,3,H,W] in [0,1]) and fill the KV-cache (reference :171-344).  `warmup_depths`: the
+        caller's depth frames of the warm-up window, a batch [F,Hd,Wd] normalised jointly as the detector's would be
+        (`encode_depth`), or None: the detector."""
         n = self.denoising_steps_num
         self._device_step = None          # a previous stream's device-side state (ring buffer, frame counter, rows) is stale
         if generator is None:
@@ -273,7 +279,11 @@ class StreamAnimateDiffusionDepth:
         xs = [self.image_processor.preprocess(f, self.height, self.width).to(**to) for f in warmup_frames]
         warmup_x = torch.cat(xs, dim=0)
         x_t_latent = self.encode_image(warmup_x).transpose(0, 1)[None]           # [1,4,F,h,w]
-        depth_latent = self.encode_depth(warmup_x, tap=getattr(getattr(self, "matte_tap", None), "prime", None)).transpose(0, 1)[None]
+        if warmup_depths is not None and (getattr(warmup_depths, "ndim", 0) != 3 or warmup_depths.shape[0] != warmup_x.shape[0]):
+            raise ValueError(f"warmup_depths: expected a batch [{warmup_x.shape[0]},Hd,Wd], one depth frame per warm-up frame, got "
+                             f"{tuple(getattr(warmup_depths, 'shape', ()))}")
+        depth_latent = self.encode_depth(warmup_x, tap=getattr(getattr(self, "matte_tap", None), "prime", None),
+                                         depth=warmup_depths).transpose(0, 1)[None]
         warm = self.unet_warmup if self.unet_warmup is not None else self.unet
         for idx, t in enumerate(self.sub_timesteps_tensor):
             if hasattr(warm, "warmup"):
@@ -325,12 +335,24 @@ class StreamAnimateDiffusionDepth:
         out = self.vae.decode(x_0_pred_out / self.vae.config.scaling_factor, return_dict=False)[0]
         return out.clip(-1, 1)
 
-    def encode_depth(self, image_tensors, tap=None):
+    def encode_depth(self, image_tensors, tap=None, depth=None):
         """reference :544-571.  On the device the arithmetic around the (caller-owned) depth detector -- the 384x384 bilinear
         resize, the min-max normalisation over the batch, x3 channels, [-1,1], the resize back -- runs as HIP ops without the
         reference's two host-visible reductions (`self.depth_glue`, vae_hip.HipDepthGlue); CPU tensors (host-logic tests)
         and `depth_glue = None` take the reference's torch expressions.  `tap(image_tensors, dn)`, when given, sees the frame and
-        its normalised depth map ([B,3,h,w] in [-1, 1]) before the map is encoded and dropped."""
+        its normalised depth map ([B,3,h,w] in [-1, 1]) before the map is encoded and dropped.
+
+        `depth` (not in the reference): the caller's own depth frame(s), uint16 or float32 [Hd,Wd] / [B,Hd,Wd] of any size, read
+        as `self.depth_input` says.  Neither the detector nor the glue is called: `dn` comes from two launches on the device
+        (depth_io.HipDepthIngest), from `depth_io.depth_ref` on CPU tensors; the tap and the encode behind it see no difference."""
+        if depth is not None:
+            image_tensors = image_tensors.to(device=self.device, dtype=getattr(self.depth_detector, "dtype", self.dtype))
+            dn = self._external_depth(image_tensors, depth)
+            if tap is not None:
+                tap(image_tensors, dn)
+            return retrieve_latents(self.vae.encode(dn.to(dtype=self.vae.dtype)), self.generator) * self.vae.config.scaling_factor
+        if self.depth_detector is None:
+            raise ValueError("depth: this stream was built without a depth detector (depth_source='input'): every frame needs its depth")
         image_tensors = image_tensors.to(device=self.device, dtype=self.depth_detector.dtype)
         h, w = image_tensors.shape[2], image_tensors.shape[3]
         glue = self.depth_glue
@@ -349,6 +371,20 @@ class StreamAnimateDiffusionDepth:
         if tap is not None:
             tap(image_tensors, dn)
         return retrieve_latents(self.vae.encode(dn.to(dtype=self.vae.dtype)), self.generator) * self.vae.config.scaling_factor
+
+    def _external_depth(self, image_tensors, depth):
+        """`dn`, [B,3,h,w] in [-1, 1], of the caller's depth frame(s) for the frames `image_tensors`"""
+        from . import depth_io
+        B, h, w = image_tensors.shape[0], image_tensors.shape[2], image_tensors.shape[3]
+        nd = getattr(depth, "ndim", None)
+        if nd not in (2, 3) or (depth.shape[0] if nd == 3 else 1) != B:
+            raise ValueError(f"depth: expected one depth frame per frame, [Hd,Wd] or [{B},Hd,Wd], got {tuple(getattr(depth, 'shape', ()))}")
+        if image_tensors.is_cuda:
+            ing = self._depth_ingest
+            if ing is None or (ing.height, ing.width) != (h, w):
+                ing = self._depth_ingest = depth_io.HipDepthIngest(h, w, device=self.device)
+            return ing.ingest(depth, **self.depth_input)
+        return torch.from_numpy(depth_io.depth_ref(depth, h, w, **self.depth_input)).to(image_tensors.dtype)
 
     def enable_device_step(self, use_graph: bool = False, seed: int = 0):
         """Opt in to the device-side frame step (stream_step_hip.HipStreamStep): after `prepare`,
@@ -383,7 +419,8 @@ class StreamAnimateDiffusionDepth:
         self._pre_stream = torch.cuda.Stream(device=self.device)
         self._pending = collections.deque()
 
-    def push(self, x: Union[torch.Tensor, np.ndarray]) -> None:
+    def push(self, x: Union[torch.Tensor, np.ndarray], depth=None) -> None:
+        """`depth`: the frame's own depth (`encode_depth`); its ingest runs on the side stream with the rest of the depth path"""
         if getattr(self, "_pending", None) is None:
             raise RuntimeError("push() needs enable_frame_pipelining() first")
         cur = torch.cuda.current_stream()
@@ -391,11 +428,13 @@ class StreamAnimateDiffusionDepth:
         self._pre_stream.wait_stream(cur)                     # the frame is ready; earlier consumers of the side buffers are done
         with torch.cuda.stream(self._pre_stream):
             x_t_latent = self.encode_image(x)
-            depth_latent = self.encode_depth(x, tap=getattr(self, "matte_tap", None))       # (the tap's copies: in front of the event)
+            depth_latent = self.encode_depth(x, tap=getattr(self, "matte_tap", None), depth=depth)  # (the tap's copies: in front of the event)
             ev = torch.cuda.Event()
             ev.record(self._pre_stream)
         if x.is_cuda:
             x.record_stream(self._pre_stream)
+        if torch.is_tensor(depth) and depth.is_cuda:
+            depth.record_stream(self._pre_stream)
         self._pending.append((x_t_latent, depth_latent, ev))
 
     def pop(self) -> torch.Tensor:
@@ -455,7 +494,9 @@ class StreamAnimateDiffusionDepth:
         return x_0_pred_out
 
     @torch.no_grad()
-    def __call__(self, x: Union[torch.Tensor, np.ndarray]) -> torch.Tensor:
+    def __call__(self, x: Union[torch.Tensor, np.ndarray], depth=None) -> torch.Tensor:
+        """`depth`: the frame's own depth in place of the detector's (`encode_depth`); a frame the near-duplicate filter drops
+        ignores it"""
         if getattr(self, "_pending", None):
             # the side stream may still be writing the static plan buffers this call would use (TAESD encoder, depth detector
             # arena, glue scratch), and the host generator's draw order would change: finish the pushed frames first
@@ -471,7 +512,7 @@ class StreamAnimateDiffusionDepth:
         x_t_latent = self.encode_image(x)
         sd, ed = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         sd.record()
-        depth_latent = self.encode_depth(x, tap=getattr(self, "matte_tap", None))
+        depth_latent = self.encode_depth(x, tap=getattr(self, "matte_tap", None), depth=depth)
         ed.record()
         x_0 = self.predict_x0_batch(x_t_latent.unsqueeze(2), depth_latent.unsqueeze(2))      # [1,4,1,h,w]
         x_output = self.decode_image(x_0[:, :, 0]).detach().clone()

@@ -23,6 +23,8 @@ with Pillow's arithmetic, behind both and in front of the JPEG encoder or the co
 `set_steady` holds the previous output pixel where the frame's source did not move (steady.py), behind the colour lock.
 `set_matte_edge` refines the matte by the source frame, so that its edges land on the frame's own (matte.edge_ref).
 `set_detail` brings the camera's fine detail into the frame at the output size, behind the resize (detail.py).
+`wrapper(image, depth=d)` conditions a frame on the caller's own depth frame -- an RGB-D camera's, another estimator's -- instead
+of the built-in detector's; `set_depth_input` says how it is read, `depth_source="input"` builds no detector at all (depth_io.py).
 
 Every frame leaves through one chain, `_route`: colour lock, then steady (`_finish`, in front of it) -> matte composite, or egress -> resize
 -> detail -> JPEG encoder, or copy to the host.  A stage that is not set is not in the chain; on the device each stage is one launch that
@@ -217,9 +219,11 @@ def text_encoder_state_dict(model_dir: str, dreambooth=None, loras=None) -> dict
 
 def load_components(cfg: dict, *, height: int, width: int, denoising_steps_num: int, device="cuda", dreambooth_path=None,
                     lora_dict=None, few_step_model_type: str = "lcm", vae_id=None, use_tiny_vae: bool = True,
-                    engine_dir: Optional[Union[str, os.PathLike]] = "engines"):
-    """config dict -> the `pipe` namespace `StreamAnimateDiffusionDepth` takes (unet, vae, depth_model, `_encode_prompt`, scheduler)"""
-    from .midas_hip import HipMidas
+                    engine_dir: Optional[Union[str, os.PathLike]] = "engines", depth_source: str = "detector"):
+    """config dict -> the `pipe` namespace `StreamAnimateDiffusionDepth` takes (unet, vae, depth_model, `_encode_prompt`, scheduler).
+    `depth_source="input"`: every frame brings its own depth, so `depth_model_path` is not needed and no detector is built
+    (`depth_model` is None)."""
+    _check_depth_source(depth_source)
     model_dir = _need("pretrained_model_path", cfg.get("pretrained_model_path"), os.path.isdir)
     ucfg = load_unet_config(model_dir, cfg)
     unet, dreambooth, lora_sds = load_style_unet(cfg, ucfg, height // 8, width // 8, denoising_steps_num, device=device,
@@ -235,7 +239,10 @@ def load_components(cfg: dict, *, height: int, width: int, denoising_steps_num: 
         from .vae_kl_hip import HipAutoencoderKL
         has_vae = dreambooth is not None and any(k.startswith(convert.LDM_VAE_PREFIX) for k in dreambooth)
         vae = HipAutoencoderKL(convert.build_vae_state_dict(load_vae_kl(model_dir), dreambooth if has_vae else None), device=device)
-    depth = HipMidas(load_depth_state_dict(cfg.get("depth_model_path")), device=device)
+    depth = None
+    if depth_source == "detector":
+        from .midas_hip import HipMidas
+        depth = HipMidas(load_depth_state_dict(cfg.get("depth_model_path")), device=device)
     return SimpleNamespace(device=torch.device(device), vae_scale_factor=8, unet=unet, vae=vae, depth_model=depth,
                            text_encoder=prompt_encoder.encoder, tokenizer=prompt_encoder.tokenizer,
                            _encode_prompt=prompt_encoder._encode_prompt, unet_config=ucfg,
@@ -255,6 +262,11 @@ def build_style_sets(cfg: dict, like_unet, like_text, *, dreambooth_path=None, l
     tsd = text_encoder_state_dict(cfg["pretrained_model_path"], dreambooth, lora_sds)
     text = HipClipTextEncoder(tsd, like_text.device, like_text.cfg, use_graph=False)
     return unet.packed_state(), text.packed_state()
+
+
+def _check_depth_source(source) -> None:
+    if source not in ("detector", "input"):
+        raise ValueError(f"depth_source={source!r}: use 'detector' or 'input'")
 
 
 def _is_jpeg(x) -> bool:
@@ -291,6 +303,7 @@ class StreamAnimateDiffusionDepthWrapper:
     _matte_edge = None                      # the edge-aware matte's settings (set_matte_edge), None: off
     _detail = None                          # the detail mode's settings (set_detail), None: off
     _detail_dev = None                      # detail.HipDetail of the current output size, made by the first frame that needs it
+    depth_source = "detector"               # "input": every frame brings its own depth and no detector was built (`_setup` sets it)
 
     def __init__(self, config_path: str, few_step_model_type: str, num_inference_steps: int,
                  t_index_list: Optional[List[int]] = None, strength: Optional[float] = None,
@@ -303,7 +316,9 @@ class StreamAnimateDiffusionDepthWrapper:
                  engine_dir: Optional[Union[str, Path]] = "engines", opt_unet: bool = False, frame_pipelining: bool = False,
                  jpeg_quality: int = 75, jpeg_decode: str = "device", output_size: Optional[Tuple[int, int]] = None,
                  output_resample: str = "lanczos", matte_source: str = "stream", steady: Optional[dict] = None,
-                 matte_edge: Optional[dict] = None, detail: Optional[dict] = None):
+                 matte_edge: Optional[dict] = None, detail: Optional[dict] = None, depth_input: Optional[dict] = None,
+                 depth_source: str = "detector"):
+        _check_depth_source(depth_source)
         self._check_keywords(few_step_model_type=few_step_model_type, acceleration=acceleration, cfg_type=cfg_type,
                              use_denoising_batch=use_denoising_batch, frame_buffer_size=frame_buffer_size, device_ids=device_ids,
                              opt_unet=opt_unet, output_type=output_type, dtype=dtype, jpeg_quality=jpeg_quality, jpeg_decode=jpeg_decode)
@@ -314,7 +329,7 @@ class StreamAnimateDiffusionDepthWrapper:
         n = len(t_index_list) if strength is None else min(int(num_inference_steps * strength), num_inference_steps)
         pipe = load_components(cfg, height=height, width=width, denoising_steps_num=n, device=device,
                                dreambooth_path=dreambooth_path, lora_dict=lora_dict, few_step_model_type=few_step_model_type,
-                               vae_id=vae_id, use_tiny_vae=use_tiny_vae, engine_dir=engine_dir)
+                               vae_id=vae_id, use_tiny_vae=use_tiny_vae, engine_dir=engine_dir, depth_source=depth_source)
         self._style_src = dict(cfg=cfg, few_step_model_type=few_step_model_type, engine_dir=engine_dir)    # what add_style builds from
         self._setup(pipe, num_inference_steps=num_inference_steps, t_index_list=t_index_list, strength=strength,
                     output_type=output_type, device=device, dtype=dtype, width=width, height=height, do_add_noise=do_add_noise,
@@ -323,13 +338,13 @@ class StreamAnimateDiffusionDepthWrapper:
                     similar_image_filter_threshold=similar_image_filter_threshold,
                     similar_image_filter_max_skip_frame=similar_image_filter_max_skip_frame, jpeg_quality=jpeg_quality,
                     jpeg_decode=jpeg_decode, output_size=output_size, output_resample=output_resample, matte_source=matte_source,
-                    steady=steady, matte_edge=matte_edge, detail=detail)
+                    steady=steady, matte_edge=matte_edge, detail=detail, depth_input=depth_input, depth_source=depth_source)
 
     @classmethod
     def from_components(cls, pipe, *, num_inference_steps: int, t_index_list: Optional[List[int]] = None,
                         strength: Optional[float] = None, **kw):
         """The wrapper around an already assembled `pipe` namespace (tests, synthetic weights).  Keywords: those of the
-        constructor that do not name files (`jpeg_quality`, `jpeg_decode`, `output_size`, `output_resample`, `matte_source`, `steady`, `matte_edge` and `detail` among them), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
+        constructor that do not name files (`jpeg_quality`, `jpeg_decode`, `output_size`, `output_resample`, `matte_source`, `steady`, `matte_edge`, `detail`, `depth_input` and `depth_source` among them; with `depth_source="input"` the namespace needs no `depth_model`), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
         self = cls.__new__(cls)
         cls._check_keywords(**{k: kw.pop(k) for k in ("acceleration", "cfg_type", "use_denoising_batch", "frame_buffer_size",
                                                       "device_ids", "opt_unet", "few_step_model_type") if k in kw},
@@ -369,8 +384,12 @@ class StreamAnimateDiffusionDepthWrapper:
                width=512, height=512, do_add_noise=True, seed=42, clip_skip=1, warmup_frames=8, window_size=16,
                scheduler_kwargs=None, frame_pipelining=False, enable_similar_image_filter=False,
                similar_image_filter_threshold=0.98, similar_image_filter_max_skip_frame=10, jpeg_quality=75, jpeg_decode="device",
-               output_size=None, output_resample="lanczos", matte_source="stream", steady=None, matte_edge=None, detail=None):
+               output_size=None, output_resample="lanczos", matte_source="stream", steady=None, matte_edge=None, detail=None,
+               depth_input=None, depth_source="detector"):
         self._check_matte_source(matte_source)
+        _check_depth_source(depth_source)
+        if depth_input is not None and not isinstance(depth_input, dict):
+            raise ValueError(f"depth_input={depth_input!r}: use a dict of set_depth_input's keywords, or None")
         if steady is not None and not isinstance(steady, dict):
             raise ValueError(f"steady={steady!r}: use a dict of set_steady's keywords, or None")
         if matte_edge is not None and not isinstance(matte_edge, dict):
@@ -418,6 +437,56 @@ class StreamAnimateDiffusionDepthWrapper:
             self.set_matte_edge(**matte_edge)
         if detail is not None:
             self.set_detail(**detail)
+        self.depth_source = depth_source
+        if depth_source == "input":
+            self.stream.depth_detector = None      # (a `pipe` that brought one: it is never called)
+        if depth_input is not None:
+            self.set_depth_input(**depth_input)
+
+    # ------------------------------------------------------------------ depth from the caller (depth_io.py)
+    @property
+    def depth_input(self) -> dict:
+        """how a `depth=` frame is read, as {kind, invalid, range}"""
+        return dict(self.stream.depth_input)
+
+    def set_depth_input(self, kind: str = "distance", invalid=0, range=None) -> None:
+        """How the depth frames handed in with `depth=` are read.  `kind="distance"`: metric samples, larger = farther (an RGB-D
+        camera's millimetres); `kind="inverse"`: MiDaS's convention, larger = nearer (another monocular estimator's output).
+        `invalid`: the sample value that marks a hole (0 for most depth cameras), or None: every value counts; non-finite
+        floats, and distances that are not positive, are holes always.  Holes smaller than the resampling filter's footprint
+        are filled by their valid neighbours; larger ones count as the farthest.  `range=None`: every frame (and the warm-up
+        batch of `prepare`, jointly) is normalised by its own nearest and farthest pixel, as the detector's map is;
+        `range=(near, far)` for "distance" -- `far` may be inf -- or `(lo, hi)` for "inverse", in the units of the samples: a
+        fixed range, so the map does not pump when something walks into view.  Without a range a frame whose own range is within
+        2^-14 of its nearest value counts as flat (all farthest: that is rounding noise of the resampling, not depth); a fixed
+        range is taken at its word however narrow.  May be called before or after `prepare` and
+        between any two frames: the settings apply from the next frame."""
+        from .depth_io import check_settings
+        self.stream.depth_input = check_settings(kind, invalid, range)
+
+    def _depth_arg(self, depth, where: str = "depth"):
+        """a `depth=` argument as the pipeline takes it: arrays and tensors pass (host or device), a PIL image of mode "I;16", "I",
+        "F" or "L" -- or a path to one -- becomes its uint16 / float32 array.  None under `depth_source="input"` raises."""
+        if depth is None:
+            if self.depth_source == "input":
+                raise ValueError(f"{where}: this wrapper was built with depth_source='input': every frame needs its depth")
+            return None
+        if isinstance(depth, (str, os.PathLike)):
+            from PIL import Image
+            depth = Image.open(depth)
+        if hasattr(depth, "mode") and hasattr(depth, "convert"):
+            if depth.mode not in ("I;16", "I;16L", "I;16B", "I", "F", "L"):
+                raise ValueError(f"{where}: a depth image must have mode 'I;16', 'I', 'F' or 'L', got {depth.mode!r}")
+            arr = np.array(depth)
+            if depth.mode == "I":              # (how some Pillow versions open a 16-bit PNG)
+                if arr.min() < 0 or arr.max() > 65535:
+                    raise ValueError(f"{where}: a mode 'I' depth image must hold 16-bit samples, 0..65535 (got {int(arr.min())}.."
+                                     f"{int(arr.max())}): hand wider data in as a float32 array")
+                arr = arr.astype(np.uint16)
+            elif arr.dtype not in (np.uint8, np.float32):
+                arr = arr.astype(np.uint16)
+            return arr
+        return depth
 
     # ------------------------------------------------------------------ depth matte (matte.py, DESIGN.md section 8.z4)
     @property
@@ -928,11 +997,19 @@ class StreamAnimateDiffusionDepthWrapper:
             self.stream.update_prompt(self._prompt)
 
     # ------------------------------------------------------------------ prepare
-    def prepare(self, warmup_frames, prompt: str, negative_prompt: str = "", guidance_scale: float = 1.2, delta: float = 1.0) -> torch.Tensor:
+    def prepare(self, warmup_frames, prompt: str, negative_prompt: str = "", guidance_scale: float = 1.2, delta: float = 1.0,
+                warmup_depths=None) -> torch.Tensor:
         """warmup_frames: float [F,3,H,W] in [0, 1] as in the reference, uint8 [F,Hs,Ws,3] (one batched ingest launch), or a list
-        of JPEG files of one size (decoded like `img2img`'s, then the uint8 route).
+        of JPEG files of one size (decoded like `img2img`'s, then the uint8 route).  warmup_depths: the frames' own depth, a batch
+        [F,Hd,Wd] (or a list of what `img2img` takes as `depth`, of one size), normalised jointly; None: the detector.
         Returns the generated warm-up frames, [F,H,W,3] in [0, 1] (wrapper.py:197-199)."""
         kw = dict(prompt=prompt, negative_prompt=negative_prompt, guidance_scale=guidance_scale, delta=delta, seed=self.seed)
+        if isinstance(warmup_depths, (list, tuple)):
+            items = [self._depth_arg(d, "warmup_depths") for d in warmup_depths]
+            warmup_depths = torch.stack(items) if torch.is_tensor(items[0]) else np.stack(items)
+        warmup_depths = self._depth_arg(warmup_depths, "warmup_depths")
+        if warmup_depths is not None:
+            kw["warmup_depths"] = warmup_depths
         self._prompt = prompt
         self._matte_skip = 0               # (`stream.prepare` primes the matte's delay line through the tap, when one is set)
         self._lock_init, self._lock_last = True, None      # an "ema" colour lock starts again; a reference image's state stays
@@ -969,37 +1046,44 @@ class StreamAnimateDiffusionDepthWrapper:
         return (frames.clip(-1, 1) + 1) / 2
 
     # ------------------------------------------------------------------ frames
-    def __call__(self, image=None, prompt: Optional[str] = None):
-        return self.img2img(image, prompt)
+    def __call__(self, image=None, prompt: Optional[str] = None, depth=None):
+        return self.img2img(image, prompt, depth)
 
-    def img2img(self, image, prompt: Optional[str] = None):
+    def img2img(self, image, prompt: Optional[str] = None, depth=None):
         """image: a path, a PIL image (resized to (width, height) on the host like the reference, :264-267), a uint8 HWC array /
         tensor of any size (resize + centre crop on the device), a JPEG file as `bytes` / `bytearray` / `memoryview` (decoded on the
         device, then treated as that uint8 frame; a damaged scan raises ValueError where the output is fetched), or a float
-        [3,H,W] tensor in [0, 1] (the reference's input)."""
+        [3,H,W] tensor in [0, 1] (the reference's input).  depth: the frame's own depth frame in place of the detector's -- a uint16
+        or float32 [Hd,Wd] array or tensor of any size, on the host or on the device, a PIL image of mode "I;16", "I", "F" or "L",
+        or a path to one -- read as `set_depth_input` says; frames with and without it may alternate (not under
+        `depth_source="input"`, where a frame without raises ValueError).  A frame the near-duplicate filter drops ignores it."""
+        depth = self._depth_arg(depth)
+        dk = {} if depth is None else {"depth": depth}
         if prompt is not None:
             self._update_prompt(prompt)
         self._camera_begin(image)
         line = self._matte_line
         if line is None and self._lock is None and self._size is None:
-            return self.postprocess_image(self.stream(self.preprocess_image(image)), output_type=self.output_type)
+            return self.postprocess_image(self.stream(self.preprocess_image(image), **dk), output_type=self.output_type)
         if line is None:
             # a frame the near-duplicate filter dropped comes back as the very tensor of the output before
             before = getattr(self.stream, "prev_image_result", None)
-            out = self.stream(self.preprocess_image(image))
+            out = self.stream(self.preprocess_image(image), **dk)
             return self._finish(out, None, repeated=before is not None and out is before)
         seen = line.tapped
-        out = self.stream(self.preprocess_image(image))
+        out = self.stream(self.preprocess_image(image), **dk)
         # a frame the near-duplicate filter dropped never reached the tap: the repeated output keeps its slot
         fresh = line.tapped > seen
         return self._finish(out, line.take() if fresh else line.last, repeated=not fresh)
 
-    def push(self, image, prompt: Optional[str] = None) -> None:
-        """pipelined mode (`frame_pipelining=True`): start a frame's encode / depth path; `pop()` returns the oldest frame's output"""
+    def push(self, image, prompt: Optional[str] = None, depth=None) -> None:
+        """pipelined mode (`frame_pipelining=True`): start a frame's encode / depth path; `pop()` returns the oldest frame's output.
+        `depth`: as `img2img`'s; its ingest runs on the side stream with the rest of the depth path."""
+        depth = self._depth_arg(depth)
         if prompt is not None:
             self._update_prompt(prompt)
         self._camera_begin(image)
-        self.stream.push(self.preprocess_image(image))
+        self.stream.push(self.preprocess_image(image), **({} if depth is None else {"depth": depth}))
         if self.io is not None and self.io.last_view is not None:
             # push() ran the ingest on this stream before ordering the side stream behind it; the side stream reads the slot
             # until the event push recorded behind its two encodes

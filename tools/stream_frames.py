@@ -5,7 +5,13 @@
 Follows the reference's test.py: the first `--skip` (2) frames are dropped, the next 8 are the warm-up window, and because the
 stream batch holds `batch_size` denoising steps in flight, the output of call t belongs to input frame t - (batch_size - 1)
 (test.py:101,169-174): the first batch_size - 1 outputs are discarded and as many trailing frames are fed again to flush.
-Frames of any size are resized + centre-cropped on the device (frame_io.HipFrameIO).  Prints `inference_time_ema`."""
+Frames of any size are resized + centre-cropped on the device (frame_io.HipFrameIO).  Prints `inference_time_ema`.
+
+    ... --depth depth/ [--depth-kind distance --depth-range 300,5000]
+
+takes every frame's conditioning depth from a 16-bit PNG of the same file name (any size; 0 marks a hole) instead of the built-in
+detector, which is then not even built (`depth_source="input"`, depth_io.py); with an .npy input, `--depth` is an .npy stack
+[F,Hd,Wd] of uint16 or float32."""
 import argparse
 import os
 import sys
@@ -36,6 +42,31 @@ def read_frames(path: str) -> np.ndarray:
     return np.stack(frames)
 
 
+def read_depths(path: str, input_path: str) -> np.ndarray:
+    """uint16 / float32 [F,Hd,Wd]: one depth frame per frame of `input_path`, matched by file name"""
+    if path.endswith(".npy"):
+        arr = np.load(path)
+        if arr.dtype not in (np.uint16, np.float32) or arr.ndim != 3:
+            raise ValueError(f"{path}: expected uint16 or float32 [F,Hd,Wd], got {arr.dtype} {arr.shape}")
+        return arr
+    if input_path.endswith(".npy"):
+        raise ValueError("--depth: an .npy input has no file names to match: give the depth frames as an .npy stack too")
+    from PIL import Image
+    by_stem = {os.path.splitext(n)[0]: n for n in os.listdir(path) if n.lower().endswith(".png")}
+    frames = []
+    for n in sorted(n for n in os.listdir(input_path) if n.lower().endswith(EXTS)):
+        stem = os.path.splitext(n)[0]
+        if stem not in by_stem:
+            raise FileNotFoundError(f"--depth: {path} has no {stem}.png for the frame {n}")
+        img = Image.open(os.path.join(path, by_stem[stem]))
+        if img.mode not in ("I;16", "I;16L", "I;16B", "I"):
+            raise ValueError(f"--depth: {by_stem[stem]} is no 16-bit PNG (mode {img.mode!r})")
+        frames.append(np.asarray(img).astype(np.uint16))
+    if len({f.shape for f in frames}) != 1:
+        raise ValueError(f"{path}: depth frames differ in size")
+    return np.stack(frames)
+
+
 def align(outputs, batch_size: int):
     """outputs of the calls -> outputs per input frame: drop the first batch_size - 1 (test.py:169-174)"""
     return outputs[batch_size - 1:]
@@ -53,6 +84,9 @@ def main(argv=None):
     ap.add_argument("--engine-dir", default="engines")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--full-vae", action="store_true", help="the SD AutoencoderKL instead of the tiny VAE")
+    ap.add_argument("--depth", default=None, help="folder of 16-bit PNGs named like the frames (or .npy [F,Hd,Wd]): depth from the caller")
+    ap.add_argument("--depth-kind", default="distance", choices=("distance", "inverse"))
+    ap.add_argument("--depth-range", default=None, help="A,B: a fixed (near, far) / (lo, hi) in the units of the samples; default: per frame")
     args = ap.parse_args(argv)
 
     from PIL import Image
@@ -63,18 +97,26 @@ def main(argv=None):
     frames = read_frames(args.input)[args.skip:]
     if len(frames) <= sink:
         raise ValueError(f"{len(frames)} frames after --skip: need more than the {sink} warm-up frames")
+    depths, more = None, {}
+    if args.depth is not None:
+        depths = read_depths(args.depth, args.input)[args.skip:]
+        if len(depths) != len(frames):
+            raise ValueError(f"--depth: {len(depths)} depth frames for {len(frames)} frames")
+        rng = None if args.depth_range is None else tuple(float(v) for v in args.depth_range.split(","))
+        more = dict(depth_source="input", depth_input=dict(kind=args.depth_kind, invalid=0, range=rng))
     w = StreamAnimateDiffusionDepthWrapper(args.config, few_step_model_type="lcm", num_inference_steps=cfg.get("num_inference_steps", 50),
                                            t_index_list=cfg.get("t_index_list"), strength=cfg.get("strength"), output_type="u8",
                                            height=args.height, width=args.width, use_tiny_vae=not args.full_vae, seed=args.seed,
-                                           engine_dir=args.engine_dir)
+                                           engine_dir=args.engine_dir, **more)
     prompt = args.prompt if args.prompt is not None else str(cfg.get("prompt", ""))
     os.makedirs(args.output, exist_ok=True)
-    warm = w.prepare(frames[:sink], prompt)
+    warm = w.prepare(frames[:sink], prompt, warmup_depths=None if depths is None else depths[:sink])
     for i, f in enumerate(warm):
         Image.fromarray((f.float().cpu().numpy() * 255).round().astype("uint8")).save(os.path.join(args.output, f"{i:05d}.png"))
     rest = frames[sink:]
     feed = list(rest) + [rest[-1]] * (w.batch_size - 1)                   # flush the frames still in the stream batch
-    outs = align([w(f) for f in feed], w.batch_size)
+    dfeed = [None] * len(feed) if depths is None else list(depths[sink:]) + [depths[-1]] * (w.batch_size - 1)
+    outs = align([w(f, depth=d) for f, d in zip(feed, dfeed)], w.batch_size)
     for i, o in enumerate(outs):
         Image.fromarray(o).save(os.path.join(args.output, f"{sink + i:05d}.png"))
     print(f"{len(warm)} warm-up + {len(outs)} frames -> {args.output}; inference_time_ema {w.stream.inference_time_ema * 1e3:.2f} ms "
