@@ -487,6 +487,23 @@ enum {
  *   constant frame); with L2D_DEPTH_FIXED_RANGE, mx <= mn only.
  *   Refused: a null or misaligned pointer, a non-positive size, H W % 8 != 0, 3 B H W >= 2^31, unknown flags, a partial count
  *   that is not B tiles, a NaN in the fixed range.
+ *
+ * Backdrop (backdrop.hip; no counterpart in the reference): the source frame blurred with the subject left out, as the kept part
+ *   of the matte composite -- p1 of L2D_OP_FRAME_MATTE, or through L2D_OP_FRAME_RESIZE p1 of L2D_OP_FRAME_MATTE_UP.
+ * L2D_OP_FRAME_BACKDROP_BLUR  one launch:  p0 source half [3][H][W] p1 depth half [H][W] p2 out half [3][H][W] (all 16-byte
+ *   aligned; p2 overlaps neither input) ; i0 H i1 W (W % 8 == 0, 3 H W < 2^31) i2 r (1..L2D_BACKDROP_MAX_R) i3 passes
+ *   (1..L2D_BACKDROP_MAX_PASSES) i4 flags (L2D_MATTE_HARD | _FAR) ; f0 lo f1 inv (as L2D_OP_FRAME_MATTE's).  Exact integers, so
+ *   that numpy restates it bit for bit (live2diff_amd/backdrop.py blur_ref, frame_of): P[c] = L2D_OP_FRAME_EGRESS' bytes of
+ *   channel c of p0; M = rint(255 m) with m as L2D_OP_FRAME_MATTE forms it in front of the feather; W = 256 - M, 1..256, never 0;
+ *   then `passes` times, with n = (2r+1)^2 and sums over the (2r+1) x (2r+1) window, coordinates clamped to the image:
+ *   D = sum W, N[c] = sum W P[c], P[c] = (2 N[c] + D) / (2 D) (floor: the weighted mean, rounded half up), W = (D + n - 1) / n
+ *   (floor: 1..256 again); 2 N + D <= 2 n 256 255 + 256 n < 2^32.  out[c] = half(float(P[c]) float(2 / 255) - 1), two fp32
+ *   operations and one rounding: the value L2D_OP_FRAME_EGRESS' expression maps back to the byte P[c].  One work-group per
+ *   16 x 64 tile; the three byte planes and W - 1 as a byte of the tile and a halo of passes r in LDS, every pass there on a
+ *   region that shrinks by r, the sums separably.  Every element of p2 is written by a plain 16-byte store on every launch:
+ *   nothing has to be zeroed.  Refused: a null or misaligned pointer, W % 8 != 0, 3 H W >= 2^31, r outside
+ *   1..L2D_BACKDROP_MAX_R, passes outside 1..L2D_BACKDROP_MAX_PASSES, unknown flags, p2 overlapping p0 or p1, lo / inv as
+ *   L2D_OP_FRAME_MATTE refuses them.
  */
 enum {
     L2D_OP_IGEMM = 1,
@@ -542,6 +559,7 @@ enum {
     L2D_OP_FRAME_DETAIL = 51,
     L2D_OP_DEPTH_INGEST = 52,
     L2D_OP_DEPTH_NORMALIZE = 53,
+    L2D_OP_FRAME_BACKDROP_BLUR = 54,
 };
 
 /* flag bits of L2D_OP_FRAME_MATTE (i4) and L2D_OP_FRAME_MATTE_UP (i6); HARD and FAR also of L2D_OP_FRAME_MATTE_EDGE (i3) */
@@ -551,6 +569,10 @@ enum {
 #define L2D_MATTE_PLANE 16 /* p2 is a float plane of ready matte values (8 is not assigned) */
 #define L2D_MATTE_MAX_R 8
 #define L2D_MATTE_EDGE_MAX_R 8 /* the largest radius of L2D_OP_FRAME_MATTE_EDGE */
+
+/* sizes of L2D_OP_FRAME_BACKDROP_BLUR (its flags, i4, are L2D_MATTE_HARD | _FAR) */
+#define L2D_BACKDROP_MAX_R 8
+#define L2D_BACKDROP_MAX_PASSES 3
 
 /* flag bits of L2D_OP_COLOR_LOCK (i2), and the sizes both colour-lock ops share */
 #define L2D_COLOR_LOCK_INIT 1

@@ -34,6 +34,7 @@ OP_FRAME_STEADY = 48
 OP_FRAME_MATTE_EDGE = 49
 OP_FRAME_DETAIL_GAIN, OP_FRAME_DETAIL = 50, 51
 OP_DEPTH_INGEST, OP_DEPTH_NORMALIZE = 52, 53
+OP_FRAME_BACKDROP_BLUR = 54
 ABI_VERSION = 6
 
 

@@ -180,17 +180,20 @@ def _unit(x) -> np.ndarray:
 
 
 def composite_ref(styled, source, depth, lo: float, hi: float, feather: int = 0, keep: str = "near", show: bool = False, *,
-                  edge: Optional[dict] = None) -> np.ndarray:
+                  edge: Optional[dict] = None, backdrop=None) -> np.ndarray:
     """L2D_OP_FRAME_MATTE on the host: fp16 [B,3,H,W] `styled` and `source` in [-1, 1] + fp16 [B,H,W] `depth` -> uint8 [B,H,W,3].
     o = v_c + m (v_s - v_c) in three fp32 operations, byte = round_half_even(255 o); `show` writes round_half_even(255 m) to all
     three channels.  Both v are multiples of 2^-24 in [0, 1], so v_s - v_c is exact: m == 1 gives the bytes of
     `egress_ref(styled)` and m == 0 those of `egress_ref(source)`, whatever the feather radius.  `edge` ({radius, eps}): the matte
-    refined by `source` first (`edge_ref`)."""
+    refined by `source` first (`edge_ref`).  `backdrop` (fp16 [B,3,H,W], backdrop.py): v_c is taken from it in place of
+    `source`; the guide of `edge` stays the real `source`."""
     m = matte_ref(depth, lo, hi, feather, keep, edge=edge, source=source if edge is not None else None)[..., None]
     scale = np.float32(255.0)
     if show:
         return np.rint(np.repeat(m, 3, axis=-1) * scale).astype(np.uint8)
-    vs, vc = _unit(styled), _unit(source)
+    vs, vc = _unit(styled), _unit(source if backdrop is None else backdrop)
+    if vs.shape != vc.shape:
+        raise ValueError(f"composite_ref: the styled frame is {vs.shape}, the kept part {vc.shape}")
     o = vc + m * (vs - vc)
     assert o.dtype == np.float32
     return np.rint(o * scale).astype(np.uint8)
@@ -239,21 +242,21 @@ def matte_up_ref(m: np.ndarray, out_height: int, out_width: int) -> np.ndarray:
 
 
 def composite_up_ref(styled_u8, camera_u8, depth, lo: float, hi: float, feather: int = 0, keep: str = "near",
-                     show: bool = False, *, edge: Optional[dict] = None, source=None) -> np.ndarray:
+                     show: bool = False, *, edge: Optional[dict] = None, source=None, backdrop=None) -> np.ndarray:
     """L2D_OP_FRAME_MATTE_UP on the host: uint8 [B,Ho,Wo,3] `styled_u8` (the styled frame at the output size) and `camera_u8` (the
     camera's own pixels at that size) + fp16 [B,H,W] `depth` -> uint8 [B,Ho,Wo,3].  M = matte_up_ref(matte_ref(depth, ...)),
     o = C + M (S - C) on the bytes as fp32 -- S - C is exact, then one multiplication and one addition --, byte =
     round_half_even(o); `show` writes round_half_even(255 M) to all three channels.  Rounding is monotone and 0 <= M <= 1, so o
     lies between C and S and nothing is clamped (asserted); M == 1 gives S and M == 0 gives C exactly.  `edge` ({radius, eps},
     with the stream-sized fp16 [B,3,H,W] `source` frames): the matte is refined at the stream's size (`edge_ref`) and sampled
-    as before."""
+    as before.  `backdrop` (uint8 [B,Ho,Wo,3], backdrop.py): C is taken from it in place of `camera_u8`, which may then be None."""
     def u8(x):
         x = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
         if x.dtype != np.uint8 or x.ndim not in (3, 4) or x.shape[-1] != 3:
             raise ValueError(f"composite_up_ref: expected uint8 [B,Ho,Wo,3], got {x.dtype} {x.shape}")
         return x[None] if x.ndim == 3 else x
 
-    S, C = u8(styled_u8), u8(camera_u8)
+    S, C = u8(styled_u8), u8(camera_u8 if backdrop is None else backdrop)
     if S.shape != C.shape:
         raise ValueError(f"composite_up_ref: the styled frame is {S.shape}, the camera frame {C.shape}")
     M = matte_up_ref(matte_ref(depth, lo, hi, feather, keep, edge=edge, source=source), S.shape[1], S.shape[2])[..., None]
@@ -410,6 +413,16 @@ class HipMatteEdge:
                                     E=edge_E(e["radius"], e["eps"]), lo32=lo32, inv32=inv32, hard=hard, far=settings["keep"] == "far")
 
 
+def _backdrop_parts(backdrop, default):
+    """(tensor, records) of a composite's `backdrop=`: None (the `default` tensor), a tensor, or (tensor, [(op, keep), ...])"""
+    if backdrop is None:
+        return default, ()
+    if torch.is_tensor(backdrop):
+        return backdrop, ()
+    tensor, records = backdrop
+    return tensor, tuple(records)
+
+
 class HipMatte:
     """Static output buffers and the launch of one `(H, W)` stream: `composite` is `HipFrameIO.egress` with a source frame and a
     depth plane beside the image.  Everything runs on `torch.cuda.current_stream()`."""
@@ -422,26 +435,34 @@ class HipMatte:
         self.host = None if ops.DRY_RUN else torch.empty(1, self.height, self.width, 3, dtype=torch.uint8).pin_memory()
         self.edge = None                       # HipMatteEdge, made by the first frame with an edge setting
 
-    def composite(self, image: torch.Tensor, slot: _Slot, settings: dict, to_host: bool = True, edge: Optional[dict] = None):
+    def composite(self, image: torch.Tensor, slot: _Slot, settings: dict, to_host: bool = True, edge: Optional[dict] = None,
+                  backdrop=None):
         """fp16 [3,H,W] on the device + a `MatteLine` slot -> uint8 [H,W,3]: a numpy view of the pinned buffer (valid until the next
         call), or with `to_host=False` the static device tensor.  `edge` ({radius, eps}): the matte refined by the slot's source
-        frame first -- one more launch in front, and the composite reads its plane."""
+        frame first -- one more launch in front, and the composite reads its plane.  `backdrop` (an fp16 [3,H,W] device tensor,
+        or `(tensor, records)` as `backdrop.HipBackdrop.stream` returns it): the tensor goes where `slot.source` goes in the
+        composite op, the records in front of it in the same list; the edge op keeps reading the slot's real source."""
         H, W = self.height, self.width
         if image.dtype != torch.float16 or tuple(image.shape) != (3, H, W):
             raise ValueError(f"composite: expected fp16 [3,{H},{W}], got {image.dtype} {tuple(image.shape)}")
         if not image.is_contiguous():
             image = image.contiguous()
+        kept, records = _backdrop_parts(backdrop, slot.source)
+        if kept.dtype != torch.float16 or tuple(kept.shape) != (3, H, W) or not kept.is_contiguous():
+            raise ValueError(f"composite: expected a contiguous fp16 [3,{H},{W}] backdrop, got {kept.dtype} {tuple(kept.shape)}")
         pl = _lib.OpList()
+        for op, keep in records:
+            pl.append(op, *keep)
         if edge is not None:
             if self.edge is None:
                 self.edge = HipMatteEdge(H, W, device=self.device)
             op, keep = self.edge.op(slot, settings, edge)
             pl.append(op, *keep)
-            op, keep = ops.frame_matte(image, slot.source, None, self.dev, B=1, H=H, W=W, show=settings["show"], r=settings["feather"],
+            op, keep = ops.frame_matte(image, kept, None, self.dev, B=1, H=H, W=W, show=settings["show"], r=settings["feather"],
                                        plane=self.edge.plane)
         else:
             lo32, inv32, hard = matte_params(settings["lo"], settings["hi"])
-            op, keep = ops.frame_matte(image, slot.source, slot.depth, self.dev, B=1, H=H, W=W, lo32=lo32, inv32=inv32, hard=hard,
+            op, keep = ops.frame_matte(image, kept, slot.depth, self.dev, B=1, H=H, W=W, lo32=lo32, inv32=inv32, hard=hard,
                                        far=settings["keep"] == "far", show=settings["show"], r=settings["feather"])
         pl.append(op, *keep)
         pl.run()
@@ -465,16 +486,23 @@ class HipMatteUp:
         self.host = None if ops.DRY_RUN else torch.empty(1, self.out_height, self.out_width, 3, dtype=torch.uint8).pin_memory()
         self.edge = None                       # HipMatteEdge, made by the first frame with an edge setting
 
-    def composite(self, styled_u8: torch.Tensor, slot: _Slot, settings: dict, to_host: bool = True, edge: Optional[dict] = None):
+    def composite(self, styled_u8: torch.Tensor, slot: _Slot, settings: dict, to_host: bool = True, edge: Optional[dict] = None,
+                  backdrop=None):
         """uint8 [Ho,Wo,3] on the device + a `MatteLine` slot that carries a camera buffer -> uint8 [Ho,Wo,3]: a numpy view of the
         pinned buffer (valid until the next call), or with `to_host=False` the static device tensor.  `edge` ({radius, eps}): the
-        matte refined at the stream's size by the slot's stream-sized source frame first, then sampled as before."""
+        matte refined at the stream's size by the slot's stream-sized source frame first, then sampled as before.  `backdrop` (a
+        uint8 [Ho,Wo,3] device tensor, or `(tensor, records)` as `backdrop.HipBackdrop.output` returns it): the tensor goes where
+        the slot's camera buffer goes in the composite op -- the slot then needs none --, the records in front of it."""
         Ho, Wo = self.out_height, self.out_width
-        camera = slot.camera.data
+        camera, records = _backdrop_parts(backdrop, None)
+        if camera is None:
+            camera = slot.camera.data
         for name, t in (("styled", styled_u8), ("camera", camera)):
             if t.dtype != torch.uint8 or tuple(t.shape) != (Ho, Wo, 3) or not t.is_contiguous():
                 raise ValueError(f"composite: expected a contiguous uint8 [{Ho},{Wo},3] {name} frame, got {t.dtype} {tuple(t.shape)}")
         pl = _lib.OpList()
+        for op, keep in records:
+            pl.append(op, *keep)
         if edge is not None:
             if self.edge is None:
                 self.edge = HipMatteEdge(self.height, self.width, device=self.device)

@@ -1488,6 +1488,35 @@ def frame_matte_edge(source, depth, out, *, H, W, r, E, lo32, inv32, hard, far=F
     return op, keep
 
 
+# ----------------------------------------------------------------------------- backdrop blur (backdrop.hip, backdrop.py)
+BACKDROP_MAX_R = 8                               # l2d.h L2D_BACKDROP_MAX_R
+BACKDROP_MAX_PASSES = 3                          # l2d.h L2D_BACKDROP_MAX_PASSES
+
+
+def frame_backdrop_blur(source, depth, out, *, H, W, r, passes, lo32, inv32, hard, far=False):
+    """fp16 [3,H,W] `source` + fp16 [H,W] `depth` -> fp16 [3,H,W] `out`: the source frame blurred with the matte's subject left
+    out, as a frame `frame_matte` takes for its kept part (backdrop.frame_of(backdrop.blur_ref(...))).  `r`: the radius,
+    1..BACKDROP_MAX_R; `passes`: 1..BACKDROP_MAX_PASSES; `lo32, inv32, hard` as `matte.matte_params` returns them."""
+    _lock_frame("frame_backdrop_blur: source", source, H, W)
+    _lock_frame("frame_backdrop_blur: out", out, H, W)
+    if depth.dtype != torch.float16 or depth.numel() != H * W or not depth.is_contiguous():
+        raise ValueError(f"frame_backdrop_blur: depth: expected a contiguous fp16 [{H},{W}] plane, got {depth.dtype} {tuple(depth.shape)}")
+    if isinstance(r, bool) or int(r) != r or not 1 <= int(r) <= BACKDROP_MAX_R:
+        raise ValueError(f"frame_backdrop_blur: r={r!r}: use an integer from 1 to {BACKDROP_MAX_R}")
+    if isinstance(passes, bool) or int(passes) != passes or not 1 <= int(passes) <= BACKDROP_MAX_PASSES:
+        raise ValueError(f"frame_backdrop_blur: passes={passes!r}: use an integer from 1 to {BACKDROP_MAX_PASSES}")
+    op = L2dOp()
+    op.kind = _lib.OP_FRAME_BACKDROP_BLUR
+    keep = (source, depth, out)
+    for j, t in enumerate(keep):
+        op.p[j] = _ptr(t)
+    flags = (MATTE_HARD if hard else 0) | (MATTE_FAR if far else 0)
+    for j, v in enumerate([H, W, r, passes, flags]):
+        op.i[j] = int(v)
+    op.f[0], op.f[1] = float(lo32), float(inv32)
+    return op, keep
+
+
 # ----------------------------------------------------------------------------- colour lock (colorlock.hip, color_lock.py)
 COLOR_LOCK_INIT, COLOR_LOCK_SOURCE, COLOR_LOCK_FREEZE = 1, 2, 4      # l2d.h L2D_COLOR_LOCK_*
 COLOR_LOCK_BLOCK_PIXELS = 4096                                       # l2d.h L2D_COLOR_LOCK_BLOCK_PIXELS

@@ -23,6 +23,7 @@ with Pillow's arithmetic, behind both and in front of the JPEG encoder or the co
 `set_steady` holds the previous output pixel where the frame's source did not move (steady.py), behind the colour lock.
 `set_matte_edge` refines the matte by the source frame, so that its edges land on the frame's own (matte.edge_ref).
 `set_detail` brings the camera's fine detail into the frame at the output size, behind the resize (detail.py).
+`set_backdrop` puts the room blurred, a colour or an image behind the matte in place of the real frame (backdrop.py).
 `wrapper(image, depth=d)` conditions a frame on the caller's own depth frame -- an RGB-D camera's, another estimator's -- instead
 of the built-in detector's; `set_depth_input` says how it is read, `depth_source="input"` builds no detector at all (depth_io.py).
 
@@ -303,6 +304,10 @@ class StreamAnimateDiffusionDepthWrapper:
     _matte_edge = None                      # the edge-aware matte's settings (set_matte_edge), None: off
     _detail = None                          # the detail mode's settings (set_detail), None: off
     _detail_dev = None                      # detail.HipDetail of the current output size, made by the first frame that needs it
+    _backdrop = None                        # the backdrop's settings (set_backdrop), None: the real frame stands behind the matte
+    _backdrop_image = None                  # the image of an "image" backdrop, as the caller gave it
+    _backdrop_dev = None                    # backdrop.HipBackdrop, made by the first frame that needs it on the device
+    _backdrop_host = None                   # {(height, width, filter): uint8 frame} of the image on the host route
     depth_source = "detector"               # "input": every frame brings its own depth and no detector was built (`_setup` sets it)
 
     def __init__(self, config_path: str, few_step_model_type: str, num_inference_steps: int,
@@ -317,7 +322,7 @@ class StreamAnimateDiffusionDepthWrapper:
                  jpeg_quality: int = 75, jpeg_decode: str = "device", output_size: Optional[Tuple[int, int]] = None,
                  output_resample: str = "lanczos", matte_source: str = "stream", steady: Optional[dict] = None,
                  matte_edge: Optional[dict] = None, detail: Optional[dict] = None, depth_input: Optional[dict] = None,
-                 depth_source: str = "detector"):
+                 depth_source: str = "detector", backdrop: Optional[dict] = None):
         _check_depth_source(depth_source)
         self._check_keywords(few_step_model_type=few_step_model_type, acceleration=acceleration, cfg_type=cfg_type,
                              use_denoising_batch=use_denoising_batch, frame_buffer_size=frame_buffer_size, device_ids=device_ids,
@@ -338,13 +343,14 @@ class StreamAnimateDiffusionDepthWrapper:
                     similar_image_filter_threshold=similar_image_filter_threshold,
                     similar_image_filter_max_skip_frame=similar_image_filter_max_skip_frame, jpeg_quality=jpeg_quality,
                     jpeg_decode=jpeg_decode, output_size=output_size, output_resample=output_resample, matte_source=matte_source,
-                    steady=steady, matte_edge=matte_edge, detail=detail, depth_input=depth_input, depth_source=depth_source)
+                    steady=steady, matte_edge=matte_edge, detail=detail, depth_input=depth_input, depth_source=depth_source,
+                    backdrop=backdrop)
 
     @classmethod
     def from_components(cls, pipe, *, num_inference_steps: int, t_index_list: Optional[List[int]] = None,
                         strength: Optional[float] = None, **kw):
         """The wrapper around an already assembled `pipe` namespace (tests, synthetic weights).  Keywords: those of the
-        constructor that do not name files (`jpeg_quality`, `jpeg_decode`, `output_size`, `output_resample`, `matte_source`, `steady`, `matte_edge`, `detail`, `depth_input` and `depth_source` among them; with `depth_source="input"` the namespace needs no `depth_model`), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
+        constructor that do not name files (`jpeg_quality`, `jpeg_decode`, `output_size`, `output_resample`, `matte_source`, `steady`, `matte_edge`, `detail`, `backdrop`, `depth_input` and `depth_source` among them; with `depth_source="input"` the namespace needs no `depth_model`), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
         self = cls.__new__(cls)
         cls._check_keywords(**{k: kw.pop(k) for k in ("acceleration", "cfg_type", "use_denoising_batch", "frame_buffer_size",
                                                       "device_ids", "opt_unet", "few_step_model_type") if k in kw},
@@ -385,8 +391,10 @@ class StreamAnimateDiffusionDepthWrapper:
                scheduler_kwargs=None, frame_pipelining=False, enable_similar_image_filter=False,
                similar_image_filter_threshold=0.98, similar_image_filter_max_skip_frame=10, jpeg_quality=75, jpeg_decode="device",
                output_size=None, output_resample="lanczos", matte_source="stream", steady=None, matte_edge=None, detail=None,
-               depth_input=None, depth_source="detector"):
+               depth_input=None, depth_source="detector", backdrop=None):
         self._check_matte_source(matte_source)
+        if backdrop is not None and not isinstance(backdrop, dict):
+            raise ValueError(f"backdrop={backdrop!r}: use a dict of set_backdrop's keywords, or None")
         _check_depth_source(depth_source)
         if depth_input is not None and not isinstance(depth_input, dict):
             raise ValueError(f"depth_input={depth_input!r}: use a dict of set_depth_input's keywords, or None")
@@ -437,6 +445,8 @@ class StreamAnimateDiffusionDepthWrapper:
             self.set_matte_edge(**matte_edge)
         if detail is not None:
             self.set_detail(**detail)
+        if backdrop is not None:
+            self.set_backdrop(**backdrop)
         self.depth_source = depth_source
         if depth_source == "input":
             self.stream.depth_detector = None      # (a `pipe` that brought one: it is never called)
@@ -578,6 +588,82 @@ class StreamAnimateDiffusionDepthWrapper:
         for dev in (self._matte_dev, self._matte_up):
             if dev is not None:
                 dev.edge = None
+
+    # ------------------------------------------------------------------ backdrop (backdrop.py)
+    @property
+    def backdrop(self) -> Optional[dict]:
+        """the current backdrop as {to: "blur" | "color" | "image", radius, passes, color}, or None"""
+        return None if self._backdrop is None else dict(self._backdrop)
+
+    def set_backdrop(self, to="blur", *, radius: int = 6, passes: int = 3, color=None) -> None:
+        """What stands behind the matte, in place of the real frame.  `to="blur"`: the room blurred ("portrait mode") -- the
+        frame's own source, blurred `passes` (1..3) times by a (2 `radius` + 1)^2 box (1..8) in which the matte's subject
+        counts 1/256 of a background pixel, so its colours do not bleed into the room around the silhouette
+        (`backdrop.blur_ref`); an `(r, g, b)` triple of bytes: that colour, for a chroma key further down (also
+        `to="color", color=(r, g, b)`, the form the `backdrop` property has); an image -- a uint8 [H,W,3] array, a PIL image or a
+        path, decoded here (a file that is no image raises ValueError now, not at a frame): its largest centred window of
+        the frame's aspect ratio, resampled with the output size's filter (`backdrop.image_ref`), prepared once per size; a
+        device uint8 tensor of the frame's size ([Ho,Wo,3] where the matte composites at the output size, else [H,W,3], or
+        fp16 [3,H,W]) is used in place, so a caller can change its content between frames at no host cost.  Such a tensor is
+        checked here against the stream's size and the output size set at this moment (`backdrop.check_tensor`); which of
+        the two sizes a frame needs is known only when it leaves -- a frame without a camera buffer, such as the first
+        N - 1 outputs, takes the stream-sized composite even under `set_matte_source("camera")` -- and a tensor of the other
+        size raises ValueError at that frame.  A uint8 tensor on the host is copied like an array.  A setting beside the matte, like `set_matte_edge`: it acts only while a matte is set,
+        on its output types; `show=True` is unaffected; feather and edge refinement shape the composite as before, and the
+        edge refinement keeps reading the real source frame.  The route of a frame does not change: where it takes the
+        composite at the output size the backdrop at that size goes in as the kept part (a blur runs at the stream's size
+        and is resampled), otherwise the stream-sized backdrop goes into the stream-sized composite.  On the device a blur is
+        one more launch in front of the composite's (two at an output size), no synchronisation.  A frame the
+        near-duplicate filter repeats is made again from the same slot: the same bytes.  May be called before or after
+        `prepare` and between any two frames; the change applies from the next output."""
+        from .backdrop import check_settings
+        if isinstance(to, str) and to == "color":
+            if color is None:
+                raise ValueError("backdrop: to='color' needs color=(r, g, b)")
+            to = tuple(color)
+        elif color is not None:
+            raise ValueError(f"backdrop: color={color!r} goes with to='color'")
+        if isinstance(to, str) and to == "image":
+            raise ValueError("backdrop: to='image': pass the image itself (an array, a PIL image, a path or a device tensor)")
+        settings = check_settings(to, radius, passes)
+        image = None
+        if settings["to"] == "image":
+            from .backdrop import check_tensor, load_image
+            on_device = getattr(self, "io", None) is not None
+            if torch.is_tensor(to) and (to.is_cuda or to.dtype == torch.float16):
+                size = self._size
+                check_tensor(to, self.height, self.width, None if size is None else (size["height"], size["width"]), on_device)
+                image = to
+            else:
+                image = load_image(to)           # (decoded now: a bad file is refused here)
+        if image is not self._backdrop_image:
+            self._backdrop_host = None
+        self._backdrop, self._backdrop_image = settings, image
+
+    def clear_backdrop(self) -> None:
+        """Back to the real frame behind the matte: no launch or buffer of the backdrop is left in the frame's path."""
+        self._backdrop = self._backdrop_image = self._backdrop_dev = self._backdrop_host = None
+
+    def _backdrop_filter(self) -> str:
+        return self._size["resample"] if self._size is not None else "lanczos"
+
+    def _backdrop_op(self, device):
+        """`backdrop.HipBackdrop` of the stream's size, made on first use"""
+        if self._backdrop_dev is None:
+            from .backdrop import HipBackdrop
+            self._backdrop_dev = HipBackdrop(self.height, self.width, device=device)
+        return self._backdrop_dev
+
+    def _backdrop_image_host(self):
+        """the image of an "image" backdrop for the host route's oracles: as given, or the prepared frame of (size, filter)"""
+        image = self._backdrop_image
+        if image is None or torch.is_tensor(image):
+            return image
+        key = (self.height, self.width, self._backdrop_filter())
+        if self._backdrop_host is None or key not in self._backdrop_host:
+            from .backdrop import image_ref
+            self._backdrop_host = {key: image_ref(image, *key)}
+        return self._backdrop_host[key]
 
     def _sync_camera(self) -> None:
         """Install the camera tap (`HipFrameIO.camera_tap`, `MatteLine.camera_source`) while an output size is set on the device
@@ -1179,14 +1265,20 @@ class StreamAnimateDiffusionDepthWrapper:
             give_detail = None
             if detail_slot is not None and size is not None:
                 give_detail = functools.partial(self._detail_op(size, dev).apply, slot=detail_slot, settings=self._detail)
+            bd = self._backdrop if slot is not None and not self._matte["show"] else None
             if camera:
                 stages.append(self._size_op(size, dev).resize)
                 if give_detail is not None:
                     stages.append(give_detail)
+                more = {} if bd is None else dict(backdrop=self._backdrop_op(dev).output(
+                    slot, self._matte, bd, size["height"], size["width"], self._backdrop_image, size["resample"]))
                 stages.append(functools.partial(self._matte_up_op(size, dev).composite, slot=slot, settings=self._matte,
-                                                edge=self._matte_edge))
+                                                edge=self._matte_edge, **more))
             elif slot is not None:
-                stages.append(functools.partial(self._matte_op(dev).composite, slot=slot, settings=self._matte, edge=self._matte_edge))
+                more = {} if bd is None else dict(backdrop=self._backdrop_op(dev).stream(
+                    slot, self._matte, bd, self._backdrop_image, self._backdrop_filter()))
+                stages.append(functools.partial(self._matte_op(dev).composite, slot=slot, settings=self._matte, edge=self._matte_edge,
+                                                **more))
             if size is not None and not camera:
                 stages.append(self._size_op(size, dev).resize)
                 if give_detail is not None:
@@ -1207,7 +1299,12 @@ class StreamAnimateDiffusionDepthWrapper:
         else:
             if slot is not None:
                 from .matte import composite_ref
-                u8 = composite_ref(image_tensor[:1], slot.source[None], slot.depth[None], **self._matte, edge=self._matte_edge)[0]
+                more = {}                   # (the keyword only with a backdrop: without one the call is the parent's)
+                if self._backdrop is not None and not self._matte["show"]:
+                    from .backdrop import stream_ref
+                    more["backdrop"] = stream_ref(self._backdrop, self._backdrop_image_host(), slot.source, slot.depth, self._matte,
+                                                  self._backdrop_filter())[None]
+                u8 = composite_ref(image_tensor[:1], slot.source[None], slot.depth[None], **self._matte, edge=self._matte_edge, **more)[0]
             else:
                 from .frame_io import egress_ref
                 u8 = egress_ref(image_tensor)[0].numpy()

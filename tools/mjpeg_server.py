@@ -57,7 +57,13 @@ camera frame's high-pass at the output size, added with the local regression slo
 windows of radius R in 1..8 pixels; EPS, default 2, is the contrast in byte levels below which a window counts as flat,
 STRENGTH, default 1, scales the injected term and LIMIT, default 64, bounds it in byte levels).  It acts only while an output
 size is set.  `POST /detail` with the same text as its body, or `off`, changes it while the stream runs; `GET /detail` answers
-the current settings as JSON (`null`: off)."""
+the current settings as JSON (`null`: off).
+
+`--backdrop blur[,R[,PASSES]] | RRGGBB | PATH` puts something else behind the matte than the real frame (`wrapper.set_backdrop`):
+the room blurred with the subject left out (PASSES boxes of radius R, defaults 6 and 3), a colour as six hex digits (for a
+chroma key further down), or an image file, cropped to the frame's aspect ratio.  It acts only while a matte is set.  `POST
+/backdrop` with the same text as its body changes it while the stream runs, an empty body (or `off`) clears it; `GET /backdrop`
+answers the current settings as JSON (`null`: off)."""
 import argparse
 import json
 import os
@@ -399,6 +405,61 @@ class DetailBox:
             self.failed += 1
 
 
+def parse_backdrop_arg(text: str):
+    """`blur[,R[,PASSES]]`, `RRGGBB` (six hex digits) or the path of an image file -> the keywords of `wrapper.set_backdrop`; `off`
+    or nothing -> None; ValueError otherwise.  The file is decoded here (`to` is its uint8 [H,W,3] array), so one that is no
+    image is refused by the option before anything is loaded and by `POST /backdrop` with a 400."""
+    from live2diff_amd.backdrop import MAX_PASSES, MAX_RADIUS, check_settings, load_image
+    text = text.strip()
+    if text in ("", "off"):
+        return None
+    parts = [t.strip() for t in text.split(",")]
+    if parts[0] == "blur":
+        if len(parts) > 3:
+            raise ValueError(f"backdrop {text!r}: use blur[,R[,PASSES]], RRGGBB, the path of an image, or off")
+        try:
+            radius, passes = (int(parts[i]) if len(parts) > i else d for i, d in ((1, 6), (2, 3)))
+        except ValueError:
+            raise ValueError(f"backdrop {text!r}: R is an integer from 1 to {MAX_RADIUS}, PASSES one from 1 to {MAX_PASSES}") from None
+        s = check_settings("blur", radius, passes)
+        return dict(to="blur", radius=s["radius"], passes=s["passes"])
+    if len(text) == 6 and all(c in "0123456789abcdefABCDEF" for c in text):
+        return dict(to=tuple(int(text[i:i + 2], 16) for i in (0, 2, 4)))
+    if not os.path.isfile(text):
+        raise ValueError(f"backdrop {text!r}: use blur[,R[,PASSES]], RRGGBB, the path of an image, or off (there is no such file)")
+    return dict(to=load_image(text))
+
+
+class BackdropBox:
+    """What `POST /backdrop` delivers: the newest requested backdrop (a dict of `set_backdrop` keywords, or None for an empty body
+    or `off`), applied by the producer between two frames.  `current` is what was last applied (the `backdrop` property);
+    `failed` counts requests the wrapper refused."""
+    _NOTHING = object()
+
+    def __init__(self, current=None):
+        self._lock = threading.Lock()
+        self.current, self._want, self.failed = current, self._NOTHING, 0
+
+    def put(self, settings) -> None:
+        with self._lock:
+            self._want = settings
+
+    def apply(self, wrapper) -> None:
+        """(producer thread, between frames)"""
+        with self._lock:
+            want, self._want = self._want, self._NOTHING
+        if want is self._NOTHING:
+            return
+        try:
+            if want is None:
+                wrapper.clear_backdrop()
+            else:
+                wrapper.set_backdrop(**want)
+            self.current = wrapper.backdrop
+        except ValueError:                         # (a file that is no image among them: `set_backdrop` decodes it)
+            self.failed += 1
+
+
 def parse_size_arg(text: str):
     """`WxH[,FILTER]` -> the keywords of `wrapper.set_output_size`, `off` -> None; ValueError otherwise (the wrapper, which knows
     the stream's size, checks the ratio once more)"""
@@ -526,9 +587,9 @@ class Latest:
 
 def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = None, mattes: "MatteBox" = None, colors: "ColorBox" = None,
                  sizes: "SizeBox" = None, sources: "MatteSourceBox" = None, steadies: "SteadyBox" = None, details: "DetailBox" = None,
-                 edges: "MatteEdgeBox" = None):
+                 backdrops: "BackdropBox" = None, edges: "MatteEdgeBox" = None):
     boxes = {"/matte": mattes, "/color": colors, "/size": sizes, "/matte-source": sources, "/steady": steadies, "/matte-edge": edges,
-             "/detail": details}
+             "/detail": details, "/backdrop": backdrops}
     page = PAGE if inbox is None else CAMERA_PAGE
 
     class Handler(BaseHTTPRequestHandler):
@@ -577,12 +638,17 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
             else:
                 self.send_error(404)
 
-        def do_matte(self, box=None, parse=parse_matte_arg):
+        def do_matte(self, box=None, parse=parse_matte_arg, empty=False):
             box = mattes if box is None else box
             try:
                 n = int(self.headers.get("Content-Length", ""))
             except ValueError:
                 self.send_error(411)
+                return
+            if n == 0 and empty:                          # (`/backdrop`: an empty body clears it)
+                box.put(None)
+                self.send_response(204)
+                self.end_headers()
                 return
             if not 1 <= n <= 256:
                 self.send_error(413 if n > 256 else 400)
@@ -640,6 +706,9 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
             if self.path == "/detail" and details is not None:
                 self.do_matte(details, parse_detail_arg)
                 return
+            if self.path == "/backdrop" and backdrops is not None:
+                self.do_matte(backdrops, parse_backdrop_arg, empty=True)
+                return
             if inbox is None or self.path != "/frame":
                 self.send_error(404)
                 return
@@ -664,9 +733,9 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
 
 def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: StyleBox = None, mattes: MatteBox = None,
             colors: ColorBox = None, sizes: SizeBox = None, sources: MatteSourceBox = None, steadies: SteadyBox = None,
-            details: DetailBox = None, edges: MatteEdgeBox = None) -> None:
+            details: DetailBox = None, backdrops: BackdropBox = None, edges: MatteEdgeBox = None) -> None:
     """the producer: loops `frames` through the wrapper until `stop` is set; a posted style, matte, colour lock, output size,
-    matte source, steady mode, matte edge or detail mode is applied between two frames"""
+    matte source, steady mode, matte edge, detail mode or backdrop is applied between two frames"""
     from live2diff_amd.jpeg import mjpeg_part
     try:
         i = 0
@@ -687,6 +756,8 @@ def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: Styl
                 edges.apply(wrapper)
             if details is not None:
                 details.apply(wrapper)
+            if backdrops is not None:
+                backdrops.apply(wrapper)
             latest.put(mjpeg_part(wrapper(frames[i % len(frames)])))
             i += 1
     finally:
@@ -695,7 +766,8 @@ def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: Styl
 
 def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: threading.Event, styles: StyleBox = None,
                    mattes: MatteBox = None, colors: ColorBox = None, sizes: SizeBox = None, sources: MatteSourceBox = None,
-                   steadies: SteadyBox = None, details: DetailBox = None, edges: MatteEdgeBox = None) -> None:
+                   steadies: SteadyBox = None, details: DetailBox = None, backdrops: BackdropBox = None,
+                   edges: MatteEdgeBox = None) -> None:
     """the producer of `--input post`: the first frames posted warm the stream up, then the newest posted frame goes through the
     wrapper, for ever; a frame the wrapper refuses (ValueError: a damaged file) is dropped and counted in `inbox.failed`"""
     from live2diff_amd.jpeg import mjpeg_part
@@ -724,6 +796,8 @@ def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: thr
                 edges.apply(wrapper)
             if details is not None:
                 details.apply(wrapper)
+            if backdrops is not None:
+                backdrops.apply(wrapper)
             try:
                 latest.put(mjpeg_part(wrapper(frame)))
             except ValueError:
@@ -771,6 +845,10 @@ def main(argv=None):
                     help="bring the camera's fine detail into the frame at the output size (windows of radius R, 1..8 pixels; EPS, default "
                          "2: the contrast in byte levels below which a window counts as flat; STRENGTH, default 1; LIMIT, default 64 byte "
                          "levels); acts while an output size is set; POST /detail with the same text, or `off`, changes it between frames")
+    ap.add_argument("--backdrop", default=None, metavar="blur[,R[,PASSES]]|RRGGBB|PATH",
+                    help="what stands behind the matte in place of the real frame: the room blurred with the subject left out (PASSES "
+                         "boxes of radius R, defaults 6 and 3), a colour as six hex digits, or an image file; acts while a matte is set; "
+                         "POST /backdrop with the same text changes it between frames, an empty body (or `off`) clears it")
     args = ap.parse_args(argv)
     style_args = [parse_style_arg(t) for t in args.style]
     matte = parse_matte_arg(args.matte) if args.matte else None
@@ -779,6 +857,7 @@ def main(argv=None):
     steady = parse_steady_arg(args.steady) if args.steady else None
     edge = parse_matte_edge_arg(args.matte_edge) if args.matte_edge else None
     detail = parse_detail_arg(args.detail) if args.detail else None
+    backdrop = parse_backdrop_arg(args.backdrop) if args.backdrop else None
 
     from stream_frames import read_frames
 
@@ -814,15 +893,18 @@ def main(argv=None):
     if detail is not None:
         w.set_detail(**detail)               # (before `prepare`: the line is primed, the first frames carry their camera frame)
     details = DetailBox(w.detail)
+    if backdrop is not None:
+        w.set_backdrop(**backdrop)
+    backdrops = BackdropBox(w.backdrop)
     prompt = args.prompt if args.prompt is not None else str(cfg.get("prompt", ""))
     latest, stop = Latest(), threading.Event()
     inbox = Inbox(sink) if post else None
     if post:
-        producer = threading.Thread(target=produce_posted, args=(w, prompt, inbox, latest, stop, styles, mattes, colors, sizes, sources, steadies, details, edges), name="producer", daemon=True)
+        producer = threading.Thread(target=produce_posted, args=(w, prompt, inbox, latest, stop, styles, mattes, colors, sizes, sources, steadies, details, backdrops, edges), name="producer", daemon=True)
     else:
         w.prepare(frames[:sink], prompt)
-        producer = threading.Thread(target=produce, args=(w, frames, latest, stop, styles, mattes, colors, sizes, sources, steadies, details, edges), name="producer", daemon=True)
-    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest, inbox, styles, mattes, colors, sizes, sources, steadies, details, edges))
+        producer = threading.Thread(target=produce, args=(w, frames, latest, stop, styles, mattes, colors, sizes, sources, steadies, details, backdrops, edges), name="producer", daemon=True)
+    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest, inbox, styles, mattes, colors, sizes, sources, steadies, details, backdrops, edges))
     server.daemon_threads = True
     producer.start()
     print(f"http://{args.host}:{args.port}/  ({args.height}x{args.width}, quality {args.quality}; Ctrl-C stops)")
