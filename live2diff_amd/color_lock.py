@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .frame_io import egress_ref
+from .frame_io import egress_ref, frame16
 
 MODES = ("source", "ema", "image")
 SERVED_OUTPUT_TYPES = ("pil", "pt", "np", "u8", "jpeg")
@@ -29,16 +29,8 @@ GAIN_MIN, GAIN_MAX = 0.25, 4.0
 
 # ----------------------------------------------------------------------------- reference arithmetic (CPU, numpy)
 def _frame16(x) -> np.ndarray:
-    """fp16 [3,H,W] of a [3,H,W] or [1,3,H,W] array / tensor"""
-    if torch.is_tensor(x):
-        x = x.detach().cpu().to(torch.float16).numpy()
-    x = np.asarray(x, dtype=np.float16)
-    if not x.flags.writeable:
-        x = x.copy()                       # (torch.from_numpy refuses to share a read-only array quietly)
-    if x.ndim == 4 and x.shape[0] == 1:
-        x = x[0]
-    if x.ndim != 3 or x.shape[0] != 3:
-        raise ValueError(f"colour lock: expected one [3,H,W] frame, got {x.shape}")
+    """fp16 [3,H,W] of a [3,H,W] or [1,3,H,W] array / tensor of at most MAX_PIXELS pixels"""
+    x = frame16(x, "colour lock")
     if x.shape[1] * x.shape[2] > MAX_PIXELS:
         raise ValueError(f"colour lock: {x.shape[1]} x {x.shape[2]} is more than {MAX_PIXELS} pixels (n S2 - S1^2 must stay inside int64)")
     return x

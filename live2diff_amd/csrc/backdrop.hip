@@ -5,7 +5,7 @@
 // counterpart.
 //
 //   P0[c] = rint(255 clamp(fp16(fp16(x / 2) + 0.5), 0, 1))   the egress op's bytes of the source frame
-//   M  = rint(255 m)                                         m: matte.hip's mt_matte of the depth plane (ramp, hard, far)
+//   M  = rint(255 m)                                         m: px_ramp of the depth plane (ramp, hard, far)
 //   W0 = 256 - M                                             1..256: never 0, so nothing divides by 0
 //   per pass, n = (2r+1)^2, window sums with clamped coordinates:
 //     D = window_sum(W);  N[c] = window_sum(W P[c]);  P[c] <- (2 N[c] + D) / (2 D);  W <- (D + n - 1) / n      (both floor)
@@ -20,7 +20,7 @@
 // apart -- lanes l and l + 16 of a 32-lane group share a bank, 2-way -- and keep their eight sums in registers, which leave as
 // 16-byte stores; the vertical pass and the frame's rows read consecutive entries of a row with consecutive lanes, conflict-free
 // inside a row.  One column per lane is conflict-free throughout and was slower: see the horizontal pass.
-#include "common.h"
+#include "frame_px.h"
 
 #define BD_MAX_R L2D_BACKDROP_MAX_R
 #define BD_MAX_PASSES L2D_BACKDROP_MAX_PASSES
@@ -32,9 +32,6 @@
 #define BD_BH (BD_TH + 2 * BD_PAD)            // 64
 #define BD_HW (BD_TW + 2 * (BD_PAD - BD_MAX_R))   // 96: a row of row sums (the widest region a pass writes, rounded up to 8)
 #define BD_TAPS (2 * BD_MAX_R + 1)
-
-#define BD_HARD L2D_MATTE_HARD
-#define BD_FAR L2D_MATTE_FAR
 
 #define BD_LDS_BYTES (4 * BD_BH * BD_BW + 2 * BD_BH * BD_HW + 4 * BD_BH * BD_HW)
 static_assert(BD_PAD % 8 == 0, "the halo is whole 8-pixel groups");
@@ -50,35 +47,9 @@ struct bd_params {
     int flags, r, passes;
 };
 
-// matte.hip's mt_matte
-__device__ __forceinline__ float bd_matte(h16 depth, const bd_params &p) {
-    const float d = (float)depth;
-    float t;
-    if (p.flags & BD_HARD) {
-        t = d >= p.lo ? 1.0f : 0.0f;
-    } else {
-        t = __fmul_rn(__fsub_rn(d, p.lo), p.inv);
-        t = fminf(fmaxf(t, 0.0f), 1.0f);
-    }
-    const float m = __fmul_rn(__fmul_rn(t, t), __fsub_rn(3.0f, __fmul_rn(2.0f, t)));
-    return (p.flags & BD_FAR) ? __fsub_rn(1.0f, m) : m;
-}
-
 // W0 - 1 = 255 - rint(255 m)
-__device__ __forceinline__ unsigned bd_w(h16 depth, const bd_params &p) { return 255u - (unsigned)rintf(__fmul_rn(bd_matte(depth, p), 255.0f)); }
-
-// the egress op's byte (frame_io.hip fio_u8, steady.hip sd_byte)
-__device__ __forceinline__ unsigned bd_byte(h16 x) {
-    const h16 t = (h16)((float)x * 0.5f);
-    float v = (float)(h16)((float)t + 0.5f);
-    v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
-    return (unsigned)rintf(255.0f * v);
-}
-
-__device__ __forceinline__ int bd_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-__device__ __forceinline__ uint2 bd_pack8(const unsigned (&v)[8]) {
-    return make_uint2(v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24), v[4] | (v[5] << 8) | (v[6] << 16) | (v[7] << 24));
+__device__ __forceinline__ unsigned bd_w(h16 depth, const bd_params &p) {
+    return 255u - (unsigned)rintf(__fmul_rn(px_ramp(depth, p.lo, p.inv, p.flags), 255.0f));
 }
 
 __global__ __launch_bounds__(BD_THREADS) void frame_backdrop_blur_kernel(const h16 *__restrict__ source, const h16 *__restrict__ depth,
@@ -102,12 +73,12 @@ __global__ __launch_bounds__(BD_THREADS) void frame_backdrop_blur_kernel(const h
         for (int g = tid; g < rows * (BD_BW / 8); g += BD_THREADS) {
             const int j = BD_PAD - halo + g / (BD_BW / 8), cg = g % (BD_BW / 8);
             if (cg * 8 + 8 <= BD_PAD - halo || cg * 8 >= BD_PAD + BD_TW + halo) continue;
-            const int yy = bd_clampi(y0 - BD_PAD + j, 0, H - 1);
+            const int yy = px_clampi(y0 - BD_PAD + j, 0, H - 1);
             const int gx = x0 - BD_PAD + cg * 8;
             unsigned v[4][8];
             if (gx < 0 || gx >= W) {
                 const long long e0 = (long long)yy * W + (gx < 0 ? 0 : W - 1);
-                const unsigned b0 = bd_byte(source[e0]), b1 = bd_byte(source[HW + e0]), b2 = bd_byte(source[2 * HW + e0]);
+                const unsigned b0 = px_byte(source[e0]), b1 = px_byte(source[HW + e0]), b2 = px_byte(source[2 * HW + e0]);
                 const unsigned w = bd_w(depth[e0], p);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) { v[0][e] = b0; v[1][e] = b1; v[2][e] = b2; v[3][e] = w; }
@@ -116,10 +87,10 @@ __global__ __launch_bounds__(BD_THREADS) void frame_backdrop_blur_kernel(const h
                 const h16x8 c0 = l2d_ld8(source + g0), c1 = l2d_ld8(source + HW + g0), c2 = l2d_ld8(source + 2 * HW + g0);
                 const h16x8 d = l2d_ld8(depth + g0);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) { v[0][e] = bd_byte(c0[e]); v[1][e] = bd_byte(c1[e]); v[2][e] = bd_byte(c2[e]); v[3][e] = bd_w(d[e], p); }
+                for (int e = 0; e < 8; ++e) { v[0][e] = px_byte(c0[e]); v[1][e] = px_byte(c1[e]); v[2][e] = px_byte(c2[e]); v[3][e] = bd_w(d[e], p); }
             }
 #pragma unroll
-            for (int c = 0; c < 4; ++c) *reinterpret_cast<uint2 *>(&pl[c][j][cg * 8]) = bd_pack8(v[c]);
+            for (int c = 0; c < 4; ++c) *reinterpret_cast<uint2 *>(&pl[c][j][cg * 8]) = px_pack8(v[c]);
         }
     }
     __syncthreads();
@@ -165,7 +136,7 @@ __global__ __launch_bounds__(BD_THREADS) void frame_backdrop_blur_kernel(const h
             // chains.)
             for (int i = tid; i < rows_out * cols_out; i += BD_THREADS) {
                 const int v = i / cols_out, u = i - v * cols_out;
-                const int yc = bd_clampi(y0 - h_out + v, 0, H - 1), xc = bd_clampi(x0 - h_out + u, 0, W - 1);
+                const int yc = px_clampi(y0 - h_out + v, 0, H - 1), xc = px_clampi(x0 - h_out + u, 0, W - 1);
                 const int jc = yc - y0 + BD_PAD, uc = xc - x0 + h_out;   // inside the region: the clamped position lies nearer to the tile
                 unsigned D = 0u, N = 0u;
                 for (int t = 0; t < taps; ++t) { D += hD[jc - r + t][uc]; N += hN[jc - r + t][uc]; }
@@ -196,29 +167,9 @@ __global__ __launch_bounds__(BD_THREADS) void frame_backdrop_blur_kernel(const h
 
 int l2d_launch_frame_backdrop_blur(const l2d_op *op, hipStream_t s) {
     const int H = op->i[0], W = op->i[1], r = op->i[2], passes = op->i[3], flags = op->i[4];
-    for (int k = 0; k < 3; ++k) {
-        if (!op->p[k]) {
-            l2d_set_error("frame_backdrop_blur(tag %d): pointer %d is null", op->tag, k);
-            return L2D_EINVAL;
-        }
-        if (((uintptr_t)op->p[k]) & 15) {
-            l2d_set_error("frame_backdrop_blur(tag %d): pointer %d is not 16-byte aligned", op->tag, k);
-            return L2D_EINVAL;
-        }
-    }
-    if (H <= 0 || W <= 0) {
-        l2d_set_error("frame_backdrop_blur(tag %d): invalid arguments (non-positive size %d x %d)", op->tag, H, W);
-        return L2D_EINVAL;
-    }
-    if (W % 8) {
-        l2d_set_error("frame_backdrop_blur(tag %d): W = %d must be a multiple of 8", op->tag, W);
-        return L2D_EINVAL;
-    }
-    const long long HW = (long long)H * W;
-    if (3 * HW >= (1ll << 31)) {
-        l2d_set_error("frame_backdrop_blur(tag %d): 3 H W = %lld must stay below 2^31", op->tag, 3 * HW);
-        return L2D_EINVAL;
-    }
+    if (!px_check_pointers16("frame_backdrop_blur", op, 3)) return L2D_EINVAL;
+    const long long HW = px_check_frame("frame_backdrop_blur", op->tag, H, W);
+    if (HW < 0) return L2D_EINVAL;
     if (r < 1 || r > BD_MAX_R) {
         l2d_set_error("frame_backdrop_blur(tag %d): radius %d, need 1..%d", op->tag, r, BD_MAX_R);
         return L2D_EINVAL;
@@ -227,24 +178,16 @@ int l2d_launch_frame_backdrop_blur(const l2d_op *op, hipStream_t s) {
         l2d_set_error("frame_backdrop_blur(tag %d): %d passes, need 1..%d", op->tag, passes, BD_MAX_PASSES);
         return L2D_EINVAL;
     }
-    if (flags & ~(BD_HARD | BD_FAR)) {
+    if (flags & ~(L2D_MATTE_HARD | L2D_MATTE_FAR)) {
         l2d_set_error("frame_backdrop_blur(tag %d): unknown flag bits 0x%x (1 hard, 2 far)", op->tag, flags);
         return L2D_EINVAL;
     }
     const float lo = op->f[0], inv = op->f[1];
-    if (!(lo >= -1.0f && lo <= 1.0f) || !(inv >= 0.0f) || inv > 3.0e38f || ((flags & BD_HARD) != 0) != (inv == 0.0f)) {
-        l2d_set_error("frame_backdrop_blur(tag %d): lo = %g must lie in [-1, 1], inv = %g be finite, and 0 exactly when the hard flag is set",
-                      op->tag, lo, inv);
-        return L2D_EINVAL;
-    }
-    {
-        const char *a = (const char *)op->p[2], *ae = a + 6 * HW;
-        for (int k = 0; k < 2; ++k) {
-            const char *b = (const char *)op->p[k], *be = b + (k == 0 ? 6 : 2) * HW;
-            if (a < be && b < ae) {
-                l2d_set_error("frame_backdrop_blur(tag %d): the output overlaps pointer %d (a tile's halo reads its neighbours' pixels)", op->tag, k);
-                return L2D_EINVAL;
-            }
+    if (!px_check_ramp("frame_backdrop_blur", op->tag, lo, inv, (flags & L2D_MATTE_HARD) != 0)) return L2D_EINVAL;
+    for (int k = 0; k < 2; ++k) {
+        if (px_overlap(op->p[2], 6 * HW, op->p[k], (k == 0 ? 6 : 2) * HW)) {
+            l2d_set_error("frame_backdrop_blur(tag %d): the output overlaps pointer %d (a tile's halo reads its neighbours' pixels)", op->tag, k);
+            return L2D_EINVAL;
         }
     }
     L2D_DRY_RETURN();

@@ -20,7 +20,7 @@
 // Latency-bound launches like the egress op: one trip over the data each, 16-byte loads, no MFMA.
 #include <string.h>
 
-#include "common.h"
+#include "frame_px.h"
 
 #define CL_THREADS 256
 #define CL_WAVES (CL_THREADS / L2D_WAVE)
@@ -34,14 +34,6 @@
 
 static_assert((long long)CL_MOM_PIX * 255 * 255 < (1ll << 32), "a block's sum of squares must fit u32");
 static_assert(CL_MOM_PIX % CL_APPLY_PIX == 0, "a moments block is a whole number of 8-pixel lane groups");
-
-// the egress op's byte (frame_io.hip fio_u8)
-__device__ __forceinline__ unsigned cl_byte(h16 x) {
-    const h16 t = (h16)((float)x * 0.5f);
-    float v = (float)(h16)((float)t + 0.5f);
-    v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
-    return (unsigned)rintf(255.0f * v);
-}
 
 // grid (blocks, tensors): block (i, t) sums pixels [i CL_MOM_PIX, (i + 1) CL_MOM_PIX) of the three planes of tensor t and writes
 // partials[t][i][0..5] = S1 of channel 0, 1, 2, S2 of channel 0, 1, 2
@@ -60,7 +52,7 @@ __global__ __launch_bounds__(CL_THREADS) void frame_moments_kernel(const h16 *__
                 const h16x8 v = l2d_ld8(src + (long long)ch * HW + p);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
-                    const unsigned q = cl_byte(v[e]);
+                    const unsigned q = px_byte(v[e]);
                     s[ch] += q;
                     s[3 + ch] += q * q;
                 }
@@ -221,11 +213,6 @@ static long long cl_check_frame(const char *what, const l2d_op *op) {
     return HW;
 }
 
-static bool cl_overlap(const void *a, long long na, const void *b, long long nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
-}
-
 int l2d_launch_frame_moments(const l2d_op *op, hipStream_t s) {
     const long long HW = cl_check_frame("frame_moments", op);
     if (HW < 0) return L2D_EINVAL;
@@ -272,11 +259,11 @@ int l2d_launch_color_lock(const l2d_op *op, hipStream_t s) {
         l2d_set_error("color_lock(tag %d): the source and freeze flags exclude one another", op->tag);
         return L2D_EINVAL;
     }
-    if (cl_overlap(op->p[3], 48, op->p[4], 48)) {
+    if (px_overlap(op->p[3], 48, op->p[4], 48)) {
         l2d_set_error("color_lock(tag %d): state_in and state_out overlap (block 0 writes what the other blocks read)", op->tag);
         return L2D_EINVAL;
     }
-    if (cl_overlap(op->p[0], HW * 6, op->p[1], HW * 6)) {
+    if (px_overlap(op->p[0], HW * 6, op->p[1], HW * 6)) {
         l2d_set_error("color_lock(tag %d): the output frame overlaps the input frame", op->tag);
         return L2D_EINVAL;
     }

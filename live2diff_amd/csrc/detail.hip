@@ -25,7 +25,7 @@
 #include <math.h>
 #include <string.h>
 
-#include "common.h"
+#include "frame_px.h"
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // the gains
@@ -55,22 +55,6 @@ static_assert(DG_AH * DG_TW <= DG_WORDS_H, "the row sums of A fit where the firs
 static_assert(261120ll * DG_TAPS * DG_TAPS < (1ll << 31), "the window sum of A fits 32 bits");
 static_assert(DG_LDS_BYTES == 79872, "the LDS size DESIGN.md section 8.z10 states");
 static_assert(DG_LDS_BYTES <= 80 * 1024 && 2 * DG_LDS_BYTES <= 160 * 1024, "two work-groups per CU");
-
-// the egress op's byte (frame_io.hip fio_u8, matte_edge.hip me_byte)
-__device__ __forceinline__ unsigned dg_byte(h16 x) {
-    const h16 t = (h16)((float)x * 0.5f);
-    float v = (float)(h16)((float)t + 0.5f);
-    v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
-    return (unsigned)rintf(255.0f * v);
-}
-
-__device__ __forceinline__ unsigned dg_luma(unsigned r, unsigned g, unsigned b) { return (77u * r + 150u * g + 29u * b + 128u) >> 8; }
-
-__device__ __forceinline__ int dg_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-__device__ __forceinline__ uint2 dg_pack8(const unsigned *v) {
-    return make_uint2(v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24), v[4] | (v[5] << 8) | (v[6] << 16) | (v[7] << 24));
-}
 
 // the three bytes of pixel `e` of an 8-pixel group of a uint8 HWC frame, held as six dwords
 __device__ __forceinline__ unsigned dg_hwc(const unsigned *w, int e, int c) {
@@ -103,7 +87,7 @@ __global__ __launch_bounds__(DG_THREADS) void frame_detail_gain_kernel(const voi
     for (int g = tid; g < rows2 * (DG_YW / 8); g += DG_THREADS) {
         const int j = g / (DG_YW / 8), cg = g % (DG_YW / 8);
         if (cg * 8 + 8 <= DG_PAD - 2 * r || cg * 8 >= DG_PAD + DG_TW + 2 * r) continue;
-        const int yy = dg_clampi(y0 - 2 * r + j, 0, H - 1);
+        const int yy = px_clampi(y0 - 2 * r + j, 0, H - 1);
         const int gx = x0 - DG_PAD + cg * 8;
         // (a group outside the image: the nearest group of the row is loaded and its edge pixel takes all eight places)
         const int edge = gx < 0 ? 0 : (gx >= W ? 7 : -1);
@@ -112,7 +96,7 @@ __global__ __launch_bounds__(DG_THREADS) void frame_detail_gain_kernel(const voi
         {
             const h16x8 cr = l2d_ld8(source + g0), cgn = l2d_ld8(source + HW + g0), cb = l2d_ld8(source + 2 * HW + g0);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) yv[e] = dg_luma(dg_byte(cr[e]), dg_byte(cgn[e]), dg_byte(cb[e]));
+            for (int e = 0; e < 8; ++e) yv[e] = px_luma(px_byte(cr[e]), px_byte(cgn[e]), px_byte(cb[e]));
         }
         if (u8) {
             // 24 bytes at a multiple of 24 from a 16-byte aligned frame: three 8-byte loads
@@ -124,7 +108,7 @@ __global__ __launch_bounds__(DG_THREADS) void frame_detail_gain_kernel(const voi
         } else {
             const h16x8 fr = l2d_ld8(fh + g0), fg = l2d_ld8(fh + HW + g0), fbl = l2d_ld8(fh + 2 * HW + g0);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) { pv[0][e] = dg_byte(fr[e]); pv[1][e] = dg_byte(fg[e]); pv[2][e] = dg_byte(fbl[e]); }
+            for (int e = 0; e < 8; ++e) { pv[0][e] = px_byte(fr[e]); pv[1][e] = px_byte(fg[e]); pv[2][e] = px_byte(fbl[e]); }
         }
         if (edge >= 0) {
             const int k = edge;                                   // 0 or 7
@@ -132,9 +116,9 @@ __global__ __launch_bounds__(DG_THREADS) void frame_detail_gain_kernel(const voi
 #pragma unroll
             for (int e = 0; e < 8; ++e) { yv[e] = ye; pv[0][e] = p0; pv[1][e] = p1; pv[2][e] = p2; }
         }
-        *reinterpret_cast<uint2 *>(&yb[j][cg * 8]) = dg_pack8(yv);
+        *reinterpret_cast<uint2 *>(&yb[j][cg * 8]) = px_pack8(yv);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) *reinterpret_cast<uint2 *>(&pb[c][j][cg * 8]) = dg_pack8(pv[c]);
+        for (int c = 0; c < 3; ++c) *reinterpret_cast<uint2 *>(&pb[c][j][cg * 8]) = px_pack8(pv[c]);
     }
     __syncthreads();
 
@@ -165,8 +149,8 @@ __global__ __launch_bounds__(DG_THREADS) void frame_detail_gain_kernel(const voi
     // the tile, so its window is in LDS as well.
     for (int i = tid; i < rows1 * cols1; i += DG_THREADS) {
         const int v = i / cols1, u = i - v * cols1;
-        const int xc = dg_clampi(x0 - r + u, 0, W - 1), yc = dg_clampi(y0 - r + v, 0, H - 1);
-        const int uc = dg_clampi(xc - (x0 - r), 0, cols1 - 1), j0 = dg_clampi(yc - y0 + r, 0, rows1 - 1);           // the window's first row
+        const int xc = px_clampi(x0 - r + u, 0, W - 1), yc = px_clampi(y0 - r + v, 0, H - 1);
+        const int uc = px_clampi(xc - (x0 - r), 0, cols1 - 1), j0 = px_clampi(yc - y0 + r, 0, rows1 - 1);           // the window's first row
         unsigned a = 0u, b = 0u;
         for (int k = 0; k < taps; ++k) { a += h1[j0 + k][uc]; b += h2[j0 + k][uc]; }
         sI[v][u] = a; sII[v][u] = b;
@@ -196,8 +180,8 @@ __global__ __launch_bounds__(DG_THREADS) void frame_detail_gain_kernel(const voi
         // its vertical pass and the coefficient
         for (int i = tid; i < rows1 * cols1; i += DG_THREADS) {
             const int v = i / cols1, u = i - v * cols1;
-            const int xc = dg_clampi(x0 - r + u, 0, W - 1), yc = dg_clampi(y0 - r + v, 0, H - 1);
-            const int uc = dg_clampi(xc - (x0 - r), 0, cols1 - 1), j0 = dg_clampi(yc - y0 + r, 0, rows1 - 1);
+            const int xc = px_clampi(x0 - r + u, 0, W - 1), yc = px_clampi(y0 - r + v, 0, H - 1);
+            const int uc = px_clampi(xc - (x0 - r), 0, cols1 - 1), j0 = px_clampi(yc - y0 + r, 0, rows1 - 1);
             unsigned sP = 0u, sIP = 0u;
             for (int k = 0; k < taps; ++k) { sP += h1[j0 + k][uc]; sIP += h2[j0 + k][uc]; }
             const unsigned si = sI[v][u];
@@ -232,29 +216,8 @@ __global__ __launch_bounds__(DG_THREADS) void frame_detail_gain_kernel(const voi
 
 int l2d_launch_frame_detail_gain(const l2d_op *op, hipStream_t s) {
     const int H = op->i[0], W = op->i[1], r = op->i[2], flags = op->i[3];
-    for (int k = 0; k < 3; ++k) {
-        if (!op->p[k]) {
-            l2d_set_error("frame_detail_gain(tag %d): pointer %d is null", op->tag, k);
-            return L2D_EINVAL;
-        }
-        if (((uintptr_t)op->p[k]) & 15) {
-            l2d_set_error("frame_detail_gain(tag %d): pointer %d is not 16-byte aligned", op->tag, k);
-            return L2D_EINVAL;
-        }
-    }
-    if (H <= 0 || W <= 0) {
-        l2d_set_error("frame_detail_gain(tag %d): invalid arguments (non-positive size %d x %d)", op->tag, H, W);
-        return L2D_EINVAL;
-    }
-    if (W % 8) {
-        l2d_set_error("frame_detail_gain(tag %d): W = %d must be a multiple of 8", op->tag, W);
-        return L2D_EINVAL;
-    }
-    const long long HW = (long long)H * W;
-    if (3 * HW >= (1ll << 31)) {
-        l2d_set_error("frame_detail_gain(tag %d): 3 H W = %lld must stay below 2^31", op->tag, 3 * HW);
-        return L2D_EINVAL;
-    }
+    if (!px_check_pointers16("frame_detail_gain", op, 3)) return L2D_EINVAL;
+    if (px_check_frame("frame_detail_gain", op->tag, H, W) < 0) return L2D_EINVAL;
     if (r < 1 || r > DG_MAX_R) {
         l2d_set_error("frame_detail_gain(tag %d): radius %d, need 1..%d", op->tag, r, DG_MAX_R);
         return L2D_EINVAL;
@@ -291,29 +254,6 @@ static_assert(DT_T * 3 / 4 + 6 <= DT_ITEMS, "a tile row is stored by DT_ITEMS la
 static_assert(DT_LDS_BYTES == 53760, "the LDS size DESIGN.md section 8.z10 states");
 static_assert(2 * DT_LDS_BYTES <= 160 * 1024, "two work-groups per CU");
 
-// One axis of the tile: the span [s0, s0 + n) of source coordinates its taps reach.  Everything read from a table is clamped
-// to the image and to the span, so a wrong table gives a wrong picture and never an access outside a buffer (matte.hip mu_span).
-__device__ __forceinline__ void dt_span(const int *__restrict__ tab, int n_out, int n_in, int o0, int t, int &s0, int &n) {
-    s0 = dg_clampi(tab[o0], 0, n_in - 1);
-    const int s1 = dg_clampi(tab[n_out + o0 + t - 1], s0, n_in - 1);
-    n = s1 - s0 + 1 > DT_SPAN ? DT_SPAN : s1 - s0 + 1;
-}
-
-__device__ __forceinline__ void dt_stage(const int *__restrict__ tab, int n_out, int n_in, int o0, int t, int s0, int n, int lane,
-                                         int *i0, int *i1, float *f) {
-    int a = 0, b = 0;
-    float w = 0.0f;
-    if (lane < t) {
-        a = dg_clampi(dg_clampi(tab[o0 + lane], 0, n_in - 1) - s0, 0, n - 1);
-        b = dg_clampi(dg_clampi(tab[n_out + o0 + lane], 0, n_in - 1) - s0, 0, n - 1);
-        w = __int_as_float(tab[2 * n_out + o0 + lane]);
-        w = fminf(fmaxf(w, 0.0f), 1.0f);          // (a weight of `up_table` lies in [0, 1]: this changes none of them)
-    }
-    i0[lane] = a;
-    i1[lane] = b;
-    f[lane] = w;
-}
-
 __global__ __launch_bounds__(DT_THREADS) void frame_detail_kernel(const uint8_t *__restrict__ styled, const uint8_t *__restrict__ camera,
                                                                   const uint8_t *__restrict__ low, const int *__restrict__ gains,
                                                                   const int *__restrict__ tx, const int *__restrict__ ty,
@@ -327,15 +267,15 @@ __global__ __launch_bounds__(DT_THREADS) void frame_detail_kernel(const uint8_t 
     const int ox0 = blockIdx.x * DT_T, oy0 = blockIdx.y * DT_T;
     const int tw = Wo - ox0 < DT_T ? Wo - ox0 : DT_T, th = Ho - oy0 < DT_T ? Ho - oy0 : DT_T;
     int sx0, nx, sy0, ny;
-    dt_span(tx, Wo, W, ox0, tw, sx0, nx);
-    dt_span(ty, Ho, H, oy0, th, sy0, ny);
+    px_span<DT_SPAN>(tx, Wo, W, ox0, tw, sx0, nx);
+    px_span<DT_SPAN>(ty, Ho, H, oy0, th, sy0, ny);
     if (tid < DT_T) {
-        dt_stage(tx, Wo, W, ox0, tw, sx0, nx, tid, x0s, x1s, fxs);
+        px_stage(tx, Wo, W, ox0, tw, sx0, nx, tid, x0s, x1s, fxs);
     } else if (tid >= 64 && tid < 64 + DT_T) {
-        dt_stage(ty, Ho, H, oy0, th, sy0, ny, tid - 64, y0s, y1s, fys);
+        px_stage(ty, Ho, H, oy0, th, sy0, ny, tid - 64, y0s, y1s, fys);
     }
 
-    // the gains of the patch: sy0 + j <= H - 1 and sx0 + c <= W - 1 by dt_span
+    // the gains of the patch: sy0 + j <= H - 1 and sx0 + c <= W - 1 by px_span
     const long long HW = (long long)H * W;
     for (int i = tid; i < 3 * ny * nx; i += DT_THREADS) {
         const int ch = i / (ny * nx), q = i - ch * (ny * nx);
@@ -348,8 +288,8 @@ __global__ __launch_bounds__(DT_THREADS) void frame_detail_kernel(const uint8_t 
     for (int i = tid; i < th * tw; i += DT_THREADS) {
         const int yy = i / tw, xx = i - yy * tw;
         const long long g = ((long long)(oy0 + yy) * Wo + ox0 + xx) * 3;
-        const int lc = (int)dg_luma(camera[g], camera[g + 1], camera[g + 2]);
-        const int ll = (int)dg_luma(low[g], low[g + 1], low[g + 2]);
+        const int lc = (int)px_luma(camera[g], camera[g + 1], camera[g + 2]);
+        const int ll = (int)px_luma(low[g], low[g + 1], low[g + 2]);
         const float d = (float)(lc - ll);
         const int r0 = y0s[yy] * DT_STRIDE, r1 = y1s[yy] * DT_STRIDE;
         const int a = x0s[xx], c = x1s[xx];
@@ -369,33 +309,15 @@ __global__ __launch_bounds__(DT_THREADS) void frame_detail_kernel(const uint8_t 
     }
     __syncthreads();
 
-    // the tile's rows: tw * 3 bytes each at an address of any alignment -- bytes up to the first dword boundary, whole dwords,
-    // bytes behind the last one; DT_ITEMS lanes per row, one store each (resize.hip's stores).  Every byte lies inside row
-    // oy0 + yy < Ho, columns ox0 .. ox0 + tw - 1 < Wo.
+    // the tile's rows: tw * 3 bytes each at an address of any alignment, DT_ITEMS lanes per row, one store each (px_store_row).
+    // Every byte lies inside row oy0 + yy < Ho, columns ox0 .. ox0 + tw - 1 < Wo.
     const int nb = tw * 3;
     for (int i = tid; i < th * DT_ITEMS; i += DT_THREADS) {
         const int yy = i / DT_ITEMS, it = i % DT_ITEMS;
         uint8_t *g = dst + ((long long)(oy0 + yy) * Wo + ox0) * 3;
         const unsigned char *o = ob + yy * DT_T * 3;
-        int head = (int)((0 - (uintptr_t)g) & 3);
-        head = head > nb ? nb : head;
-        const int ndw = (nb - head) >> 2;
-        const int tail = nb - head - ndw * 4;
-        if (it < head) {
-            g[it] = o[it];
-        } else if (it < head + ndw) {
-            const int e = head + (it - head) * 4;
-            *reinterpret_cast<unsigned *>(g + e) =
-                (unsigned)o[e] | ((unsigned)o[e + 1] << 8) | ((unsigned)o[e + 2] << 16) | ((unsigned)o[e + 3] << 24);
-        } else if (it < head + ndw + tail) {
-            const int e = head + ndw * 4 + (it - head - ndw);
-            g[e] = o[e];
-        }
+        px_store_row(g, o, nb, it);
     }
-}
-
-static bool dt_axis_ok(int n_in, int n_out) {
-    return n_out >= 1 && n_out <= L2D_RESIZE_MAX_SIZE && 2ll * n_out >= n_in && n_out <= 8ll * n_in;
 }
 
 int l2d_launch_frame_detail(const l2d_op *op, hipStream_t s) {
@@ -411,7 +333,7 @@ int l2d_launch_frame_detail(const l2d_op *op, hipStream_t s) {
         l2d_set_error("frame_detail(tag %d): non-positive size (H %d, W %d)", op->tag, H, W);
         return L2D_EINVAL;
     }
-    if (!dt_axis_ok(H, Ho) || !dt_axis_ok(W, Wo)) {
+    if (!px_axis_ok(H, Ho) || !px_axis_ok(W, Wo)) {
         l2d_set_error("frame_detail(tag %d): %d x %d -> %d x %d: an output size must lie in 1..%d and between half and 8 times the "
                       "gains' size", op->tag, H, W, Ho, Wo, L2D_RESIZE_MAX_SIZE);
         return L2D_EINVAL;
@@ -435,10 +357,8 @@ int l2d_launch_frame_detail(const l2d_op *op, hipStream_t s) {
         l2d_set_error("frame_detail(tag %d): limit = %g and k = %g must be finite and not negative", op->tag, limit, k);
         return L2D_EINVAL;
     }
-    const uintptr_t d0 = (uintptr_t)op->p[6];
     for (int j = 0; j < 3; ++j) {
-        const uintptr_t a0 = (uintptr_t)op->p[j];
-        if (d0 < a0 + (uintptr_t)nbytes && a0 < d0 + (uintptr_t)nbytes) {
+        if (px_overlap(op->p[6], nbytes, op->p[j], nbytes)) {
             l2d_set_error("frame_detail(tag %d): dst overlaps input %d (a tile reads what another may have written)", op->tag, j);
             return L2D_EINVAL;
         }

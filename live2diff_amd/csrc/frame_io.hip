@@ -3,7 +3,7 @@
 // `2 x - 1` from VaeImageProcessor), `x / 2 + 0.5 -> clamp -> x 255 -> round -> uint8` on the way out
 // (image_utils.py:9-37) -- as one launch each on uint8 frames.  Both are launch-bound (6 MB in for 1080p, 0.75 MB out for
 // 512 x 512): no LDS, no MFMA, 16-byte stores.
-#include "common.h"
+#include "frame_px.h"
 
 #define FIO_MAX_SCALE 8.0f        // 2 * 8 + 1 = 17 taps per axis at most
 
@@ -112,14 +112,7 @@ int l2d_launch_frame_ingest(const l2d_op *op, hipStream_t s) {
 }
 
 // fp16 [B][3][HW] -> uint8 [B][HW][3]: u = rint(255 clamp(fp16(fp16(x / 2) + 0.5), 0, 1)), the reference's expression on an fp16 tensor
-// with its rounding points (image_utils.py:13,30).  One lane = 16 pixels = 48 bytes, three 16-byte stores.
-__device__ __forceinline__ unsigned fio_u8(h16 x) {
-    const h16 t = (h16)((float)x * 0.5f);
-    float v = (float)(h16)((float)t + 0.5f);
-    v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
-    return (unsigned)rintf(255.0f * v);        // 255 v is exact in fp32 (11 x 8 bits); rint rounds half to even
-}
-
+// with its rounding points (frame_px.h px_byte).  One lane = 16 pixels = 48 bytes, three 16-byte stores.
 __global__ __launch_bounds__(256) void frame_egress_kernel(const h16 *__restrict__ src, uint8_t *__restrict__ dst, int B, int HW) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     const int per = HW >> 4;
@@ -133,8 +126,8 @@ __global__ __launch_bounds__(256) void frame_egress_kernel(const h16 *__restrict
         const h16x8 v0 = l2d_ld8(pl + (long long)c * HW), v1 = l2d_ld8(pl + (long long)c * HW + 8);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            q[e * 3 + c] = (unsigned char)fio_u8(v0[e]);
-            q[(e + 8) * 3 + c] = (unsigned char)fio_u8(v1[e]);
+            q[e * 3 + c] = (unsigned char)px_byte(v0[e]);
+            q[(e + 8) * 3 + c] = (unsigned char)px_byte(v1[e]);
         }
     }
     uint4 *out = reinterpret_cast<uint4 *>(dst + ((long long)b * HW + p0) * 3);

@@ -12,7 +12,7 @@
 //
 // Every step is one fp32 operation with one rounding (the file is built with -ffp-contract=off, see the Makefile), so that numpy
 // restates it bit for bit (live2diff_amd/matte.py `composite_ref`).  A bandwidth kernel: 16-byte loads of fp16 rows, no MFMA.
-#include "common.h"
+#include "frame_px.h"
 
 #define MT_MAX_R L2D_MATTE_MAX_R
 #define MT_TW 64                              // tile width in pixels: 8 lanes of 8 pixels
@@ -25,24 +25,12 @@
 #define MT_FAR L2D_MATTE_FAR
 #define MT_SHOW L2D_MATTE_SHOW
 #define MT_PLANE L2D_MATTE_PLANE
+static_assert(MT_HARD == 1 && MT_FAR == 2, "px_ramp reads the hard and far bits of the flags");
 
 struct mt_params {
     float lo, inv;
     int flags, r;
 };
-
-__device__ __forceinline__ float mt_matte(h16 depth, const mt_params &p) {
-    const float d = (float)depth;
-    float t;
-    if (p.flags & MT_HARD) {
-        t = d >= p.lo ? 1.0f : 0.0f;
-    } else {
-        t = __fmul_rn(__fsub_rn(d, p.lo), p.inv);
-        t = fminf(fmaxf(t, 0.0f), 1.0f);
-    }
-    const float m = __fmul_rn(__fmul_rn(t, t), __fsub_rn(3.0f, __fmul_rn(2.0f, t)));
-    return (p.flags & MT_FAR) ? __fsub_rn(1.0f, m) : m;
-}
 
 // L2D_MATTE_PLANE: the `depth` operand is an fp32 plane of ready matte values (L2D_OP_FRAME_MATTE_EDGE
 // writes one) and the ramp is skipped.  PLANE is a template parameter of the three kernel bodies, so the kernels of the flag-clear
@@ -50,7 +38,7 @@ __device__ __forceinline__ float mt_matte(h16 depth, const mt_params &p) {
 template <bool PLANE>
 __device__ __forceinline__ float mt_value(const void *depth, long long i, const mt_params &p) {
     if constexpr (PLANE) return reinterpret_cast<const float *>(depth)[i];
-    else return mt_matte(reinterpret_cast<const h16 *>(depth)[i], p);
+    else return px_ramp(reinterpret_cast<const h16 *>(depth)[i], p.lo, p.inv, p.flags);
 }
 
 // eight consecutive values from element i (a multiple of 8) on
@@ -64,15 +52,8 @@ __device__ __forceinline__ void mt_value8(const void *depth, long long i, const 
     } else {
         const h16x8 d = l2d_ld8(reinterpret_cast<const h16 *>(depth) + i);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = mt_matte(d[e], p);
+        for (int e = 0; e < 8; ++e) v[e] = px_ramp(d[e], p.lo, p.inv, p.flags);
     }
-}
-
-// the egress op's fp16 chain (frame_io.hip fio_u8), widened to fp32
-__device__ __forceinline__ float mt_unit(h16 x) {
-    const h16 t = (h16)((float)x * 0.5f);
-    const float v = (float)(h16)((float)t + 0.5f);
-    return v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
 }
 
 __device__ __forceinline__ unsigned mt_byte(float vs, float vc, float m) {
@@ -90,7 +71,7 @@ __device__ __forceinline__ void mt_blend(const h16 (&s)[3][N], const h16 (&c)[3]
             q[e * 3] = q[e * 3 + 1] = q[e * 3 + 2] = (unsigned char)(unsigned)rintf(__fmul_rn(m[e], 255.0f));
         } else {
 #pragma unroll
-            for (int ch = 0; ch < 3; ++ch) q[e * 3 + ch] = (unsigned char)mt_byte(mt_unit(s[ch][e]), mt_unit(c[ch][e]), m[e]);
+            for (int ch = 0; ch < 3; ++ch) q[e * 3 + ch] = (unsigned char)mt_byte(px_unit(s[ch][e]), px_unit(c[ch][e]), m[e]);
         }
     }
 #pragma unroll
@@ -290,11 +271,7 @@ int l2d_launch_frame_matte(const l2d_op *op, hipStream_t s) {
         return L2D_EINVAL;
     }
     const float lo = plane ? 0.0f : op->f[0], inv = plane ? 0.0f : op->f[1];          // (a plane: the ramp is not read)
-    if (!plane && (!(lo >= -1.0f && lo <= 1.0f) || !(inv >= 0.0f) || inv > 3.0e38f || ((flags & MT_HARD) != 0) != (inv == 0.0f))) {
-        l2d_set_error("frame_matte(tag %d): lo = %g must lie in [-1, 1], inv = %g be finite, and 0 exactly when the hard flag is set", op->tag,
-                      lo, inv);
-        return L2D_EINVAL;
-    }
+    if (!plane && !px_check_ramp("frame_matte", op->tag, lo, inv, (flags & MT_HARD) != 0)) return L2D_EINVAL;
     L2D_DRY_RETURN();
     mt_params p;
     p.lo = lo; p.inv = inv; p.flags = flags; p.r = r;
@@ -322,7 +299,7 @@ int l2d_launch_frame_matte(const l2d_op *op, hipStream_t s) {
 // L2D_OP_FRAME_RESIZE, composited over the CAMERA's own pixels at that size by the matte of the stream-sized depth plane, sampled
 // bilinearly (half-pixel centres).  live2diff_amd/matte.py `composite_up_ref` restates it bit for bit:
 //
-//   m        the matte of L2D_OP_FRAME_MATTE at the stream's size, feather applied there (mt_matte + the two box passes)
+//   m        the matte of L2D_OP_FRAME_MATTE at the stream's size, feather applied there (px_ramp + the two box passes)
 //   a_top = m[y0][x0] + fx (m[y0][x1] - m[y0][x0])     a_bot likewise on row y1     M = a_top + fy (a_bot - a_top)
 //   o = C + M (S - C) on the bytes as fp32             byte = rint(o)               (show: rint(255 M) in all three channels)
 //
@@ -343,31 +320,6 @@ static_assert(MU_T * 3 / 4 + 6 <= MU_ITEMS, "a tile row is stored by MU_ITEMS la
 static_assert(MU_LDS_BYTES == 59136, "the LDS size DESIGN.md section 8.z7 states");
 static_assert(2 * MU_LDS_BYTES <= 160 * 1024, "two work-groups per CU");
 
-__device__ __forceinline__ int mu_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// One axis of the tile: the span [s0, s0 + n) of source coordinates its taps reach.  Everything read from a table is clamped
-// to the image and to the span, so a wrong table gives a wrong picture and never an access outside a buffer.
-__device__ __forceinline__ void mu_span(const int *__restrict__ tab, int n_out, int n_in, int o0, int t, int &s0, int &n) {
-    s0 = mu_clampi(tab[o0], 0, n_in - 1);
-    const int s1 = mu_clampi(tab[n_out + o0 + t - 1], s0, n_in - 1);
-    n = s1 - s0 + 1 > MU_SPAN ? MU_SPAN : s1 - s0 + 1;
-}
-
-__device__ __forceinline__ void mu_stage(const int *__restrict__ tab, int n_out, int n_in, int o0, int t, int s0, int n, int lane,
-                                         int *i0, int *i1, float *f) {
-    int a = 0, b = 0;
-    float w = 0.0f;
-    if (lane < t) {
-        a = mu_clampi(mu_clampi(tab[o0 + lane], 0, n_in - 1) - s0, 0, n - 1);
-        b = mu_clampi(mu_clampi(tab[n_out + o0 + lane], 0, n_in - 1) - s0, 0, n - 1);
-        w = __int_as_float(tab[2 * n_out + o0 + lane]);
-        w = fminf(fmaxf(w, 0.0f), 1.0f);          // (a weight of `up_table` lies in [0, 1]: this changes none of them)
-    }
-    i0[lane] = a;
-    i1[lane] = b;
-    f[lane] = w;
-}
-
 template <bool PLANE>
 __device__ __forceinline__ void mu_body(const uint8_t *__restrict__ styled, const uint8_t *__restrict__ camera, const void *__restrict__ depth,
                                         uint8_t *__restrict__ dst, const int *__restrict__ tx, const int *__restrict__ ty, int H, int W, int Ho,
@@ -383,12 +335,12 @@ __device__ __forceinline__ void mu_body(const uint8_t *__restrict__ styled, cons
     const int tw = Wo - ox0 < MU_T ? Wo - ox0 : MU_T, th = Ho - oy0 < MU_T ? Ho - oy0 : MU_T;
     const int r = p.r, taps = 2 * r + 1;
     int sx0, nx, sy0, ny;
-    mu_span(tx, Wo, W, ox0, tw, sx0, nx);
-    mu_span(ty, Ho, H, oy0, th, sy0, ny);
+    px_span<MU_SPAN>(tx, Wo, W, ox0, tw, sx0, nx);
+    px_span<MU_SPAN>(ty, Ho, H, oy0, th, sy0, ny);
     if (tid < MU_T) {
-        mu_stage(tx, Wo, W, ox0, tw, sx0, nx, tid, x0s, x1s, fxs);
+        px_stage(tx, Wo, W, ox0, tw, sx0, nx, tid, x0s, x1s, fxs);
     } else if (tid >= 64 && tid < 64 + MU_T) {
-        mu_stage(ty, Ho, H, oy0, th, sy0, ny, tid - 64, y0s, y1s, fys);
+        px_stage(ty, Ho, H, oy0, th, sy0, ny, tid - 64, y0s, y1s, fys);
     }
 
     // m of the patch and its halo: mm[j][c] = m(clamp(sy0 - r + j), clamp(sx0 - r + c))
@@ -396,7 +348,7 @@ __device__ __forceinline__ void mu_body(const uint8_t *__restrict__ styled, cons
     const long long dp = (long long)b * dstride;
     for (int i = tid; i < rows * cols; i += MU_THREADS) {
         const int j = i / cols, c = i - j * cols;
-        const int yy = mu_clampi(sy0 - r + j, 0, H - 1), xx = mu_clampi(sx0 - r + c, 0, W - 1);
+        const int yy = px_clampi(sy0 - r + j, 0, H - 1), xx = px_clampi(sx0 - r + c, 0, W - 1);
         mm[j * MU_STRIDE + c] = mt_value<PLANE>(depth, dp + (long long)yy * W + xx, p);
     }
     __syncthreads();
@@ -453,27 +405,13 @@ __device__ __forceinline__ void mu_body(const uint8_t *__restrict__ styled, cons
     }
     __syncthreads();
 
-    // the tile's rows: tw * 3 bytes each at an address of any alignment -- bytes up to the first dword boundary, whole dwords,
-    // bytes behind the last one; MU_ITEMS lanes per row, one store each (resize.hip's stores).  Every byte lies inside row
-    // oy0 + yy < Ho, columns ox0 .. ox0 + tw - 1 < Wo.
+    // the tile's rows: tw * 3 bytes each at an address of any alignment, MU_ITEMS lanes per row, one store each (px_store_row).
+    // Every byte lies inside row oy0 + yy < Ho, columns ox0 .. ox0 + tw - 1 < Wo.
     for (int i = tid; i < th * MU_ITEMS; i += MU_THREADS) {
         const int yy = i / MU_ITEMS, it = i % MU_ITEMS;
         uint8_t *g = dst + (((long long)b * Ho + oy0 + yy) * Wo + ox0) * 3;
         const unsigned char *o = ob + yy * MU_T * 3;
-        int head = (int)((0 - (uintptr_t)g) & 3);
-        head = head > nb ? nb : head;
-        const int ndw = (nb - head) >> 2;
-        const int tail = nb - head - ndw * 4;
-        if (it < head) {
-            g[it] = o[it];
-        } else if (it < head + ndw) {
-            const int e = head + (it - head) * 4;
-            *reinterpret_cast<unsigned *>(g + e) =
-                (unsigned)o[e] | ((unsigned)o[e + 1] << 8) | ((unsigned)o[e + 2] << 16) | ((unsigned)o[e + 3] << 24);
-        } else if (it < head + ndw + tail) {
-            const int e = head + ndw * 4 + (it - head - ndw);
-            g[e] = o[e];
-        }
+        px_store_row(g, o, nb, it);
     }
 }
 
@@ -492,10 +430,6 @@ __global__ __launch_bounds__(MU_THREADS) void frame_plane_up_kernel(const uint8_
     mu_body<true>(styled, camera, plane, dst, tx, ty, H, W, Ho, Wo, dstride, p);
 }
 
-static bool mu_axis_ok(int n_in, int n_out) {
-    return n_out >= 1 && n_out <= L2D_RESIZE_MAX_SIZE && 2ll * n_out >= n_in && n_out <= 8ll * n_in;
-}
-
 int l2d_launch_frame_matte_up(const l2d_op *op, hipStream_t s) {
     const int B = op->i[0], H = op->i[1], W = op->i[2], Ho = op->i[3], Wo = op->i[4], r = op->i[5], flags = op->i[6];
     const long long dstride = op->l[0];
@@ -509,7 +443,7 @@ int l2d_launch_frame_matte_up(const l2d_op *op, hipStream_t s) {
         l2d_set_error("frame_matte_up(tag %d): non-positive size (B %d, H %d, W %d)", op->tag, B, H, W);
         return L2D_EINVAL;
     }
-    if (!mu_axis_ok(H, Ho) || !mu_axis_ok(W, Wo)) {
+    if (!px_axis_ok(H, Ho) || !px_axis_ok(W, Wo)) {
         l2d_set_error("frame_matte_up(tag %d): %d x %d -> %d x %d: an output size must lie in 1..%d and between half and 8 times the "
                       "matte's size", op->tag, H, W, Ho, Wo, L2D_RESIZE_MAX_SIZE);
         return L2D_EINVAL;
@@ -540,11 +474,7 @@ int l2d_launch_frame_matte_up(const l2d_op *op, hipStream_t s) {
         }
     }
     const float lo = plane ? 0.0f : op->f[0], inv = plane ? 0.0f : op->f[1];          // (a plane: the ramp is not read)
-    if (!plane && (!(lo >= -1.0f && lo <= 1.0f) || !(inv >= 0.0f) || inv > 3.0e38f || ((flags & MT_HARD) != 0) != (inv == 0.0f))) {
-        l2d_set_error("frame_matte_up(tag %d): lo = %g must lie in [-1, 1], inv = %g be finite, and 0 exactly when the hard flag is set",
-                      op->tag, lo, inv);
-        return L2D_EINVAL;
-    }
+    if (!plane && !px_check_ramp("frame_matte_up", op->tag, lo, inv, (flags & MT_HARD) != 0)) return L2D_EINVAL;
     L2D_DRY_RETURN();
     mt_params p;
     p.lo = lo; p.inv = inv; p.flags = flags; p.r = r;

@@ -3,7 +3,7 @@
 // edges are instead of a few pixels beside them.  One launch in front of the composite (L2D_OP_FRAME_MATTE / _UP with
 // L2D_MATTE_PLANE), which reads the fp32 plane this one writes.  The reference has no counterpart.
 //
-//   P = rint(255 m)                                          m: matte.hip's mt_matte of the depth plane (ramp, hard, far)
+//   P = rint(255 m)                                          m: px_ramp of the depth plane (ramp, hard, far)
 //   b = rint(255 clamp(fp16(fp16(x / 2) + 0.5), 0, 1))       the egress op's bytes of the source frame
 //   Y = (77 R + 150 G + 29 B + 128) >> 8                     the guide, 0..255
 //   S_I, S_P, S_II, S_IP                                     sums of Y, P, Y Y, Y P over the (2r+1)^2 window, coordinates clamped
@@ -21,7 +21,7 @@
 // the four sums as a horizontal and a vertical pass, A and B on the tile and a halo of r, their sums the same way.
 #include <string.h>
 
-#include "common.h"
+#include "frame_px.h"
 
 #define ME_MAX_R L2D_MATTE_EDGE_MAX_R
 #define ME_TW 64                              // the tile: L2D_OP_FRAME_MATTE's
@@ -33,9 +33,6 @@
 #define ME_AW (ME_TW + 2 * ME_MAX_R)          // 80: a row of A / B, and of the first horizontal sums
 #define ME_AH (ME_TH + 2 * ME_MAX_R)          // 32
 #define ME_TAPS (2 * ME_MAX_R + 1)
-
-#define ME_HARD L2D_MATTE_HARD
-#define ME_FAR L2D_MATTE_FAR
 
 // LDS: the bytes, the first pass' row sums (S_I and S_P packed into one word, S_II, S_IP; the second pass' row sums of A and B
 // take their place), A and B
@@ -59,33 +56,10 @@ struct me_params {
     double E;
 };
 
-// matte.hip's mt_matte
-__device__ __forceinline__ float me_matte(h16 depth, const me_params &p) {
-    const float d = (float)depth;
-    float t;
-    if (p.flags & ME_HARD) {
-        t = d >= p.lo ? 1.0f : 0.0f;
-    } else {
-        t = __fmul_rn(__fsub_rn(d, p.lo), p.inv);
-        t = fminf(fmaxf(t, 0.0f), 1.0f);
-    }
-    const float m = __fmul_rn(__fmul_rn(t, t), __fsub_rn(3.0f, __fmul_rn(2.0f, t)));
-    return (p.flags & ME_FAR) ? __fsub_rn(1.0f, m) : m;
+__device__ __forceinline__ unsigned me_p(h16 depth, const me_params &p) {
+    return (unsigned)rintf(__fmul_rn(px_ramp(depth, p.lo, p.inv, p.flags), 255.0f));
 }
 
-__device__ __forceinline__ unsigned me_p(h16 depth, const me_params &p) { return (unsigned)rintf(__fmul_rn(me_matte(depth, p), 255.0f)); }
-
-// the egress op's byte (frame_io.hip fio_u8, steady.hip sd_byte)
-__device__ __forceinline__ unsigned me_byte(h16 x) {
-    const h16 t = (h16)((float)x * 0.5f);
-    float v = (float)(h16)((float)t + 0.5f);
-    v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
-    return (unsigned)rintf(255.0f * v);
-}
-
-__device__ __forceinline__ unsigned me_luma(h16 r, h16 g, h16 b) { return (77u * me_byte(r) + 150u * me_byte(g) + 29u * me_byte(b) + 128u) >> 8; }
-
-__device__ __forceinline__ int me_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 __global__ __launch_bounds__(ME_THREADS) void frame_matte_edge_kernel(const h16 *__restrict__ source, const h16 *__restrict__ depth,
                                                                       float *__restrict__ out, int H, int W, me_params p) {
@@ -111,12 +85,12 @@ __global__ __launch_bounds__(ME_THREADS) void frame_matte_edge_kernel(const h16 
     for (int g = tid; g < rows2 * (ME_YW / 8); g += ME_THREADS) {
         const int j = g / (ME_YW / 8), cg = g % (ME_YW / 8);
         if (cg * 8 + 8 <= ME_PAD - 2 * r || cg * 8 >= ME_PAD + ME_TW + 2 * r) continue;
-        const int yy = me_clampi(y0 - 2 * r + j, 0, H - 1);
+        const int yy = px_clampi(y0 - 2 * r + j, 0, H - 1);
         const int gx = x0 - ME_PAD + cg * 8;
         unsigned yv[8], pv[8];
         if (gx < 0 || gx >= W) {
             const long long e0 = (long long)yy * W + (gx < 0 ? 0 : W - 1);
-            const unsigned ye = me_luma(source[e0], source[HW + e0], source[2 * HW + e0]), pe = me_p(depth[e0], p);
+            const unsigned ye = px_luma(px_byte(source[e0]), px_byte(source[HW + e0]), px_byte(source[2 * HW + e0])), pe = me_p(depth[e0], p);
 #pragma unroll
             for (int e = 0; e < 8; ++e) { yv[e] = ye; pv[e] = pe; }
         } else {
@@ -124,12 +98,10 @@ __global__ __launch_bounds__(ME_THREADS) void frame_matte_edge_kernel(const h16 
             const h16x8 cr = l2d_ld8(source + g0), cgn = l2d_ld8(source + HW + g0), cb = l2d_ld8(source + 2 * HW + g0);
             const h16x8 d = l2d_ld8(depth + g0);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) { yv[e] = me_luma(cr[e], cgn[e], cb[e]); pv[e] = me_p(d[e], p); }
+            for (int e = 0; e < 8; ++e) { yv[e] = px_luma(px_byte(cr[e]), px_byte(cgn[e]), px_byte(cb[e])); pv[e] = me_p(d[e], p); }
         }
-        *reinterpret_cast<uint2 *>(&yb[j][cg * 8]) = make_uint2(yv[0] | (yv[1] << 8) | (yv[2] << 16) | (yv[3] << 24),
-                                                               yv[4] | (yv[5] << 8) | (yv[6] << 16) | (yv[7] << 24));
-        *reinterpret_cast<uint2 *>(&pb[j][cg * 8]) = make_uint2(pv[0] | (pv[1] << 8) | (pv[2] << 16) | (pv[3] << 24),
-                                                               pv[4] | (pv[5] << 8) | (pv[6] << 16) | (pv[7] << 24));
+        *reinterpret_cast<uint2 *>(&yb[j][cg * 8]) = px_pack8(yv);
+        *reinterpret_cast<uint2 *>(&pb[j][cg * 8]) = px_pack8(pv);
     }
     __syncthreads();
 
@@ -164,8 +136,8 @@ __global__ __launch_bounds__(ME_THREADS) void frame_matte_edge_kernel(const h16 
         const double dn = (double)n;
         for (int i = tid; i < rows1 * cols1; i += ME_THREADS) {
             const int v = i / cols1, u = i - v * cols1;
-            const int xc = me_clampi(x0 - r + u, 0, W - 1), yc = me_clampi(y0 - r + v, 0, H - 1);
-            const int uc = me_clampi(xc - (x0 - r), 0, cols1 - 1), j0 = me_clampi(yc - y0 + r, 0, rows1 - 1);       // the window's first row
+            const int xc = px_clampi(x0 - r + u, 0, W - 1), yc = px_clampi(y0 - r + v, 0, H - 1);
+            const int uc = px_clampi(xc - (x0 - r), 0, cols1 - 1), j0 = px_clampi(yc - y0 + r, 0, rows1 - 1);       // the window's first row
             unsigned sI = 0u, sP = 0u, sII = 0u, sIP = 0u;
             for (int k = 0; k < taps; ++k) {
                 const unsigned w = hSS[j0 + k][uc];
@@ -209,34 +181,13 @@ __global__ __launch_bounds__(ME_THREADS) void frame_matte_edge_kernel(const h16 
 
 int l2d_launch_frame_matte_edge(const l2d_op *op, hipStream_t s) {
     const int H = op->i[0], W = op->i[1], r = op->i[2], flags = op->i[3];
-    for (int k = 0; k < 3; ++k) {
-        if (!op->p[k]) {
-            l2d_set_error("frame_matte_edge(tag %d): pointer %d is null", op->tag, k);
-            return L2D_EINVAL;
-        }
-        if (((uintptr_t)op->p[k]) & 15) {
-            l2d_set_error("frame_matte_edge(tag %d): pointer %d is not 16-byte aligned", op->tag, k);
-            return L2D_EINVAL;
-        }
-    }
-    if (H <= 0 || W <= 0) {
-        l2d_set_error("frame_matte_edge(tag %d): invalid arguments (non-positive size %d x %d)", op->tag, H, W);
-        return L2D_EINVAL;
-    }
-    if (W % 8) {
-        l2d_set_error("frame_matte_edge(tag %d): W = %d must be a multiple of 8", op->tag, W);
-        return L2D_EINVAL;
-    }
-    const long long HW = (long long)H * W;
-    if (3 * HW >= (1ll << 31)) {
-        l2d_set_error("frame_matte_edge(tag %d): 3 H W = %lld must stay below 2^31", op->tag, 3 * HW);
-        return L2D_EINVAL;
-    }
+    if (!px_check_pointers16("frame_matte_edge", op, 3)) return L2D_EINVAL;
+    if (px_check_frame("frame_matte_edge", op->tag, H, W) < 0) return L2D_EINVAL;
     if (r < 1 || r > ME_MAX_R) {
         l2d_set_error("frame_matte_edge(tag %d): radius %d, need 1..%d", op->tag, r, ME_MAX_R);
         return L2D_EINVAL;
     }
-    if (flags & ~(ME_HARD | ME_FAR)) {
+    if (flags & ~(L2D_MATTE_HARD | L2D_MATTE_FAR)) {
         l2d_set_error("frame_matte_edge(tag %d): unknown flag bits 0x%x (1 hard, 2 far)", op->tag, flags);
         return L2D_EINVAL;
     }
@@ -250,11 +201,7 @@ int l2d_launch_frame_matte_edge(const l2d_op *op, hipStream_t s) {
         return L2D_EINVAL;
     }
     const float lo = op->f[0], inv = op->f[1];
-    if (!(lo >= -1.0f && lo <= 1.0f) || !(inv >= 0.0f) || inv > 3.0e38f || ((flags & ME_HARD) != 0) != (inv == 0.0f)) {
-        l2d_set_error("frame_matte_edge(tag %d): lo = %g must lie in [-1, 1], inv = %g be finite, and 0 exactly when the hard flag is set",
-                      op->tag, lo, inv);
-        return L2D_EINVAL;
-    }
+    if (!px_check_ramp("frame_matte_edge", op->tag, lo, inv, (flags & L2D_MATTE_HARD) != 0)) return L2D_EINVAL;
     L2D_DRY_RETURN();
     p.lo = lo; p.inv = inv; p.flags = flags; p.r = r;
     hipLaunchKernelGGL(frame_matte_edge_kernel, dim3((W + ME_TW - 1) / ME_TW, (H + ME_TH - 1) / ME_TH), dim3(ME_THREADS), 0, s,

@@ -11,7 +11,7 @@
 // Integer arithmetic throughout, so the frame equals `resize_ref` (and Pillow) byte for byte; the only floating point is the
 // egress chain of the fp16 source.  One work-group per RS_TH x RS_TW output tile and frame: the source patch the tile needs lies
 // in LDS as bytes, the horizontally resampled rows of the patch in a second LDS buffer, the vertical pass reads that one.
-#include "common.h"
+#include "frame_px.h"
 
 #define RS_TW 32                                  // output tile, pixels
 #define RS_TH 32
@@ -30,20 +30,10 @@ static_assert(RS_TH * RS_TW * 3 <= RS_SPAN * RS_PSTRIDE, "the output tile reuses
 #define RS_LDS_BYTES (RS_SPAN * RS_PSTRIDE + RS_SPAN * RS_TW * 3 + (RS_TW + RS_TH) * (RS_MAX_KS + 2) * 4)
 static_assert(2 * RS_LDS_BYTES <= 160 * 1024, "two work-groups per CU");
 
-// the egress op's byte (frame_io.hip fio_u8)
-__device__ __forceinline__ unsigned rs_u8(h16 x) {
-    const h16 t = (h16)((float)x * 0.5f);
-    float v = (float)(h16)((float)t + 0.5f);
-    v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
-    return (unsigned)rintf(255.0f * v);
-}
-
 __device__ __forceinline__ unsigned char rs_clip(int acc) {
     const int v = acc >> RS_BITS;                 // (arithmetic: acc may be negative, Lanczos and bicubic undershoot)
     return (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v));
 }
-
-__device__ __forceinline__ int rs_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // One axis of the tile: the span [s0, s0 + n) of source coordinates it reads, and per output its first tap relative to s0, its
 // count and its weights, copied to LDS.  Everything read from the tables is clamped to the image, to the KS the launcher was
@@ -55,9 +45,9 @@ struct rs_axis {
 __device__ __forceinline__ rs_axis rs_span(const int *__restrict__ tab, int n_out, int n_in, int o0, int t) {
     const int *tmin = tab, *tcnt = tab + n_out;
     rs_axis a;
-    a.s0 = rs_clampi(tmin[o0], 0, n_in);
+    a.s0 = px_clampi(tmin[o0], 0, n_in);
     const int last = o0 + t - 1;
-    const int s1 = rs_clampi(tmin[last] + tcnt[last], a.s0, n_in);
+    const int s1 = px_clampi(tmin[last] + tcnt[last], a.s0, n_in);
     a.n = s1 - a.s0 > RS_SPAN ? RS_SPAN : s1 - a.s0;
     return a;
 }
@@ -68,8 +58,8 @@ __device__ __forceinline__ void rs_stage(const int *__restrict__ tab, int n_out,
     if (lane < RS_TW) {
         int lo = 0, n = 0;
         if (lane < t) {
-            lo = rs_clampi(tmin[o0 + lane] - a.s0, 0, a.n);
-            n = rs_clampi(tcnt[o0 + lane], 0, ks);
+            lo = px_clampi(tmin[o0 + lane] - a.s0, 0, a.n);
+            n = px_clampi(tcnt[o0 + lane], 0, ks);
             n = n > a.n - lo ? a.n - lo : n;
         }
         first[lane] = lo;
@@ -113,7 +103,7 @@ __global__ __launch_bounds__(RS_THREADS) void frame_resize_kernel(const void *__
         for (int i = tid; i < 3 * plane; i += RS_THREADS) {
             const int c = i / plane, r = i - c * plane;
             const int j = r / ax.n, x = r - j * ax.n;
-            patch[j * RS_PSTRIDE + x * 3 + c] = (unsigned char)rs_u8(s16[((long long)c * H + j) * W + x]);
+            patch[j * RS_PSTRIDE + x * 3 + c] = (unsigned char)px_byte(s16[((long long)c * H + j) * W + x]);
         }
     }
     __syncthreads();
@@ -158,33 +148,15 @@ __global__ __launch_bounds__(RS_THREADS) void frame_resize_kernel(const void *__
     }
     __syncthreads();
 
-    // the tile's rows: tw * 3 bytes each at an address of any alignment -- bytes up to the first dword boundary, whole dwords,
-    // bytes behind the last one; RS_ITEMS lanes per row, one store each.  Every byte lies inside row oy0 + yy < Ho, columns
-    // ox0 .. ox0 + tw - 1 < Wo.
+    // the tile's rows: tw * 3 bytes each at an address of any alignment, RS_ITEMS lanes per row, one store each (px_store_row).
+    // Every byte lies inside row oy0 + yy < Ho, columns ox0 .. ox0 + tw - 1 < Wo.
     const int nb = tw * 3;
     for (int i = tid; i < th * RS_ITEMS; i += RS_THREADS) {
         const int yy = i / RS_ITEMS, it = i % RS_ITEMS;
         uint8_t *g = dst + (((long long)b * Ho + oy0 + yy) * Wo + ox0) * 3;
         const unsigned char *o = patch + yy * RS_TW * 3;
-        int head = (int)((0 - (uintptr_t)g) & 3);
-        head = head > nb ? nb : head;
-        const int ndw = (nb - head) >> 2;
-        const int tail = nb - head - ndw * 4;
-        if (it < head) {
-            g[it] = o[it];
-        } else if (it < head + ndw) {
-            const int e = head + (it - head) * 4;
-            *reinterpret_cast<unsigned *>(g + e) =
-                (unsigned)o[e] | ((unsigned)o[e + 1] << 8) | ((unsigned)o[e + 2] << 16) | ((unsigned)o[e + 3] << 24);
-        } else if (it < head + ndw + tail) {
-            const int e = head + ndw * 4 + (it - head - ndw);
-            g[e] = o[e];
-        }
+        px_store_row(g, o, nb, it);
     }
-}
-
-static bool rs_axis_ok(int n_in, int n_out) {
-    return n_out >= 1 && n_out <= L2D_RESIZE_MAX_SIZE && 2ll * n_out >= n_in && n_out <= 8ll * n_in;
 }
 
 int l2d_launch_frame_resize(const l2d_op *op, hipStream_t s) {
@@ -193,7 +165,7 @@ int l2d_launch_frame_resize(const l2d_op *op, hipStream_t s) {
         l2d_set_error("frame_resize(tag %d): invalid arguments (null pointer, non-positive size or source kind %d)", op->tag, kind);
         return L2D_EINVAL;
     }
-    if (!rs_axis_ok(H, Ho) || !rs_axis_ok(W, Wo)) {
+    if (!px_axis_ok(H, Ho) || !px_axis_ok(W, Wo)) {
         l2d_set_error("frame_resize(tag %d): %d x %d -> %d x %d: an output size must lie in 1..%d and between half and 8 times its "
                       "source size", op->tag, H, W, Ho, Wo, L2D_RESIZE_MAX_SIZE);
         return L2D_EINVAL;

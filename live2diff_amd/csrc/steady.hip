@@ -4,7 +4,7 @@
 // source moved since the source of the output before, holds the previous output pixel where it did not (a per-pixel EMA) and
 // lets the new styled pixel through untouched where it did.  The reference has no counterpart.
 //
-//   b = rint(255 clamp(fp16(fp16(x / 2) + 0.5), 0, 1))      the egress op's byte of the source frame (frame_io.hip fio_u8)
+//   b = rint(255 clamp(fp16(fp16(x / 2) + 0.5), 0, 1))      the egress op's byte of the source frame (frame_px.h px_byte)
 //   d = max_c |b_c - bp_c|                                   bp: the bytes of the previous output's source; an integer in 0..255
 //   D = sum of d over the (2r+1) x (2r+1) window             coordinates clamped to the image; an integer: any order
 //   dbar = float(D) / float((2r+1)^2)                        one correctly rounded division (r = 0: float(d))
@@ -19,7 +19,7 @@
 // Makefile), so that numpy restates it bit for bit (live2diff_amd/steady.py `steady_ref`).  The new state (o, b) goes to a
 // second pair of buffers: the tile form's halo reads neighbours' previous bytes, so no block may read what another writes.
 // A bandwidth kernel: 16-byte accesses to the fp16 rows, 8-byte accesses to the planar bytes, plain stores, no MFMA.
-#include "common.h"
+#include "frame_px.h"
 
 #define SD_MAX_R L2D_STEADY_MAX_R
 #define SD_TW 64                              // tile width in pixels: 8 lanes of 8 pixels
@@ -41,14 +41,6 @@ struct sd_params {
     int flags, r;
 };
 
-// the egress op's byte (frame_io.hip fio_u8, colorlock.hip cl_byte)
-__device__ __forceinline__ unsigned sd_byte(h16 x) {
-    const h16 t = (h16)((float)x * 0.5f);
-    float v = (float)(h16)((float)t + 0.5f);
-    v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
-    return (unsigned)rintf(255.0f * v);
-}
-
 __device__ __forceinline__ unsigned sd_absdiff(unsigned a, unsigned b) { return a > b ? a - b : b - a; }
 
 // 8 pixels of one source plane -> their 8 bytes, packed lowest pixel first
@@ -56,8 +48,8 @@ __device__ __forceinline__ uint2 sd_bytes8(h16x8 c) {
     unsigned lo = 0u, hi = 0u;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        lo |= sd_byte(c[e]) << (8 * e);
-        hi |= sd_byte(c[e + 4]) << (8 * e);
+        lo |= px_byte(c[e]) << (8 * e);
+        hi |= px_byte(c[e + 4]) << (8 * e);
     }
     return make_uint2(lo, hi);
 }
@@ -182,7 +174,7 @@ __global__ __launch_bounds__(SD_THREADS) void frame_steady_box_kernel(const h16 
             unsigned m = 0u;
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) {
-                const unsigned a = sd_absdiff(sd_byte(source[ch * HW + e0]), (unsigned)prev_bytes[ch * HW + e0]);
+                const unsigned a = sd_absdiff(px_byte(source[ch * HW + e0]), (unsigned)prev_bytes[ch * HW + e0]);
                 m = a > m ? a : m;
             }
 #pragma unroll
@@ -197,8 +189,7 @@ __global__ __launch_bounds__(SD_THREADS) void frame_steady_box_kernel(const h16 
                 if (own) *reinterpret_cast<uint2 *>(next_bytes + ch * HW + g0) = now;
             }
         }
-        *reinterpret_cast<uint2 *>(&dd[j][cg * 8]) = make_uint2(d[0] | (d[1] << 8) | (d[2] << 16) | (d[3] << 24),
-                                                               d[4] | (d[5] << 8) | (d[6] << 16) | (d[7] << 24));
+        *reinterpret_cast<uint2 *>(&dd[j][cg * 8]) = px_pack8(d);
     }
     __syncthreads();
 
@@ -235,11 +226,6 @@ __global__ __launch_bounds__(SD_THREADS) void frame_steady_box_kernel(const h16 
     }
 }
 
-static bool sd_overlap(const void *a, long long na, const void *b, long long nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
-}
-
 int l2d_launch_frame_steady(const l2d_op *op, hipStream_t s) {
     const int H = op->i[0], W = op->i[1], r = op->i[2], flags = op->i[3];
     if (flags & ~(SD_HARD | SD_SHOW | SD_INIT)) {
@@ -258,19 +244,8 @@ int l2d_launch_frame_steady(const l2d_op *op, hipStream_t s) {
             return L2D_EINVAL;
         }
     }
-    if (H <= 0 || W <= 0) {
-        l2d_set_error("frame_steady(tag %d): invalid arguments (non-positive size %d x %d)", op->tag, H, W);
-        return L2D_EINVAL;
-    }
-    if (W % 8) {
-        l2d_set_error("frame_steady(tag %d): W = %d must be a multiple of 8", op->tag, W);
-        return L2D_EINVAL;
-    }
-    const long long HW = (long long)H * W;
-    if (3 * HW >= (1ll << 31)) {
-        l2d_set_error("frame_steady(tag %d): 3 H W = %lld must stay below 2^31", op->tag, 3 * HW);
-        return L2D_EINVAL;
-    }
+    const long long HW = px_check_frame("frame_steady", op->tag, H, W);
+    if (HW < 0) return L2D_EINVAL;
     if (r < 0 || r > SD_MAX_R) {
         l2d_set_error("frame_steady(tag %d): radius %d, need 0..%d", op->tag, r, SD_MAX_R);
         return L2D_EINVAL;
@@ -281,18 +256,18 @@ int l2d_launch_frame_steady(const l2d_op *op, hipStream_t s) {
     const void *const hwrite[2] = {op->p[4], show ? op->p[6] : nullptr};
     for (int a = 0; a < 2; ++a) {
         for (int b = 0; b < 3; ++b) {
-            if (sd_overlap(hwrite[a], HW * 6, hread[b], HW * 6)) {
+            if (px_overlap(hwrite[a], HW * 6, hread[b], HW * 6)) {
                 l2d_set_error("frame_steady(tag %d): output frame %d overlaps input frame %d (out / the picture against styled, source, "
                               "prev_out)", op->tag, a ? 6 : 4, b);
                 return L2D_EINVAL;
             }
         }
     }
-    if (show && sd_overlap(op->p[4], HW * 6, op->p[6], HW * 6)) {
+    if (show && px_overlap(op->p[4], HW * 6, op->p[6], HW * 6)) {
         l2d_set_error("frame_steady(tag %d): the picture overlaps the output frame", op->tag);
         return L2D_EINVAL;
     }
-    if (sd_overlap(op->p[5], HW * 3, op->p[3], HW * 3)) {
+    if (px_overlap(op->p[5], HW * 3, op->p[3], HW * 3)) {
         l2d_set_error("frame_steady(tag %d): next_bytes overlaps prev_bytes (a tile's halo reads what its neighbour would write)", op->tag);
         return L2D_EINVAL;
     }

@@ -32,7 +32,7 @@ import torch
 
 from . import _lib, ops
 from .frame_io import to_pinned
-from .matte import EDGE_SHIFT, MAX_EDGE_RADIUS, edge_E, edge_coefficients, guide_ref, matte_up_ref, table_words
+from .matte import EDGE_SHIFT, MAX_EDGE_RADIUS, edge_E, edge_coefficients, guide_ref, luma, matte_up_ref, table_words
 from .resize import axis_table, check_filter, check_size, resize_ref
 from .steady import source_bytes, window_sum
 
@@ -83,12 +83,6 @@ def frame_bytes(frame_or_u8) -> np.ndarray:
     if dt == torch.uint8 or dt == np.uint8:
         return _u8_hwc(frame_or_u8, "frame")
     return np.ascontiguousarray(source_bytes(frame_or_u8).transpose(1, 2, 0))
-
-
-def luma(x: np.ndarray) -> np.ndarray:
-    """int64 [...]: (77 R + 150 G + 29 B + 128) >> 8 of uint8 [..., 3]"""
-    b = np.asarray(x).astype(np.int64)
-    return (77 * b[..., 0] + 150 * b[..., 1] + 29 * b[..., 2] + 128) >> 8
 
 
 def gains_ref(frame_or_u8, source, radius: int, eps: float) -> np.ndarray:

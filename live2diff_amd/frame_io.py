@@ -90,6 +90,21 @@ def egress_ref(x: torch.Tensor) -> torch.Tensor:
     return (v.permute(0, 2, 3, 1).float() * 255.0).round().to(torch.uint8).contiguous()
 
 
+def frame16(x, prefix: str, what: str = "frame") -> np.ndarray:
+    """fp16 [3,H,W] of a [3,H,W] or [1,3,H,W] array / tensor, for the oracles of the output chain; `prefix` names the caller in
+    the error"""
+    if torch.is_tensor(x):
+        x = x.detach().cpu().to(torch.float16).numpy()
+    x = np.asarray(x, dtype=np.float16)
+    if not x.flags.writeable:
+        x = x.copy()                       # (torch.from_numpy refuses to share a read-only array quietly)
+    if x.ndim == 4 and x.shape[0] == 1:
+        x = x[0]
+    if x.ndim != 3 or x.shape[0] != 3:
+        raise ValueError(f"{prefix}: expected one [3,H,W] {what}, got {x.shape}")
+    return x
+
+
 # ----------------------------------------------------------------------------- the device side
 def to_pinned(dev: torch.Tensor, host: torch.Tensor) -> np.ndarray:
     """a static device buffer copied into its pinned twin on the current stream and waited for: the numpy view of the pinned

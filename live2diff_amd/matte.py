@@ -120,11 +120,16 @@ def edge_E(radius: int, eps: float) -> float:
     return float(n * n) * float(eps) * float(eps)
 
 
+def luma(x: np.ndarray) -> np.ndarray:
+    """int64 [...]: (77 R + 150 G + 29 B + 128) >> 8 of uint8 [..., 3]"""
+    b = np.asarray(x).astype(np.int64)
+    return (77 * b[..., 0] + 150 * b[..., 1] + 29 * b[..., 2] + 128) >> 8
+
+
 def guide_ref(source) -> np.ndarray:
-    """int64 [H,W] in 0..255: the guide Y = (77 R + 150 G + 29 B + 128) >> 8 of the egress bytes of the fp16 [3,H,W] frame"""
+    """int64 [H,W] in 0..255: the guide Y, the luma of the egress bytes of the fp16 [3,H,W] frame"""
     from .steady import source_bytes
-    b = source_bytes(source).astype(np.int64)
-    return (77 * b[0] + 150 * b[1] + 29 * b[2] + 128) >> 8
+    return luma(source_bytes(source).transpose(1, 2, 0))
 
 
 def edge_coefficients(P: np.ndarray, Y: np.ndarray, radius: int, eps: float) -> Tuple[np.ndarray, np.ndarray]:

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .frame_io import egress_ref
+from .frame_io import egress_ref, frame16
 
 MAX_RADIUS = ops.STEADY_MAX_R
 SERVED_OUTPUT_TYPES = ("pil", "pt", "np", "u8", "jpeg")
@@ -44,24 +44,10 @@ def steady_params(lo: float, hi: float) -> Tuple[np.float32, np.float32, bool]:
     return np.float32(lo), inv, bool(hard)
 
 
-def _frame16(x, what: str = "frame") -> np.ndarray:
-    """fp16 [3,H,W] of a [3,H,W] or [1,3,H,W] array / tensor"""
-    if torch.is_tensor(x):
-        x = x.detach().cpu().to(torch.float16).numpy()
-    x = np.asarray(x, dtype=np.float16)
-    if not x.flags.writeable:
-        x = x.copy()                       # (torch.from_numpy refuses to share a read-only array quietly)
-    if x.ndim == 4 and x.shape[0] == 1:
-        x = x[0]
-    if x.ndim != 3 or x.shape[0] != 3:
-        raise ValueError(f"steady: expected one [3,H,W] {what}, got {x.shape}")
-    return x
-
-
 def source_bytes(source) -> np.ndarray:
     """planar uint8 [3,H,W]: the bytes `egress_ref` makes of the finite fp16 frame `source` -- the fp16 chain
     clamp(fp16(fp16(x / 2) + 0.5), 0, 1), then rint(255 v), half to even: what a viewer would see of it"""
-    x = np.ascontiguousarray(_frame16(source, "source frame"))
+    x = np.ascontiguousarray(frame16(source, "steady", "source frame"))
     return np.ascontiguousarray(egress_ref(torch.from_numpy(x))[0].numpy().transpose(2, 0, 1))
 
 
@@ -108,7 +94,7 @@ def steady_ref(styled, source, state, *, lo: float, hi: float, strength: float, 
     rounding per operation; where a == 1 the output is S's own bits.  o lies between S and P (rounding is monotone; asserted),
     nothing is clamped.  `show` returns fp16(2 w - 1) in all three channels instead; the new state is (o, b) either way.  With
     `init` the output and the state's frame are `styled` itself."""
-    S16 = np.ascontiguousarray(_frame16(styled, "styled frame"))
+    S16 = np.ascontiguousarray(frame16(styled, "steady", "styled frame"))
     b = source_bytes(source)
     if b.shape != S16.shape:
         raise ValueError(f"steady: the styled frame is {S16.shape}, its source {b.shape}")
@@ -119,7 +105,7 @@ def steady_ref(styled, source, state, *, lo: float, hi: float, strength: float, 
         steady_params(lo, hi)
         return S16[None].copy(), (S16.copy(), b)
     P16, bp = state
-    P16 = _frame16(P16, "previous frame")
+    P16 = frame16(P16, "steady", "previous frame")
     if P16.shape != S16.shape:
         raise ValueError(f"steady: the styled frame is {S16.shape}, the previous output {P16.shape}")
     w = weight_ref(b, bp, lo=lo, hi=hi, radius=radius)
