@@ -504,6 +504,37 @@ enum {
  *   nothing has to be zeroed.  Refused: a null or misaligned pointer, W % 8 != 0, 3 H W >= 2^31, r outside
  *   1..L2D_BACKDROP_MAX_R, passes outside 1..L2D_BACKDROP_MAX_PASSES, unknown flags, p2 overlapping p0 or p1, lo / inv as
  *   L2D_OP_FRAME_MATTE refuses them.
+ *
+ * Follow (steady_follow.hip; no counterpart in the reference): steady along the source's motion.  L2D_OP_FRAME_STEADY compares the
+ *   source bytes at the same coordinates, so under a moving camera it holds nothing; these two ops find, per 8 x 8 block, where in
+ *   the previous frame to look, and run the same arithmetic there.  Exact integers in the search, L2D_OP_FRAME_STEADY's operations
+ *   behind it, so that numpy restates both bit for bit (live2diff_amd/steady.py motion_ref, follow_ref).
+ * L2D_OP_FRAME_MOTION  one launch:  p0 source half [3][H][W] (16-byte aligned) p1 prev_bytes uint8 [3][H][W] (planar, 8-byte aligned:
+ *   p3 of L2D_OP_FRAME_STEADY) p2 field int8 [ceil(H/8)][W/8][2] (dy, dx per block; any alignment) ; i0 H i1 W (W % 8 == 0, 3 H W <
+ *   2^31) i2 search R (1..L2D_FOLLOW_MAX_SEARCH) i3 bias (0..L2D_FOLLOW_MAX_BIAS).  now = L2D_OP_FRAME_EGRESS' bytes of p0.  The
+ *   window of block (i, j) is rows 8i - L2D_FOLLOW_APRON .. 8i + 11 and columns 8j - 4 .. 8j + 11; cost(dy, dx) = the sum over the
+ *   window and the three channels of |now[c][cl(y)][cl(x)] - p1[c][cl(y + dy)][cl(x + dx)]|, every coordinate clamped to the image
+ *   on its own (<= 768 * 255); key = (cost + bias (|dy| + |dx|)) 512 + rank, rank the position of (dy, dx) among [-R, R]^2 in the
+ *   order (|dy| + |dx|, dy, dx) (key < 2^27); the block's vector is the candidate of the smallest key: ties go to the shortest
+ *   vector, then the smaller dy, then the smaller dx, and the zero vector wins any tie.  bias is in summed byte levels per pixel of
+ *   L1 displacement.  One work-group per strip of eight blocks: now of its windows (16 x 72 x 3 bytes) and p1 with the search
+ *   margin (at most 32 x 88 x 3) staged once in LDS, clamped while staged; 32 lanes per block take the candidates, four
+ *   neighbouring dx at a time, with v_sad_u8; the minimum over the packed keys goes through LDS -- no atomics, any order gives
+ *   the same field.  Every block of p2 is written by plain stores on every launch: nothing has to be zeroed.  Refused: a null or
+ *   misaligned pointer, W % 8 != 0, 3 H W >= 2^31, R or bias out of range, p2 overlapping p0 or p1.
+ * L2D_OP_FRAME_STEADY_FOLLOW  one launch:  p0 .. p6 as L2D_OP_FRAME_STEADY's p7 field int8 [ceil(H/8)][W/8][2] (p2 of
+ *   L2D_OP_FRAME_MOTION; any alignment) ; i0 H i1 W i2 r (0..L2D_STEADY_MAX_R) i3 flags (L2D_STEADY_HARD | _SHOW; an init frame is
+ *   L2D_OP_FRAME_STEADY's: it looks nowhere) ; f0 lo f1 inv f2 s.  With (dy, dx) the vector of block (y / 8, x / 8):
+ *   bp[c][y][x] = p3[c][cl(y + dy)][cl(x + dx)] and P[c][y][x] = p2[c][cl(y + dy)][cl(x + dx)]; then L2D_OP_FRAME_STEADY's
+ *   arithmetic on them, operation for operation: d = max_c |b - bp| (each pixel with its own block's vector), its window sum with
+ *   clamped coordinates, dbar, t, w, a, o = half(P + a (S - P)) and S's own bits where a == 1, SHOW.  p4 = o and p5 = b (the
+ *   bytes of p1 where they are, not displaced) are the next frame's p2 and p3.  An all-zero field gives L2D_OP_FRAME_STEADY's
+ *   bits.  A vector is used only through clamped coordinates: whatever p7 holds, nothing outside p2 and p3 is read.  One
+ *   work-group per 16 x 64 tile, d of the tile and its halo, then the row sums, in LDS, as L2D_OP_FRAME_STEADY's tile form (r = 0
+ *   takes the same kernel); an 8-aligned pixel group lies inside one block, so it has one vector.  Every element of p4 and p5 is
+ *   written by a plain store on every launch.  Refused: a null pointer (p6 only without SHOW), a misaligned one, W % 8 != 0,
+ *   3 H W >= 2^31, r out of range, unknown flags (INIT among them), p4 (or p6) overlapping p0 .. p3 or one another, p5
+ *   overlapping p0 .. p3, p7 overlapping p4, p5 or p6, lo / inv / s as L2D_OP_FRAME_STEADY refuses them.
  */
 enum {
     L2D_OP_IGEMM = 1,
@@ -560,6 +591,8 @@ enum {
     L2D_OP_DEPTH_INGEST = 52,
     L2D_OP_DEPTH_NORMALIZE = 53,
     L2D_OP_FRAME_BACKDROP_BLUR = 54,
+    L2D_OP_FRAME_MOTION = 55,
+    L2D_OP_FRAME_STEADY_FOLLOW = 56,
 };
 
 /* flag bits of L2D_OP_FRAME_MATTE (i4) and L2D_OP_FRAME_MATTE_UP (i6); HARD and FAR also of L2D_OP_FRAME_MATTE_EDGE (i3) */
@@ -586,6 +619,12 @@ enum {
 #define L2D_STEADY_SHOW 2
 #define L2D_STEADY_INIT 4
 #define L2D_STEADY_MAX_R 8
+
+/* sizes of L2D_OP_FRAME_MOTION and L2D_OP_FRAME_STEADY_FOLLOW (the flags of the latter, i3, are L2D_STEADY_HARD | _SHOW) */
+#define L2D_FOLLOW_BLOCK 8 /* one vector per 8 x 8 pixels */
+#define L2D_FOLLOW_APRON 4 /* the matching window is the block and 4 pixels around it: 16 x 16 */
+#define L2D_FOLLOW_MAX_SEARCH 8
+#define L2D_FOLLOW_MAX_BIAS 4096
 
 /* flag bits of L2D_OP_FRAME_DETAIL_GAIN (i3: U8) and L2D_OP_FRAME_DETAIL (i4: SHOW) */
 #define L2D_DETAIL_U8 1 /* p0 is the uint8 [H][W][3] frame of the matte, not the half frame */

@@ -35,6 +35,8 @@ OP_FRAME_MATTE_EDGE = 49
 OP_FRAME_DETAIL_GAIN, OP_FRAME_DETAIL = 50, 51
 OP_DEPTH_INGEST, OP_DEPTH_NORMALIZE = 52, 53
 OP_FRAME_BACKDROP_BLUR = 54
+OP_FRAME_MOTION = 55
+OP_FRAME_STEADY_FOLLOW = 56
 ABI_VERSION = 6
 
 

@@ -1685,6 +1685,71 @@ def frame_steady(styled, source, prev_out, prev_bytes, out, next_bytes, *, H, W,
     return op, keep
 
 
+# ----------------------------------------------------------------------------- follow (steady_follow.hip, steady.py)
+FOLLOW_BLOCK, FOLLOW_APRON = 8, 4                    # l2d.h L2D_FOLLOW_*
+FOLLOW_MAX_SEARCH, FOLLOW_MAX_BIAS = 8, 4096
+
+
+def _follow_field(name, field, H, W):
+    shape = ((H + FOLLOW_BLOCK - 1) // FOLLOW_BLOCK, W // FOLLOW_BLOCK, 2)
+    if field.dtype != torch.int8 or tuple(field.shape) != shape or not field.is_contiguous():
+        raise ValueError(f"{name}: field: expected a contiguous int8 {list(shape)} field, got {field.dtype} {tuple(field.shape)}")
+
+
+def _steady_plane(name, t, H, W):
+    if t.dtype != torch.uint8 or tuple(t.shape[-3:]) != (3, H, W) or t.numel() != 3 * H * W or not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous planar uint8 [3,{H},{W}] record, got {t.dtype} {tuple(t.shape)}")
+
+
+def frame_motion(source, prev_bytes, field, *, H, W, search, bias):
+    """the fp16 [3,H,W] `source` frame + the planar uint8 [3,H,W] `prev_bytes` of the steady state -> int8 [ceil(H/8), W/8, 2]
+    `field`: per 8 x 8 block the vector (dy, dx) of the best match of the frame's bytes in the previous ones
+    (steady.motion_ref).  `search`: 1..FOLLOW_MAX_SEARCH pixels; `bias`: 0..FOLLOW_MAX_BIAS summed byte levels per pixel of L1
+    displacement."""
+    _lock_frame("frame_motion: source", source, H, W)
+    _steady_plane("frame_motion: prev_bytes", prev_bytes, H, W)
+    _follow_field("frame_motion", field, H, W)
+    if isinstance(search, bool) or int(search) != search or not 1 <= int(search) <= FOLLOW_MAX_SEARCH:
+        raise ValueError(f"frame_motion: search={search!r}: use an integer from 1 to {FOLLOW_MAX_SEARCH}")
+    if isinstance(bias, bool) or int(bias) != bias or not 0 <= int(bias) <= FOLLOW_MAX_BIAS:
+        raise ValueError(f"frame_motion: bias={bias!r}: use an integer from 0 to {FOLLOW_MAX_BIAS}")
+    op = L2dOp()
+    op.kind = _lib.OP_FRAME_MOTION
+    keep = (source, prev_bytes, field)
+    for j, t in enumerate(keep):
+        op.p[j] = _ptr(t)
+    for j, v in enumerate([H, W, search, bias]):
+        op.i[j] = int(v)
+    return op, keep
+
+
+def frame_steady_follow(styled, source, prev_out, prev_bytes, out, next_bytes, field, *, H, W, lo32, inv32, s32, r=0, hard=False,
+                        show=False, picture=None):
+    """`frame_steady` with the previous record fetched along `field` (`frame_motion`'s; steady.follow_ref): the previous output
+    held where the source's bytes did not move relative to where they came from.  No `init`: an init frame is `frame_steady`'s."""
+    for name, t in (("styled", styled), ("source", source), ("prev_out", prev_out), ("out", out)):
+        _lock_frame(f"frame_steady_follow: {name}", t, H, W)
+    _steady_plane("frame_steady_follow: prev_bytes", prev_bytes, H, W)
+    _steady_plane("frame_steady_follow: next_bytes", next_bytes, H, W)
+    _follow_field("frame_steady_follow", field, H, W)
+    if bool(show) != (picture is not None):
+        raise ValueError("frame_steady_follow: a picture buffer goes with show=True, and with nothing else")
+    if picture is not None:
+        _lock_frame("frame_steady_follow: picture", picture, H, W)
+    if isinstance(r, bool) or int(r) != r or not 0 <= int(r) <= STEADY_MAX_R:
+        raise ValueError(f"frame_steady_follow: r={r!r}: use an integer from 0 to {STEADY_MAX_R}")
+    op = L2dOp()
+    op.kind = _lib.OP_FRAME_STEADY_FOLLOW
+    keep = (styled, source, prev_out, prev_bytes, out, next_bytes, picture, field)
+    for j, t in enumerate(keep):
+        op.p[j] = _ptr(t)
+    flags = (STEADY_HARD if hard else 0) | (STEADY_SHOW if show else 0)
+    for j, v in enumerate([H, W, r, flags]):
+        op.i[j] = int(v)
+    op.f[0], op.f[1], op.f[2] = float(lo32), float(inv32), float(s32)
+    return op, keep
+
+
 # ----------------------------------------------------------------------------- detail mode (detail.hip, detail.py)
 DETAIL_U8, DETAIL_SHOW = 1, 2                        # l2d.h L2D_DETAIL_*
 DETAIL_MAX_GAIN = 261120                             # |A| = |rint(4096 a)| with |a| <= 127.5 / 2 (eps >= 1): detail.hip states it

@@ -21,6 +21,7 @@ device (jpeg_io.HipJpegDecoder) and ingested there like a uint8 frame (`jpeg_dec
 with Pillow's arithmetic, behind both and in front of the JPEG encoder or the copy to the host (resize.py).
 `set_matte_source("camera")` composites the matte at the output size over the camera's own pixels (matte.HipMatteUp).
 `set_steady` holds the previous output pixel where the frame's source did not move (steady.py), behind the colour lock.
+`set_steady_follow` lets it look where each 8 x 8 block of the source came from, so that it also holds under a moving camera.
 `set_matte_edge` refines the matte by the source frame, so that its edges land on the frame's own (matte.edge_ref).
 `set_detail` brings the camera's fine detail into the frame at the output size, behind the resize (detail.py).
 `set_backdrop` puts the room blurred, a colour or an image behind the matte in place of the real frame (backdrop.py).
@@ -295,6 +296,7 @@ class StreamAnimateDiffusionDepthWrapper:
     _steady_state = None                    # (previous output, previous source bytes) on the host route; on the device it stays there
     _steady_init = True                     # the next steadied frame starts the sequence: it passes as it is
     _steady_last = None                     # the last steadied frame: what a dropped frame's repeated output reuses
+    _steady_follow = None                   # the follow setting beside steady (set_steady_follow), None: the same coordinates
     _size = None                            # the output size's settings (set_output_size), None: the UNet's geometry
     _size_dev = None                        # resize.HipResize of the current size, made by the first resized frame on the device
     _size_jpeg = None                       # {(height, width): jpeg_io.HipJpegEncoder}, one per output size "jpeg" frames left at
@@ -322,7 +324,7 @@ class StreamAnimateDiffusionDepthWrapper:
                  jpeg_quality: int = 75, jpeg_decode: str = "device", output_size: Optional[Tuple[int, int]] = None,
                  output_resample: str = "lanczos", matte_source: str = "stream", steady: Optional[dict] = None,
                  matte_edge: Optional[dict] = None, detail: Optional[dict] = None, depth_input: Optional[dict] = None,
-                 depth_source: str = "detector", backdrop: Optional[dict] = None):
+                 depth_source: str = "detector", backdrop: Optional[dict] = None, steady_follow: Optional[dict] = None):
         _check_depth_source(depth_source)
         self._check_keywords(few_step_model_type=few_step_model_type, acceleration=acceleration, cfg_type=cfg_type,
                              use_denoising_batch=use_denoising_batch, frame_buffer_size=frame_buffer_size, device_ids=device_ids,
@@ -344,13 +346,13 @@ class StreamAnimateDiffusionDepthWrapper:
                     similar_image_filter_max_skip_frame=similar_image_filter_max_skip_frame, jpeg_quality=jpeg_quality,
                     jpeg_decode=jpeg_decode, output_size=output_size, output_resample=output_resample, matte_source=matte_source,
                     steady=steady, matte_edge=matte_edge, detail=detail, depth_input=depth_input, depth_source=depth_source,
-                    backdrop=backdrop)
+                    backdrop=backdrop, steady_follow=steady_follow)
 
     @classmethod
     def from_components(cls, pipe, *, num_inference_steps: int, t_index_list: Optional[List[int]] = None,
                         strength: Optional[float] = None, **kw):
         """The wrapper around an already assembled `pipe` namespace (tests, synthetic weights).  Keywords: those of the
-        constructor that do not name files (`jpeg_quality`, `jpeg_decode`, `output_size`, `output_resample`, `matte_source`, `steady`, `matte_edge`, `detail`, `backdrop`, `depth_input` and `depth_source` among them; with `depth_source="input"` the namespace needs no `depth_model`), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
+        constructor that do not name files (`jpeg_quality`, `jpeg_decode`, `output_size`, `output_resample`, `matte_source`, `steady`, `steady_follow`, `matte_edge`, `detail`, `backdrop`, `depth_input` and `depth_source` among them; with `depth_source="input"` the namespace needs no `depth_model`), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
         self = cls.__new__(cls)
         cls._check_keywords(**{k: kw.pop(k) for k in ("acceleration", "cfg_type", "use_denoising_batch", "frame_buffer_size",
                                                       "device_ids", "opt_unet", "few_step_model_type") if k in kw},
@@ -391,7 +393,7 @@ class StreamAnimateDiffusionDepthWrapper:
                scheduler_kwargs=None, frame_pipelining=False, enable_similar_image_filter=False,
                similar_image_filter_threshold=0.98, similar_image_filter_max_skip_frame=10, jpeg_quality=75, jpeg_decode="device",
                output_size=None, output_resample="lanczos", matte_source="stream", steady=None, matte_edge=None, detail=None,
-               depth_input=None, depth_source="detector", backdrop=None):
+               depth_input=None, depth_source="detector", backdrop=None, steady_follow=None):
         self._check_matte_source(matte_source)
         if backdrop is not None and not isinstance(backdrop, dict):
             raise ValueError(f"backdrop={backdrop!r}: use a dict of set_backdrop's keywords, or None")
@@ -400,6 +402,8 @@ class StreamAnimateDiffusionDepthWrapper:
             raise ValueError(f"depth_input={depth_input!r}: use a dict of set_depth_input's keywords, or None")
         if steady is not None and not isinstance(steady, dict):
             raise ValueError(f"steady={steady!r}: use a dict of set_steady's keywords, or None")
+        if steady_follow is not None and not isinstance(steady_follow, dict):
+            raise ValueError(f"steady_follow={steady_follow!r}: use a dict of set_steady_follow's keywords, or None")
         if matte_edge is not None and not isinstance(matte_edge, dict):
             raise ValueError(f"matte_edge={matte_edge!r}: use a dict of set_matte_edge's keywords, or None")
         if detail is not None and not isinstance(detail, dict):
@@ -441,6 +445,8 @@ class StreamAnimateDiffusionDepthWrapper:
         self.set_matte_source(matte_source)
         if steady is not None:
             self.set_steady(**steady)
+        if steady_follow is not None:
+            self.set_steady_follow(**steady_follow)
         if matte_edge is not None:
             self.set_matte_edge(**matte_edge)
         if detail is not None:
@@ -845,10 +851,36 @@ class StreamAnimateDiffusionDepthWrapper:
         self._steady_init = True
         self._release_line()
 
+    # ------------------------------------------------------------------ follow (steady.py)
+    @property
+    def steady_follow(self) -> Optional[dict]:
+        """the current follow setting as {search, bias}, or None"""
+        return None if self._steady_follow is None else dict(self._steady_follow)
+
+    def set_steady_follow(self, search: int = 4, bias: int = 256) -> None:
+        """Let steady follow the source's motion.  Steady compares the source at the same coordinates, so under a hand-held
+        camera, a slow pan or a person walking through the frame it holds nothing.  With this setting every 8 x 8 block of the
+        frame's source is matched against the source of the output before, over displacements of up to `search` pixels (1..8)
+        on either axis, on the bytes a viewer would see; the previous output and the previous source are then read where the
+        block came from, and steady's arithmetic runs on them unchanged: what moved rigidly counts as still and is held along
+        its path, what changed passes.  `bias` (0..4096, in summed byte levels over the block's 16 x 16 window per pixel of
+        displacement) keeps sensor noise in flat areas from producing vectors; the default was chosen on synthetic noise, not
+        on footage.  A setting beside steady, like `set_matte_edge` beside the matte: it acts only while steady is set, on
+        its output types, and `steady` keeps its five keys; `show` shows the weight along the vectors.  One more launch on
+        the device in front of steady's, no synchronisation.  The state is steady's own, so a change applies from the next
+        output and does not restart the sequence; the init frame, repeated frames and `prepare` behave as under `set_steady`.
+        May be called before or after `prepare` and between any two frames."""
+        from .steady import check_follow
+        self._steady_follow = check_follow(search, bias)
+
+    def clear_steady_follow(self) -> None:
+        """Back to steady at the same coordinates; the sequence goes on."""
+        self._steady_follow = None
+
     def _steadied(self, image_tensor: torch.Tensor, slot, repeated: bool) -> torch.Tensor:
-        """the frame under the steady mode, fp16 [1,3,H,W]: op 48 on the device, `steady_ref` without one.  `repeated`: the
-        near-duplicate filter dropped the frame and `image_tensor` is the output of the one before; its steadied frame is
-        reused and the state does not move."""
+        """the frame under the steady mode, fp16 [1,3,H,W]: op 48 (with follow: ops 55 and 56) on the device, `steady_ref`
+        (`follow_ref`) without one.  `repeated`: the near-duplicate filter dropped the frame and `image_tensor` is the output of
+        the one before; its steadied frame is reused and the state does not move."""
         st = self._steady
         if repeated and self._steady_last is not None:
             return self._steady_last
@@ -862,7 +894,12 @@ class StreamAnimateDiffusionDepthWrapper:
             if self._steady_dev is None:
                 from .steady import HipSteady
                 self._steady_dev = HipSteady(self.height, self.width, device=image_tensor.device)
-            out = self._steady_dev.steady(image_tensor[0], slot.source, st, init=self._steady_init)
+            out = self._steady_dev.steady(image_tensor[0], slot.source, st, init=self._steady_init, follow=self._steady_follow)
+        elif self._steady_follow is not None:
+            from .steady import follow_ref
+            out, self._steady_state, _ = follow_ref(image_tensor[:1], slot.source, self._steady_state, **self._steady_follow, **st,
+                                                    init=self._steady_init)
+            out = torch.from_numpy(out)
         else:
             from .steady import steady_ref
             out, self._steady_state = steady_ref(image_tensor[:1], slot.source, self._steady_state, lo=st["lo"], hi=st["hi"],

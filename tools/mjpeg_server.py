@@ -46,6 +46,12 @@ answers the current one as a JSON string.
 motion).  `POST /steady` with the same text as its body, or `off`, changes it while the stream runs; `GET /steady` answers the
 current settings as JSON (`null`: off).
 
+`--steady-follow R[,BIAS]` lets the steady mode follow the source's motion (`wrapper.set_steady_follow`: every 8 x 8 block is
+matched against the frame before over up to R pixels, 1..8, and the previous output is held along the vectors -- under a
+hand-held camera or a pan, where plain steady holds nothing; BIAS, default 256, keeps noise in flat areas from producing
+vectors).  It acts only while `--steady` is set.  `POST /steady-follow` with the same text changes it while the stream runs, an
+empty body or `off` clears it; `GET /steady-follow` answers the current settings as JSON.
+
 `--matte-edge R[,EPS]` refines the matte by the frame it cuts, so that its edges land on the frame's own edges
 (`wrapper.set_matte_edge`: a guided filter of radius R in 1..8 pixels, one more launch in front of the composite; EPS, default
 10, is the contrast in byte levels below which a window counts as flat).  It acts only while a matte is set.  `POST /matte-edge`
@@ -305,6 +311,54 @@ class SteadyBox:
             else:
                 wrapper.set_steady(want["lo"], want["hi"], strength=want["strength"], radius=want["radius"])
             self.current = wrapper.steady
+        except ValueError:
+            self.failed += 1
+
+
+def parse_steady_follow_arg(text: str):
+    """`R[,BIAS]` -> the keywords of `wrapper.set_steady_follow`, `off` -> None; ValueError otherwise"""
+    from live2diff_amd.steady import FOLLOW_MAX_BIAS, FOLLOW_MAX_SEARCH, check_follow
+    text = text.strip()
+    if text == "off":
+        return None
+    parts = [t.strip() for t in text.split(",")]
+    if not 1 <= len(parts) <= 2:
+        raise ValueError(f"steady follow {text!r}: use R[,BIAS] or off")
+    try:
+        search = int(parts[0])
+        bias = int(parts[1]) if len(parts) > 1 else 256
+    except ValueError:
+        raise ValueError(f"steady follow {text!r}: R is an integer from 1 to {FOLLOW_MAX_SEARCH}, BIAS an integer from 0 to "
+                         f"{FOLLOW_MAX_BIAS}") from None
+    return check_follow(search, bias)
+
+
+class SteadyFollowBox:
+    """What `POST /steady-follow` delivers: the newest requested follow setting (a dict of `set_steady_follow` keywords, or None
+    for `off` and for an empty body), applied by the producer between two frames.  `current` is what was last applied; `failed`
+    counts requests the wrapper refused."""
+    _NOTHING = object()
+
+    def __init__(self, current=None):
+        self._lock = threading.Lock()
+        self.current, self._want, self.failed = current, self._NOTHING, 0
+
+    def put(self, settings) -> None:
+        with self._lock:
+            self._want = settings
+
+    def apply(self, wrapper) -> None:
+        """(producer thread, between frames)"""
+        with self._lock:
+            want, self._want = self._want, self._NOTHING
+        if want is self._NOTHING:
+            return
+        try:
+            if want is None:
+                wrapper.clear_steady_follow()
+            else:
+                wrapper.set_steady_follow(want["search"], want["bias"])
+            self.current = wrapper.steady_follow
         except ValueError:
             self.failed += 1
 
@@ -587,9 +641,9 @@ class Latest:
 
 def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = None, mattes: "MatteBox" = None, colors: "ColorBox" = None,
                  sizes: "SizeBox" = None, sources: "MatteSourceBox" = None, steadies: "SteadyBox" = None, details: "DetailBox" = None,
-                 backdrops: "BackdropBox" = None, edges: "MatteEdgeBox" = None):
+                 backdrops: "BackdropBox" = None, follows: "SteadyFollowBox" = None, edges: "MatteEdgeBox" = None):
     boxes = {"/matte": mattes, "/color": colors, "/size": sizes, "/matte-source": sources, "/steady": steadies, "/matte-edge": edges,
-             "/detail": details, "/backdrop": backdrops}
+             "/detail": details, "/backdrop": backdrops, "/steady-follow": follows}
     page = PAGE if inbox is None else CAMERA_PAGE
 
     class Handler(BaseHTTPRequestHandler):
@@ -645,7 +699,7 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
             except ValueError:
                 self.send_error(411)
                 return
-            if n == 0 and empty:                          # (`/backdrop`: an empty body clears it)
+            if n == 0 and empty:                          # (`/backdrop`, `/steady-follow`: an empty body clears it)
                 box.put(None)
                 self.send_response(204)
                 self.end_headers()
@@ -703,6 +757,9 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
             if self.path == "/matte-edge" and edges is not None:
                 self.do_matte(edges, parse_matte_edge_arg)
                 return
+            if self.path == "/steady-follow" and follows is not None:
+                self.do_matte(follows, parse_steady_follow_arg, empty=True)
+                return
             if self.path == "/detail" and details is not None:
                 self.do_matte(details, parse_detail_arg)
                 return
@@ -733,9 +790,10 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
 
 def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: StyleBox = None, mattes: MatteBox = None,
             colors: ColorBox = None, sizes: SizeBox = None, sources: MatteSourceBox = None, steadies: SteadyBox = None,
-            details: DetailBox = None, backdrops: BackdropBox = None, edges: MatteEdgeBox = None) -> None:
+            details: DetailBox = None, backdrops: BackdropBox = None, follows: SteadyFollowBox = None,
+            edges: MatteEdgeBox = None) -> None:
     """the producer: loops `frames` through the wrapper until `stop` is set; a posted style, matte, colour lock, output size,
-    matte source, steady mode, matte edge, detail mode or backdrop is applied between two frames"""
+    matte source, steady mode, follow setting, matte edge, detail mode or backdrop is applied between two frames"""
     from live2diff_amd.jpeg import mjpeg_part
     try:
         i = 0
@@ -752,6 +810,8 @@ def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: Styl
                 sources.apply(wrapper)
             if steadies is not None:
                 steadies.apply(wrapper)
+            if follows is not None:
+                follows.apply(wrapper)
             if edges is not None:
                 edges.apply(wrapper)
             if details is not None:
@@ -767,7 +827,7 @@ def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: Styl
 def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: threading.Event, styles: StyleBox = None,
                    mattes: MatteBox = None, colors: ColorBox = None, sizes: SizeBox = None, sources: MatteSourceBox = None,
                    steadies: SteadyBox = None, details: DetailBox = None, backdrops: BackdropBox = None,
-                   edges: MatteEdgeBox = None) -> None:
+                   follows: SteadyFollowBox = None, edges: MatteEdgeBox = None) -> None:
     """the producer of `--input post`: the first frames posted warm the stream up, then the newest posted frame goes through the
     wrapper, for ever; a frame the wrapper refuses (ValueError: a damaged file) is dropped and counted in `inbox.failed`"""
     from live2diff_amd.jpeg import mjpeg_part
@@ -792,6 +852,8 @@ def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: thr
                 sources.apply(wrapper)
             if steadies is not None:
                 steadies.apply(wrapper)
+            if follows is not None:
+                follows.apply(wrapper)
             if edges is not None:
                 edges.apply(wrapper)
             if details is not None:
@@ -837,6 +899,11 @@ def main(argv=None):
                     help="hold the previous output pixel where the source moved by LO byte levels or less (moving from HI on), by "
                          "STRENGTH (default 0.8), the motion averaged over a radius of RADIUS pixels (default 2); POST /steady with "
                          "the same text, or `off`, changes it between frames")
+    ap.add_argument("--steady-follow", default=None, metavar="R[,BIAS]",
+                    help="let the steady mode follow the source's motion: every 8 x 8 block is matched against the frame before over "
+                         "displacements of up to R pixels (1..8); BIAS (default 256, 0..4096) keeps noise in flat areas from producing "
+                         "vectors; acts while --steady is set; POST /steady-follow with the same text changes it between frames, an "
+                         "empty body (or `off`) clears it")
     ap.add_argument("--matte-edge", default=None, metavar="R[,EPS]",
                     help="refine the matte by the frame it cuts (a guided filter of radius R, 1..8 pixels; EPS, default 10: the contrast in "
                          "byte levels below which a window counts as flat); acts while a matte is set; POST /matte-edge with the same "
@@ -855,6 +922,7 @@ def main(argv=None):
     color = parse_color_arg(args.color_lock) if args.color_lock else None
     size = parse_size_arg(args.output_size) if args.output_size else None
     steady = parse_steady_arg(args.steady) if args.steady else None
+    follow = parse_steady_follow_arg(args.steady_follow) if args.steady_follow else None
     edge = parse_matte_edge_arg(args.matte_edge) if args.matte_edge else None
     detail = parse_detail_arg(args.detail) if args.detail else None
     backdrop = parse_backdrop_arg(args.backdrop) if args.backdrop else None
@@ -887,6 +955,9 @@ def main(argv=None):
     if steady is not None:
         w.set_steady(steady["lo"], steady["hi"], strength=steady["strength"], radius=steady["radius"])      # (before `prepare` too)
     steadies = SteadyBox(w.steady)
+    if follow is not None:
+        w.set_steady_follow(follow["search"], follow["bias"])
+    follows = SteadyFollowBox(w.steady_follow)
     if edge is not None:
         w.set_matte_edge(edge["radius"], edge["eps"])
     edges = MatteEdgeBox(w.matte_edge)
@@ -900,11 +971,11 @@ def main(argv=None):
     latest, stop = Latest(), threading.Event()
     inbox = Inbox(sink) if post else None
     if post:
-        producer = threading.Thread(target=produce_posted, args=(w, prompt, inbox, latest, stop, styles, mattes, colors, sizes, sources, steadies, details, backdrops, edges), name="producer", daemon=True)
+        producer = threading.Thread(target=produce_posted, args=(w, prompt, inbox, latest, stop, styles, mattes, colors, sizes, sources, steadies, details, backdrops, follows, edges), name="producer", daemon=True)
     else:
         w.prepare(frames[:sink], prompt)
-        producer = threading.Thread(target=produce, args=(w, frames, latest, stop, styles, mattes, colors, sizes, sources, steadies, details, backdrops, edges), name="producer", daemon=True)
-    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest, inbox, styles, mattes, colors, sizes, sources, steadies, details, backdrops, edges))
+        producer = threading.Thread(target=produce, args=(w, frames, latest, stop, styles, mattes, colors, sizes, sources, steadies, details, backdrops, follows, edges), name="producer", daemon=True)
+    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest, inbox, styles, mattes, colors, sizes, sources, steadies, details, backdrops, follows, edges))
     server.daemon_threads = True
     producer.start()
     print(f"http://{args.host}:{args.port}/  ({args.height}x{args.width}, quality {args.quality}; Ctrl-C stops)")

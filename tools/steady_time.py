@@ -10,7 +10,13 @@
   route    host uint8 frame -> host uint8 frame through the wrapper's "u8" output at full size (SD-1.5 widths, 512x512, 4
            denoising steps, synthetic weights as bench.py builds them), wall clock per frame, three stacks alternating frame
            by frame in one process: steady off, steady on (defaults), and steady off again -- off against off is the run-to-run
-           spread of one route against itself.  The frames hold three quarters of the picture still."""
+           spread of one route against itself.  The frames hold three quarters of the picture still.
+
+    timeout -k 10 120 python tools/steady_time.py kernels --follow 4 --out profiles/steady_follow_time.txt
+
+  kernels --follow R[,BIAS]   follow (csrc/steady_follow.hip): L2D_OP_FRAME_STEADY alone beside
+           L2D_OP_FRAME_MOTION + L2D_OP_FRAME_STEADY_FOLLOW in one OpList, at 512x512 and 1280x720, at the search range R given and
+           at 4 and 8, in the same run with the same device events; the source is the previous one panned by (3, -2) pixels."""
 import argparse
 import os
 import statistics
@@ -34,7 +40,58 @@ def say(out, line):
             f.write(line + "\n")
 
 
+def parse_follow(text):
+    """`R[,BIAS]` -> `steady.check_follow`'s dict"""
+    from live2diff_amd.steady import check_follow
+    parts = [t.strip() for t in text.split(",")]
+    if not 1 <= len(parts) <= 2:
+        raise ValueError(f"--follow {text!r}: use R[,BIAS]")
+    return check_follow(int(parts[0]), int(parts[1]) if len(parts) > 1 else 256)
+
+
+def follow_kernels(args):
+    from live2diff_amd import _lib, ops
+    from live2diff_amd.steady import HipSteady, steady_params
+    dev, follow = "cuda", parse_follow(args.follow)
+    say(args.out, f"# steady_time kernels --follow: {_lib.device_name()}, bias {follow['bias']}, steady r = 2, {args.reps} back-to-back replays "
+                  f"per figure (device events), minimum of 3 runs; the source is the previous one panned by (3, -2)")
+    lo32, inv32, hard = steady_params(2, 10)
+    settings = dict(lo=2.0, hi=10.0, strength=0.8, radius=2, show=False)
+    for H, W in ((512, 512), (720, 1280)):
+        g = torch.Generator().manual_seed(0)
+        x = (torch.randn(1, 3, H, W, generator=g) * 0.6).half().to(dev)
+        canvas = torch.nn.functional.avg_pool2d(torch.randint(0, 256, (3, H + 16, W + 16), generator=g).float()[None], 3, 1, 1)[0].round()
+        src0, src1 = ((canvas[:, 8 + oy:8 + oy + H, 8 + ox:8 + ox + W] / 127.5 - 1.0).half().to(dev)[None].contiguous()
+                      for oy, ox in ((0, 0), (-3, 2)))
+        st = HipSteady(H, W, device=dev)
+        st.steady(x, src0, settings, init=True)                                      # (a state for what follows)
+        st.steady(x, src1, settings, follow=follow)                                  # (... and a field buffer)
+        moved = float((st.field != 0).any(dim=-1).float().mean())
+        (prev_out, prev_bytes), (out, next_bytes) = st.records[st._cur], st.records[1 - st._cur]
+        common = dict(H=H, W=W, lo32=lo32, inv32=inv32, s32=0.8, r=2, hard=hard)
+
+        def timed(name, *ops_):
+            pl = _lib.OpList()
+            for op in ops_:
+                pl.append(op[0], *op[1])
+            pl.time_ms(20)
+            us = [pl.time_ms(args.reps) * 1e3 for _ in range(3)]
+            say(args.out, f"{H}x{W} {name:40s}: {min(us):7.2f} us (3 runs: {', '.join(f'{u:.2f}' for u in us)})")
+            return min(us)
+
+        base = timed("op 48 steady alone", ops.frame_steady(x, src1, prev_out, prev_bytes, out, next_bytes, **common))
+        timed("op 56 follow alone (the field as it is)", ops.frame_steady_follow(x, src1, prev_out, prev_bytes, out, next_bytes, st.field, **common))
+        for R in sorted({follow["search"], 4, 8}):
+            motion = ops.frame_motion(src1, prev_bytes, st.field, H=H, W=W, search=R, bias=follow["bias"])
+            timed(f"op 55 motion alone, R = {R}", motion)
+            both = timed(f"ops 55 + 56, R = {R}", motion, ops.frame_steady_follow(x, src1, prev_out, prev_bytes, out, next_bytes, st.field, **common))
+            say(args.out, f"{H}x{W} ops 55 + 56 at R = {R} against op 48: {both / base:.2f} x, {both - base:+.2f} us")
+        say(args.out, f"{H}x{W} share of blocks with a vector at R = {follow['search']}: {moved:.2f}")
+
+
 def kernels(args):
+    if args.follow:
+        return follow_kernels(args)
     from live2diff_amd import _lib, ops
     from live2diff_amd.matte import matte_params
     from live2diff_amd.steady import HipSteady, steady_params
@@ -141,6 +198,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("part", choices=["kernels", "route"])
     ap.add_argument("--out", default=None, help="append the result lines to this file")
+    ap.add_argument("--follow", default=None, metavar="R[,BIAS]", help="with `kernels`: time op 48 beside ops 55 + 56 instead")
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--frames", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
