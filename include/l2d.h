@@ -535,6 +535,34 @@ enum {
  *   written by a plain store on every launch.  Refused: a null pointer (p6 only without SHOW), a misaligned one, W % 8 != 0,
  *   3 H W >= 2^31, r out of range, unknown flags (INIT among them), p4 (or p6) overlapping p0 .. p3 or one another, p5
  *   overlapping p0 .. p3, p7 overlapping p4, p5 or p6, lo / inv / s as L2D_OP_FRAME_STEADY refuses them.
+ *
+ * Matte hold (matte_hold.hip; no counterpart in the reference): the matte filtered in time where the camera holds still.  The
+ *   depth matte is a fresh draw in every frame, so its silhouette crawls while nothing moves; this op blends the frame's matte,
+ *   in front of the feather, with the previous held one by L2D_OP_FRAME_STEADY's measure of where the source moved.  Its output
+ *   plane is what L2D_OP_FRAME_MATTE and L2D_OP_FRAME_MATTE_UP then read under L2D_MATTE_PLANE.
+ * L2D_OP_FRAME_MATTE_HOLD  one launch:  p0 source half [3][H][W] p1 the matte input: depth half [H][W], or with
+ *   L2D_MATTE_HOLD_PLANE float [H][W] (p2 of L2D_OP_FRAME_MATTE_EDGE) p2 prev_plane float [H][W] p3 prev_bytes uint8 [3][H][W]
+ *   (planar) p4 out_plane float [H][W] p5 next_bytes uint8 [3][H][W] p6 field int8 [ceil(H/8)][W/8][2] (p2 of L2D_OP_FRAME_MOTION,
+ *   read only with L2D_MATTE_HOLD_FOLLOW; any alignment; the planes and the frame 16-byte aligned, the byte planes 8) ; i0 H i1 W
+ *   (W % 8 == 0, 3 H W < 2^31) i2 r (0..L2D_STEADY_MAX_R) i3 flags (L2D_MATTE_HOLD_*) i4 i5 the BITS of the floats lo and inv of
+ *   the depth ramp (as L2D_OP_FRAME_MATTE's f0 f1; not read with PLANE) ; f0 lo f1 inv f2 s (as L2D_OP_FRAME_STEADY's: the motion
+ *   ramp in byte levels and the strength).  Arithmetic, the motion in exact integers and every floating-point step one fp32
+ *   operation with one rounding and no fma, so that numpy restates it bit for bit (live2diff_amd/matte.py hold_ref): m0 = the
+ *   matte as L2D_OP_FRAME_MATTE forms it in front of the feather (RAMP_HARD, RAMP_FAR), or p1's values; b, d, D, dbar, t, w as
+ *   L2D_OP_FRAME_STEADY's with p3 as the previous bytes (HARD); a = 1 - s (1 - w); h = P + a (m0 - P) with P = p2; h = min(max(h,
+ *   min(m0, P)), max(m0, P)) -- the fp32 blend may leave the interval by an ulp, the clamp is part of the arithmetic: h stays in
+ *   [0, 1], and exactly 0 or 1 where m0 and P both are --; m0's own bits where a == 1.  FOLLOW: P and the previous bytes are
+ *   fetched at (cl(y + dy), cl(x + dx)) with (dy, dx) the vector of block (y / 8, x / 8), as L2D_OP_FRAME_STEADY_FOLLOW's; every
+ *   coordinate is clamped on its own, so whatever p6 holds, nothing outside p2 and p3 is read.  p4 = h and p5 = b (where they
+ *   are, not displaced) are the next launch's p2 and p3: the two records ping-pong, because a tile's halo and a displaced fetch
+ *   read what a neighbour would write.  INIT: h = m0, p5 = b, and p2, p3 and p6 are not read -- they may be null.  One
+ *   work-group per 16 x 64 tile for every r, 8 pixels per lane: the lane's source, matte input and previous record are loaded
+ *   first (16-byte accesses to the planes, 8-byte to the bytes; displaced element loads under FOLLOW), d of the tile and its
+ *   halo, then the row sums, go through 6,656 bytes of LDS.  Every element of p4 and p5 is written by a plain store on every
+ *   launch: nothing has to be zeroed, no atomics.  Refused: a null pointer (p2, p3 only with INIT, p6 with INIT or without
+ *   FOLLOW), a misaligned one, W % 8 != 0, 3 H W >= 2^31, r out of range, unknown flags, ramp flags beside PLANE, lo / inv / s as
+ *   L2D_OP_FRAME_STEADY refuses them, the depth ramp as L2D_OP_FRAME_MATTE refuses it, p4 or p5 overlapping p0 .. p3 or each
+ *   other, p6 overlapping p4 or p5.
  */
 enum {
     L2D_OP_IGEMM = 1,
@@ -593,6 +621,7 @@ enum {
     L2D_OP_FRAME_BACKDROP_BLUR = 54,
     L2D_OP_FRAME_MOTION = 55,
     L2D_OP_FRAME_STEADY_FOLLOW = 56,
+    L2D_OP_FRAME_MATTE_HOLD = 57,
 };
 
 /* flag bits of L2D_OP_FRAME_MATTE (i4) and L2D_OP_FRAME_MATTE_UP (i6); HARD and FAR also of L2D_OP_FRAME_MATTE_EDGE (i3) */
@@ -625,6 +654,14 @@ enum {
 #define L2D_FOLLOW_APRON 4 /* the matching window is the block and 4 pixels around it: 16 x 16 */
 #define L2D_FOLLOW_MAX_SEARCH 8
 #define L2D_FOLLOW_MAX_BIAS 4096
+
+/* flag bits of L2D_OP_FRAME_MATTE_HOLD (i3); its radius is L2D_OP_FRAME_STEADY's, its field L2D_OP_FRAME_MOTION's */
+#define L2D_MATTE_HOLD_HARD 1 /* the motion ramp is a step (L2D_STEADY_HARD) */
+#define L2D_MATTE_HOLD_INIT 4 /* the first frame of a sequence (L2D_STEADY_INIT) */
+#define L2D_MATTE_HOLD_PLANE 16 /* p1 is a float plane of ready matte values (L2D_MATTE_PLANE) */
+#define L2D_MATTE_HOLD_FOLLOW 32 /* p6 is a field: the previous record is fetched along it */
+#define L2D_MATTE_HOLD_RAMP_HARD 64 /* L2D_MATTE_HARD of the depth ramp */
+#define L2D_MATTE_HOLD_RAMP_FAR 128 /* L2D_MATTE_FAR of the depth ramp */
 
 /* flag bits of L2D_OP_FRAME_DETAIL_GAIN (i3: U8) and L2D_OP_FRAME_DETAIL (i4: SHOW) */
 #define L2D_DETAIL_U8 1 /* p0 is the uint8 [H][W][3] frame of the matte, not the half frame */

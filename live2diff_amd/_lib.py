@@ -37,6 +37,7 @@ OP_DEPTH_INGEST, OP_DEPTH_NORMALIZE = 52, 53
 OP_FRAME_BACKDROP_BLUR = 54
 OP_FRAME_MOTION = 55
 OP_FRAME_STEADY_FOLLOW = 56
+OP_FRAME_MATTE_HOLD = 57
 ABI_VERSION = 6
 
 

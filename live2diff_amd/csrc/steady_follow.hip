@@ -144,14 +144,6 @@ __global__ __launch_bounds__(MF_THREADS) void frame_motion_kernel(const h16 *__r
     }
 }
 
-// 8 consecutive pixels of a byte row from column x on, each column clamped to the image on its own
-__device__ __forceinline__ uint2 fl_bytes8(const uint8_t *__restrict__ row, int x, int W) {
-    unsigned q[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) q[e] = row[px_clampi(x + e, 0, W - 1)];
-    return px_pack8(q);
-}
-
 // the box kernel of steady.hip with displaced fetches of the previous record: an 8-aligned pixel group lies inside one block of
 // the field, so it has one vector; its previous samples are 8 consecutive pixels of row cl(y + dy) from column x + dx on.  A
 // vector is used only through clamped coordinates: whatever a field holds, nothing outside the previous record is read.

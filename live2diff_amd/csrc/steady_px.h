@@ -1,6 +1,7 @@
-// The steady mode's pixel helpers (DESIGN.md sections 8.z8 and 8.z14): the byte motion, the weight, the alpha and the blend, shared
-// by steady.hip (L2D_OP_FRAME_STEADY) and steady_follow.hip (L2D_OP_FRAME_STEADY_FOLLOW), so that both give the same bits.
-// Everything written with __f*_rn is bit-exact only in a file built with -ffp-contract=off (frame_px.h's second rule): both are.
+// The steady mode's pixel helpers (DESIGN.md sections 8.z8, 8.z14 and 8.z15): the byte motion, the weight, the alpha and the blend,
+// shared by steady.hip (L2D_OP_FRAME_STEADY), steady_follow.hip (L2D_OP_FRAME_STEADY_FOLLOW) and matte_hold.hip
+// (L2D_OP_FRAME_MATTE_HOLD), so that all give the same bits.
+// Everything written with __f*_rn is bit-exact only in a file built with -ffp-contract=off (frame_px.h's second rule): all are.
 #pragma once
 #include "frame_px.h"
 
@@ -46,6 +47,14 @@ __device__ __forceinline__ void sd_motion8(uint2 now, uint2 before, unsigned (&d
         d[e] = a > d[e] ? a : d[e];
         d[e + 4] = b > d[e + 4] ? b : d[e + 4];
     }
+}
+
+// 8 consecutive pixels of a byte row from column x on, each column clamped to the image on its own
+__device__ __forceinline__ uint2 fl_bytes8(const uint8_t *__restrict__ row, int x, int W) {
+    unsigned q[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) q[e] = row[px_clampi(x + e, 0, W - 1)];
+    return px_pack8(q);
 }
 
 // dbar -> w

@@ -15,7 +15,10 @@ the stream's output over the stream's own source frame, on the device, in the la
                       over the camera's own -- and its launch;
   * `check_edge`, `guide_ref`, `edge_ref`, `HipMatteEdge`   the edge-aware matte: the matte re-fitted
                       locally as a linear function of the source frame's luma (a guided filter), in exact integers and a few
-                      individually rounded fp64 steps -- the arithmetic of L2D_OP_FRAME_MATTE_EDGE -- and its launch.
+                      individually rounded fp64 steps -- the arithmetic of L2D_OP_FRAME_MATTE_EDGE -- and its launch;
+  * `check_hold`, `hold_ref`, `HipMatteHold`   the matte hold: the matte in front of the feather blended
+                      with the previous held one where the source's bytes did not move (steady's weight, optionally along the
+                      source's motion) -- the arithmetic of L2D_OP_FRAME_MATTE_HOLD -- and its records and launches.
 """
 import collections
 from typing import Optional, Tuple
@@ -67,12 +70,23 @@ def _box_pass(m: np.ndarray, r: int, axis: int) -> np.ndarray:
     return acc / np.float32(2 * r + 1)
 
 
-def matte_ref(depth, lo: float, hi: float, feather: int = 0, keep: str = "near", *, edge: Optional[dict] = None, source=None) -> np.ndarray:
+def matte_ref(depth, lo: float, hi: float, feather: int = 0, keep: str = "near", *, edge: Optional[dict] = None, source=None,
+              plane=None) -> np.ndarray:
     """fp16 [B,H,W] depth planes (channel 0 of `encode_depth`'s `dn`: min-max normalised, in [-1, 1], at frame size) -> fp32
     [B,H,W] matte in [0, 1]: t = clamp((d - lo32) inv32, 0, 1) (hard: d >= lo32), m = (t t) (3 - 2 t), `keep="far"`: 1 - m, then
     the (2r+1) x (2r+1) box filter as a horizontal and a vertical pass.  `edge` ({radius, eps}, with the fp16 [B,3,H,W] `source`
-    frames as the guide): `edge_ref` refines m in front of the box filter."""
+    frames as the guide): `edge_ref` refines m in front of the box filter.  `plane` (fp32 [B,H,W]): a ready matte in front of
+    the box filter, in place of the ramp and `edge` -- the host twin of L2D_MATTE_PLANE; `depth` is then not read."""
     check_settings(lo, hi, keep=keep, feather=feather)
+    if plane is not None:
+        m = np.asarray(plane.detach().cpu().numpy() if torch.is_tensor(plane) else plane)
+        if m.dtype != np.float32 or m.ndim not in (2, 3):
+            raise ValueError(f"matte_ref: plane: expected float32 [B,H,W], got {m.dtype} {m.shape}")
+        m = m[None] if m.ndim == 2 else m
+        if feather:
+            m = _box_pass(_box_pass(m, feather, 2), feather, 1)
+        assert m.dtype == np.float32
+        return m
     lo32, inv32, hard = matte_params(lo, hi)
     d = _np16(depth).astype(np.float32)
     if d.ndim == 2:
@@ -185,14 +199,18 @@ def _unit(x) -> np.ndarray:
 
 
 def composite_ref(styled, source, depth, lo: float, hi: float, feather: int = 0, keep: str = "near", show: bool = False, *,
-                  edge: Optional[dict] = None, backdrop=None) -> np.ndarray:
+                  edge: Optional[dict] = None, backdrop=None, plane=None) -> np.ndarray:
     """L2D_OP_FRAME_MATTE on the host: fp16 [B,3,H,W] `styled` and `source` in [-1, 1] + fp16 [B,H,W] `depth` -> uint8 [B,H,W,3].
     o = v_c + m (v_s - v_c) in three fp32 operations, byte = round_half_even(255 o); `show` writes round_half_even(255 m) to all
     three channels.  Both v are multiples of 2^-24 in [0, 1], so v_s - v_c is exact: m == 1 gives the bytes of
     `egress_ref(styled)` and m == 0 those of `egress_ref(source)`, whatever the feather radius.  `edge` ({radius, eps}): the matte
     refined by `source` first (`edge_ref`).  `backdrop` (fp16 [B,3,H,W], backdrop.py): v_c is taken from it in place of
-    `source`; the guide of `edge` stays the real `source`."""
-    m = matte_ref(depth, lo, hi, feather, keep, edge=edge, source=source if edge is not None else None)[..., None]
+    `source`; the guide of `edge` stays the real `source`.  `plane` (fp32 [B,H,W]): a ready matte in front of the feather, in
+    place of the ramp and `edge` (`matte_ref`), as `hold_ref` returns one."""
+    if plane is not None:
+        m = matte_ref(depth, lo, hi, feather, keep, plane=plane)[..., None]
+    else:
+        m = matte_ref(depth, lo, hi, feather, keep, edge=edge, source=source if edge is not None else None)[..., None]
     scale = np.float32(255.0)
     if show:
         return np.rint(np.repeat(m, 3, axis=-1) * scale).astype(np.uint8)
@@ -247,14 +265,16 @@ def matte_up_ref(m: np.ndarray, out_height: int, out_width: int) -> np.ndarray:
 
 
 def composite_up_ref(styled_u8, camera_u8, depth, lo: float, hi: float, feather: int = 0, keep: str = "near",
-                     show: bool = False, *, edge: Optional[dict] = None, source=None, backdrop=None) -> np.ndarray:
+                     show: bool = False, *, edge: Optional[dict] = None, source=None, backdrop=None, plane=None) -> np.ndarray:
     """L2D_OP_FRAME_MATTE_UP on the host: uint8 [B,Ho,Wo,3] `styled_u8` (the styled frame at the output size) and `camera_u8` (the
     camera's own pixels at that size) + fp16 [B,H,W] `depth` -> uint8 [B,Ho,Wo,3].  M = matte_up_ref(matte_ref(depth, ...)),
     o = C + M (S - C) on the bytes as fp32 -- S - C is exact, then one multiplication and one addition --, byte =
     round_half_even(o); `show` writes round_half_even(255 M) to all three channels.  Rounding is monotone and 0 <= M <= 1, so o
     lies between C and S and nothing is clamped (asserted); M == 1 gives S and M == 0 gives C exactly.  `edge` ({radius, eps},
     with the stream-sized fp16 [B,3,H,W] `source` frames): the matte is refined at the stream's size (`edge_ref`) and sampled
-    as before.  `backdrop` (uint8 [B,Ho,Wo,3], backdrop.py): C is taken from it in place of `camera_u8`, which may then be None."""
+    as before.  `backdrop` (uint8 [B,Ho,Wo,3], backdrop.py): C is taken from it in place of `camera_u8`, which may then be None.
+    `plane` (fp32 [B,H,W], stream-sized): a ready matte in front of the feather, in place of the ramp and `edge` (`matte_ref`),
+    sampled as before."""
     def u8(x):
         x = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
         if x.dtype != np.uint8 or x.ndim not in (3, 4) or x.shape[-1] != 3:
@@ -264,7 +284,9 @@ def composite_up_ref(styled_u8, camera_u8, depth, lo: float, hi: float, feather:
     S, C = u8(styled_u8), u8(camera_u8 if backdrop is None else backdrop)
     if S.shape != C.shape:
         raise ValueError(f"composite_up_ref: the styled frame is {S.shape}, the camera frame {C.shape}")
-    M = matte_up_ref(matte_ref(depth, lo, hi, feather, keep, edge=edge, source=source), S.shape[1], S.shape[2])[..., None]
+    m = (matte_ref(depth, lo, hi, feather, keep, plane=plane) if plane is not None
+         else matte_ref(depth, lo, hi, feather, keep, edge=edge, source=source))
+    M = matte_up_ref(m, S.shape[1], S.shape[2])[..., None]
     assert M.shape[0] == S.shape[0] and float(M.min()) >= 0.0 and float(M.max()) <= 1.0
     if show:
         return np.rint(np.repeat(M, 3, axis=-1) * np.float32(255.0)).astype(np.uint8)
@@ -286,6 +308,65 @@ def check_settings(lo, hi, *, keep="near", feather=0, show=False) -> dict:
     if keep not in ("near", "far"):
         raise ValueError(f"matte: keep={keep!r}: use 'near' or 'far'")
     return dict(lo=float(lo), hi=float(hi), keep=keep, feather=int(feather), show=bool(show))
+
+
+# ----------------------------------------------------------------------------- matte hold
+def check_hold(lo=2.0, hi=10.0, strength=0.8, radius=2, search=0, bias=256) -> dict:
+    """the hold's settings as {lo, hi, strength, radius, search, bias}, or ValueError.  `lo`, `hi`, `strength` and `radius` mean
+    what they mean in `steady.check_settings` (byte levels of the locally averaged source motion, a number in [0, 1], an integer
+    in 0..8); `search` is an integer in 0..8 -- 0 compares the same coordinates, 1..8 follows the source's motion with
+    `steady.motion_ref(search, bias)` --, `bias` an integer in 0..4096.  The defaults are steady's; nobody has tuned them on
+    camera footage."""
+    from . import steady
+    try:
+        st = steady.check_settings(lo, hi, strength, radius)
+    except ValueError as e:
+        raise ValueError(f"matte hold: {e}") from None
+    if isinstance(search, bool) or not isinstance(search, (int, np.integer)) or not 0 <= int(search) <= steady.FOLLOW_MAX_SEARCH:
+        raise ValueError(f"matte hold: search={search!r}: use an integer from 0 to {steady.FOLLOW_MAX_SEARCH} (0: the same coordinates)")
+    if isinstance(bias, bool) or not isinstance(bias, (int, np.integer)) or not 0 <= int(bias) <= steady.FOLLOW_MAX_BIAS:
+        raise ValueError(f"matte hold: bias={bias!r}: use an integer from 0 to {steady.FOLLOW_MAX_BIAS}")
+    return dict(lo=st["lo"], hi=st["hi"], strength=st["strength"], radius=st["radius"], search=int(search), bias=int(bias))
+
+
+def hold_ref(m0, source, state, *, lo: float = 2.0, hi: float = 10.0, strength: float = 0.8, radius: int = 2, search: int = 0,
+             bias: int = 256, init: bool = False):
+    """L2D_OP_FRAME_MATTE_HOLD (behind L2D_OP_FRAME_MOTION where `search > 0`) on the host: the fp32 [H,W] matte `m0` in front of
+    the feather (`matte_ref` with feather 0, or `edge_ref`'s plane), the fp16 [3,H,W] `source` frame and the state `(prev_plane
+    fp32 [H,W], prev_bytes uint8 [3,H,W])` (ignored with `init`, where it may be None) -> (h fp32 [H,W], new state, int8 field).
+    b = `steady.source_bytes(source)`; with `search > 0` the field is `steady.motion_ref(b, prev_bytes, search, bias)` and P, bp
+    are the state fetched along it (`steady.warp_ref`), else the state as it is and a zero field; w =
+    `steady.weight_ref(b, bp, lo, hi, radius)`, a = 1 - s32 (1 - w), h = P + a (m0 - P) in three fp32 operations, then
+    h = min(max(h, min(m0, P)), max(m0, P)) -- the fp32 blend may leave the interval by an ulp; with the clamp h stays in [0, 1]
+    and exactly 0 or 1 where m0 and P both are --, and m0's own bits where a == 1.  The new state is (h, b), b where it is.
+    With `init` h is m0 with its bits and nothing is read from a state."""
+    from .steady import FOLLOW_BLOCK, motion_ref, source_bytes, warp_ref, weight_ref
+    st = check_hold(lo, hi, strength, radius, search, bias)
+    m0 = np.ascontiguousarray(m0.detach().cpu().numpy() if torch.is_tensor(m0) else m0)
+    if m0.dtype != np.float32 or m0.ndim != 2:
+        raise ValueError(f"hold_ref: expected one float32 [H,W] matte, got {m0.dtype} {m0.shape}")
+    b = source_bytes(source)
+    H, W = m0.shape
+    if b.shape != (3, H, W):
+        raise ValueError(f"hold_ref: the matte is {m0.shape}, the source frame {b.shape}")
+    field = np.zeros((-(-H // FOLLOW_BLOCK), -(-W // FOLLOW_BLOCK), 2), dtype=np.int8)
+    if init:
+        return m0.copy(), (m0.copy(), b), field
+    P, bp = state
+    P, bp = np.asarray(P), np.asarray(bp)
+    if P.dtype != np.float32 or P.shape != m0.shape:
+        raise ValueError(f"hold_ref: the matte is {m0.shape}, the previous plane {P.dtype} {P.shape}")
+    if st["search"] > 0:
+        field = motion_ref(b, bp, st["search"], st["bias"])
+        P, bp = warp_ref(P[None], field)[0], warp_ref(bp, field)
+    w = weight_ref(b, bp, lo=st["lo"], hi=st["hi"], radius=st["radius"])
+    one = np.float32(1.0)
+    a = one - np.float32(st["strength"]) * (one - w)
+    h = P + a * (m0 - P)                                   # numpy: three separate fp32 operations
+    h = np.minimum(np.maximum(h, np.minimum(m0, P)), np.maximum(m0, P))
+    h = np.ascontiguousarray(np.where(a == one, m0, h))
+    assert h.dtype == np.float32 and a.dtype == np.float32
+    return h, (h.copy(), b), field
 
 
 # ----------------------------------------------------------------------------- the delay line
@@ -418,6 +499,83 @@ class HipMatteEdge:
                                     E=edge_E(e["radius"], e["eps"]), lo32=lo32, inv32=inv32, hard=hard, far=settings["keep"] == "far")
 
 
+class HipMatteHold:
+    """The two `(plane, bytes)` records and the field of the matte hold of one `(H, W)` stream, and its launches.  The records
+    ping-pong (a tile's halo and a displaced fetch read what a neighbour would write); nothing is ever zeroed: the first frame
+    carries `init` and reads neither record.  `append` puts the frame's ops into the `OpList` that carries the composite -- op 55
+    when `search > 0` and the frame is no init frame, then op 57 -- so a frame stays one run, with no synchronisation and no
+    read-back.  `records` (two (fp32 [H,W], uint8 [3,H,W]) pairs) and `field` (int8 [ceil(H/8), W/8, 2]) may be the caller's:
+    tests place them inside guarded buffers."""
+
+    def __init__(self, height: int, width: int, device="cuda:0", records=None, field=None):
+        if width % 8 or height < 1 or 3 * height * width >= 1 << 31:
+            raise ValueError(f"HipMatteHold: width {width} must be a multiple of 8, height {height} at least 1 and 3 H W below 2^31")
+        self.height, self.width, self.device = int(height), int(width), torch.device(device)
+        H, W = self.height, self.width
+        self.records = records if records is not None else [
+            (torch.empty(H, W, dtype=torch.float32, device=self.device), torch.empty(3, H, W, dtype=torch.uint8, device=self.device))
+            for _ in range(2)]
+        self.field = field                  # made by the first followed frame, or the caller's
+        self._cur = 0                       # the record that holds the current state
+
+    @property
+    def state(self):
+        """the current `(plane, bytes)` record (device tensors; reading them synchronises)"""
+        return self.records[self._cur]
+
+    @property
+    def plane(self) -> torch.Tensor:
+        """the held plane of the last frame: what the composite reads under L2D_MATTE_PLANE"""
+        return self.records[self._cur][0]
+
+    def append(self, pl, slot: "_Slot", matte_settings: dict, settings: dict, plane: Optional[torch.Tensor] = None,
+               init: bool = False) -> torch.Tensor:
+        """append the frame's ops to `pl` and return the plane they write.  The matte input is `plane` (op 49's fp32 plane) or,
+        without one, `slot.depth` under the ramp of `matte_settings`; `settings` is `check_hold`'s dict."""
+        from .steady import FOLLOW_BLOCK, steady_params
+        H, W = self.height, self.width
+        (prev_plane, prev_bytes), (out_plane, next_bytes) = self.records[self._cur], self.records[1 - self._cur]
+        lo32, inv32, hard = steady_params(settings["lo"], settings["hi"])
+        kw = dict(H=H, W=W, lo32=lo32, inv32=inv32, s32=np.float32(settings["strength"]), r=settings["radius"], hard=hard, init=init)
+        if plane is None:
+            ramp_lo32, ramp_inv32, ramp_hard = matte_params(matte_settings["lo"], matte_settings["hi"])
+            kw.update(ramp_lo32=ramp_lo32, ramp_inv32=ramp_inv32, ramp_hard=ramp_hard, far=matte_settings["keep"] == "far")
+        field = None
+        if settings["search"] > 0 and not init:
+            if self.field is None:
+                self.field = torch.empty((H + FOLLOW_BLOCK - 1) // FOLLOW_BLOCK, W // FOLLOW_BLOCK, 2, dtype=torch.int8, device=self.device)
+            field = self.field
+            op, keep = ops.frame_motion(slot.source, prev_bytes, field, H=H, W=W, search=settings["search"], bias=settings["bias"])
+            pl.append(op, *keep)
+        op, keep = ops.frame_matte_hold(slot.source, slot.depth if plane is None else None, prev_plane, prev_bytes, out_plane, next_bytes,
+                                        plane=plane, field=field, **kw)
+        pl.append(op, *keep)
+        self._cur = 1 - self._cur
+        return out_plane
+
+
+class HoldStep(collections.namedtuple("HoldStep", "dev settings init repeat")):
+    """the `hold=` of a composite: `dev` the stream's `HipMatteHold`, `settings` `check_hold`'s dict, `init` the frame starts the
+    sequence, `repeat` the frame is a repeated output -- it is composited with the last held plane and moves nothing"""
+
+
+def _front(owner, pl, slot: "_Slot", settings: dict, edge: Optional[dict], hold: Optional[HoldStep]) -> Optional[torch.Tensor]:
+    """append what stands in front of a composite's own op -- the edge op, then the hold's -- and return the fp32 plane the
+    composite reads in place of the depth plane, or None"""
+    if hold is not None and hold.repeat:
+        return hold.dev.plane
+    plane = None
+    if edge is not None:
+        if owner.edge is None:
+            owner.edge = HipMatteEdge(owner.height, owner.width, device=owner.device)
+        op, keep = owner.edge.op(slot, settings, edge)
+        pl.append(op, *keep)
+        plane = owner.edge.plane
+    if hold is not None:
+        plane = hold.dev.append(pl, slot, settings, hold.settings, plane, init=hold.init)
+    return plane
+
+
 def _backdrop_parts(backdrop, default):
     """(tensor, records) of a composite's `backdrop=`: None (the `default` tensor), a tensor, or (tensor, [(op, keep), ...])"""
     if backdrop is None:
@@ -441,12 +599,13 @@ class HipMatte:
         self.edge = None                       # HipMatteEdge, made by the first frame with an edge setting
 
     def composite(self, image: torch.Tensor, slot: _Slot, settings: dict, to_host: bool = True, edge: Optional[dict] = None,
-                  backdrop=None):
+                  backdrop=None, hold: Optional[HoldStep] = None):
         """fp16 [3,H,W] on the device + a `MatteLine` slot -> uint8 [H,W,3]: a numpy view of the pinned buffer (valid until the next
         call), or with `to_host=False` the static device tensor.  `edge` ({radius, eps}): the matte refined by the slot's source
         frame first -- one more launch in front, and the composite reads its plane.  `backdrop` (an fp16 [3,H,W] device tensor,
         or `(tensor, records)` as `backdrop.HipBackdrop.stream` returns it): the tensor goes where `slot.source` goes in the
-        composite op, the records in front of it in the same list; the edge op keeps reading the slot's real source."""
+        composite op, the records in front of it in the same list; the edge op keeps reading the slot's real source.  `hold` (a
+        `HoldStep`): the matte hold's ops behind the edge op, in the same list, and the composite reads the held plane."""
         H, W = self.height, self.width
         if image.dtype != torch.float16 or tuple(image.shape) != (3, H, W):
             raise ValueError(f"composite: expected fp16 [3,{H},{W}], got {image.dtype} {tuple(image.shape)}")
@@ -458,13 +617,10 @@ class HipMatte:
         pl = _lib.OpList()
         for op, keep in records:
             pl.append(op, *keep)
-        if edge is not None:
-            if self.edge is None:
-                self.edge = HipMatteEdge(H, W, device=self.device)
-            op, keep = self.edge.op(slot, settings, edge)
-            pl.append(op, *keep)
+        plane = _front(self, pl, slot, settings, edge, hold)
+        if plane is not None:
             op, keep = ops.frame_matte(image, kept, None, self.dev, B=1, H=H, W=W, show=settings["show"], r=settings["feather"],
-                                       plane=self.edge.plane)
+                                       plane=plane)
         else:
             lo32, inv32, hard = matte_params(settings["lo"], settings["hi"])
             op, keep = ops.frame_matte(image, kept, slot.depth, self.dev, B=1, H=H, W=W, lo32=lo32, inv32=inv32, hard=hard,
@@ -492,12 +648,13 @@ class HipMatteUp:
         self.edge = None                       # HipMatteEdge, made by the first frame with an edge setting
 
     def composite(self, styled_u8: torch.Tensor, slot: _Slot, settings: dict, to_host: bool = True, edge: Optional[dict] = None,
-                  backdrop=None):
+                  backdrop=None, hold: Optional[HoldStep] = None):
         """uint8 [Ho,Wo,3] on the device + a `MatteLine` slot that carries a camera buffer -> uint8 [Ho,Wo,3]: a numpy view of the
         pinned buffer (valid until the next call), or with `to_host=False` the static device tensor.  `edge` ({radius, eps}): the
         matte refined at the stream's size by the slot's stream-sized source frame first, then sampled as before.  `backdrop` (a
         uint8 [Ho,Wo,3] device tensor, or `(tensor, records)` as `backdrop.HipBackdrop.output` returns it): the tensor goes where
-        the slot's camera buffer goes in the composite op -- the slot then needs none --, the records in front of it."""
+        the slot's camera buffer goes in the composite op -- the slot then needs none --, the records in front of it.  `hold` (a
+        `HoldStep`): the matte hold's ops behind the edge op; the held plane is sampled as the edge plane is."""
         Ho, Wo = self.out_height, self.out_width
         camera, records = _backdrop_parts(backdrop, None)
         if camera is None:
@@ -508,13 +665,10 @@ class HipMatteUp:
         pl = _lib.OpList()
         for op, keep in records:
             pl.append(op, *keep)
-        if edge is not None:
-            if self.edge is None:
-                self.edge = HipMatteEdge(self.height, self.width, device=self.device)
-            op, keep = self.edge.op(slot, settings, edge)
-            pl.append(op, *keep)
+        plane = _front(self, pl, slot, settings, edge, hold)
+        if plane is not None:
             op, keep = ops.frame_matte_up(styled_u8, camera, None, self.dev, self.tx, self.ty, B=1, H=self.height, W=self.width, Ho=Ho,
-                                          Wo=Wo, show=settings["show"], r=settings["feather"], plane=self.edge.plane)
+                                          Wo=Wo, show=settings["show"], r=settings["feather"], plane=plane)
         else:
             lo32, inv32, hard = matte_params(settings["lo"], settings["hi"])
             op, keep = ops.frame_matte_up(styled_u8, camera, slot.depth, self.dev, self.tx, self.ty, B=1, H=self.height, W=self.width,

@@ -1750,6 +1750,58 @@ def frame_steady_follow(styled, source, prev_out, prev_bytes, out, next_bytes, f
     return op, keep
 
 
+# ----------------------------------------------------------------------------- matte hold (matte_hold.hip, matte.py)
+MATTE_HOLD_HARD, MATTE_HOLD_INIT, MATTE_HOLD_PLANE, MATTE_HOLD_FOLLOW = 1, 4, 16, 32      # l2d.h L2D_MATTE_HOLD_*
+MATTE_HOLD_RAMP_HARD, MATTE_HOLD_RAMP_FAR = 64, 128
+
+
+def _hold_plane(name, t, H, W):
+    if t.dtype != torch.float32 or t.numel() != H * W or tuple(t.shape[-2:]) != (H, W) or not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous float32 [{H},{W}] plane, got {t.dtype} {tuple(t.shape)}")
+
+
+def frame_matte_hold(source, depth, prev_plane, prev_bytes, out_plane, next_bytes, *, H, W, lo32, inv32, s32, r=0, hard=False,
+                     init=False, plane=None, ramp_lo32=0.0, ramp_inv32=0.0, ramp_hard=False, far=False, field=None):
+    """the fp16 [3,H,W] `source` frame + the matte input + the previous record (`prev_plane` fp32 [H,W], `prev_bytes` planar uint8
+    [3,H,W]) -> the next record (`out_plane`, `next_bytes`): the matte held where the source's bytes did not move
+    (matte.hold_ref).  The matte input is the fp16 [H,W] `depth` plane under the ramp `ramp_lo32, ramp_inv32, ramp_hard`
+    (`matte.matte_params`) and `far`, or `plane` (fp32 [H,W], with `depth=None`): ready matte values, as `frame_matte_edge` writes
+    them.  `lo32, inv32, hard` as `steady.steady_params` returns them, `s32` the strength; `field` (`frame_motion`'s): the
+    previous record is fetched along it; with `init` the previous record and the field are not read and may be None."""
+    _lock_frame("frame_matte_hold: source", source, H, W)
+    if plane is not None:
+        if depth is not None or ramp_hard or far:
+            raise ValueError("frame_matte_hold: plane= goes with depth=None, and without ramp_hard / far (the plane carries them)")
+        _hold_plane("frame_matte_hold: plane", plane, H, W)
+        ramp_lo32 = ramp_inv32 = 0.0
+    elif depth is None or depth.dtype != torch.float16 or depth.numel() != H * W or not depth.is_contiguous():
+        raise ValueError(f"frame_matte_hold: depth: expected a contiguous fp16 [{H},{W}] plane, got "
+                         f"{getattr(depth, 'dtype', None)} {tuple(getattr(depth, 'shape', ()))}")
+    if prev_plane is not None or not init:
+        _hold_plane("frame_matte_hold: prev_plane", prev_plane, H, W)
+    if prev_bytes is not None or not init:
+        _steady_plane("frame_matte_hold: prev_bytes", prev_bytes, H, W)
+    _hold_plane("frame_matte_hold: out_plane", out_plane, H, W)
+    _steady_plane("frame_matte_hold: next_bytes", next_bytes, H, W)
+    if field is not None:
+        _follow_field("frame_matte_hold", field, H, W)
+    if isinstance(r, bool) or int(r) != r or not 0 <= int(r) <= STEADY_MAX_R:
+        raise ValueError(f"frame_matte_hold: r={r!r}: use an integer from 0 to {STEADY_MAX_R}")
+    op = L2dOp()
+    op.kind = _lib.OP_FRAME_MATTE_HOLD
+    keep = (source, depth if plane is None else plane, prev_plane, prev_bytes, out_plane, next_bytes, field)
+    for j, t in enumerate(keep):
+        op.p[j] = _ptr(t)
+    flags = ((MATTE_HOLD_HARD if hard else 0) | (MATTE_HOLD_INIT if init else 0) | (MATTE_HOLD_PLANE if plane is not None else 0)
+             | (MATTE_HOLD_FOLLOW if field is not None else 0) | (MATTE_HOLD_RAMP_HARD if ramp_hard else 0)
+             | (MATTE_HOLD_RAMP_FAR if far else 0))
+    for j, v in enumerate([H, W, r, flags]):
+        op.i[j] = int(v)
+    op.i[4], op.i[5] = (int(np.float32(v).view(np.int32)) for v in (ramp_lo32, ramp_inv32))       # the bits of the two floats
+    op.f[0], op.f[1], op.f[2] = float(lo32), float(inv32), float(s32)
+    return op, keep
+
+
 # ----------------------------------------------------------------------------- detail mode (detail.hip, detail.py)
 DETAIL_U8, DETAIL_SHOW = 1, 2                        # l2d.h L2D_DETAIL_*
 DETAIL_MAX_GAIN = 261120                             # |A| = |rint(4096 a)| with |a| <= 127.5 / 2 (eps >= 1): detail.hip states it

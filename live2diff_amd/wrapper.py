@@ -23,6 +23,7 @@ with Pillow's arithmetic, behind both and in front of the JPEG encoder or the co
 `set_steady` holds the previous output pixel where the frame's source did not move (steady.py), behind the colour lock.
 `set_steady_follow` lets it look where each 8 x 8 block of the source came from, so that it also holds under a moving camera.
 `set_matte_edge` refines the matte by the source frame, so that its edges land on the frame's own (matte.edge_ref).
+`set_matte_hold` keeps the matte still where the camera is still: the matte filtered in time by steady's measure (matte.hold_ref).
 `set_detail` brings the camera's fine detail into the frame at the output size, behind the resize (detail.py).
 `set_backdrop` puts the room blurred, a colour or an image behind the matte in place of the real frame (backdrop.py).
 `wrapper(image, depth=d)` conditions a frame on the caller's own depth frame -- an RGB-D camera's, another estimator's -- instead
@@ -304,6 +305,10 @@ class StreamAnimateDiffusionDepthWrapper:
     _camera = None                          # resize.CameraTap, while "camera", a matte and an output size are all set on the device
     _matte_up = None                        # matte.HipMatteUp of the current output size, made by the first frame that needs it
     _matte_edge = None                      # the edge-aware matte's settings (set_matte_edge), None: off
+    _hold = None                            # the matte hold's settings (set_matte_hold), None: off
+    _hold_dev = None                        # matte.HipMatteHold, made by the first held frame on the device
+    _hold_state = None                      # (previous held plane, previous source bytes) on the host route; on the device it stays there
+    _hold_init = True                       # the next held frame starts the sequence: its matte passes as it is
     _detail = None                          # the detail mode's settings (set_detail), None: off
     _detail_dev = None                      # detail.HipDetail of the current output size, made by the first frame that needs it
     _backdrop = None                        # the backdrop's settings (set_backdrop), None: the real frame stands behind the matte
@@ -324,7 +329,8 @@ class StreamAnimateDiffusionDepthWrapper:
                  jpeg_quality: int = 75, jpeg_decode: str = "device", output_size: Optional[Tuple[int, int]] = None,
                  output_resample: str = "lanczos", matte_source: str = "stream", steady: Optional[dict] = None,
                  matte_edge: Optional[dict] = None, detail: Optional[dict] = None, depth_input: Optional[dict] = None,
-                 depth_source: str = "detector", backdrop: Optional[dict] = None, steady_follow: Optional[dict] = None):
+                 depth_source: str = "detector", backdrop: Optional[dict] = None, steady_follow: Optional[dict] = None,
+                 matte_hold: Optional[dict] = None):
         _check_depth_source(depth_source)
         self._check_keywords(few_step_model_type=few_step_model_type, acceleration=acceleration, cfg_type=cfg_type,
                              use_denoising_batch=use_denoising_batch, frame_buffer_size=frame_buffer_size, device_ids=device_ids,
@@ -346,13 +352,13 @@ class StreamAnimateDiffusionDepthWrapper:
                     similar_image_filter_max_skip_frame=similar_image_filter_max_skip_frame, jpeg_quality=jpeg_quality,
                     jpeg_decode=jpeg_decode, output_size=output_size, output_resample=output_resample, matte_source=matte_source,
                     steady=steady, matte_edge=matte_edge, detail=detail, depth_input=depth_input, depth_source=depth_source,
-                    backdrop=backdrop, steady_follow=steady_follow)
+                    backdrop=backdrop, steady_follow=steady_follow, matte_hold=matte_hold)
 
     @classmethod
     def from_components(cls, pipe, *, num_inference_steps: int, t_index_list: Optional[List[int]] = None,
                         strength: Optional[float] = None, **kw):
         """The wrapper around an already assembled `pipe` namespace (tests, synthetic weights).  Keywords: those of the
-        constructor that do not name files (`jpeg_quality`, `jpeg_decode`, `output_size`, `output_resample`, `matte_source`, `steady`, `steady_follow`, `matte_edge`, `detail`, `backdrop`, `depth_input` and `depth_source` among them; with `depth_source="input"` the namespace needs no `depth_model`), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
+        constructor that do not name files (`jpeg_quality`, `jpeg_decode`, `output_size`, `output_resample`, `matte_source`, `steady`, `steady_follow`, `matte_edge`, `matte_hold`, `detail`, `backdrop`, `depth_input` and `depth_source` among them; with `depth_source="input"` the namespace needs no `depth_model`), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
         self = cls.__new__(cls)
         cls._check_keywords(**{k: kw.pop(k) for k in ("acceleration", "cfg_type", "use_denoising_batch", "frame_buffer_size",
                                                       "device_ids", "opt_unet", "few_step_model_type") if k in kw},
@@ -393,8 +399,10 @@ class StreamAnimateDiffusionDepthWrapper:
                scheduler_kwargs=None, frame_pipelining=False, enable_similar_image_filter=False,
                similar_image_filter_threshold=0.98, similar_image_filter_max_skip_frame=10, jpeg_quality=75, jpeg_decode="device",
                output_size=None, output_resample="lanczos", matte_source="stream", steady=None, matte_edge=None, detail=None,
-               depth_input=None, depth_source="detector", backdrop=None, steady_follow=None):
+               depth_input=None, depth_source="detector", backdrop=None, steady_follow=None, matte_hold=None):
         self._check_matte_source(matte_source)
+        if matte_hold is not None and not isinstance(matte_hold, dict):
+            raise ValueError(f"matte_hold={matte_hold!r}: use a dict of set_matte_hold's keywords, or None")
         if backdrop is not None and not isinstance(backdrop, dict):
             raise ValueError(f"backdrop={backdrop!r}: use a dict of set_backdrop's keywords, or None")
         _check_depth_source(depth_source)
@@ -449,6 +457,8 @@ class StreamAnimateDiffusionDepthWrapper:
             self.set_steady_follow(**steady_follow)
         if matte_edge is not None:
             self.set_matte_edge(**matte_edge)
+        if matte_hold is not None:
+            self.set_matte_hold(**matte_hold)
         if detail is not None:
             self.set_detail(**detail)
         if backdrop is not None:
@@ -526,6 +536,7 @@ class StreamAnimateDiffusionDepthWrapper:
         settings = check_settings(lo, hi, keep=keep, feather=feather, show=show)
         self._need_line()
         self._matte = settings
+        self._hold_init = True             # (a new ramp or a `keep` flip must not linger in a held matte)
         self._sync_camera()
 
     def clear_matte(self) -> None:
@@ -533,6 +544,8 @@ class StreamAnimateDiffusionDepthWrapper:
         buffers of `set_matte_source("camera")` included.  (A colour lock to "source" keeps the delay line it shares with the
         matte.)"""
         self._matte = self._matte_dev = self._matte_up = None
+        self._hold_dev = self._hold_state = None
+        self._hold_init = True
         self._release_line()
         self._sync_camera()
 
@@ -587,13 +600,77 @@ class StreamAnimateDiffusionDepthWrapper:
         `prepare` and between any two frames; the change applies from the next output."""
         from .matte import check_edge
         self._matte_edge = check_edge(radius, eps)
+        self._hold_init = True             # (a held matte starts again from the refined one)
 
     def clear_matte_edge(self) -> None:
         """Back to the matte as the depth map gives it: no launch or buffer of the refinement is left in the frame's path."""
         self._matte_edge = None
+        self._hold_init = True
         for dev in (self._matte_dev, self._matte_up):
             if dev is not None:
                 dev.edge = None
+
+    # ------------------------------------------------------------------ matte hold (DESIGN.md section 8.z15)
+    @property
+    def matte_hold(self) -> Optional[dict]:
+        """the current matte hold as {lo, hi, strength, radius, search, bias}, or None"""
+        return None if self._hold is None else dict(self._hold)
+
+    def set_matte_hold(self, lo: float = 2.0, hi: float = 10.0, *, strength: float = 0.8, radius: int = 2, search: int = 0,
+                       bias: int = 256) -> None:
+        """Keep the matte still where the camera is still.  The matte is a fresh draw in every frame -- a smoothstep over that
+        frame's depth map, normalised on that frame alone --, so the silhouette between the real and the styled part crawls by
+        a few pixels while nothing moves.  With this setting the matte in front of the feather (ramp and `keep` applied, refined
+        by `set_matte_edge` when that is set) is blended per pixel with the previous held matte by steady's measure of where
+        the source moved (`matte.hold_ref`): `lo`, `hi` (byte levels of the source's motion averaged over a (2 `radius` + 1)^2
+        window, `radius` 0..8) and `strength` (0..1) mean what they mean in `set_steady`; where the source moved, and on a
+        hard cut, the frame's own matte passes untouched.  `search` 1..8 lets it look where each 8 x 8 block of the source came
+        from (`set_steady_follow`'s search, with `bias`), so that it also holds under a moving camera; 0 compares the same
+        coordinates.  The defaults are steady's: nobody has tuned them on camera footage.
+
+        A setting beside the matte, like `set_matte_edge`: it acts only while a matte is set, on its output types, and `matte`
+        keeps its five keys.  The order on a frame is ramp or edge, hold, then feather and composite; `show` shows the held
+        matte, `set_matte_source("camera")` samples the held plane as it samples the edge plane, and the backdrop's blur
+        keeps weighing by the raw matte of the frame.  One more launch on the device in front of the composite's (two with
+        `search`), in the same run, no synchronisation.  The hold advances once per composited frame, in output order; a frame
+        the near-duplicate filter repeats is composited with the last held matte and moves nothing.  `prepare`, every
+        `set_matte` call, `set_matte_edge` and `clear_matte_edge` start the sequence again with the next frame; changing
+        these settings mid-stream does not.  With `search` it runs its own motion search against its own previous frame
+        (steady's field is not shared: the two sequences may have started at different frames).  May be called before or
+        after `set_matte` and `prepare` and between any two frames."""
+        from .matte import check_hold
+        settings = check_hold(lo, hi, strength, radius, search, bias)
+        if self._hold is None:
+            self._hold_init = True
+        self._hold = settings
+
+    def clear_matte_hold(self) -> None:
+        """Back to the matte of each frame alone: no launch or buffer of the hold is left in the frame's path."""
+        self._hold = self._hold_dev = self._hold_state = None
+        self._hold_init = True
+
+    def _hold_step(self, device, repeated: bool):
+        """the `hold=` of the device composites for this frame (`matte.HoldStep`); the sequence has started behind it"""
+        from .matte import HipMatteHold, HoldStep
+        if self._hold_dev is None:
+            self._hold_dev = HipMatteHold(self.height, self.width, device=device)
+            self._hold_init = True
+        step = HoldStep(self._hold_dev, self._hold, self._hold_init, repeated and not self._hold_init)
+        self._hold_init = False
+        return step
+
+    def _held_plane(self, slot, repeated: bool) -> np.ndarray:
+        """the held matte of this frame on the host route, fp32 [1,H,W]: `hold_ref` where op 57 would run"""
+        from .matte import hold_ref, matte_ref
+        if repeated and not self._hold_init and self._hold_state is not None:
+            return self._hold_state[0][None]
+        mt = self._matte
+        m0 = matte_ref(slot.depth[None], mt["lo"], mt["hi"], 0, mt["keep"], edge=self._matte_edge,
+                       source=slot.source[None] if self._matte_edge is not None else None)[0]
+        init = self._hold_init or self._hold_state is None
+        h, self._hold_state, _ = hold_ref(m0, slot.source, self._hold_state, **self._hold, init=init)
+        self._hold_init = False
+        return h[None]
 
     # ------------------------------------------------------------------ backdrop (backdrop.py, DESIGN.md section 8.z13)
     @property
@@ -943,7 +1020,7 @@ class StreamAnimateDiffusionDepthWrapper:
         detail_slot = slot if self._detail_slot(slot, image_tensor) else None
         slot = slot if self._matte is not None else None
         return self._route(image_tensor, self.output_type, slot, self._size, camera=self._camera_slot(slot, image_tensor),
-                           detail_slot=detail_slot)
+                           detail_slot=detail_slot, repeated=repeated)
 
     # ------------------------------------------------------------------ detail mode (detail.py)
     @property
@@ -1139,6 +1216,7 @@ class StreamAnimateDiffusionDepthWrapper:
         if self._lock is not None and self._lock["mode"] != "image":
             self._lock_state = None
         self._steady_init, self._steady_last, self._steady_state = True, None, None      # the steady mode starts again too
+        self._hold_init, self._hold_state = True, None                                   # and the matte hold
         if isinstance(warmup_frames, (list, tuple)) and warmup_frames and all(_is_jpeg(f) for f in warmup_frames):
             # (a device frame is a view of one of the decoder's two static slots: it is copied before the slot's next turn)
             decoded = [d.clone() if torch.is_tensor(d) else torch.from_numpy(d).to(self.io.device) if self.io is not None else d
@@ -1277,13 +1355,14 @@ class StreamAnimateDiffusionDepthWrapper:
         return self._route(image_tensor, output_type)
 
     def _route(self, image_tensor: torch.Tensor, output_type: str, slot=None, size: Optional[dict] = None, camera: bool = False,
-               detail_slot=None):
+               detail_slot=None, repeated: bool = False):
         """The one way out for a frame (fp16 [1,3,H,W] in [-1, 1], behind the colour lock and the steady mode when set): the matte's composite
         with `slot` (a `MatteLine` slot; None: no matte, or its line has seen no frame yet) or the egress bytes, resampled to
         `size` (the setting of `set_output_size`, or None), then the JPEG encoder or the copy to the host.  `camera` (the slot
         carries the camera's pixels at `size`, `_camera_slot`): the resize of the styled frame first, then the composite at the
         output size, in place of those two stages.  `detail_slot` (the frame's slot where the detail mode acts on it,
-        `_detail_slot`): the detail launches behind the resize, on the frame the resize read.  On the device every
+        `_detail_slot`): the detail launches behind the resize, on the frame the resize read.  `repeated` (the near-duplicate filter
+        dropped the frame): a matte hold composites with the last held matte and does not advance.  On the device every
         stage is one launch that hands its static device buffer to the next and only the last one copies to the host; the
         resize takes the fp16 frame itself, and so does the encoder, so neither has an egress launch in front of it.  The float
         output types leave as the reference's do."""
@@ -1303,6 +1382,9 @@ class StreamAnimateDiffusionDepthWrapper:
             if detail_slot is not None and size is not None:
                 give_detail = functools.partial(self._detail_op(size, dev).apply, slot=detail_slot, settings=self._detail)
             bd = self._backdrop if slot is not None and not self._matte["show"] else None
+            held = {}                       # (the keyword only with a hold: without one the calls are the parent's)
+            if slot is not None and self._hold is not None:
+                held["hold"] = self._hold_step(dev, repeated)
             if camera:
                 stages.append(self._size_op(size, dev).resize)
                 if give_detail is not None:
@@ -1310,12 +1392,12 @@ class StreamAnimateDiffusionDepthWrapper:
                 more = {} if bd is None else dict(backdrop=self._backdrop_op(dev).output(
                     slot, self._matte, bd, size["height"], size["width"], self._backdrop_image, size["resample"]))
                 stages.append(functools.partial(self._matte_up_op(size, dev).composite, slot=slot, settings=self._matte,
-                                                edge=self._matte_edge, **more))
+                                                edge=self._matte_edge, **more, **held))
             elif slot is not None:
                 more = {} if bd is None else dict(backdrop=self._backdrop_op(dev).stream(
                     slot, self._matte, bd, self._backdrop_image, self._backdrop_filter()))
                 stages.append(functools.partial(self._matte_op(dev).composite, slot=slot, settings=self._matte, edge=self._matte_edge,
-                                                **more))
+                                                **more, **held))
             if size is not None and not camera:
                 stages.append(self._size_op(size, dev).resize)
                 if give_detail is not None:
@@ -1341,6 +1423,8 @@ class StreamAnimateDiffusionDepthWrapper:
                     from .backdrop import stream_ref
                     more["backdrop"] = stream_ref(self._backdrop, self._backdrop_image_host(), slot.source, slot.depth, self._matte,
                                                   self._backdrop_filter())[None]
+                if self._hold is not None:
+                    more["plane"] = self._held_plane(slot, repeated)
                 u8 = composite_ref(image_tensor[:1], slot.source[None], slot.depth[None], **self._matte, edge=self._matte_edge, **more)[0]
             else:
                 from .frame_io import egress_ref

@@ -52,6 +52,11 @@ hand-held camera or a pan, where plain steady holds nothing; BIAS, default 256, 
 vectors).  It acts only while `--steady` is set.  `POST /steady-follow` with the same text changes it while the stream runs, an
 empty body or `off` clears it; `GET /steady-follow` answers the current settings as JSON.
 
+`--matte-hold LO,HI[,STRENGTH[,RADIUS[,SEARCH[,BIAS]]]]` keeps the matte still where the camera is still
+(`wrapper.set_matte_hold`: the matte blended in time with the previous held one by steady's measure of where the source moved;
+SEARCH 1..8 follows the source's motion).  It acts only while `--matte` is set.  `POST /matte-hold` with the same text changes
+it while the stream runs, an empty body or `off` clears it; `GET /matte-hold` answers the current settings as JSON.
+
 `--matte-edge R[,EPS]` refines the matte by the frame it cuts, so that its edges land on the frame's own edges
 (`wrapper.set_matte_edge`: a guided filter of radius R in 1..8 pixels, one more launch in front of the composite; EPS, default
 10, is the contrast in byte levels below which a window counts as flat).  It acts only while a matte is set.  `POST /matte-edge`
@@ -363,6 +368,55 @@ class SteadyFollowBox:
             self.failed += 1
 
 
+def parse_matte_hold_arg(text: str):
+    """`LO,HI[,STRENGTH[,RADIUS[,SEARCH[,BIAS]]]]` -> the keywords of `wrapper.set_matte_hold`, `off` -> None; ValueError otherwise"""
+    from live2diff_amd.matte import check_hold
+    text = text.strip()
+    if text == "off":
+        return None
+    parts = [t.strip() for t in text.split(",")]
+    if not 2 <= len(parts) <= 6:
+        raise ValueError(f"matte hold {text!r}: use LO,HI[,STRENGTH[,RADIUS[,SEARCH[,BIAS]]]] or off")
+    try:
+        lo, hi = float(parts[0]), float(parts[1])
+        strength = float(parts[2]) if len(parts) > 2 else 0.8
+        radius, search, bias = (int(parts[k]) if len(parts) > k else d for k, d in ((3, 2), (4, 0), (5, 256)))
+    except ValueError:
+        raise ValueError(f"matte hold {text!r}: LO, HI and STRENGTH are numbers, RADIUS, SEARCH and BIAS integers") from None
+    return check_hold(lo, hi, strength, radius, search, bias)
+
+
+class MatteHoldBox:
+    """What `POST /matte-hold` delivers: the newest requested hold (a dict of `set_matte_hold` keywords, or None for `off` and for
+    an empty body), applied by the producer between two frames.  `current` is what was last applied; `failed` counts requests
+    the wrapper refused."""
+    _NOTHING = object()
+
+    def __init__(self, current=None):
+        self._lock = threading.Lock()
+        self.current, self._want, self.failed = current, self._NOTHING, 0
+
+    def put(self, settings) -> None:
+        with self._lock:
+            self._want = settings
+
+    def apply(self, wrapper) -> None:
+        """(producer thread, between frames)"""
+        with self._lock:
+            want, self._want = self._want, self._NOTHING
+        if want is self._NOTHING:
+            return
+        try:
+            if want is None:
+                wrapper.clear_matte_hold()
+            else:
+                wrapper.set_matte_hold(want["lo"], want["hi"], strength=want["strength"], radius=want["radius"], search=want["search"],
+                                       bias=want["bias"])
+            self.current = wrapper.matte_hold
+        except ValueError:
+            self.failed += 1
+
+
 def parse_matte_edge_arg(text: str):
     """`R[,EPS]` -> the keywords of `wrapper.set_matte_edge`, `off` -> None; ValueError otherwise"""
     from live2diff_amd.matte import MAX_EDGE_RADIUS, check_edge
@@ -641,9 +695,10 @@ class Latest:
 
 def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = None, mattes: "MatteBox" = None, colors: "ColorBox" = None,
                  sizes: "SizeBox" = None, sources: "MatteSourceBox" = None, steadies: "SteadyBox" = None, details: "DetailBox" = None,
-                 backdrops: "BackdropBox" = None, follows: "SteadyFollowBox" = None, edges: "MatteEdgeBox" = None):
+                 backdrops: "BackdropBox" = None, follows: "SteadyFollowBox" = None, holds: "MatteHoldBox" = None,
+                 edges: "MatteEdgeBox" = None):
     boxes = {"/matte": mattes, "/color": colors, "/size": sizes, "/matte-source": sources, "/steady": steadies, "/matte-edge": edges,
-             "/detail": details, "/backdrop": backdrops, "/steady-follow": follows}
+             "/detail": details, "/backdrop": backdrops, "/steady-follow": follows, "/matte-hold": holds}
     page = PAGE if inbox is None else CAMERA_PAGE
 
     class Handler(BaseHTTPRequestHandler):
@@ -760,6 +815,9 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
             if self.path == "/steady-follow" and follows is not None:
                 self.do_matte(follows, parse_steady_follow_arg, empty=True)
                 return
+            if self.path == "/matte-hold" and holds is not None:
+                self.do_matte(holds, parse_matte_hold_arg, empty=True)
+                return
             if self.path == "/detail" and details is not None:
                 self.do_matte(details, parse_detail_arg)
                 return
@@ -791,9 +849,9 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
 def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: StyleBox = None, mattes: MatteBox = None,
             colors: ColorBox = None, sizes: SizeBox = None, sources: MatteSourceBox = None, steadies: SteadyBox = None,
             details: DetailBox = None, backdrops: BackdropBox = None, follows: SteadyFollowBox = None,
-            edges: MatteEdgeBox = None) -> None:
+            holds: MatteHoldBox = None, edges: MatteEdgeBox = None) -> None:
     """the producer: loops `frames` through the wrapper until `stop` is set; a posted style, matte, colour lock, output size,
-    matte source, steady mode, follow setting, matte edge, detail mode or backdrop is applied between two frames"""
+    matte source, steady mode, follow setting, matte edge, matte hold, detail mode or backdrop is applied between two frames"""
     from live2diff_amd.jpeg import mjpeg_part
     try:
         i = 0
@@ -814,6 +872,8 @@ def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: Styl
                 follows.apply(wrapper)
             if edges is not None:
                 edges.apply(wrapper)
+            if holds is not None:
+                holds.apply(wrapper)
             if details is not None:
                 details.apply(wrapper)
             if backdrops is not None:
@@ -827,7 +887,8 @@ def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: Styl
 def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: threading.Event, styles: StyleBox = None,
                    mattes: MatteBox = None, colors: ColorBox = None, sizes: SizeBox = None, sources: MatteSourceBox = None,
                    steadies: SteadyBox = None, details: DetailBox = None, backdrops: BackdropBox = None,
-                   follows: SteadyFollowBox = None, edges: MatteEdgeBox = None) -> None:
+                   follows: SteadyFollowBox = None, holds: "MatteHoldBox" = None,
+                   edges: MatteEdgeBox = None) -> None:
     """the producer of `--input post`: the first frames posted warm the stream up, then the newest posted frame goes through the
     wrapper, for ever; a frame the wrapper refuses (ValueError: a damaged file) is dropped and counted in `inbox.failed`"""
     from live2diff_amd.jpeg import mjpeg_part
@@ -856,6 +917,8 @@ def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: thr
                 follows.apply(wrapper)
             if edges is not None:
                 edges.apply(wrapper)
+            if holds is not None:
+                holds.apply(wrapper)
             if details is not None:
                 details.apply(wrapper)
             if backdrops is not None:
@@ -904,6 +967,11 @@ def main(argv=None):
                          "displacements of up to R pixels (1..8); BIAS (default 256, 0..4096) keeps noise in flat areas from producing "
                          "vectors; acts while --steady is set; POST /steady-follow with the same text changes it between frames, an "
                          "empty body (or `off`) clears it")
+    ap.add_argument("--matte-hold", default=None, metavar="LO,HI[,STRENGTH[,RADIUS[,SEARCH[,BIAS]]]]",
+                    help="keep the matte still where the source moved by LO byte levels or less (moving from HI on), by STRENGTH "
+                         "(default 0.8), the motion averaged over a radius of RADIUS pixels (default 2); SEARCH 1..8 (default 0: the "
+                         "same coordinates) follows the source's motion, with BIAS (default 256); acts while --matte is set; POST "
+                         "/matte-hold with the same text changes it between frames, an empty body (or `off`) clears it")
     ap.add_argument("--matte-edge", default=None, metavar="R[,EPS]",
                     help="refine the matte by the frame it cuts (a guided filter of radius R, 1..8 pixels; EPS, default 10: the contrast in "
                          "byte levels below which a window counts as flat); acts while a matte is set; POST /matte-edge with the same "
@@ -924,6 +992,7 @@ def main(argv=None):
     steady = parse_steady_arg(args.steady) if args.steady else None
     follow = parse_steady_follow_arg(args.steady_follow) if args.steady_follow else None
     edge = parse_matte_edge_arg(args.matte_edge) if args.matte_edge else None
+    hold = parse_matte_hold_arg(args.matte_hold) if args.matte_hold else None
     detail = parse_detail_arg(args.detail) if args.detail else None
     backdrop = parse_backdrop_arg(args.backdrop) if args.backdrop else None
 
@@ -961,6 +1030,9 @@ def main(argv=None):
     if edge is not None:
         w.set_matte_edge(edge["radius"], edge["eps"])
     edges = MatteEdgeBox(w.matte_edge)
+    if hold is not None:
+        w.set_matte_hold(hold["lo"], hold["hi"], strength=hold["strength"], radius=hold["radius"], search=hold["search"], bias=hold["bias"])
+    holds = MatteHoldBox(w.matte_hold)
     if detail is not None:
         w.set_detail(**detail)               # (before `prepare`: the line is primed, the first frames carry their camera frame)
     details = DetailBox(w.detail)
@@ -971,11 +1043,11 @@ def main(argv=None):
     latest, stop = Latest(), threading.Event()
     inbox = Inbox(sink) if post else None
     if post:
-        producer = threading.Thread(target=produce_posted, args=(w, prompt, inbox, latest, stop, styles, mattes, colors, sizes, sources, steadies, details, backdrops, follows, edges), name="producer", daemon=True)
+        producer = threading.Thread(target=produce_posted, args=(w, prompt, inbox, latest, stop, styles, mattes, colors, sizes, sources, steadies, details, backdrops, follows, holds, edges), name="producer", daemon=True)
     else:
         w.prepare(frames[:sink], prompt)
-        producer = threading.Thread(target=produce, args=(w, frames, latest, stop, styles, mattes, colors, sizes, sources, steadies, details, backdrops, follows, edges), name="producer", daemon=True)
-    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest, inbox, styles, mattes, colors, sizes, sources, steadies, details, backdrops, follows, edges))
+        producer = threading.Thread(target=produce, args=(w, frames, latest, stop, styles, mattes, colors, sizes, sources, steadies, details, backdrops, follows, holds, edges), name="producer", daemon=True)
+    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest, inbox, styles, mattes, colors, sizes, sources, steadies, details, backdrops, follows, holds, edges))
     server.daemon_threads = True
     producer.start()
     print(f"http://{args.host}:{args.port}/  ({args.height}x{args.width}, quality {args.quality}; Ctrl-C stops)")
