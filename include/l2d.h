@@ -409,6 +409,9 @@ enum {
  *   bytes in LDS, the sums separably.  Every element of p2 is written by a plain store on every launch: nothing has to be zeroed.
  *   Refused: a null or misaligned pointer, W % 8 != 0, 3 H W >= 2^31, r outside 1..L2D_MATTE_EDGE_MAX_R, unknown flags, an E
  *   that is not finite or below n n, lo / inv as L2D_OP_FRAME_MATTE refuses them.
+ *   L2D_MATTE_EDGE_PLANE: p1 is a float plane [H][W] of ready matte values (p1 of L2D_OP_MASK_INGEST), 16-byte aligned, read
+ *   where the tile and its halo are staged: P = rint(255 min(max(p1, 0), 1)); HARD, FAR, f0 and f1 are not read (HARD or FAR
+ *   beside it is refused, and so is p2 overlapping p1).  With the flag clear every bit is as before.
  *
  * Steady (steady.hip; no counterpart in the reference).  Where the frame's source did not move since the source of the output
  *   before, the previous output pixel is held (a per-pixel EMA); where it moved, the styled pixel passes untouched.  The result is
@@ -504,6 +507,9 @@ enum {
  *   nothing has to be zeroed.  Refused: a null or misaligned pointer, W % 8 != 0, 3 H W >= 2^31, r outside
  *   1..L2D_BACKDROP_MAX_R, passes outside 1..L2D_BACKDROP_MAX_PASSES, unknown flags, p2 overlapping p0 or p1, lo / inv as
  *   L2D_OP_FRAME_MATTE refuses them.
+ *   L2D_BACKDROP_PLANE: p1 is a float plane [H][W] of ready matte values (p1 of L2D_OP_MASK_INGEST), 16-byte aligned, read
+ *   where the tile and its halo are staged: W = 256 - rint(255 min(max(p1, 0), 1)); HARD, FAR, f0 and f1 are not read (HARD or
+ *   FAR beside it is refused).  With the flag clear every bit is as before.
  *
  * Follow (steady_follow.hip; no counterpart in the reference): steady along the source's motion.  L2D_OP_FRAME_STEADY compares the
  *   source bytes at the same coordinates, so under a moving camera it holds nothing; these two ops find, per 8 x 8 block, where in
@@ -563,6 +569,26 @@ enum {
  *   FOLLOW), a misaligned one, W % 8 != 0, 3 H W >= 2^31, r out of range, unknown flags, ramp flags beside PLANE, lo / inv / s as
  *   L2D_OP_FRAME_STEADY refuses them, the depth ramp as L2D_OP_FRAME_MATTE refuses it, p4 or p5 overlapping p0 .. p3 or each
  *   other, p6 overlapping p4 or p5.
+ *
+ * The matte from the caller (mask_in.hip; no counterpart in the reference): a mask of any size and sample type becomes the raw
+ *   matte plane at the stream's size, in place of the depth ramp or combined with it.  Individually rounded fp32 operations, no
+ *   fma, so that numpy restates it bit for bit (live2diff_amd/mask_io.py mask_ref, front_ref).
+ * L2D_OP_MASK_INGEST  one launch:  p0 mask uint8, (L2D_MASK_U16) uint16 or (L2D_MASK_F32) float [Hm][Wm] (aligned to its element)
+ *   p1 out float [H][W] (16-byte aligned) p2 depth half [H][W] (read only with L2D_MASK_AND / _OR; may be null without) p3 xmin
+ *   int32 [W] p4 wx float [W][Kx] p5 ymin int32 [H] p6 wy float [H][Ky] (the tables of L2D_OP_DEPTH_INGEST, of the mask's own
+ *   size) ; i0 Hm i1 Wm i2 H i3 W i4 nh i5 nw i6 top i7 left (L2D_OP_FRAME_INGEST's geometry, of the mask's own size) i8 Kx i9 Ky
+ *   (1..L2D_DEPTH_MAX_TAPS) i10 flags (L2D_MASK_*) ; f0 lo f1 inv of the depth ramp (as L2D_OP_FRAME_MATTE's; read only with AND /
+ *   OR).  Per sample v = float(s) / 255 (uint8), float(s) / 65535 (uint16), min(max(x, 0), 1) with NaN -> 0 (float).  r = sum_y wy
+ *   (sum_x wx v), the horizontal pass first, taps ascending, every product and sum rounded to fp32; P = rint(255 min(max(r, 0),
+ *   1)), half to even; INVERT: P = 255 - P; mu = float(P) / 255; out = mu, or with AND min(m_r, mu), with OR max(m_r, mu), m_r
+ *   the matte as L2D_OP_FRAME_MATTE forms it of p2 in front of the feather (RAMP_HARD, RAMP_FAR).  The mask is quantised to byte
+ *   levels at the stream's size: a constant mask comes back exactly 0 or 1, and rint(255 out) of a replacing mask is P.  One
+ *   work-group per L2D_DEPTH_TILE_H x L2D_DEPTH_TILE_W output tile, the horizontal sums of the source rows its taps reach in
+ *   20,736 bytes of LDS, then the vertical pass.  Every element of p1 is written by a plain store on every launch: nothing has
+ *   to be zeroed, no atomics; W may be any width.  Table entries are clamped to the image.  Refused: a null or misaligned
+ *   pointer, a non-positive size, Hm Wm or H W >= 2^31, a window outside the resized image, a scale above 8, taps outside
+ *   1..L2D_DEPTH_MAX_TAPS, unknown flags, two sample types or two combines at once, ramp flags without AND / OR, the ramp as
+ *   L2D_OP_FRAME_MATTE refuses it, p1 overlapping p0 or p2.
  */
 enum {
     L2D_OP_IGEMM = 1,
@@ -622,6 +648,7 @@ enum {
     L2D_OP_FRAME_MOTION = 55,
     L2D_OP_FRAME_STEADY_FOLLOW = 56,
     L2D_OP_FRAME_MATTE_HOLD = 57,
+    L2D_OP_MASK_INGEST = 58,
 };
 
 /* flag bits of L2D_OP_FRAME_MATTE (i4) and L2D_OP_FRAME_MATTE_UP (i6); HARD and FAR also of L2D_OP_FRAME_MATTE_EDGE (i3) */
@@ -631,8 +658,11 @@ enum {
 #define L2D_MATTE_PLANE 16 /* p2 is a float plane of ready matte values (8 is not assigned) */
 #define L2D_MATTE_MAX_R 8
 #define L2D_MATTE_EDGE_MAX_R 8 /* the largest radius of L2D_OP_FRAME_MATTE_EDGE */
+#define L2D_MATTE_EDGE_PLANE 32 /* L2D_OP_FRAME_MATTE_EDGE: p1 is a float plane of ready matte values (what L2D_MATTE_PLANE is to
+                                   L2D_OP_FRAME_MATTE; 4 and 16 are not assigned here and stay refused) */
 
-/* sizes of L2D_OP_FRAME_BACKDROP_BLUR (its flags, i4, are L2D_MATTE_HARD | _FAR) */
+/* sizes of L2D_OP_FRAME_BACKDROP_BLUR (its flags, i4, are L2D_MATTE_HARD | _FAR, or L2D_BACKDROP_PLANE) */
+#define L2D_BACKDROP_PLANE 32 /* p1 is a float plane of ready matte values (as L2D_MATTE_EDGE_PLANE; 4 and 16 stay refused) */
 #define L2D_BACKDROP_MAX_R 8
 #define L2D_BACKDROP_MAX_PASSES 3
 
@@ -675,6 +705,15 @@ enum {
 #define L2D_DEPTH_TILE_H 16 /* the output tile of one work-group: one {min, max, any} partial each */
 #define L2D_DEPTH_TILE_W 32
 #define L2D_DEPTH_MAX_TAPS 17 /* per axis, at a down-scale of 8 */
+
+/* flag bits of L2D_OP_MASK_INGEST (i10); its tile and its taps are L2D_OP_DEPTH_INGEST's */
+#define L2D_MASK_U16 1 /* p0 holds uint16 samples (neither U16 nor F32: uint8) */
+#define L2D_MASK_F32 2 /* p0 holds fp32 samples */
+#define L2D_MASK_INVERT 4 /* P = 255 - P */
+#define L2D_MASK_AND 8 /* out = min(ramp, mask) (neither AND nor OR: the mask replaces the ramp) */
+#define L2D_MASK_OR 16 /* out = max(ramp, mask) */
+#define L2D_MASK_RAMP_HARD 64 /* L2D_MATTE_HARD of the depth ramp */
+#define L2D_MASK_RAMP_FAR 128 /* L2D_MATTE_FAR of the depth ramp */
 
 /* sizes of L2D_OP_FRAME_RESIZE */
 #define L2D_RESIZE_MAX_KS 13 /* taps per output: Lanczos (support 3) at a 2x down-scale, 2 * 6 + 1 */

@@ -38,6 +38,7 @@ OP_FRAME_BACKDROP_BLUR = 54
 OP_FRAME_MOTION = 55
 OP_FRAME_STEADY_FOLLOW = 56
 OP_FRAME_MATTE_HOLD = 57
+OP_MASK_INGEST = 58
 ABI_VERSION = 6
 
 

@@ -79,10 +79,11 @@ def check_settings(to="blur", radius=6, passes=3) -> dict:
 
 
 # ----------------------------------------------------------------------------- reference arithmetic (CPU, numpy)
-def weight_ref(depth, lo: float, hi: float, keep: str = "near") -> np.ndarray:
+def weight_ref(depth, lo: float, hi: float, keep: str = "near", plane=None) -> np.ndarray:
     """int64 [H,W] in 1..256: W0 = 256 - rint(255 m) with m the raw matte (ramp and `keep`, no feather, no edge), P formed as
-    `matte.edge_ref` forms its own"""
-    m = matte_ref(depth, lo, hi, 0, keep)
+    `matte.edge_ref` forms its own.  `plane` (fp32 [H,W]): a ready raw matte in place of the ramp (`mask_io.front_ref`), the
+    host twin of L2D_BACKDROP_PLANE; `depth` is then not read."""
+    m = matte_ref(depth, lo, hi, 0, keep) if plane is None else matte_ref(depth, lo, hi, 0, keep, plane=plane)
     if m.shape[0] != 1:
         raise ValueError(f"backdrop: expected one [H,W] depth plane, got {m.shape[0]}")
     M = np.rint(m[0] * np.float32(255.0)).astype(np.int64)
@@ -107,13 +108,14 @@ def blur_weighted(P0: np.ndarray, W0: np.ndarray, radius: int, passes: int) -> n
     return P.astype(np.uint8)
 
 
-def blur_ref(source, depth, lo: float, hi: float, keep: str = "near", radius: int = 6, passes: int = 3) -> np.ndarray:
+def blur_ref(source, depth, lo: float, hi: float, keep: str = "near", radius: int = 6, passes: int = 3, plane=None) -> np.ndarray:
     """L2D_OP_FRAME_BACKDROP_BLUR on the host, in front of `frame_of`: the fp16 [3,H,W] `source` frame and its fp16 [H,W] `depth`
     plane under the matte's `lo`, `hi`, `keep` -> uint8 [3,H,W] (planar, as `steady.source_bytes`): the frame's egress bytes
-    blurred `passes` times by a (2 radius + 1)^2 box in which a pixel counts 256 - M (module docstring)."""
+    blurred `passes` times by a (2 radius + 1)^2 box in which a pixel counts 256 - M (module docstring).  `plane`: as
+    `weight_ref`'s."""
     s = check_settings("blur", radius, passes)
     P0 = source_bytes(source)
-    W0 = weight_ref(depth, lo, hi, keep)
+    W0 = weight_ref(depth, lo, hi, keep, plane=plane)
     if W0.shape != P0.shape[1:]:
         raise ValueError(f"blur_ref: the depth plane is {W0.shape}, the source frame {P0.shape[1:]}")
     return blur_weighted(P0, W0, s["radius"], s["passes"])
@@ -215,22 +217,23 @@ def bytes_ref(setting: dict, image, height: int, width: int, resample: str = "la
     return image_ref(image, height, width, resample)
 
 
-def stream_ref(setting: dict, image, source, depth, matte: dict, resample: str = "lanczos") -> np.ndarray:
+def stream_ref(setting: dict, image, source, depth, matte: dict, resample: str = "lanczos", plane=None) -> np.ndarray:
     """fp16 [3,H,W]: the backdrop of one frame at the stream's size, as `matte.composite_ref(backdrop=)` takes it -- `frame_of` of
     the blurred source frame under the `matte` settings, of the colour or of the image"""
     H, W = tuple(source.shape[-2:])
     if setting["to"] == "blur":
-        return frame_of(blur_ref(source, depth, matte["lo"], matte["hi"], matte["keep"], setting["radius"], setting["passes"]))
+        return frame_of(blur_ref(source, depth, matte["lo"], matte["hi"], matte["keep"], setting["radius"], setting["passes"], plane=plane))
     if torch.is_tensor(image) and image.dtype == torch.float16:
         return image.detach().cpu().numpy()
     return frame_of(np.ascontiguousarray(bytes_ref(setting, image, H, W, resample).transpose(2, 0, 1)))
 
 
-def output_ref(setting: dict, image, source, depth, matte: dict, out_height: int, out_width: int, resample: str = "lanczos") -> np.ndarray:
+def output_ref(setting: dict, image, source, depth, matte: dict, out_height: int, out_width: int, resample: str = "lanczos",
+               plane=None) -> np.ndarray:
     """uint8 [Ho,Wo,3]: the backdrop of one frame at an output size, as `matte.composite_up_ref(backdrop=)` takes it.  A blur runs
     at the stream's size and its bytes go through `resize_ref`: a blurred frame loses nothing by being scaled up."""
     if setting["to"] == "blur":
-        b = blur_ref(source, depth, matte["lo"], matte["hi"], matte["keep"], setting["radius"], setting["passes"])
+        b = blur_ref(source, depth, matte["lo"], matte["hi"], matte["keep"], setting["radius"], setting["passes"], plane=plane)
         return resize_ref(np.ascontiguousarray(b.transpose(1, 2, 0)), out_height, out_width, resample)
     return bytes_ref(setting, image, out_height, out_width, resample)
 
@@ -254,10 +257,14 @@ class HipBackdrop:
         self._up = None                     # resize.HipResize of its own: the blurred frame's way to an output size
         self._prepared = {}                 # key -> (tensor, the image it was made of)
 
-    def blur_record(self, slot, matte: dict, setting: dict):
-        """the record of L2D_OP_FRAME_BACKDROP_BLUR for a `MatteLine` slot under the `matte` settings -> `frame`"""
+    def blur_record(self, slot, matte: dict, setting: dict, plane=None):
+        """the record of L2D_OP_FRAME_BACKDROP_BLUR for a `MatteLine` slot under the `matte` settings -> `frame`; with `plane`
+        (op 58's raw matte) that plane in place of the depth plane and the ramp"""
         if self.frame is None:
             self.frame = torch.empty(3, self.height, self.width, dtype=torch.float16, device=self.device)
+        if plane is not None:
+            return ops.frame_backdrop_blur(slot.source, None, self.frame, H=self.height, W=self.width, r=setting["radius"],
+                                           passes=setting["passes"], plane=plane)
         check_matte(matte["lo"], matte["hi"], keep=matte["keep"])
         lo32, inv32, hard = matte_params(matte["lo"], matte["hi"])
         return ops.frame_backdrop_blur(slot.source, slot.depth, self.frame, H=self.height, W=self.width, r=setting["radius"],
@@ -284,11 +291,11 @@ class HipBackdrop:
         return self._prepare(("u8", setting["to"], ident, height, width, resample), image,
                              lambda: torch.from_numpy(bytes_ref(setting, image, height, width, resample)).to(self.device))
 
-    def stream(self, slot, matte: dict, setting: dict, image=None, resample: str = "lanczos"):
+    def stream(self, slot, matte: dict, setting: dict, image=None, resample: str = "lanczos", plane=None):
         """(fp16 [3,H,W], records): the backdrop of the slot's frame at the stream's size, for `HipMatte.composite(backdrop=)`"""
         H, W = self.height, self.width
         if setting["to"] == "blur":
-            blur = self.blur_record(slot, matte, setting)
+            blur = self.blur_record(slot, matte, setting, plane)
             return self.frame, [blur]
         if torch.is_tensor(image) and image.is_cuda:
             if image.dtype == torch.float16 and tuple(image.shape) == (3, H, W) and image.is_contiguous():
@@ -301,7 +308,8 @@ class HipBackdrop:
             frame_of(bytes_ref(setting, image, H, W, resample).transpose(2, 0, 1)))).to(self.device))
         return t, []
 
-    def output(self, slot, matte: dict, setting: dict, out_height: int, out_width: int, image=None, resample: str = "lanczos"):
+    def output(self, slot, matte: dict, setting: dict, out_height: int, out_width: int, image=None, resample: str = "lanczos",
+               plane=None):
         """(uint8 [Ho,Wo,3], records): the backdrop of the slot's frame at an output size, for `HipMatteUp.composite(backdrop=)`"""
         H, W = self.height, self.width
         if setting["to"] != "blur":
@@ -311,6 +319,6 @@ class HipBackdrop:
         if rs is None or (rs.out_height, rs.out_width, rs.resample) != key:
             from .resize import HipResize
             rs = self._up = HipResize(H, W, key[0], key[1], key[2], device=self.device)
-        blur = self.blur_record(slot, matte, setting)
+        blur = self.blur_record(slot, matte, setting, plane)
         up = ops.frame_resize(self.frame, rs.dev, rs.tx, rs.ty, B=1, H=H, W=W, Ho=key[0], Wo=key[1])
         return rs.dev[0], [blur, up]

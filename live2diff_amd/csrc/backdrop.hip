@@ -52,6 +52,9 @@ __device__ __forceinline__ unsigned bd_w(h16 depth, const bd_params &p) {
     return 255u - (unsigned)rintf(__fmul_rn(px_ramp(depth, p.lo, p.inv, p.flags), 255.0f));
 }
 
+// L2D_BACKDROP_PLANE: W0 - 1 of a ready matte value (clamped: whatever the plane holds, the weight fits its byte)
+__device__ __forceinline__ unsigned bd_wm(float m) { return 255u - (unsigned)rintf(__fmul_rn(fminf(fmaxf(m, 0.0f), 1.0f), 255.0f)); }
+
 __global__ __launch_bounds__(BD_THREADS) void frame_backdrop_blur_kernel(const h16 *__restrict__ source, const h16 *__restrict__ depth,
                                                                          h16 *__restrict__ out, int H, int W, bd_params p) {
     // plane c at (y0 - BD_PAD + j, x0 - BD_PAD + cb), clamped: P[0..2] and W - 1
@@ -65,6 +68,8 @@ __global__ __launch_bounds__(BD_THREADS) void frame_backdrop_blur_kernel(const h
     const unsigned n = (unsigned)(taps * taps);
     const int halo = p.passes * r;                              // <= BD_PAD
     const long long HW = (long long)H * W;
+    const bool from_plane = (p.flags & L2D_BACKDROP_PLANE) != 0;                   // uniform over the launch
+    const float *__restrict__ mplane = reinterpret_cast<const float *>(depth);
 
     // the bytes of the tile and its halo.  An 8-pixel group lies wholly inside or wholly outside the image (W % 8 == 0); one
     // outside holds the edge pixel's values; a group no window reaches is skipped.
@@ -79,15 +84,23 @@ __global__ __launch_bounds__(BD_THREADS) void frame_backdrop_blur_kernel(const h
             if (gx < 0 || gx >= W) {
                 const long long e0 = (long long)yy * W + (gx < 0 ? 0 : W - 1);
                 const unsigned b0 = px_byte(source[e0]), b1 = px_byte(source[HW + e0]), b2 = px_byte(source[2 * HW + e0]);
-                const unsigned w = bd_w(depth[e0], p);
+                const unsigned w = from_plane ? bd_wm(mplane[e0]) : bd_w(depth[e0], p);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) { v[0][e] = b0; v[1][e] = b1; v[2][e] = b2; v[3][e] = w; }
             } else {
                 const long long g0 = (long long)yy * W + gx;
                 const h16x8 c0 = l2d_ld8(source + g0), c1 = l2d_ld8(source + HW + g0), c2 = l2d_ld8(source + 2 * HW + g0);
-                const h16x8 d = l2d_ld8(depth + g0);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) { v[0][e] = px_byte(c0[e]); v[1][e] = px_byte(c1[e]); v[2][e] = px_byte(c2[e]); v[3][e] = bd_w(d[e], p); }
+                for (int e = 0; e < 8; ++e) { v[0][e] = px_byte(c0[e]); v[1][e] = px_byte(c1[e]); v[2][e] = px_byte(c2[e]); }
+                if (from_plane) {
+                    const f32x4 m0 = *reinterpret_cast<const f32x4 *>(mplane + g0), m1 = *reinterpret_cast<const f32x4 *>(mplane + g0 + 4);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) v[3][e] = bd_wm(e < 4 ? m0[e & 3] : m1[e & 3]);
+                } else {
+                    const h16x8 d = l2d_ld8(depth + g0);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) v[3][e] = bd_w(d[e], p);
+                }
             }
 #pragma unroll
             for (int c = 0; c < 4; ++c) *reinterpret_cast<uint2 *>(&pl[c][j][cg * 8]) = px_pack8(v[c]);
@@ -178,14 +191,19 @@ int l2d_launch_frame_backdrop_blur(const l2d_op *op, hipStream_t s) {
         l2d_set_error("frame_backdrop_blur(tag %d): %d passes, need 1..%d", op->tag, passes, BD_MAX_PASSES);
         return L2D_EINVAL;
     }
-    if (flags & ~(L2D_MATTE_HARD | L2D_MATTE_FAR)) {
-        l2d_set_error("frame_backdrop_blur(tag %d): unknown flag bits 0x%x (1 hard, 2 far)", op->tag, flags);
+    if (flags & ~(L2D_MATTE_HARD | L2D_MATTE_FAR | L2D_BACKDROP_PLANE)) {
+        l2d_set_error("frame_backdrop_blur(tag %d): unknown flag bits 0x%x (1 hard, 2 far, 32 plane)", op->tag, flags);
+        return L2D_EINVAL;
+    }
+    const bool plane = (flags & L2D_BACKDROP_PLANE) != 0;
+    if (plane && (flags & (L2D_MATTE_HARD | L2D_MATTE_FAR))) {
+        l2d_set_error("frame_backdrop_blur(tag %d): ramp flags beside L2D_BACKDROP_PLANE (the plane carries them)", op->tag);
         return L2D_EINVAL;
     }
     const float lo = op->f[0], inv = op->f[1];
-    if (!px_check_ramp("frame_backdrop_blur", op->tag, lo, inv, (flags & L2D_MATTE_HARD) != 0)) return L2D_EINVAL;
+    if (!plane && !px_check_ramp("frame_backdrop_blur", op->tag, lo, inv, (flags & L2D_MATTE_HARD) != 0)) return L2D_EINVAL;
     for (int k = 0; k < 2; ++k) {
-        if (px_overlap(op->p[2], 6 * HW, op->p[k], (k == 0 ? 6 : 2) * HW)) {
+        if (px_overlap(op->p[2], 6 * HW, op->p[k], (k == 0 ? 6 : (plane ? 4 : 2)) * HW)) {
             l2d_set_error("frame_backdrop_blur(tag %d): the output overlaps pointer %d (a tile's halo reads its neighbours' pixels)", op->tag, k);
             return L2D_EINVAL;
         }

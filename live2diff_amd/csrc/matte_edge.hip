@@ -60,7 +60,14 @@ __device__ __forceinline__ unsigned me_p(h16 depth, const me_params &p) {
     return (unsigned)rintf(__fmul_rn(px_ramp(depth, p.lo, p.inv, p.flags), 255.0f));
 }
 
+// L2D_MATTE_EDGE_PLANE: P of a ready matte value (clamped: whatever the plane holds, P fits its byte)
+__device__ __forceinline__ unsigned me_pm(float m) { return (unsigned)rintf(__fmul_rn(fminf(fmaxf(m, 0.0f), 1.0f), 255.0f)); }
 
+
+// PLANE (L2D_MATTE_EDGE_PLANE): `depth` is the fp32 plane of ready matte values.  A template parameter, not a branch: the
+// instance without it is the kernel as it was (a branch that is uniform over the launch cost the flag-clear form 0.4 - 0.65 us
+// of 12.1 at 512 x 512).
+template <bool PLANE>
 __global__ __launch_bounds__(ME_THREADS) void frame_matte_edge_kernel(const h16 *__restrict__ source, const h16 *__restrict__ depth,
                                                                       float *__restrict__ out, int H, int W, me_params p) {
     __shared__ __attribute__((aligned(16))) unsigned char yb[ME_YH][ME_YW];       // Y at (y0 - 2r + j, x0 - ME_PAD + c), clamped
@@ -79,6 +86,8 @@ __global__ __launch_bounds__(ME_THREADS) void frame_matte_edge_kernel(const h16 
     const int r = p.r, taps = 2 * r + 1, n = taps * taps;
     const int rows2 = ME_TH + 4 * r, rows1 = ME_TH + 2 * r, cols1 = ME_TW + 2 * r;
     const long long HW = (long long)H * W;
+    constexpr bool from_plane = PLANE;
+    const float *__restrict__ mplane = reinterpret_cast<const float *>(depth);
 
     // Y and P of the tile and its halo of 2r.  An 8-pixel group lies wholly inside or wholly outside the image (W % 8 == 0);
     // one outside holds the edge pixel's values; a group no window reaches is skipped.
@@ -90,15 +99,26 @@ __global__ __launch_bounds__(ME_THREADS) void frame_matte_edge_kernel(const h16 
         unsigned yv[8], pv[8];
         if (gx < 0 || gx >= W) {
             const long long e0 = (long long)yy * W + (gx < 0 ? 0 : W - 1);
-            const unsigned ye = px_luma(px_byte(source[e0]), px_byte(source[HW + e0]), px_byte(source[2 * HW + e0])), pe = me_p(depth[e0], p);
+            const unsigned ye = px_luma(px_byte(source[e0]), px_byte(source[HW + e0]), px_byte(source[2 * HW + e0]));
+            const unsigned pe = from_plane ? me_pm(mplane[e0]) : me_p(depth[e0], p);
 #pragma unroll
             for (int e = 0; e < 8; ++e) { yv[e] = ye; pv[e] = pe; }
         } else {
             const long long g0 = (long long)yy * W + gx;
             const h16x8 cr = l2d_ld8(source + g0), cgn = l2d_ld8(source + HW + g0), cb = l2d_ld8(source + 2 * HW + g0);
-            const h16x8 d = l2d_ld8(depth + g0);
+            // (either form issues the matte input's loads beside the frame's, in front of the arithmetic)
+            if (from_plane) {
+                const f32x4 m0 = *reinterpret_cast<const f32x4 *>(mplane + g0), m1 = *reinterpret_cast<const f32x4 *>(mplane + g0 + 4);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) { yv[e] = px_luma(px_byte(cr[e]), px_byte(cgn[e]), px_byte(cb[e])); pv[e] = me_p(d[e], p); }
+                for (int e = 0; e < 8; ++e) {
+                    yv[e] = px_luma(px_byte(cr[e]), px_byte(cgn[e]), px_byte(cb[e]));
+                    pv[e] = me_pm(e < 4 ? m0[e & 3] : m1[e & 3]);
+                }
+            } else {
+                const h16x8 d = l2d_ld8(depth + g0);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { yv[e] = px_luma(px_byte(cr[e]), px_byte(cgn[e]), px_byte(cb[e])); pv[e] = me_p(d[e], p); }
+            }
         }
         *reinterpret_cast<uint2 *>(&yb[j][cg * 8]) = px_pack8(yv);
         *reinterpret_cast<uint2 *>(&pb[j][cg * 8]) = px_pack8(pv);
@@ -187,8 +207,12 @@ int l2d_launch_frame_matte_edge(const l2d_op *op, hipStream_t s) {
         l2d_set_error("frame_matte_edge(tag %d): radius %d, need 1..%d", op->tag, r, ME_MAX_R);
         return L2D_EINVAL;
     }
-    if (flags & ~(L2D_MATTE_HARD | L2D_MATTE_FAR)) {
-        l2d_set_error("frame_matte_edge(tag %d): unknown flag bits 0x%x (1 hard, 2 far)", op->tag, flags);
+    if (flags & ~(L2D_MATTE_HARD | L2D_MATTE_FAR | L2D_MATTE_EDGE_PLANE)) {
+        l2d_set_error("frame_matte_edge(tag %d): unknown flag bits 0x%x (1 hard, 2 far, 32 plane)", op->tag, flags);
+        return L2D_EINVAL;
+    }
+    if ((flags & L2D_MATTE_EDGE_PLANE) && (flags & (L2D_MATTE_HARD | L2D_MATTE_FAR))) {
+        l2d_set_error("frame_matte_edge(tag %d): ramp flags beside L2D_MATTE_EDGE_PLANE (the plane carries them)", op->tag);
         return L2D_EINVAL;
     }
     me_params p;
@@ -201,10 +225,16 @@ int l2d_launch_frame_matte_edge(const l2d_op *op, hipStream_t s) {
         return L2D_EINVAL;
     }
     const float lo = op->f[0], inv = op->f[1];
-    if (!px_check_ramp("frame_matte_edge", op->tag, lo, inv, (flags & L2D_MATTE_HARD) != 0)) return L2D_EINVAL;
+    if (!(flags & L2D_MATTE_EDGE_PLANE) && !px_check_ramp("frame_matte_edge", op->tag, lo, inv, (flags & L2D_MATTE_HARD) != 0))
+        return L2D_EINVAL;
+    if ((flags & L2D_MATTE_EDGE_PLANE) && px_overlap(op->p[2], 4ll * H * W, op->p[1], 4ll * H * W)) {
+        l2d_set_error("frame_matte_edge(tag %d): the output overlaps the input plane (a tile's halo reads its neighbours' pixels)", op->tag);
+        return L2D_EINVAL;
+    }
     L2D_DRY_RETURN();
     p.lo = lo; p.inv = inv; p.flags = flags; p.r = r;
-    hipLaunchKernelGGL(frame_matte_edge_kernel, dim3((W + ME_TW - 1) / ME_TW, (H + ME_TH - 1) / ME_TH), dim3(ME_THREADS), 0, s,
+    auto kernel = (flags & L2D_MATTE_EDGE_PLANE) ? frame_matte_edge_kernel<true> : frame_matte_edge_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((W + ME_TW - 1) / ME_TW, (H + ME_TH - 1) / ME_TH), dim3(ME_THREADS), 0, s,
                        (const h16 *)op->p[0], (const h16 *)op->p[1], (float *)op->p[2], H, W, p);
     return l2d_check_launch("frame_matte_edge", op->tag);
 }

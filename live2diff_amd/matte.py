@@ -375,6 +375,7 @@ class _Slot:
         self.source = torch.empty(3, height, width, dtype=torch.float16, device=device)
         self.depth = torch.empty(height, width, dtype=torch.float16, device=device)
         self.camera = None                     # the frame's own pixels at the output size (resize.CameraBuffer), or None
+        self.mask = None                       # the frame's own raw mask (mask_io.MaskBuffer; a numpy array on CPU tensors), or None
 
 
 class MatteLine:
@@ -403,12 +404,19 @@ class MatteLine:
     camera frame.  The rule that makes the buffers safe without events of their own: EVERY launch that writes or reads a camera
     buffer runs on the caller's stream -- the resample inside `ingest`, the composite inside the wrapper's `_finish` -- so a
     buffer that went back to the pool is overwritten only behind its last reader.  A frame that was not ingested on the device
-    (a float tensor, a batch) leaves `slot.camera` None; `last` keeps its buffer as it keeps its slot."""
+    (a float tensor, a batch) leaves `slot.camera` None; `last` keeps its buffer as it keeps its slot.
+
+    The mask.  While `mask_source` is set (a `mask_io.HipMaskIngest`, or anything with `pending` and
+    `give_back`), a slot takes the raw mask the source holds as `pending` as `slot.mask`, exactly as it takes a camera buffer: a
+    move of a reference with no launch on the side stream, the slot's previous buffer back to the pool, and the same rule --
+    the copy that fills a buffer and L2D_OP_MASK_INGEST, its only reader, both run on the caller's stream.  A frame that
+    brought no mask leaves `slot.mask` None and is cut by the ramp alone."""
 
     def __init__(self, n_steps: int, height: int, width: int, device="cpu"):
         self.n, self.height, self.width, self.device = int(n_steps), int(height), int(width), torch.device(device)
         self.slots = []
         self.camera_source = None
+        self.mask_source = None
         self.clear()
 
     def clear(self) -> None:
@@ -440,12 +448,23 @@ class MatteLine:
         old, s.camera = s.camera, camera
         if old is not None and src is not None:
             src.give_back(old)
+        src, mask = self.mask_source, None
+        if src is not None and src.pending is not None:
+            mask, src.pending = src.pending, None
+        old, s.mask = s.mask, mask
+        if old is not None and src is not None:
+            src.give_back(old)
         return i
 
     def drop_cameras(self) -> None:
         """forget every camera buffer (the output size or the filter changed, or the feature was turned off)"""
         for s in self.slots:
             s.camera = None
+
+    def drop_masks(self) -> None:
+        """forget every mask (the matte was turned off)"""
+        for s in self.slots:
+            s.mask = None
 
     def prime(self, x: torch.Tensor, dn: torch.Tensor) -> None:
         """`x` [F,3,H,W], `dn` [F,3,H,W]: the warm-up frames of `prepare` and their normalised depth; the last one is kept"""
@@ -491,9 +510,13 @@ class HipMatteEdge:
         self.height, self.width, self.device = int(height), int(width), torch.device(device)
         self.plane = torch.empty(self.height, self.width, dtype=torch.float32, device=self.device)
 
-    def op(self, slot: "_Slot", settings: dict, edge: dict):
-        """(record, tensors to keep): `slot.source` and `slot.depth` under the matte `settings` and the `edge` setting -> `plane`"""
+    def op(self, slot: "_Slot", settings: dict, edge: dict, plane: Optional[torch.Tensor] = None):
+        """(record, tensors to keep): `slot.source` and `slot.depth` under the matte `settings` and the `edge` setting -> `plane`;
+        with `plane` (op 58's raw matte) that plane in place of the depth plane and the ramp"""
         e = check_edge(edge["radius"], edge["eps"])
+        if plane is not None:
+            return ops.frame_matte_edge(slot.source, None, self.plane, H=self.height, W=self.width, r=e["radius"],
+                                        E=edge_E(e["radius"], e["eps"]), plane=plane)
         lo32, inv32, hard = matte_params(settings["lo"], settings["hi"])
         return ops.frame_matte_edge(slot.source, slot.depth, self.plane, H=self.height, W=self.width, r=e["radius"],
                                     E=edge_E(e["radius"], e["eps"]), lo32=lo32, inv32=inv32, hard=hard, far=settings["keep"] == "far")
@@ -559,20 +582,32 @@ class HoldStep(collections.namedtuple("HoldStep", "dev settings init repeat")):
     sequence, `repeat` the frame is a repeated output -- it is composited with the last held plane and moves nothing"""
 
 
-def _front(owner, pl, slot: "_Slot", settings: dict, edge: Optional[dict], hold: Optional[HoldStep]) -> Optional[torch.Tensor]:
+def _front(owner, pl, slot: "_Slot", settings: dict, edge: Optional[dict], hold: Optional[HoldStep],
+           raw: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
     """append what stands in front of a composite's own op -- the edge op, then the hold's -- and return the fp32 plane the
-    composite reads in place of the depth plane, or None"""
+    composite reads in place of the depth plane, or None.  `raw` (the plane L2D_OP_MASK_INGEST wrote at the head of the list):
+    the raw matte in place of the ramp -- the edge op and the hold read it, and without either the composite does."""
     if hold is not None and hold.repeat:
         return hold.dev.plane
-    plane = None
+    plane = raw
     if edge is not None:
         if owner.edge is None:
             owner.edge = HipMatteEdge(owner.height, owner.width, device=owner.device)
-        op, keep = owner.edge.op(slot, settings, edge)
+        op, keep = owner.edge.op(slot, settings, edge, plane=raw)
         pl.append(op, *keep)
         plane = owner.edge.plane
     if hold is not None:
         plane = hold.dev.append(pl, slot, settings, hold.settings, plane, init=hold.init)
+    return plane
+
+
+def _mask_head(pl, mask) -> Optional[torch.Tensor]:
+    """a composite's `mask=`: None, or `(record, keep, plane)` of L2D_OP_MASK_INGEST -- appended first, in front of the
+    backdrop's records, which read its plane too"""
+    if mask is None:
+        return None
+    op, keep, plane = mask
+    pl.append(op, *keep)
     return plane
 
 
@@ -599,13 +634,14 @@ class HipMatte:
         self.edge = None                       # HipMatteEdge, made by the first frame with an edge setting
 
     def composite(self, image: torch.Tensor, slot: _Slot, settings: dict, to_host: bool = True, edge: Optional[dict] = None,
-                  backdrop=None, hold: Optional[HoldStep] = None):
+                  backdrop=None, hold: Optional[HoldStep] = None, mask=None):
         """fp16 [3,H,W] on the device + a `MatteLine` slot -> uint8 [H,W,3]: a numpy view of the pinned buffer (valid until the next
         call), or with `to_host=False` the static device tensor.  `edge` ({radius, eps}): the matte refined by the slot's source
         frame first -- one more launch in front, and the composite reads its plane.  `backdrop` (an fp16 [3,H,W] device tensor,
         or `(tensor, records)` as `backdrop.HipBackdrop.stream` returns it): the tensor goes where `slot.source` goes in the
         composite op, the records in front of it in the same list; the edge op keeps reading the slot's real source.  `hold` (a
-        `HoldStep`): the matte hold's ops behind the edge op, in the same list, and the composite reads the held plane."""
+        `HoldStep`): the matte hold's ops behind the edge op, in the same list, and the composite reads the held plane.  `mask`
+        (`(record, keep, plane)` of L2D_OP_MASK_INGEST): the record at the head of the list, its plane the raw matte."""
         H, W = self.height, self.width
         if image.dtype != torch.float16 or tuple(image.shape) != (3, H, W):
             raise ValueError(f"composite: expected fp16 [3,{H},{W}], got {image.dtype} {tuple(image.shape)}")
@@ -615,9 +651,10 @@ class HipMatte:
         if kept.dtype != torch.float16 or tuple(kept.shape) != (3, H, W) or not kept.is_contiguous():
             raise ValueError(f"composite: expected a contiguous fp16 [3,{H},{W}] backdrop, got {kept.dtype} {tuple(kept.shape)}")
         pl = _lib.OpList()
+        raw = _mask_head(pl, mask)
         for op, keep in records:
             pl.append(op, *keep)
-        plane = _front(self, pl, slot, settings, edge, hold)
+        plane = _front(self, pl, slot, settings, edge, hold, raw)
         if plane is not None:
             op, keep = ops.frame_matte(image, kept, None, self.dev, B=1, H=H, W=W, show=settings["show"], r=settings["feather"],
                                        plane=plane)
@@ -648,13 +685,14 @@ class HipMatteUp:
         self.edge = None                       # HipMatteEdge, made by the first frame with an edge setting
 
     def composite(self, styled_u8: torch.Tensor, slot: _Slot, settings: dict, to_host: bool = True, edge: Optional[dict] = None,
-                  backdrop=None, hold: Optional[HoldStep] = None):
+                  backdrop=None, hold: Optional[HoldStep] = None, mask=None):
         """uint8 [Ho,Wo,3] on the device + a `MatteLine` slot that carries a camera buffer -> uint8 [Ho,Wo,3]: a numpy view of the
         pinned buffer (valid until the next call), or with `to_host=False` the static device tensor.  `edge` ({radius, eps}): the
         matte refined at the stream's size by the slot's stream-sized source frame first, then sampled as before.  `backdrop` (a
         uint8 [Ho,Wo,3] device tensor, or `(tensor, records)` as `backdrop.HipBackdrop.output` returns it): the tensor goes where
         the slot's camera buffer goes in the composite op -- the slot then needs none --, the records in front of it.  `hold` (a
-        `HoldStep`): the matte hold's ops behind the edge op; the held plane is sampled as the edge plane is."""
+        `HoldStep`): the matte hold's ops behind the edge op; the held plane is sampled as the edge plane is.  `mask`: as
+        `HipMatte.composite`'s."""
         Ho, Wo = self.out_height, self.out_width
         camera, records = _backdrop_parts(backdrop, None)
         if camera is None:
@@ -663,9 +701,10 @@ class HipMatteUp:
             if t.dtype != torch.uint8 or tuple(t.shape) != (Ho, Wo, 3) or not t.is_contiguous():
                 raise ValueError(f"composite: expected a contiguous uint8 [{Ho},{Wo},3] {name} frame, got {t.dtype} {tuple(t.shape)}")
         pl = _lib.OpList()
+        raw = _mask_head(pl, mask)
         for op, keep in records:
             pl.append(op, *keep)
-        plane = _front(self, pl, slot, settings, edge, hold)
+        plane = _front(self, pl, slot, settings, edge, hold, raw)
         if plane is not None:
             op, keep = ops.frame_matte_up(styled_u8, camera, None, self.dev, self.tx, self.ty, B=1, H=self.height, W=self.width, Ho=Ho,
                                           Wo=Wo, show=settings["show"], r=settings["feather"], plane=plane)

@@ -1427,6 +1427,7 @@ MATTE_HARD, MATTE_FAR, MATTE_SHOW = 1, 2, 4      # l2d.h L2D_MATTE_*
 MATTE_MAX_R = 8                                  # l2d.h L2D_MATTE_MAX_R
 MATTE_PLANE = 16                                 # l2d.h L2D_MATTE_PLANE
 MATTE_EDGE_MAX_R = 8                             # l2d.h L2D_MATTE_EDGE_MAX_R
+MATTE_EDGE_PLANE = 32                            # l2d.h L2D_MATTE_EDGE_PLANE
 
 
 def _matte_plane(name, plane, B, H, W, stride):
@@ -1464,13 +1465,20 @@ def frame_matte(styled, source, depth, dst, *, B, H, W, lo32=0.0, inv32=0.0, har
     return op, (styled, source, depth, dst)
 
 
-def frame_matte_edge(source, depth, out, *, H, W, r, E, lo32, inv32, hard, far=False):
+def frame_matte_edge(source, depth, out, *, H, W, r, E, lo32=0.0, inv32=0.0, hard=False, far=False, plane=None):
     """fp16 [3,H,W] `source` + fp16 [H,W] `depth` -> fp32 [H,W] `out`: the matte of `frame_matte` in front of its feather, refined
     by the source frame (matte.edge_ref).  `r`: the radius, 1..MATTE_EDGE_MAX_R; `E`: `matte.edge_E(r, eps)`, a Python float;
-    `lo32, inv32, hard` as `matte.matte_params` returns them."""
+    `lo32, inv32, hard` as `matte.matte_params` returns them.  `plane` (fp32 [H,W], with `depth=None`): a ready raw matte, as
+    `mask_ingest` writes it, in place of the depth plane; the ramp, `hard` and `far` do not apply."""
     _lock_frame("frame_matte_edge: source", source, H, W)
-    if depth.dtype != torch.float16 or depth.numel() != H * W or not depth.is_contiguous():
-        raise ValueError(f"frame_matte_edge: depth: expected a contiguous fp16 [{H},{W}] plane, got {depth.dtype} {tuple(depth.shape)}")
+    if plane is not None:
+        if depth is not None or hard or far:
+            raise ValueError("frame_matte_edge: plane= goes with depth=None, and without hard / far (the plane carries them)")
+        _hold_plane("frame_matte_edge: plane", plane, H, W)
+        depth, lo32, inv32 = plane, 0.0, 0.0
+    elif depth is None or depth.dtype != torch.float16 or depth.numel() != H * W or not depth.is_contiguous():
+        raise ValueError(f"frame_matte_edge: depth: expected a contiguous fp16 [{H},{W}] plane, got "
+                         f"{getattr(depth, 'dtype', None)} {tuple(getattr(depth, 'shape', ()))}")
     if out.dtype != torch.float32 or out.numel() != H * W or not out.is_contiguous():
         raise ValueError(f"frame_matte_edge: out: expected a contiguous float32 [{H},{W}] plane, got {out.dtype} {tuple(out.shape)}")
     if isinstance(r, bool) or int(r) != r or not 1 <= int(r) <= MATTE_EDGE_MAX_R:
@@ -1480,7 +1488,7 @@ def frame_matte_edge(source, depth, out, *, H, W, r, E, lo32, inv32, hard, far=F
     keep = (source, depth, out)
     for j, t in enumerate(keep):
         op.p[j] = _ptr(t)
-    flags = (MATTE_HARD if hard else 0) | (MATTE_FAR if far else 0)
+    flags = (MATTE_HARD if hard else 0) | (MATTE_FAR if far else 0) | (MATTE_EDGE_PLANE if plane is not None else 0)
     for j, v in enumerate([H, W, r, flags]):
         op.i[j] = int(v)
     op.l[0] = int(np.float64(E).view(np.int64))                                              # the bits of the double
@@ -1491,16 +1499,25 @@ def frame_matte_edge(source, depth, out, *, H, W, r, E, lo32, inv32, hard, far=F
 # ----------------------------------------------------------------------------- backdrop blur (backdrop.hip, backdrop.py)
 BACKDROP_MAX_R = 8                               # l2d.h L2D_BACKDROP_MAX_R
 BACKDROP_MAX_PASSES = 3                          # l2d.h L2D_BACKDROP_MAX_PASSES
+BACKDROP_PLANE = 32                              # l2d.h L2D_BACKDROP_PLANE
 
 
-def frame_backdrop_blur(source, depth, out, *, H, W, r, passes, lo32, inv32, hard, far=False):
+def frame_backdrop_blur(source, depth, out, *, H, W, r, passes, lo32=0.0, inv32=0.0, hard=False, far=False, plane=None):
     """fp16 [3,H,W] `source` + fp16 [H,W] `depth` -> fp16 [3,H,W] `out`: the source frame blurred with the matte's subject left
     out, as a frame `frame_matte` takes for its kept part (backdrop.frame_of(backdrop.blur_ref(...))).  `r`: the radius,
-    1..BACKDROP_MAX_R; `passes`: 1..BACKDROP_MAX_PASSES; `lo32, inv32, hard` as `matte.matte_params` returns them."""
+    1..BACKDROP_MAX_R; `passes`: 1..BACKDROP_MAX_PASSES; `lo32, inv32, hard` as `matte.matte_params` returns them.  `plane` (fp32
+    [H,W], with `depth=None`): a ready raw matte, as `mask_ingest` writes it, in place of the depth plane; the ramp, `hard` and
+    `far` do not apply."""
     _lock_frame("frame_backdrop_blur: source", source, H, W)
     _lock_frame("frame_backdrop_blur: out", out, H, W)
-    if depth.dtype != torch.float16 or depth.numel() != H * W or not depth.is_contiguous():
-        raise ValueError(f"frame_backdrop_blur: depth: expected a contiguous fp16 [{H},{W}] plane, got {depth.dtype} {tuple(depth.shape)}")
+    if plane is not None:
+        if depth is not None or hard or far:
+            raise ValueError("frame_backdrop_blur: plane= goes with depth=None, and without hard / far (the plane carries them)")
+        _hold_plane("frame_backdrop_blur: plane", plane, H, W)
+        depth, lo32, inv32 = plane, 0.0, 0.0
+    elif depth is None or depth.dtype != torch.float16 or depth.numel() != H * W or not depth.is_contiguous():
+        raise ValueError(f"frame_backdrop_blur: depth: expected a contiguous fp16 [{H},{W}] plane, got "
+                         f"{getattr(depth, 'dtype', None)} {tuple(getattr(depth, 'shape', ()))}")
     if isinstance(r, bool) or int(r) != r or not 1 <= int(r) <= BACKDROP_MAX_R:
         raise ValueError(f"frame_backdrop_blur: r={r!r}: use an integer from 1 to {BACKDROP_MAX_R}")
     if isinstance(passes, bool) or int(passes) != passes or not 1 <= int(passes) <= BACKDROP_MAX_PASSES:
@@ -1510,7 +1527,7 @@ def frame_backdrop_blur(source, depth, out, *, H, W, r, passes, lo32, inv32, har
     keep = (source, depth, out)
     for j, t in enumerate(keep):
         op.p[j] = _ptr(t)
-    flags = (MATTE_HARD if hard else 0) | (MATTE_FAR if far else 0)
+    flags = (MATTE_HARD if hard else 0) | (MATTE_FAR if far else 0) | (BACKDROP_PLANE if plane is not None else 0)
     for j, v in enumerate([H, W, r, passes, flags]):
         op.i[j] = int(v)
     op.f[0], op.f[1] = float(lo32), float(inv32)
@@ -1932,4 +1949,46 @@ def depth_normalize(R, partials, out, *, B, H, W, fixed=None):
         op.i[j] = int(v)
     if fixed is not None:
         op.f[0], op.f[1] = float(fixed[0]), float(fixed[1])
+    return op, keep
+
+
+# ----------------------------------------------------------------------------- the matte from the caller (mask_in.hip, mask_io.py)
+MASK_U16, MASK_F32, MASK_INVERT, MASK_AND, MASK_OR, MASK_RAMP_HARD, MASK_RAMP_FAR = 1, 2, 4, 8, 16, 64, 128      # l2d.h L2D_MASK_*
+MASK_COMBINE = {"replace": 0, "and": MASK_AND, "or": MASK_OR}
+
+
+def mask_ingest(src, out, depth, xmin, wx, ymin, wy, *, Hm, Wm, H, W, nh, nw, top, left, combine="replace", invert=False, lo32=0.0,
+                inv32=0.0, hard=False, far=False):
+    """uint8 / uint16 / fp32 [Hm,Wm] `src` -> fp32 [H,W] `out`: the raw matte of a caller's mask (mask_io.front_ref of
+    mask_io.mask_ref).  `xmin`, `wx`, `ymin`, `wy`: the tables of `mask_io.tables`; `combine`: "replace", or "and" / "or" with
+    the ramp `lo32, inv32, hard` (`matte.matte_params`) and `far` over the fp16 [H,W] `depth` plane, which "replace" does not
+    read (it may be None)."""
+    kinds = {torch.uint8: 0, torch.uint16: MASK_U16, torch.int16: MASK_U16, torch.float32: MASK_F32}      # (int16: the bits of uint16 samples)
+    if src.dtype not in kinds:
+        raise ValueError(f"mask_ingest: src: expected uint8, uint16 or float32 samples, got {src.dtype}")
+    if src.numel() != Hm * Wm or not src.is_contiguous():
+        raise ValueError(f"mask_ingest: src: expected a contiguous [{Hm},{Wm}] mask, got {tuple(src.shape)}")
+    if out.dtype != torch.float32 or out.numel() != H * W or not out.is_contiguous():
+        raise ValueError(f"mask_ingest: out: expected a contiguous float32 [{H},{W}] plane, got {out.dtype} {tuple(out.shape)}")
+    if combine not in MASK_COMBINE:
+        raise ValueError(f"mask_ingest: combine={combine!r}: use 'replace', 'and' or 'or'")
+    if combine == "replace":
+        depth, lo32, inv32, hard, far = None, 0.0, 0.0, False, False
+    elif depth is None or depth.dtype != torch.float16 or depth.numel() != H * W or not depth.is_contiguous():
+        raise ValueError(f"mask_ingest: depth: expected a contiguous fp16 [{H},{W}] plane, got "
+                         f"{getattr(depth, 'dtype', None)} {tuple(getattr(depth, 'shape', ()))}")
+    for name, idx, w, n in (("x", xmin, wx, W), ("y", ymin, wy, H)):
+        if idx.dtype != torch.int32 or idx.numel() != n or w.dtype != torch.float32 or w.ndim != 2 or w.shape[0] != n \
+                or not idx.is_contiguous() or not w.is_contiguous():
+            raise ValueError(f"mask_ingest: the {name} tables must be contiguous int32 [{n}] and fp32 [{n}, taps]")
+    flags = (kinds[src.dtype] | MASK_COMBINE[combine] | (MASK_INVERT if invert else 0) | (MASK_RAMP_HARD if hard else 0)
+             | (MASK_RAMP_FAR if far else 0))
+    op = L2dOp()
+    op.kind = _lib.OP_MASK_INGEST
+    keep = (src, out, depth, xmin, wx, ymin, wy)
+    for j, t in enumerate(keep):
+        op.p[j] = _ptr(t)
+    for j, v in enumerate([Hm, Wm, H, W, nh, nw, top, left, wx.shape[1], wy.shape[1], flags]):
+        op.i[j] = int(v)
+    op.f[0], op.f[1] = float(lo32), float(inv32)
     return op, keep

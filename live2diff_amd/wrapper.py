@@ -315,6 +315,10 @@ class StreamAnimateDiffusionDepthWrapper:
     _backdrop_image = None                  # the image of an "image" backdrop, as the caller gave it
     _backdrop_dev = None                    # backdrop.HipBackdrop, made by the first frame that needs it on the device
     _backdrop_host = None                   # {(height, width, filter): uint8 frame} of the image on the host route
+    _mask_input = None                      # how a mask is read (set_mask_input), None: mask_io.DEFAULTS
+    _mask_tap = None                        # mask_io.HipMaskIngest (HostMaskTap on CPU tensors), made by the first mask
+    _mask_sticky = None                     # the sticky mask (set_mask), as the caller gave it (an array or a tensor of its own)
+    _mask_shared = None                     # ... staged for the delay line: one buffer that every frame without a mask names
     depth_source = "detector"               # "input": every frame brings its own depth and no detector was built (`_setup` sets it)
 
     def __init__(self, config_path: str, few_step_model_type: str, num_inference_steps: int,
@@ -330,7 +334,7 @@ class StreamAnimateDiffusionDepthWrapper:
                  output_resample: str = "lanczos", matte_source: str = "stream", steady: Optional[dict] = None,
                  matte_edge: Optional[dict] = None, detail: Optional[dict] = None, depth_input: Optional[dict] = None,
                  depth_source: str = "detector", backdrop: Optional[dict] = None, steady_follow: Optional[dict] = None,
-                 matte_hold: Optional[dict] = None):
+                 matte_hold: Optional[dict] = None, mask_input: Optional[dict] = None):
         _check_depth_source(depth_source)
         self._check_keywords(few_step_model_type=few_step_model_type, acceleration=acceleration, cfg_type=cfg_type,
                              use_denoising_batch=use_denoising_batch, frame_buffer_size=frame_buffer_size, device_ids=device_ids,
@@ -352,13 +356,13 @@ class StreamAnimateDiffusionDepthWrapper:
                     similar_image_filter_max_skip_frame=similar_image_filter_max_skip_frame, jpeg_quality=jpeg_quality,
                     jpeg_decode=jpeg_decode, output_size=output_size, output_resample=output_resample, matte_source=matte_source,
                     steady=steady, matte_edge=matte_edge, detail=detail, depth_input=depth_input, depth_source=depth_source,
-                    backdrop=backdrop, steady_follow=steady_follow, matte_hold=matte_hold)
+                    backdrop=backdrop, steady_follow=steady_follow, matte_hold=matte_hold, mask_input=mask_input)
 
     @classmethod
     def from_components(cls, pipe, *, num_inference_steps: int, t_index_list: Optional[List[int]] = None,
                         strength: Optional[float] = None, **kw):
         """The wrapper around an already assembled `pipe` namespace (tests, synthetic weights).  Keywords: those of the
-        constructor that do not name files (`jpeg_quality`, `jpeg_decode`, `output_size`, `output_resample`, `matte_source`, `steady`, `steady_follow`, `matte_edge`, `matte_hold`, `detail`, `backdrop`, `depth_input` and `depth_source` among them; with `depth_source="input"` the namespace needs no `depth_model`), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
+        constructor that do not name files (`jpeg_quality`, `jpeg_decode`, `output_size`, `output_resample`, `matte_source`, `steady`, `steady_follow`, `matte_edge`, `matte_hold`, `detail`, `backdrop`, `depth_input`, `mask_input` and `depth_source` among them; with `depth_source="input"` the namespace needs no `depth_model`), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
         self = cls.__new__(cls)
         cls._check_keywords(**{k: kw.pop(k) for k in ("acceleration", "cfg_type", "use_denoising_batch", "frame_buffer_size",
                                                       "device_ids", "opt_unet", "few_step_model_type") if k in kw},
@@ -399,8 +403,10 @@ class StreamAnimateDiffusionDepthWrapper:
                scheduler_kwargs=None, frame_pipelining=False, enable_similar_image_filter=False,
                similar_image_filter_threshold=0.98, similar_image_filter_max_skip_frame=10, jpeg_quality=75, jpeg_decode="device",
                output_size=None, output_resample="lanczos", matte_source="stream", steady=None, matte_edge=None, detail=None,
-               depth_input=None, depth_source="detector", backdrop=None, steady_follow=None, matte_hold=None):
+               depth_input=None, depth_source="detector", backdrop=None, steady_follow=None, matte_hold=None, mask_input=None):
         self._check_matte_source(matte_source)
+        if mask_input is not None and not isinstance(mask_input, dict):
+            raise ValueError(f"mask_input={mask_input!r}: use a dict of set_mask_input's keywords, or None")
         if matte_hold is not None and not isinstance(matte_hold, dict):
             raise ValueError(f"matte_hold={matte_hold!r}: use a dict of set_matte_hold's keywords, or None")
         if backdrop is not None and not isinstance(backdrop, dict):
@@ -468,6 +474,8 @@ class StreamAnimateDiffusionDepthWrapper:
             self.stream.depth_detector = None      # (a `pipe` that brought one: it is never called)
         if depth_input is not None:
             self.set_depth_input(**depth_input)
+        if mask_input is not None:
+            self.set_mask_input(**mask_input)
 
     # ------------------------------------------------------------------ depth from the caller (depth_io.py)
     @property
@@ -514,6 +522,87 @@ class StreamAnimateDiffusionDepthWrapper:
             return arr
         return depth
 
+    # ------------------------------------------------------------------ the matte from the caller (mask_io.py)
+    @property
+    def mask_input(self) -> dict:
+        """how a mask is read, as {combine, invert}"""
+        from .mask_io import DEFAULTS
+        return dict(self._mask_input or DEFAULTS)
+
+    def set_mask_input(self, combine: str = "replace", invert: bool = False) -> None:
+        """How the masks handed in with `mask=` (and the sticky mask of `set_mask`) cut the frame.  `combine="replace"`: the mask
+        alone is the raw matte, and the matte's `lo`, `hi` and `keep` are not read; "and": the smaller of the depth ramp and
+        the mask (the person, but only in front of the wall); "or": the larger.  `invert` flips the mask first.  Read when a
+        frame is composited: it applies from the next output on.  May be called before or after `set_matte` and `prepare` and
+        between any two frames."""
+        from .mask_io import check_settings
+        self._mask_input = check_settings(combine, invert)
+        self._hold_init = True             # (a held matte starts again from the new raw matte)
+
+    @property
+    def mask(self) -> bool:
+        """is a sticky mask set (`set_mask`)?"""
+        return self._mask_sticky is not None
+
+    def set_mask(self, mask) -> None:
+        """A sticky mask: the mask of every frame that brings none of its own -- a fixed region ("only the window").  What
+        `img2img`'s `mask=` takes; needs a matte (`set_matte`), and is kept as a copy of the caller's.  It joins each frame as
+        the frame enters, so it reaches the output with that frame, N - 1 frames on."""
+        from . import mask_io
+        if self._matte is None:
+            raise ValueError("set_mask: a mask needs a matte: call set_matte first (its feather, show and keep act on the mask)")
+        m = mask_io.load(mask, "set_mask")
+        m = mask_io._torch_mask(m).clone() if torch.is_tensor(m) and m.is_cuda else mask_io._as_mask(m).copy()
+        mask_io.tables(m.shape[0], m.shape[1], self.height, self.width)
+        self._mask_sticky, self._mask_shared = m, None
+
+    def clear_mask(self) -> None:
+        """No sticky mask: a frame that brings no mask is cut by the depth ramp alone again (frames already in the stream keep
+        the mask they entered with)."""
+        self._mask_sticky = self._mask_shared = None
+
+    def _mask_begin(self, mask, where: str = "mask") -> None:
+        """In front of every frame, beside `_camera_begin`: a raw mask nobody claimed belongs to no later frame; the frame's own
+        mask, or the sticky one, is copied into a pooled device buffer on the caller's stream and offered to the delay line,
+        whose tap moves it into the frame's slot."""
+        tap = self._mask_tap
+        if tap is not None:
+            tap.begin()
+        if mask is not None and self._matte is None:
+            raise ValueError(f"{where}: a mask needs a matte: call set_matte first (its feather, show and keep act on the mask)")
+        sticky = mask is None
+        if sticky:
+            mask = self._mask_sticky
+        if mask is None or self._matte is None:
+            return
+        from . import mask_io
+        if tap is None:
+            tap = (mask_io.HipMaskIngest(self.height, self.width, device=self.io.device) if self.io is not None
+                   else mask_io.HostMaskTap(self.height, self.width))
+            self._mask_tap = self._matte_line.mask_source = tap
+        if not sticky:
+            tap.offer(mask_io.load(mask, where))
+        elif isinstance(tap, mask_io.HostMaskTap):
+            tap.pending = self._mask_sticky
+        else:
+            if self._mask_shared is None:
+                self._mask_shared = tap.stage(self._mask_sticky, shared=True)
+            tap.offer(self._mask_shared)
+
+    def _mask_front(self, slot):
+        """`(record, keep, plane)` of L2D_OP_MASK_INGEST for the slot's mask under the settings of this moment, or None"""
+        if slot is None or getattr(slot, "mask", None) is None or self._mask_tap is None:
+            return None
+        op, keep = self._mask_tap.record(slot.mask, slot.depth, self._matte, self.mask_input)
+        return op, keep, self._mask_tap.plane
+
+    def _mask_plane(self, slot) -> Optional[np.ndarray]:
+        """the raw matte of the slot's mask on the host route, fp32 [H,W]: `mask_io.raw_ref` where op 58 would run; or None"""
+        if slot is None or getattr(slot, "mask", None) is None:
+            return None
+        from .mask_io import raw_ref
+        return raw_ref(slot.mask, slot.depth[None], self._matte, self.mask_input, self.height, self.width)
+
     # ------------------------------------------------------------------ depth matte (matte.py, DESIGN.md section 8.z4)
     @property
     def matte(self) -> Optional[dict]:
@@ -546,6 +635,10 @@ class StreamAnimateDiffusionDepthWrapper:
         self._matte = self._matte_dev = self._matte_up = None
         self._hold_dev = self._hold_state = None
         self._hold_init = True
+        self._mask_tap = self._mask_sticky = self._mask_shared = None      # (a mask needs a matte: none outlives it)
+        if self._matte_line is not None:
+            self._matte_line.mask_source = None
+            self._matte_line.drop_masks()
         self._release_line()
         self._sync_camera()
 
@@ -659,14 +752,18 @@ class StreamAnimateDiffusionDepthWrapper:
         self._hold_init = False
         return step
 
-    def _held_plane(self, slot, repeated: bool) -> np.ndarray:
-        """the held matte of this frame on the host route, fp32 [1,H,W]: `hold_ref` where op 57 would run"""
-        from .matte import hold_ref, matte_ref
+    def _held_plane(self, slot, repeated: bool, raw: Optional[np.ndarray] = None) -> np.ndarray:
+        """the held matte of this frame on the host route, fp32 [1,H,W]: `hold_ref` where op 57 would run.  `raw`: the raw matte
+        of the slot's mask in place of the ramp (`_mask_plane`)."""
+        from .matte import edge_ref, hold_ref, matte_ref
         if repeated and not self._hold_init and self._hold_state is not None:
             return self._hold_state[0][None]
         mt = self._matte
-        m0 = matte_ref(slot.depth[None], mt["lo"], mt["hi"], 0, mt["keep"], edge=self._matte_edge,
-                       source=slot.source[None] if self._matte_edge is not None else None)[0]
+        if raw is not None:
+            m0 = raw if self._matte_edge is None else edge_ref(raw, slot.source, **self._matte_edge)
+        else:
+            m0 = matte_ref(slot.depth[None], mt["lo"], mt["hi"], 0, mt["keep"], edge=self._matte_edge,
+                           source=slot.source[None] if self._matte_edge is not None else None)[0]
         init = self._hold_init or self._hold_state is None
         h, self._hold_state, _ = hold_ref(m0, slot.source, self._hold_state, **self._hold, init=init)
         self._hold_init = False
@@ -796,6 +893,7 @@ class StreamAnimateDiffusionDepthWrapper:
             from .matte import MatteLine
             self._matte_line = MatteLine(self.batch_size, self.height, self.width, device=self.stream.device)
             self.stream.matte_tap = self._matte_line
+            self._matte_line.mask_source = self._mask_tap
             self._matte_skip = len(getattr(self.stream, "_pending", None) or ())
 
     def _release_line(self) -> None:
@@ -1198,10 +1296,13 @@ class StreamAnimateDiffusionDepthWrapper:
 
     # ------------------------------------------------------------------ prepare
     def prepare(self, warmup_frames, prompt: str, negative_prompt: str = "", guidance_scale: float = 1.2, delta: float = 1.0,
-                warmup_depths=None) -> torch.Tensor:
+                warmup_depths=None, warmup_masks=None) -> torch.Tensor:
         """warmup_frames: float [F,3,H,W] in [0, 1] as in the reference, uint8 [F,Hs,Ws,3] (one batched ingest launch), or a list
         of JPEG files of one size (decoded like `img2img`'s, then the uint8 route).  warmup_depths: the frames' own depth, a batch
         [F,Hd,Wd] (or a list of what `img2img` takes as `depth`, of one size), normalised jointly; None: the detector.
+        warmup_masks: one mask per warm-up frame, a batch [F,Hm,Wm] or a list of what `img2img` takes as `mask`; the last one
+        cuts the N - 1 primed positions of the delay line; None: those positions have no mask of their own (a sticky mask
+        applies to them as to any frame).  Needs a matte.
         Returns the generated warm-up frames, [F,H,W,3] in [0, 1] (wrapper.py:197-199)."""
         kw = dict(prompt=prompt, negative_prompt=negative_prompt, guidance_scale=guidance_scale, delta=delta, seed=self.seed)
         if isinstance(warmup_depths, (list, tuple)):
@@ -1210,6 +1311,15 @@ class StreamAnimateDiffusionDepthWrapper:
         warmup_depths = self._depth_arg(warmup_depths, "warmup_depths")
         if warmup_depths is not None:
             kw["warmup_depths"] = warmup_depths
+        last_mask = None
+        if warmup_masks is not None:
+            if self._matte is None:
+                raise ValueError("warmup_masks: a mask needs a matte: call set_matte first")
+            n_frames = len(warmup_frames) if hasattr(warmup_frames, "__len__") else None
+            if not hasattr(warmup_masks, "__len__") or len(warmup_masks) == 0 or (n_frames is not None and len(warmup_masks) != n_frames):
+                raise ValueError(f"warmup_masks: expected one mask per warm-up frame ({n_frames}), a batch [F,Hm,Wm] or a list")
+            last_mask = warmup_masks[-1]
+        self._mask_begin(last_mask, "warmup_masks")        # (claimed by the line's `prime`; with N = 1 by nobody)
         self._prompt = prompt
         self._matte_skip = 0               # (`stream.prepare` primes the matte's delay line through the tap, when one is set)
         self._lock_init, self._lock_last = True, None      # an "ema" colour lock starts again; a reference image's state stays
@@ -1247,22 +1357,27 @@ class StreamAnimateDiffusionDepthWrapper:
         return (frames.clip(-1, 1) + 1) / 2
 
     # ------------------------------------------------------------------ frames
-    def __call__(self, image=None, prompt: Optional[str] = None, depth=None):
-        return self.img2img(image, prompt, depth)
+    def __call__(self, image=None, prompt: Optional[str] = None, depth=None, mask=None):
+        return self.img2img(image, prompt, depth, mask)
 
-    def img2img(self, image, prompt: Optional[str] = None, depth=None):
+    def img2img(self, image, prompt: Optional[str] = None, depth=None, mask=None):
         """image: a path, a PIL image (resized to (width, height) on the host like the reference, :264-267), a uint8 HWC array /
         tensor of any size (resize + centre crop on the device), a JPEG file as `bytes` / `bytearray` / `memoryview` (decoded on the
         device, then treated as that uint8 frame; a damaged scan raises ValueError where the output is fetched), or a float
         [3,H,W] tensor in [0, 1] (the reference's input).  depth: the frame's own depth frame in place of the detector's -- a uint16
         or float32 [Hd,Wd] array or tensor of any size, on the host or on the device, a PIL image of mode "I;16", "I", "F" or "L",
         or a path to one -- read as `set_depth_input` says; frames with and without it may alternate (not under
-        `depth_source="input"`, where a frame without raises ValueError).  A frame the near-duplicate filter drops ignores it."""
+        `depth_source="input"`, where a frame without raises ValueError).  A frame the near-duplicate filter drops ignores it.
+        mask: the frame's own matte in place of (or combined with, `set_mask_input`) the depth ramp -- a uint8, uint16, bool or
+        float32 [Hm,Wm] array or tensor of any size, on the host or on the device, a PIL image of mode "L", "1", "I;16" or "F",
+        or a path to one --, covering the camera frame's field of view; it needs a matte, is delayed with its frame and cuts
+        that frame's output N - 1 frames on.  Frames with and without one may alternate; a dropped frame ignores it."""
         depth = self._depth_arg(depth)
         dk = {} if depth is None else {"depth": depth}
         if prompt is not None:
             self._update_prompt(prompt)
         self._camera_begin(image)
+        self._mask_begin(mask)
         line = self._matte_line
         if line is None and self._lock is None and self._size is None:
             return self.postprocess_image(self.stream(self.preprocess_image(image), **dk), output_type=self.output_type)
@@ -1277,13 +1392,15 @@ class StreamAnimateDiffusionDepthWrapper:
         fresh = line.tapped > seen
         return self._finish(out, line.take() if fresh else line.last, repeated=not fresh)
 
-    def push(self, image, prompt: Optional[str] = None, depth=None) -> None:
+    def push(self, image, prompt: Optional[str] = None, depth=None, mask=None) -> None:
         """pipelined mode (`frame_pipelining=True`): start a frame's encode / depth path; `pop()` returns the oldest frame's output.
-        `depth`: as `img2img`'s; its ingest runs on the side stream with the rest of the depth path."""
+        `depth`: as `img2img`'s; its ingest runs on the side stream with the rest of the depth path.  `mask`: as `img2img`'s; its
+        copy runs here, on the caller's stream, and its ingest with the composite in `pop`."""
         depth = self._depth_arg(depth)
         if prompt is not None:
             self._update_prompt(prompt)
         self._camera_begin(image)
+        self._mask_begin(mask)
         self.stream.push(self.preprocess_image(image), **({} if depth is None else {"depth": depth}))
         if self.io is not None and self.io.last_view is not None:
             # push() ran the ingest on this stream before ordering the side stream behind it; the side stream reads the slot
@@ -1382,20 +1499,25 @@ class StreamAnimateDiffusionDepthWrapper:
             if detail_slot is not None and size is not None:
                 give_detail = functools.partial(self._detail_op(size, dev).apply, slot=detail_slot, settings=self._detail)
             bd = self._backdrop if slot is not None and not self._matte["show"] else None
-            held = {}                       # (the keyword only with a hold: without one the calls are the parent's)
+            held = {}                       # (the keywords only with a hold or a mask: without them the calls are the parent's)
             if slot is not None and self._hold is not None:
                 held["hold"] = self._hold_step(dev, repeated)
+            front = self._mask_front(slot)
+            bdk = {}
+            if front is not None:
+                held["mask"] = front
+                bdk["plane"] = front[2]
             if camera:
                 stages.append(self._size_op(size, dev).resize)
                 if give_detail is not None:
                     stages.append(give_detail)
                 more = {} if bd is None else dict(backdrop=self._backdrop_op(dev).output(
-                    slot, self._matte, bd, size["height"], size["width"], self._backdrop_image, size["resample"]))
+                    slot, self._matte, bd, size["height"], size["width"], self._backdrop_image, size["resample"], **bdk))
                 stages.append(functools.partial(self._matte_up_op(size, dev).composite, slot=slot, settings=self._matte,
                                                 edge=self._matte_edge, **more, **held))
             elif slot is not None:
                 more = {} if bd is None else dict(backdrop=self._backdrop_op(dev).stream(
-                    slot, self._matte, bd, self._backdrop_image, self._backdrop_filter()))
+                    slot, self._matte, bd, self._backdrop_image, self._backdrop_filter(), **bdk))
                 stages.append(functools.partial(self._matte_op(dev).composite, slot=slot, settings=self._matte, edge=self._matte_edge,
                                                 **more, **held))
             if size is not None and not camera:
@@ -1419,12 +1541,16 @@ class StreamAnimateDiffusionDepthWrapper:
             if slot is not None:
                 from .matte import composite_ref
                 more = {}                   # (the keyword only with a backdrop: without one the call is the parent's)
+                raw = self._mask_plane(slot)
                 if self._backdrop is not None and not self._matte["show"]:
                     from .backdrop import stream_ref
                     more["backdrop"] = stream_ref(self._backdrop, self._backdrop_image_host(), slot.source, slot.depth, self._matte,
-                                                  self._backdrop_filter())[None]
+                                                  self._backdrop_filter(), **({} if raw is None else {"plane": raw}))[None]
                 if self._hold is not None:
-                    more["plane"] = self._held_plane(slot, repeated)
+                    more["plane"] = self._held_plane(slot, repeated, **({} if raw is None else {"raw": raw}))
+                elif raw is not None:
+                    from .matte import edge_ref
+                    more["plane"] = (raw if self._matte_edge is None else edge_ref(raw, slot.source, **self._matte_edge))[None]
                 u8 = composite_ref(image_tensor[:1], slot.source[None], slot.depth[None], **self._matte, edge=self._matte_edge, **more)[0]
             else:
                 from .frame_io import egress_ref

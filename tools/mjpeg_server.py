@@ -74,7 +74,15 @@ the current settings as JSON (`null`: off).
 the room blurred with the subject left out (PASSES boxes of radius R, defaults 6 and 3), a colour as six hex digits (for a
 chroma key further down), or an image file, cropped to the frame's aspect ratio.  It acts only while a matte is set.  `POST
 /backdrop` with the same text as its body changes it while the stream runs, an empty body (or `off`) clears it; `GET /backdrop`
-answers the current settings as JSON (`null`: off)."""
+answers the current settings as JSON (`null`: off).
+
+`--mask PATH` sets a sticky mask (`wrapper.set_mask`: an image of mode L, 1, I;16 or F, of any size, covering the camera frame's
+field of view): the matte of every frame, in place of the depth ramp or combined with it -- a fixed region, "only the window".
+It needs `--matte`, whose feather and `far` keep acting on it.  `POST /mask` with an image file as its body (decoded on the host)
+replaces it while the stream runs, an empty body or `off` clears it; `GET /mask` answers `{"size": [h, w]}` or `null`.
+`--mask-input COMBINE[,invert]` says how a mask meets the ramp (`wrapper.set_mask_input`: `replace`, `and` or `or`); `POST
+/mask-input` with the same text changes it, `GET /mask-input` answers the current settings as JSON.  A body either route
+refuses gets a 400 and is counted (`failed`)."""
 import argparse
 import json
 import os
@@ -417,6 +425,78 @@ class MatteHoldBox:
             self.failed += 1
 
 
+def parse_mask_input_arg(text: str):
+    """`COMBINE[,invert]` -> the keywords of `wrapper.set_mask_input`; ValueError otherwise"""
+    from live2diff_amd.mask_io import check_settings
+    parts = [t.strip() for t in text.strip().split(",")]
+    if not 1 <= len(parts) <= 2 or (len(parts) == 2 and parts[1] != "invert"):
+        raise ValueError(f"mask input {text!r}: use replace, and or or, optionally followed by ,invert")
+    return check_settings(parts[0], len(parts) == 2)
+
+
+def parse_mask_body(body: bytes):
+    """the body of `POST /mask`: an image file -> its array as `wrapper.set_mask` takes it; empty or `off` -> None; ValueError for
+    anything Pillow cannot decode or whose mode is no mask's"""
+    import io
+
+    from live2diff_amd.mask_io import _as_mask, load
+    if body.strip() in (b"", b"off"):
+        return None
+    from PIL import Image
+    try:
+        with Image.open(io.BytesIO(body)) as im:
+            im.load()
+            return _as_mask(load(im.copy(), "POST /mask"))
+    except (OSError, SyntaxError, EOFError) as e:          # (what Pillow raises on a body that is no image, or a damaged one)
+        raise ValueError(f"POST /mask: the body cannot be read as an image: {e}") from None
+
+
+class MaskBox:
+    """What `POST /mask` and `POST /mask-input` deliver: the newest requested sticky mask (an array, or None for `off` and for an
+    empty body) and the newest requested mask input (a dict of `set_mask_input` keywords), applied by the producer between two
+    frames.  `current` / `current_input` are what was last applied; `failed` counts bodies the routes refused with a 400 and
+    requests the wrapper refused."""
+    _NOTHING = object()
+
+    def __init__(self, current=None, current_input=None):
+        self._lock = threading.Lock()
+        self.current, self.current_input, self.failed = current, current_input, 0
+        self._want = self._want_input = self._NOTHING
+
+    def put(self, mask) -> None:
+        with self._lock:
+            self._want = mask
+
+    def put_input(self, settings) -> None:
+        with self._lock:
+            self._want_input = settings
+
+    def refused(self) -> None:
+        with self._lock:
+            self.failed += 1
+
+    def apply(self, wrapper) -> None:
+        """(producer thread, between frames)"""
+        with self._lock:
+            want, self._want = self._want, self._NOTHING
+            want_input, self._want_input = self._want_input, self._NOTHING
+        try:
+            if want_input is not self._NOTHING:
+                wrapper.set_mask_input(**want_input)
+                self.current_input = wrapper.mask_input
+        except ValueError:
+            self.refused()
+        try:
+            if want is None:
+                wrapper.clear_mask()
+                self.current = None
+            elif want is not self._NOTHING:
+                wrapper.set_mask(want)
+                self.current = dict(size=[int(want.shape[0]), int(want.shape[1])])
+        except ValueError:                         # (no matte, or a geometry the ingest refuses)
+            self.refused()
+
+
 def parse_matte_edge_arg(text: str):
     """`R[,EPS]` -> the keywords of `wrapper.set_matte_edge`, `off` -> None; ValueError otherwise"""
     from live2diff_amd.matte import MAX_EDGE_RADIUS, check_edge
@@ -696,7 +776,7 @@ class Latest:
 def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = None, mattes: "MatteBox" = None, colors: "ColorBox" = None,
                  sizes: "SizeBox" = None, sources: "MatteSourceBox" = None, steadies: "SteadyBox" = None, details: "DetailBox" = None,
                  backdrops: "BackdropBox" = None, follows: "SteadyFollowBox" = None, holds: "MatteHoldBox" = None,
-                 edges: "MatteEdgeBox" = None):
+                 masks: "MaskBox" = None, edges: "MatteEdgeBox" = None):
     boxes = {"/matte": mattes, "/color": colors, "/size": sizes, "/matte-source": sources, "/steady": steadies, "/matte-edge": edges,
              "/detail": details, "/backdrop": backdrops, "/steady-follow": follows, "/matte-hold": holds}
     page = PAGE if inbox is None else CAMERA_PAGE
@@ -737,8 +817,10 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
                 self.send_header("Content-Length", str(len(body)))
                 self.end_headers()
                 self.wfile.write(body)
-            elif boxes.get(self.path) is not None:
-                body = json.dumps(boxes[self.path].current).encode()
+            elif boxes.get(self.path) is not None or (masks is not None and self.path in ("/mask", "/mask-input")):
+                current = (boxes[self.path].current if self.path in boxes else
+                           masks.current if self.path == "/mask" else masks.current_input)
+                body = json.dumps(current).encode()
                 self.send_response(200)
                 self.send_header("Content-Type", "application/json")
                 self.send_header("Content-Length", str(len(body)))
@@ -768,6 +850,30 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
                 self.send_error(400, str(e.args[0] if e.args else e)[:200])
                 return
             box.put(want)
+            self.send_response(204)
+            self.end_headers()
+
+        def do_mask(self):
+            try:
+                n = int(self.headers.get("Content-Length", ""))
+            except ValueError:
+                self.send_error(411)
+                return
+            if not 0 <= n <= MAX_POST:
+                self.send_error(413 if n > MAX_POST else 400)
+                return
+            body = self.rfile.read(n) if n else b""
+            try:
+                if len(body) != n:
+                    raise ValueError("the body is shorter than its Content-Length")
+                if self.path == "/mask":
+                    masks.put(parse_mask_body(body))
+                else:
+                    masks.put_input(parse_mask_input_arg(body.decode()))
+            except ValueError as e:                       # (UnicodeDecodeError is a ValueError)
+                masks.refused()
+                self.send_error(400, str(e.args[0] if e.args else e)[:200])
+                return
             self.send_response(204)
             self.end_headers()
 
@@ -824,6 +930,9 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
             if self.path == "/backdrop" and backdrops is not None:
                 self.do_matte(backdrops, parse_backdrop_arg, empty=True)
                 return
+            if masks is not None and self.path in ("/mask", "/mask-input"):
+                self.do_mask()
+                return
             if inbox is None or self.path != "/frame":
                 self.send_error(404)
                 return
@@ -849,9 +958,10 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
 def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: StyleBox = None, mattes: MatteBox = None,
             colors: ColorBox = None, sizes: SizeBox = None, sources: MatteSourceBox = None, steadies: SteadyBox = None,
             details: DetailBox = None, backdrops: BackdropBox = None, follows: SteadyFollowBox = None,
-            holds: MatteHoldBox = None, edges: MatteEdgeBox = None) -> None:
+            holds: MatteHoldBox = None, masks: "MaskBox" = None, edges: MatteEdgeBox = None) -> None:
     """the producer: loops `frames` through the wrapper until `stop` is set; a posted style, matte, colour lock, output size,
-    matte source, steady mode, follow setting, matte edge, matte hold, detail mode or backdrop is applied between two frames"""
+    matte source, steady mode, follow setting, matte edge, matte hold, detail mode, backdrop, mask or mask input is applied between
+    two frames"""
     from live2diff_amd.jpeg import mjpeg_part
     try:
         i = 0
@@ -878,6 +988,8 @@ def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: Styl
                 details.apply(wrapper)
             if backdrops is not None:
                 backdrops.apply(wrapper)
+            if masks is not None:
+                masks.apply(wrapper)
             latest.put(mjpeg_part(wrapper(frames[i % len(frames)])))
             i += 1
     finally:
@@ -888,7 +1000,7 @@ def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: thr
                    mattes: MatteBox = None, colors: ColorBox = None, sizes: SizeBox = None, sources: MatteSourceBox = None,
                    steadies: SteadyBox = None, details: DetailBox = None, backdrops: BackdropBox = None,
                    follows: SteadyFollowBox = None, holds: "MatteHoldBox" = None,
-                   edges: MatteEdgeBox = None) -> None:
+                   masks: "MaskBox" = None, edges: MatteEdgeBox = None) -> None:
     """the producer of `--input post`: the first frames posted warm the stream up, then the newest posted frame goes through the
     wrapper, for ever; a frame the wrapper refuses (ValueError: a damaged file) is dropped and counted in `inbox.failed`"""
     from live2diff_amd.jpeg import mjpeg_part
@@ -923,6 +1035,8 @@ def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: thr
                 details.apply(wrapper)
             if backdrops is not None:
                 backdrops.apply(wrapper)
+            if masks is not None:
+                masks.apply(wrapper)
             try:
                 latest.put(mjpeg_part(wrapper(frame)))
             except ValueError:
@@ -984,7 +1098,17 @@ def main(argv=None):
                     help="what stands behind the matte in place of the real frame: the room blurred with the subject left out (PASSES "
                          "boxes of radius R, defaults 6 and 3), a colour as six hex digits, or an image file; acts while a matte is set; "
                          "POST /backdrop with the same text changes it between frames, an empty body (or `off`) clears it")
+    ap.add_argument("--mask", default=None, metavar="PATH",
+                    help="a sticky mask: an image (mode L, 1, I;16 or F, any size) that cuts every frame in place of the depth ramp, or "
+                         "combined with it (--mask-input); needs --matte; POST /mask with an image file as its body replaces it between "
+                         "frames, an empty body (or `off`) clears it")
+    ap.add_argument("--mask-input", default=None, metavar="COMBINE[,invert]",
+                    help="how a mask meets the depth ramp: replace (default), and, or; `invert` flips the mask first; POST /mask-input "
+                         "with the same text changes it between frames")
     args = ap.parse_args(argv)
+    if args.mask is not None and not args.matte:
+        ap.error("--mask needs --matte (its feather and `far` act on the mask)")
+    mask_input = parse_mask_input_arg(args.mask_input) if args.mask_input else None
     style_args = [parse_style_arg(t) for t in args.style]
     matte = parse_matte_arg(args.matte) if args.matte else None
     color = parse_color_arg(args.color_lock) if args.color_lock else None
@@ -1039,15 +1163,24 @@ def main(argv=None):
     if backdrop is not None:
         w.set_backdrop(**backdrop)
     backdrops = BackdropBox(w.backdrop)
+    if mask_input is not None:
+        w.set_mask_input(**mask_input)
+    mask_size = None
+    if args.mask is not None:
+        from live2diff_amd.mask_io import _as_mask, load
+        sticky = _as_mask(load(args.mask, "--mask"))
+        w.set_mask(sticky)                   # (before `prepare`: the primed positions of the delay line carry it)
+        mask_size = dict(size=[int(sticky.shape[0]), int(sticky.shape[1])])
+    masks = MaskBox(mask_size, w.mask_input)
     prompt = args.prompt if args.prompt is not None else str(cfg.get("prompt", ""))
     latest, stop = Latest(), threading.Event()
     inbox = Inbox(sink) if post else None
     if post:
-        producer = threading.Thread(target=produce_posted, args=(w, prompt, inbox, latest, stop, styles, mattes, colors, sizes, sources, steadies, details, backdrops, follows, holds, edges), name="producer", daemon=True)
+        producer = threading.Thread(target=produce_posted, args=(w, prompt, inbox, latest, stop, styles, mattes, colors, sizes, sources, steadies, details, backdrops, follows, holds, masks, edges), name="producer", daemon=True)
     else:
         w.prepare(frames[:sink], prompt)
-        producer = threading.Thread(target=produce, args=(w, frames, latest, stop, styles, mattes, colors, sizes, sources, steadies, details, backdrops, follows, holds, edges), name="producer", daemon=True)
-    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest, inbox, styles, mattes, colors, sizes, sources, steadies, details, backdrops, follows, holds, edges))
+        producer = threading.Thread(target=produce, args=(w, frames, latest, stop, styles, mattes, colors, sizes, sources, steadies, details, backdrops, follows, holds, masks, edges), name="producer", daemon=True)
+    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest, inbox, styles, mattes, colors, sizes, sources, steadies, details, backdrops, follows, holds, masks, edges))
     server.daemon_threads = True
     producer.start()
     print(f"http://{args.host}:{args.port}/  ({args.height}x{args.width}, quality {args.quality}; Ctrl-C stops)")

@@ -11,7 +11,14 @@ Frames of any size are resized + centre-cropped on the device (frame_io.HipFrame
 
 takes every frame's conditioning depth from a 16-bit PNG of the same file name (any size; 0 marks a hole) instead of the built-in
 detector, which is then not even built (`depth_source="input"`, depth_io.py); with an .npy input, `--depth` is an .npy stack
-[F,Hd,Wd] of uint16 or float32."""
+[F,Hd,Wd] of uint16 or float32.
+
+    ... --mask masks/ [--matte 0,1,2] [--mask-input and,invert]
+
+cuts every frame by its own mask -- an image of the same file name (any size; mode L, 1, I;16 or F), the output of a person
+segmenter or a keyer -- in place of the depth ramp, or combined with it (`mask=`, mask_io.py); with an .npy input, `--mask` is an
+.npy stack [F,Hm,Wm] of uint8, uint16, bool or float32.  A mask needs a matte: `--matte LO,HI[,FEATHER[,far]]` (default `0,1`)
+gives the ramp that `and` / `or` combine with, and the feather."""
 import argparse
 import os
 import sys
@@ -67,6 +74,40 @@ def read_depths(path: str, input_path: str) -> np.ndarray:
     return np.stack(frames)
 
 
+def read_masks(path: str, input_path: str) -> list:
+    """one mask per frame of `input_path`, matched by file name: uint8 / uint16 / float32 [Hm,Wm] arrays (an .npy stack: its rows)"""
+    from live2diff_amd.mask_io import _as_mask, load
+    if path.endswith(".npy"):
+        arr = np.load(path)
+        if arr.ndim != 3:
+            raise ValueError(f"{path}: expected [F,Hm,Wm], got {arr.shape}")
+        return [_as_mask(m) for m in arr]
+    if input_path.endswith(".npy"):
+        raise ValueError("--mask: an .npy input has no file names to match: give the masks as an .npy stack too")
+    by_stem = {os.path.splitext(n)[0]: n for n in os.listdir(path) if n.lower().endswith(EXTS + (".tif", ".tiff"))}
+    masks = []
+    for n in sorted(n for n in os.listdir(input_path) if n.lower().endswith(EXTS)):
+        stem = os.path.splitext(n)[0]
+        if stem not in by_stem:
+            raise FileNotFoundError(f"--mask: {path} has no image named {stem} for the frame {n}")
+        masks.append(_as_mask(load(os.path.join(path, by_stem[stem]), f"--mask: {by_stem[stem]}")))
+    return masks
+
+
+def parse_matte(text: str) -> dict:
+    """`LO,HI[,FEATHER[,far]]` -> the keywords of `wrapper.set_matte`"""
+    from live2diff_amd.matte import check_settings
+    parts = [t.strip() for t in text.split(",")]
+    if not 2 <= len(parts) <= 4 or (len(parts) == 4 and parts[3] != "far"):
+        raise ValueError(f"--matte {text!r}: use LO,HI[,FEATHER[,far]]")
+    try:
+        lo, hi, feather = float(parts[0]), float(parts[1]), int(parts[2]) if len(parts) > 2 else 0
+    except ValueError:
+        raise ValueError(f"--matte {text!r}: LO and HI are numbers in [0, 1], FEATHER an integer") from None
+    s = check_settings(lo, hi, keep="far" if len(parts) == 4 else "near", feather=feather)
+    return dict(lo=s["lo"], hi=s["hi"], keep=s["keep"], feather=s["feather"])
+
+
 def align(outputs, batch_size: int):
     """outputs of the calls -> outputs per input frame: drop the first batch_size - 1 (test.py:169-174)"""
     return outputs[batch_size - 1:]
@@ -87,6 +128,9 @@ def main(argv=None):
     ap.add_argument("--depth", default=None, help="folder of 16-bit PNGs named like the frames (or .npy [F,Hd,Wd]): depth from the caller")
     ap.add_argument("--depth-kind", default="distance", choices=("distance", "inverse"))
     ap.add_argument("--depth-range", default=None, help="A,B: a fixed (near, far) / (lo, hi) in the units of the samples; default: per frame")
+    ap.add_argument("--mask", default=None, help="folder of mask images named like the frames (or .npy [F,Hm,Wm]): the matte from the caller")
+    ap.add_argument("--mask-input", default="replace", help="COMBINE[,invert]: replace (default), and, or -- how a mask meets the depth ramp")
+    ap.add_argument("--matte", default=None, help="LO,HI[,FEATHER[,far]]: the depth matte (with --mask, default 0,1: the ramp `and` / `or` read)")
     args = ap.parse_args(argv)
 
     from PIL import Image
@@ -104,19 +148,34 @@ def main(argv=None):
             raise ValueError(f"--depth: {len(depths)} depth frames for {len(frames)} frames")
         rng = None if args.depth_range is None else tuple(float(v) for v in args.depth_range.split(","))
         more = dict(depth_source="input", depth_input=dict(kind=args.depth_kind, invalid=0, range=rng))
+    masks = None
+    if args.mask is not None:
+        from live2diff_amd.mask_io import check_settings as check_mask_input
+        masks = read_masks(args.mask, args.input)[args.skip:]
+        if len(masks) != len(frames):
+            raise ValueError(f"--mask: {len(masks)} masks for {len(frames)} frames")
+        parts = [t.strip() for t in args.mask_input.split(",")]
+        if len(parts) > 2 or (len(parts) == 2 and parts[1] != "invert"):
+            raise ValueError(f"--mask-input {args.mask_input!r}: use replace, and or or, optionally followed by ,invert")
+        more["mask_input"] = check_mask_input(parts[0], len(parts) == 2)
+    matte = parse_matte(args.matte if args.matte is not None else "0,1") if (args.matte is not None or masks is not None) else None
     w = StreamAnimateDiffusionDepthWrapper(args.config, few_step_model_type="lcm", num_inference_steps=cfg.get("num_inference_steps", 50),
                                            t_index_list=cfg.get("t_index_list"), strength=cfg.get("strength"), output_type="u8",
                                            height=args.height, width=args.width, use_tiny_vae=not args.full_vae, seed=args.seed,
                                            engine_dir=args.engine_dir, **more)
     prompt = args.prompt if args.prompt is not None else str(cfg.get("prompt", ""))
     os.makedirs(args.output, exist_ok=True)
-    warm = w.prepare(frames[:sink], prompt, warmup_depths=None if depths is None else depths[:sink])
+    if matte is not None:
+        w.set_matte(matte["lo"], matte["hi"], keep=matte["keep"], feather=matte["feather"])      # (before `prepare`: the line is primed)
+    warm = w.prepare(frames[:sink], prompt, warmup_depths=None if depths is None else depths[:sink],
+                     **({} if masks is None else {"warmup_masks": masks[:sink]}))
     for i, f in enumerate(warm):
         Image.fromarray((f.float().cpu().numpy() * 255).round().astype("uint8")).save(os.path.join(args.output, f"{i:05d}.png"))
     rest = frames[sink:]
     feed = list(rest) + [rest[-1]] * (w.batch_size - 1)                   # flush the frames still in the stream batch
     dfeed = [None] * len(feed) if depths is None else list(depths[sink:]) + [depths[-1]] * (w.batch_size - 1)
-    outs = align([w(f, depth=d) for f, d in zip(feed, dfeed)], w.batch_size)
+    mfeed = [None] * len(feed) if masks is None else list(masks[sink:]) + [masks[-1]] * (w.batch_size - 1)
+    outs = align([w(f, depth=d, **({} if m is None else {"mask": m})) for f, d, m in zip(feed, dfeed, mfeed)], w.batch_size)
     for i, o in enumerate(outs):
         Image.fromarray(o).save(os.path.join(args.output, f"{sink + i:05d}.png"))
     print(f"{len(warm)} warm-up + {len(outs)} frames -> {args.output}; inference_time_ema {w.stream.inference_time_ema * 1e3:.2f} ms "
