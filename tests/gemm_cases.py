@@ -40,8 +40,10 @@ Restatement (`restate`): plain torch, fp32: accumulation in BK-sized stages, S s
 bias, then row bias (the 128 x 128 staged tile that lies in one sample adds bias + rowbias first: `b += rbp[n]` in load_bias), then the
 activation, then the residual, the staged double rounding, and the row-bias source per row when a tile crosses a sample.
 
-Out of scope: the norm-folding prologues of rowgemm / wsgemm (pro != 0, LN fold: their error is the norm's), the
-GroupNorm-statistics epilogue (norm_cases.check_acc) and clip_linear.
+Elsewhere: the norm-folding prologues of rowgemm / wsgemm (pro != 0, the LayerNorm fold), their GEGLU and V^T forms, the rowchain
+stages and clip_linear are held to the same kind of bound in fused_cases.py (test_fused_envelope_cpu.py, test_gpu_fused_envelope.py),
+which widens this module's terms by the norm's own (`extra` of exact_and_bound); the GroupNorm-statistics epilogue has
+norm_cases.check_acc.
 """
 import math
 
@@ -293,11 +295,12 @@ def act64(x, epi):
     return x
 
 
-def exact_and_bound(case, y, A, *, epi=0, bias=True, rowbias=False, res=False, S=1, form=("igemm", "direct")):
+def exact_and_bound(case, y, A, *, epi=0, bias=True, rowbias=False, res=False, S=1, form=("igemm", "direct"), extra=None):
     """(exact result, bound, the single-rounding part of the bound) fp64 [M, NoutO], per the module docstring.  The third value is what
     the form's SINGLE roundings contribute -- the fp16 store(s) and the fp32 bias / row-bias / residual adds, each of which may use all of
     its term whatever the order of anything else: the CPU file's half-the-bound test applies to what is left beyond it, the
-    accumulation and activation terms, whose order a restatement cannot know."""
+    accumulation and activation terms, whose order a restatement cannot know.  extra (fused_cases.py): what a norm in front of the GEMM
+    adds to the error of the pre-activation value, [M, Nout]."""
     double_round, out_f32 = SWITCHES[form]
     M, Nout = case["M"], case["Nout"]
     b = case["bias"].double()[None].expand(M, Nout) if bias else torch.zeros(M, Nout, dtype=F64)
@@ -307,6 +310,8 @@ def exact_and_bound(case, y, A, *, epi=0, bias=True, rowbias=False, res=False, S
     pre = y + b + rb
     adds = (int(bias) + int(rowbias)) * E32 * (y.abs() + b.abs() + rb.abs())
     e0 = (case["taps"] * case["K"] + S + 2) * E32 * A + adds
+    if extra is not None:
+        e0 = e0 + extra
     if epi == 1:
         No = Nout // 2
         v, g, ev, eg = pre[:, :No], pre[:, No:], e0[:, :No], e0[:, No:]

@@ -19,8 +19,8 @@ one planted conv shape each, in every schedule / geometry / patch / K-group coun
 kernels are documented as bit-identical (wsgemm and rowgemm fragment packing, rowchain against its unfused launches) the existing
 torch.equal tests stay the check.
 
-Out of scope: the norm-folding prologues (pro != 0, LN fold: their error is the norm's), the GroupNorm-statistics
-epilogue (norm_cases.check_acc), clip_linear.
+Elsewhere: the norm-folding prologues (pro != 0, the LayerNorm fold) with their GEGLU and V^T forms, the rowchain stages and
+clip_linear have test_gpu_fused_envelope.py (fused_cases.py); the GroupNorm-statistics epilogue has norm_cases.check_acc.
 """
 import os
 import sys
