@@ -589,6 +589,30 @@ enum {
  *   pointer, a non-positive size, Hm Wm or H W >= 2^31, a window outside the resized image, a scale above 8, taps outside
  *   1..L2D_DEPTH_MAX_TAPS, unknown flags, two sample types or two combines at once, ramp flags without AND / OR, the ramp as
  *   L2D_OP_FRAME_MATTE refuses it, p1 overlapping p0 or p2.
+ *
+ * Matte key (matte_key.hip; no counterpart in the reference): the raw matte plane from a comparison of the frame's source, on
+ *   the bytes a viewer would see, against a key colour or a clean plate -- the third source of a matte beside the depth ramp and
+ *   L2D_OP_MASK_INGEST, and written exactly as that op writes its plane.  Exact integers, then individually rounded fp32
+ *   operations, no fma, so that numpy restates it bit for bit (live2diff_amd/matte_key.py key_ref, mask_io.front_ref).
+ * L2D_OP_MATTE_KEY  one launch:  p0 source half [3][H][W] p1 out float [H][W] p2 depth half [H][W] (read only with
+ *   L2D_MATTE_KEY_AND / _OR; may be null without) p3 plate uint8 [3][H][W], planar (read only with L2D_MATTE_KEY_PLATE; may be
+ *   null without; 8-byte aligned, the others 16) ; i0 H i1 W (W % 8 == 0, 3 H W < 2^31) i2 r (0..L2D_MATTE_KEY_MAX_R) i3 flags
+ *   (L2D_MATTE_KEY_*) i4 L = rint(256 luma) (0..256) i5 i6 i7 the key colour's bytes R G B (not read with PLATE) ; f0 lo2 f1 inv
+ *   of the key's ramp over the mean squared distance (lo2 = lo^2, inv = 1 / (hi^2 - lo^2), lo and hi in byte levels) f2 lo f3
+ *   inv of the depth ramp (as L2D_OP_FRAME_MATTE's f0 f1; read only with AND / OR).  b = the egress bytes of p0, k = the key;
+ *   dR, dG, dB = b - k; dy = (77 dR + 150 dG + 29 dB + 128) >> 8 (arithmetic shift); cb = dB - dy, cr = dR - dy; D = cb^2 + cr^2
+ *   + ((L dy^2 + 128) >> 8) <= 585,225 < 2^20; S = the sum of D over the (2 r + 1)^2 window, coordinates clamped to the image
+ *   (< 2^31); mean = float(S) / float((2 r + 1)^2); t = clamp((mean - lo2) inv, 0, 1) (HARD: mean >= lo2); m = t t (3 - 2 t); P
+ *   = rint(255 m), half to even; INVERT: P = 255 - P; mu = float(P) / 255; out = mu, or with AND min(m_r, mu), with OR max(m_r,
+ *   mu), m_r the matte as L2D_OP_FRAME_MATTE forms it of p2 in front of the feather (RAMP_HARD, RAMP_FAR).  One work-group per
+ *   16 x 64 tile for every r, 8 pixels per lane; D of the tile and its halo, then the row sums, go through 13,824 bytes of LDS
+ *   as 32-bit integers.  Every element of p1 is written by a plain store on every launch: nothing has to be zeroed, no atomics.
+ *   Refused: a null or misaligned pointer, W % 8 != 0, 3 H W >= 2^31, r, L or a key byte out of range, unknown flags, two
+ *   combines at once, ramp flags without AND / OR, lo2 or inv negative or not finite, inv == 0 without HARD or HARD with inv !=
+ *   0, the depth ramp as L2D_OP_FRAME_MATTE refuses it, p1 overlapping p0, p2 or p3.
+ * L2D_OP_FRAME_PLANAR_BYTES  one launch (the plate capture):  p0 source half [3][H][W] p1 out uint8 [3][H][W], planar (both
+ *   16-byte aligned) ; i0 H i1 W (W % 8 == 0, 3 H W < 2^31).  out = the egress bytes of p0 (L2D_OP_FRAME_EGRESS's byte), one
+ *   lane per 8 pixels, plain stores.  Refused: a null or misaligned pointer, W % 8 != 0, 3 H W >= 2^31, p1 overlapping p0.
  */
 enum {
     L2D_OP_IGEMM = 1,
@@ -649,6 +673,8 @@ enum {
     L2D_OP_FRAME_STEADY_FOLLOW = 56,
     L2D_OP_FRAME_MATTE_HOLD = 57,
     L2D_OP_MASK_INGEST = 58,
+    L2D_OP_MATTE_KEY = 59,
+    L2D_OP_FRAME_PLANAR_BYTES = 60,
 };
 
 /* flag bits of L2D_OP_FRAME_MATTE (i4) and L2D_OP_FRAME_MATTE_UP (i6); HARD and FAR also of L2D_OP_FRAME_MATTE_EDGE (i3) */
@@ -714,6 +740,16 @@ enum {
 #define L2D_MASK_OR 16 /* out = max(ramp, mask) */
 #define L2D_MASK_RAMP_HARD 64 /* L2D_MATTE_HARD of the depth ramp */
 #define L2D_MASK_RAMP_FAR 128 /* L2D_MATTE_FAR of the depth ramp */
+
+/* flag bits of L2D_OP_MATTE_KEY (i3), and its largest radius; its tile is L2D_OP_FRAME_MATTE_HOLD's */
+#define L2D_MATTE_KEY_PLATE 1 /* the key is the plate p3, not the colour i5 i6 i7 */
+#define L2D_MATTE_KEY_HARD 2 /* the key's ramp is a step */
+#define L2D_MATTE_KEY_INVERT 4 /* P = 255 - P */
+#define L2D_MATTE_KEY_AND 8 /* out = min(ramp, key) (neither AND nor OR: the key replaces the ramp) */
+#define L2D_MATTE_KEY_OR 16 /* out = max(ramp, key) */
+#define L2D_MATTE_KEY_RAMP_HARD 64 /* L2D_MATTE_HARD of the depth ramp */
+#define L2D_MATTE_KEY_RAMP_FAR 128 /* L2D_MATTE_FAR of the depth ramp */
+#define L2D_MATTE_KEY_MAX_R 4
 
 /* sizes of L2D_OP_FRAME_RESIZE */
 #define L2D_RESIZE_MAX_KS 13 /* taps per output: Lanczos (support 3) at a 2x down-scale, 2 * 6 + 1 */

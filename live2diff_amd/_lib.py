@@ -39,6 +39,8 @@ OP_FRAME_MOTION = 55
 OP_FRAME_STEADY_FOLLOW = 56
 OP_FRAME_MATTE_HOLD = 57
 OP_MASK_INGEST = 58
+OP_MATTE_KEY = 59
+OP_FRAME_PLANAR_BYTES = 60
 ABI_VERSION = 6
 
 

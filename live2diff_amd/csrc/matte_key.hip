@@ -1,0 +1,278 @@
+// Matte key: cut the frame by a colour or by a clean plate.  Every pixel of the frame's source is
+// compared, on the bytes a viewer would see, against a key colour (a green or blue screen) or against a picture of the empty room
+// taken by a camera that does not move; where it differs is the subject.  The launch writes the raw matte plane of the output
+// chain, fp32 [H][W] in [0, 1], exactly as L2D_OP_MASK_INGEST writes it, so everything behind the raw matte -- edge refit, hold,
+// feather, backdrop, both composites, `show` -- reads it under its plane flag.  The reference has no counterpart.
+//
+//   b = px_byte of the fp16 source (3 channels)      k = the key: three bytes of the record, or (PLATE) planar uint8 [3][H][W]
+//   dR, dG, dB = b - k                               integers in -255 .. 255
+//   dy = (77 dR + 150 dG + 29 dB + 128) >> 8         arithmetic shift; formed as px_luma(d + 255) - 255, which is the same integer
+//   cb = dB - dy, cr = dR - dy
+//   D = cb^2 + cr^2 + ((L dy^2 + 128) >> 8)          L = rint(256 luma) in 0 .. 256
+//   S = the sum of D over the (2 r + 1)^2 window, coordinates clamped to the image, r in 0 .. 4
+//   mean = float(S) / float((2 r + 1)^2)             one correctly rounded conversion, one correctly rounded division
+//   t = clamp((mean - lo2) inv, 0, 1)  (HARD: mean >= lo2), m = t t (3 - 2 t)            sd_weight of steady_px.h
+//   P = rint(255 m), half to even; INVERT: 255 - P;  mu = float(P) / 255
+//   out = mu (replace), min(m_r, mu) (AND), max(m_r, mu) (OR)                            m_r: px_ramp of the depth plane
+//
+// Bounds: |cb|, |cr| <= 510 and dy^2 <= 255^2, so D <= 2 * 510^2 + 255^2 = 585,225 < 2^20, and a window sum <= 81 D < 2^26 < 2^31:
+// 32-bit integers hold everything (the static_asserts below).  The integers are exact and every floating-point step is one fp32
+// operation with one rounding (the file is built with -ffp-contract=off, see the Makefile), so numpy restates the plane bit for
+// bit (live2diff_amd/matte_key.py key_ref, mask_io.front_ref).  L2D_OP_FRAME_MATTE_HOLD's tile form: one work-group per SD_TH x
+// SD_TW tile, 8 pixels per lane; D of the tile and of one 8-pixel group of halo on either side goes to LDS as 32-bit integers,
+// then the row sums, then the column sums in the owner's layout.  Every element of the plane is written by a plain store on every
+// launch: nothing is zeroed, there is no atomic.
+//
+// L2D_OP_FRAME_PLANAR_BYTES is the plate capture: the fp16 source -> its planar egress bytes, one lane per 8 pixels.
+#include "steady_px.h"                        // the tile's sizes, sd_weight; frame_px.h: px_byte, px_luma, px_pack8, px_ramp, the checks
+
+#define MK_MAX_R L2D_MATTE_KEY_MAX_R
+#define MK_PLATE L2D_MATTE_KEY_PLATE
+#define MK_HARD L2D_MATTE_KEY_HARD
+#define MK_INVERT L2D_MATTE_KEY_INVERT
+#define MK_AND L2D_MATTE_KEY_AND
+#define MK_OR L2D_MATTE_KEY_OR
+#define MK_RAMP_HARD L2D_MATTE_KEY_RAMP_HARD
+#define MK_RAMP_FAR L2D_MATTE_KEY_RAMP_FAR
+#define MK_DH (SD_TH + 2 * MK_MAX_R)          // the rows of D under one tile: 24
+#define MK_MAX_L 256
+#define MK_MAX_D (2 * 510 * 510 + ((MK_MAX_L * 255 * 255 + 128) >> 8))
+
+#define MK_LDS_BYTES (MK_DH * SD_DW * 4 + MK_DH * SD_TW * 4)
+static_assert(MK_LDS_BYTES == 13824, "DESIGN.md section 8.z17, l2d.h and tests/test_matte_key_resources.py state this size");
+static_assert(MK_MAX_R <= 8, "the halo is one 8-pixel group on either side");
+static_assert(MK_MAX_D == 585225 && MK_MAX_D < (1 << 20), "D stays below 2^20");
+static_assert((long long)MK_MAX_D * (2 * MK_MAX_R + 1) * (2 * MK_MAX_R + 1) < (1ll << 31), "a window sum of D fits 32 bits");
+
+struct mk_params {
+    sd_params th;                             // lo2, inv of the key's ramp; flags: SD_HARD; r
+    int L, kr, kg, kb;                        // the luma weight; the key colour (not read with PLATE)
+    int flags;                                // MK_INVERT | MK_AND | MK_OR
+    float rlo, rinv;                          // the depth ramp (read only with AND / OR)
+    int rflags;                               // L2D_MATTE_HARD | L2D_MATTE_FAR of the depth ramp
+};
+
+// D of one pixel: its bytes against the key's
+__device__ __forceinline__ unsigned mk_D(unsigned r, unsigned g, unsigned b, int kr, int kg, int kb, int L) {
+    const int dR = (int)r - kr, dG = (int)g - kg, dB = (int)b - kb;
+    // 77 + 150 + 29 = 256: the luma of the differences raised by 255 is dy + 255, and every argument is non-negative
+    const int dy = (int)px_luma((unsigned)(dR + 255), (unsigned)(dG + 255), (unsigned)(dB + 255)) - 255;
+    const int cb = dB - dy, cr = dR - dy;
+    return (unsigned)(cb * cb + cr * cr + ((L * dy * dy + 128) >> 8));
+}
+
+// D of the 8-pixel group at row yy (clamped by the caller), column gx (a multiple of 8, inside the image or one group beside it):
+// a group beside the image holds the edge pixel's value, which is what a clamped coordinate reads
+template <bool PLATE>
+__device__ __forceinline__ void mk_group(const h16 *__restrict__ source, const uint8_t *__restrict__ plate, int W, long long HW, int yy,
+                                         int gx, const mk_params &p, unsigned (&D)[8]) {
+    if (gx < 0 || gx >= W) {
+        const long long e0 = (long long)yy * W + (gx < 0 ? 0 : W - 1);
+        int kr = p.kr, kg = p.kg, kb = p.kb;
+        if constexpr (PLATE) {
+            kr = plate[e0];
+            kg = plate[HW + e0];
+            kb = plate[2 * HW + e0];
+        }
+        const unsigned d = mk_D(px_byte(source[e0]), px_byte(source[HW + e0]), px_byte(source[2 * HW + e0]), kr, kg, kb, p.L);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) D[e] = d;
+    } else {
+        const long long g0 = (long long)yy * W + gx;
+        const h16x8 R = l2d_ld8(source + g0), G = l2d_ld8(source + HW + g0), B = l2d_ld8(source + 2 * HW + g0);
+        uint2 k[3] = {make_uint2(0u, 0u), make_uint2(0u, 0u), make_uint2(0u, 0u)};
+        if constexpr (PLATE) {
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) k[ch] = *reinterpret_cast<const uint2 *>(plate + ch * HW + g0);
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            int kr = p.kr, kg = p.kg, kb = p.kb;
+            if constexpr (PLATE) {
+                const int sh = 8 * (e & 3);
+                kr = (int)(((e < 4 ? k[0].x : k[0].y) >> sh) & 255u);
+                kg = (int)(((e < 4 ? k[1].x : k[1].y) >> sh) & 255u);
+                kb = (int)(((e < 4 ? k[2].x : k[2].y) >> sh) & 255u);
+            }
+            D[e] = mk_D(px_byte(R[e]), px_byte(G[e]), px_byte(B[e]), kr, kg, kb, p.L);
+        }
+    }
+}
+
+// grid (tiles x, tiles y), SD_THREADS lanes.  Every index into the frame is formed of a row clamped to [0, H - 1] and a column
+// group inside [0, W - 8] (or the edge pixel): nothing outside the source, the plate and the depth plane is read.
+template <bool PLATE>
+__device__ __forceinline__ void mk_body(const h16 *__restrict__ source, float *__restrict__ out, const h16 *__restrict__ depth,
+                                        const uint8_t *__restrict__ plate, int H, int W, const mk_params &p) {
+    __shared__ __attribute__((aligned(16))) unsigned dd[MK_DH][SD_DW];            // D of the tile and its halo
+    __shared__ __attribute__((aligned(16))) unsigned hh[MK_DH][SD_TW];            // the row sums
+    static_assert(sizeof(dd) + sizeof(hh) == MK_LDS_BYTES, "the LDS size the file states");
+    const int tid = threadIdx.x;
+    const int x0 = blockIdx.x * SD_TW, y0 = blockIdx.y * SD_TH;
+    const int r = p.th.r, taps = 2 * r + 1, rows = SD_TH + 2 * r;
+    const long long HW = (long long)H * W;
+
+    for (int g = tid; g < rows * (SD_DW / 8); g += SD_THREADS) {
+        const int j = g / (SD_DW / 8), cg = g % (SD_DW / 8);
+        if (r == 0 && (cg == 0 || cg == SD_DW / 8 - 1)) continue;                 // no tap reaches the side halo
+        const int yy = px_clampi(y0 - r + j, 0, H - 1);
+        unsigned D[8];
+        mk_group<PLATE>(source, plate, W, HW, yy, x0 - 8 + cg * 8, p, D);
+        uint4 *d4 = reinterpret_cast<uint4 *>(&dd[j][cg * 8]);
+        d4[0] = make_uint4(D[0], D[1], D[2], D[3]);
+        d4[1] = make_uint4(D[4], D[5], D[6], D[7]);
+    }
+    __syncthreads();
+
+    // rows: hh[j][c] = dd[j][8 + c - r] + ... + dd[j][8 + c + r]
+    for (int i = tid; i < rows * SD_TW; i += SD_THREADS) {
+        const int j = i / SD_TW, cc = i % SD_TW;
+        const unsigned *s = &dd[j][8 + cc - r];
+        unsigned acc = 0u;
+        for (int k = 0; k < taps; ++k) acc += s[k];
+        hh[j][cc] = acc;
+    }
+    __syncthreads();
+
+    const int by = tid >> 3, bx = (tid & 7) * 8;
+    const int y = y0 + by, x = x0 + bx;
+    if (y >= H || x >= W) return;                // (x + 8 <= W otherwise: W % 8 == 0)
+    // columns: S[e] = hh[by][bx + e] + ... + hh[by + 2 r][bx + e]
+    unsigned S[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    for (int k = 0; k < taps; ++k) {
+        const uint4 a = *reinterpret_cast<const uint4 *>(&hh[by + k][bx]);
+        const uint4 b = *reinterpret_cast<const uint4 *>(&hh[by + k][bx + 4]);
+        S[0] += a.x; S[1] += a.y; S[2] += a.z; S[3] += a.w;
+        S[4] += b.x; S[5] += b.y; S[6] += b.z; S[7] += b.w;
+    }
+    const float n = (float)(taps * taps);
+    const long long px = (long long)y * W + x;
+    float m[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        float P = rintf(__fmul_rn(255.0f, sd_weight(__fdiv_rn((float)S[e], n), p.th)));
+        if (p.flags & MK_INVERT) P = __fsub_rn(255.0f, P);
+        m[e] = __fdiv_rn(P, 255.0f);
+    }
+    if (p.flags & (MK_AND | MK_OR)) {
+        const h16x8 dv = l2d_ld8(depth + px);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float mr = px_ramp(dv[e], p.rlo, p.rinv, p.rflags);
+            m[e] = (p.flags & MK_AND) ? fminf(mr, m[e]) : fmaxf(mr, m[e]);
+        }
+    }
+    f32x4 *op = reinterpret_cast<f32x4 *>(out + px);
+    op[0] = f32x4{m[0], m[1], m[2], m[3]};
+    op[1] = f32x4{m[4], m[5], m[6], m[7]};
+}
+
+__global__ __launch_bounds__(SD_THREADS) void matte_key_color_kernel(const h16 *__restrict__ source, float *__restrict__ out,
+                                                                     const h16 *__restrict__ depth, int H, int W, mk_params p) {
+    mk_body<false>(source, out, depth, nullptr, H, W, p);
+}
+
+__global__ __launch_bounds__(SD_THREADS) void matte_key_plate_kernel(const h16 *__restrict__ source, float *__restrict__ out,
+                                                                     const h16 *__restrict__ depth, const uint8_t *__restrict__ plate,
+                                                                     int H, int W, mk_params p) {
+    mk_body<true>(source, out, depth, plate, H, W, p);
+}
+
+// one lane per 8 consecutive elements of the [3][H][W] frame: n8 = 3 H W / 8 groups
+__global__ __launch_bounds__(256) void frame_planar_bytes_kernel(const h16 *__restrict__ source, uint8_t *__restrict__ out, int n8) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= n8) return;
+    const h16x8 v = l2d_ld8(source + 8ll * g);
+    unsigned b[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) b[e] = px_byte(v[e]);
+    *reinterpret_cast<uint2 *>(out + 8ll * g) = px_pack8(b);
+}
+
+int l2d_launch_matte_key(const l2d_op *op, hipStream_t s) {
+    const int H = op->i[0], W = op->i[1], r = op->i[2], flags = op->i[3], L = op->i[4];
+    if (flags & ~(MK_PLATE | MK_HARD | MK_INVERT | MK_AND | MK_OR | MK_RAMP_HARD | MK_RAMP_FAR)) {
+        l2d_set_error("matte_key(tag %d): unknown flag bits 0x%x (1 plate, 2 hard, 4 invert, 8 and, 16 or, 64 hard ramp, 128 far)", op->tag,
+                      flags);
+        return L2D_EINVAL;
+    }
+    if ((flags & MK_AND) && (flags & MK_OR)) {
+        l2d_set_error("matte_key(tag %d): flags 0x%x name two ways to combine", op->tag, flags);
+        return L2D_EINVAL;
+    }
+    const bool ramp = (flags & (MK_AND | MK_OR)) != 0, plate = (flags & MK_PLATE) != 0;
+    if (!ramp && (flags & (MK_RAMP_HARD | MK_RAMP_FAR))) {
+        l2d_set_error("matte_key(tag %d): ramp flags without L2D_MATTE_KEY_AND / _OR (a replacing key reads no depth)", op->tag);
+        return L2D_EINVAL;
+    }
+    if (!px_check_pointers16("matte_key", op, 2)) return L2D_EINVAL;
+    if (ramp && (!op->p[2] || (((uintptr_t)op->p[2]) & 15))) {
+        l2d_set_error("matte_key(tag %d): pointer 2 (the depth plane of AND / OR) is null or not 16-byte aligned", op->tag);
+        return L2D_EINVAL;
+    }
+    if (plate && (!op->p[3] || (((uintptr_t)op->p[3]) & 7))) {
+        l2d_set_error("matte_key(tag %d): pointer 3 (the plate) is null or not 8-byte aligned", op->tag);
+        return L2D_EINVAL;
+    }
+    const long long HW = px_check_frame("matte_key", op->tag, H, W);
+    if (HW < 0) return L2D_EINVAL;
+    if (r < 0 || r > MK_MAX_R) {
+        l2d_set_error("matte_key(tag %d): radius %d, need 0..%d", op->tag, r, MK_MAX_R);
+        return L2D_EINVAL;
+    }
+    if (L < 0 || L > MK_MAX_L) {
+        l2d_set_error("matte_key(tag %d): luma weight L = %d, need 0..%d", op->tag, L, MK_MAX_L);
+        return L2D_EINVAL;
+    }
+    if (!plate) {
+        for (int k = 5; k < 8; ++k) {
+            if (op->i[k] < 0 || op->i[k] > 255) {
+                l2d_set_error("matte_key(tag %d): key colour (%d, %d, %d): need bytes", op->tag, op->i[5], op->i[6], op->i[7]);
+                return L2D_EINVAL;
+            }
+        }
+    }
+    const float lo2 = op->f[0], inv = op->f[1], rlo = op->f[2], rinv = op->f[3];
+    if (!(lo2 >= 0.0f && lo2 <= 3.0e38f) || !(inv >= 0.0f && inv <= 3.0e38f) || ((flags & MK_HARD) != 0) != (inv == 0.0f)) {
+        l2d_set_error("matte_key(tag %d): lo2 = %g and inv = %g must be finite and not negative, inv 0 exactly when the hard flag is set",
+                      op->tag, lo2, inv);
+        return L2D_EINVAL;
+    }
+    if (ramp && !px_check_ramp("matte_key", op->tag, rlo, rinv, (flags & MK_RAMP_HARD) != 0)) return L2D_EINVAL;
+    if (px_overlap(op->p[1], 4 * HW, op->p[0], 6 * HW) || (ramp && px_overlap(op->p[1], 4 * HW, op->p[2], 2 * HW))
+        || (plate && px_overlap(op->p[1], 4 * HW, op->p[3], 3 * HW))) {
+        l2d_set_error("matte_key(tag %d): the plane overlaps the source, the depth plane or the plate", op->tag);
+        return L2D_EINVAL;
+    }
+    L2D_DRY_RETURN();
+    mk_params p;
+    p.th.lo = lo2; p.th.inv = inv; p.th.s = 0.0f; p.th.flags = (flags & MK_HARD) ? SD_HARD : 0; p.th.r = r;
+    p.L = L; p.kr = op->i[5]; p.kg = op->i[6]; p.kb = op->i[7];
+    p.flags = flags & (MK_INVERT | MK_AND | MK_OR);
+    p.rlo = rlo; p.rinv = rinv;
+    p.rflags = ((flags & MK_RAMP_HARD) ? L2D_MATTE_HARD : 0) | ((flags & MK_RAMP_FAR) ? L2D_MATTE_FAR : 0);
+    const dim3 tiles((W + SD_TW - 1) / SD_TW, (H + SD_TH - 1) / SD_TH), threads(SD_THREADS);
+    if (plate)
+        hipLaunchKernelGGL(matte_key_plate_kernel, tiles, threads, 0, s, (const h16 *)op->p[0], (float *)op->p[1], (const h16 *)op->p[2],
+                           (const uint8_t *)op->p[3], H, W, p);
+    else
+        hipLaunchKernelGGL(matte_key_color_kernel, tiles, threads, 0, s, (const h16 *)op->p[0], (float *)op->p[1], (const h16 *)op->p[2], H,
+                           W, p);
+    return l2d_check_launch("matte_key", op->tag);
+}
+
+int l2d_launch_frame_planar_bytes(const l2d_op *op, hipStream_t s) {
+    const int H = op->i[0], W = op->i[1];
+    if (!px_check_pointers16("frame_planar_bytes", op, 2)) return L2D_EINVAL;
+    const long long HW = px_check_frame("frame_planar_bytes", op->tag, H, W);
+    if (HW < 0) return L2D_EINVAL;
+    if (px_overlap(op->p[1], 3 * HW, op->p[0], 6 * HW)) {
+        l2d_set_error("frame_planar_bytes(tag %d): the bytes overlap the frame", op->tag);
+        return L2D_EINVAL;
+    }
+    L2D_DRY_RETURN();
+    const int n8 = (int)(3 * HW / 8);
+    hipLaunchKernelGGL(frame_planar_bytes_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, (const h16 *)op->p[0],
+                       (uint8_t *)op->p[1], n8);
+    return l2d_check_launch("frame_planar_bytes", op->tag);
+}

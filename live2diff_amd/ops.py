@@ -1992,3 +1992,78 @@ def mask_ingest(src, out, depth, xmin, wx, ymin, wy, *, Hm, Wm, H, W, nh, nw, to
         op.i[j] = int(v)
     op.f[0], op.f[1] = float(lo32), float(inv32)
     return op, keep
+
+
+# ----------------------------------------------------------------------------- the matte key (matte_key.hip, matte_key.py)
+MATTE_KEY_PLATE, MATTE_KEY_HARD, MATTE_KEY_INVERT, MATTE_KEY_AND, MATTE_KEY_OR, MATTE_KEY_RAMP_HARD, MATTE_KEY_RAMP_FAR = \
+    1, 2, 4, 8, 16, 64, 128                                                                              # l2d.h L2D_MATTE_KEY_*
+MATTE_KEY_MAX_R = 4
+MATTE_KEY_COMBINE = {"replace": 0, "and": MATTE_KEY_AND, "or": MATTE_KEY_OR}
+
+
+def matte_key(source, out, depth, key, *, H, W, r, L, lo2, inv, hard, combine="replace", invert=False, lo32=0.0, inv32=0.0,
+              ramp_hard=False, far=False):
+    """fp16 [3,H,W] `source` -> fp32 [H,W] `out`: the raw matte of a key (mask_io.front_ref of matte_key.key_ref).  `key`: three
+    bytes (a colour), or a planar uint8 [3,H,W] tensor (a plate); `r`: the window's radius; `L`: rint(256 luma); `lo2, inv,
+    hard`: `matte_key.key_params`; `combine`: "replace", or "and" / "or" with the ramp `lo32, inv32, ramp_hard`
+    (`matte.matte_params`) and `far` over the fp16 [H,W] `depth` plane, which "replace" does not read (it may be None)."""
+    if source.dtype != torch.float16 or source.numel() != 3 * H * W or tuple(source.shape[-3:]) != (3, H, W) or not source.is_contiguous():
+        raise ValueError(f"matte_key: source: expected a contiguous fp16 [3,{H},{W}] frame, got {source.dtype} {tuple(source.shape)}")
+    if out.dtype != torch.float32 or out.numel() != H * W or not out.is_contiguous():
+        raise ValueError(f"matte_key: out: expected a contiguous float32 [{H},{W}] plane, got {out.dtype} {tuple(out.shape)}")
+    if W % 8:
+        raise ValueError(f"matte_key: W = {W} must be a multiple of 8")
+    if combine not in MATTE_KEY_COMBINE:
+        raise ValueError(f"matte_key: combine={combine!r}: use 'replace', 'and' or 'or'")
+    if combine == "replace":
+        depth, lo32, inv32, ramp_hard, far = None, 0.0, 0.0, False, False
+    elif depth is None or depth.dtype != torch.float16 or depth.numel() != H * W or not depth.is_contiguous():
+        raise ValueError(f"matte_key: depth: expected a contiguous fp16 [{H},{W}] plane, got "
+                         f"{getattr(depth, 'dtype', None)} {tuple(getattr(depth, 'shape', ()))}")
+    if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 0 <= int(r) <= MATTE_KEY_MAX_R:
+        raise ValueError(f"matte_key: r={r!r}: use an integer from 0 to {MATTE_KEY_MAX_R}")
+    if isinstance(L, bool) or not isinstance(L, (int, np.integer)) or not 0 <= int(L) <= 256:
+        raise ValueError(f"matte_key: L={L!r}: use an integer from 0 to 256")
+    lo2, inv = float(lo2), float(inv)
+    if not (np.isfinite(lo2) and lo2 >= 0.0 and np.isfinite(inv) and inv >= 0.0) or bool(hard) != (inv == 0.0):
+        raise ValueError(f"matte_key: lo2={lo2!r} and inv={inv!r} must be finite and not negative, inv 0 exactly with hard={hard!r}")
+    plate, colour = None, (0, 0, 0)
+    if torch.is_tensor(key):
+        plate = key
+        if plate.dtype != torch.uint8 or tuple(plate.shape) != (3, H, W) or not plate.is_contiguous():
+            raise ValueError(f"matte_key: key: a plate is a contiguous planar uint8 [3,{H},{W}] tensor, got {plate.dtype} {tuple(plate.shape)}")
+    else:
+        try:
+            colour = tuple(int(c) for c in key)
+        except (TypeError, ValueError):
+            colour = ()
+        if len(colour) != 3 or any(isinstance(c, bool) or int(c) != c for c in key) or not all(0 <= c <= 255 for c in colour):
+            raise ValueError(f"matte_key: key={key!r}: use three bytes (r, g, b), or a plate tensor")
+    flags = ((MATTE_KEY_PLATE if plate is not None else 0) | (MATTE_KEY_HARD if hard else 0) | MATTE_KEY_COMBINE[combine]
+             | (MATTE_KEY_INVERT if invert else 0) | (MATTE_KEY_RAMP_HARD if ramp_hard else 0) | (MATTE_KEY_RAMP_FAR if far else 0))
+    op = L2dOp()
+    op.kind = _lib.OP_MATTE_KEY
+    keep = (source, out, depth, plate)
+    for j, t in enumerate(keep):
+        op.p[j] = _ptr(t)
+    for j, v in enumerate([H, W, r, flags, L, *colour]):
+        op.i[j] = int(v)
+    op.f[0], op.f[1], op.f[2], op.f[3] = lo2, inv, float(lo32), float(inv32)
+    return op, keep
+
+
+def frame_planar_bytes(source, out, *, H, W):
+    """fp16 [3,H,W] `source` -> planar uint8 [3,H,W] `out`: its egress bytes (steady.source_bytes) -- the plate capture"""
+    if source.dtype != torch.float16 or source.numel() != 3 * H * W or tuple(source.shape[-3:]) != (3, H, W) or not source.is_contiguous():
+        raise ValueError(f"frame_planar_bytes: source: expected a contiguous fp16 [3,{H},{W}] frame, got {source.dtype} {tuple(source.shape)}")
+    if out.dtype != torch.uint8 or tuple(out.shape) != (3, H, W) or not out.is_contiguous():
+        raise ValueError(f"frame_planar_bytes: out: expected a contiguous planar uint8 [3,{H},{W}] tensor, got {out.dtype} {tuple(out.shape)}")
+    if W % 8:
+        raise ValueError(f"frame_planar_bytes: W = {W} must be a multiple of 8")
+    op = L2dOp()
+    op.kind = _lib.OP_FRAME_PLANAR_BYTES
+    keep = (source, out)
+    for j, t in enumerate(keep):
+        op.p[j] = _ptr(t)
+    op.i[0], op.i[1] = int(H), int(W)
+    return op, keep

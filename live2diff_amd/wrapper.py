@@ -319,6 +319,10 @@ class StreamAnimateDiffusionDepthWrapper:
     _mask_tap = None                        # mask_io.HipMaskIngest (HostMaskTap on CPU tensors), made by the first mask
     _mask_sticky = None                     # the sticky mask (set_mask), as the caller gave it (an array or a tensor of its own)
     _mask_shared = None                     # ... staged for the delay line: one buffer that every frame without a mask names
+    _key = None                             # the matte key's settings (set_matte_key), None: off
+    _key_plate = None                       # the plate on the host, planar uint8 [3,H,W]: of an image, or captured on the host route
+    _key_capture = False                    # the next composited output's source frame becomes the plate
+    _key_dev = None                         # matte_key.HipMatteKey, made by the first keyed frame on the device
     depth_source = "detector"               # "input": every frame brings its own depth and no detector was built (`_setup` sets it)
 
     def __init__(self, config_path: str, few_step_model_type: str, num_inference_steps: int,
@@ -334,7 +338,7 @@ class StreamAnimateDiffusionDepthWrapper:
                  output_resample: str = "lanczos", matte_source: str = "stream", steady: Optional[dict] = None,
                  matte_edge: Optional[dict] = None, detail: Optional[dict] = None, depth_input: Optional[dict] = None,
                  depth_source: str = "detector", backdrop: Optional[dict] = None, steady_follow: Optional[dict] = None,
-                 matte_hold: Optional[dict] = None, mask_input: Optional[dict] = None):
+                 matte_hold: Optional[dict] = None, mask_input: Optional[dict] = None, matte_key: Optional[dict] = None):
         _check_depth_source(depth_source)
         self._check_keywords(few_step_model_type=few_step_model_type, acceleration=acceleration, cfg_type=cfg_type,
                              use_denoising_batch=use_denoising_batch, frame_buffer_size=frame_buffer_size, device_ids=device_ids,
@@ -356,13 +360,13 @@ class StreamAnimateDiffusionDepthWrapper:
                     similar_image_filter_max_skip_frame=similar_image_filter_max_skip_frame, jpeg_quality=jpeg_quality,
                     jpeg_decode=jpeg_decode, output_size=output_size, output_resample=output_resample, matte_source=matte_source,
                     steady=steady, matte_edge=matte_edge, detail=detail, depth_input=depth_input, depth_source=depth_source,
-                    backdrop=backdrop, steady_follow=steady_follow, matte_hold=matte_hold, mask_input=mask_input)
+                    backdrop=backdrop, steady_follow=steady_follow, matte_hold=matte_hold, mask_input=mask_input, matte_key=matte_key)
 
     @classmethod
     def from_components(cls, pipe, *, num_inference_steps: int, t_index_list: Optional[List[int]] = None,
                         strength: Optional[float] = None, **kw):
         """The wrapper around an already assembled `pipe` namespace (tests, synthetic weights).  Keywords: those of the
-        constructor that do not name files (`jpeg_quality`, `jpeg_decode`, `output_size`, `output_resample`, `matte_source`, `steady`, `steady_follow`, `matte_edge`, `matte_hold`, `detail`, `backdrop`, `depth_input`, `mask_input` and `depth_source` among them; with `depth_source="input"` the namespace needs no `depth_model`), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
+        constructor that do not name files (`jpeg_quality`, `jpeg_decode`, `output_size`, `output_resample`, `matte_source`, `steady`, `steady_follow`, `matte_edge`, `matte_hold`, `detail`, `backdrop`, `depth_input`, `mask_input`, `matte_key` and `depth_source` among them; with `depth_source="input"` the namespace needs no `depth_model`), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
         self = cls.__new__(cls)
         cls._check_keywords(**{k: kw.pop(k) for k in ("acceleration", "cfg_type", "use_denoising_batch", "frame_buffer_size",
                                                       "device_ids", "opt_unet", "few_step_model_type") if k in kw},
@@ -403,8 +407,10 @@ class StreamAnimateDiffusionDepthWrapper:
                scheduler_kwargs=None, frame_pipelining=False, enable_similar_image_filter=False,
                similar_image_filter_threshold=0.98, similar_image_filter_max_skip_frame=10, jpeg_quality=75, jpeg_decode="device",
                output_size=None, output_resample="lanczos", matte_source="stream", steady=None, matte_edge=None, detail=None,
-               depth_input=None, depth_source="detector", backdrop=None, steady_follow=None, matte_hold=None, mask_input=None):
+               depth_input=None, depth_source="detector", backdrop=None, steady_follow=None, matte_hold=None, mask_input=None, matte_key=None):
         self._check_matte_source(matte_source)
+        if matte_key is not None and not isinstance(matte_key, dict):
+            raise ValueError(f"matte_key={matte_key!r}: use a dict of set_matte_key's keywords (with `to`), or None")
         if mask_input is not None and not isinstance(mask_input, dict):
             raise ValueError(f"mask_input={mask_input!r}: use a dict of set_mask_input's keywords, or None")
         if matte_hold is not None and not isinstance(matte_hold, dict):
@@ -476,6 +482,10 @@ class StreamAnimateDiffusionDepthWrapper:
             self.set_depth_input(**depth_input)
         if mask_input is not None:
             self.set_mask_input(**mask_input)
+        if matte_key is not None:
+            if "to" not in matte_key:
+                raise ValueError(f"matte_key={matte_key!r}: the dict needs `to` (a colour, an image or 'capture')")
+            self._set_matte_key(**matte_key, needs_matte=False)      # (no matte can be set yet: the key waits for the first set_matte)
 
     # ------------------------------------------------------------------ depth from the caller (depth_io.py)
     @property
@@ -551,6 +561,8 @@ class StreamAnimateDiffusionDepthWrapper:
         from . import mask_io
         if self._matte is None:
             raise ValueError("set_mask: a mask needs a matte: call set_matte first (its feather, show and keep act on the mask)")
+        if self._key is not None:
+            raise ValueError("set_mask: a mask and a matte key exclude each other: call clear_matte_key first")
         m = mask_io.load(mask, "set_mask")
         m = mask_io._torch_mask(m).clone() if torch.is_tensor(m) and m.is_cuda else mask_io._as_mask(m).copy()
         mask_io.tables(m.shape[0], m.shape[1], self.height, self.width)
@@ -570,6 +582,8 @@ class StreamAnimateDiffusionDepthWrapper:
             tap.begin()
         if mask is not None and self._matte is None:
             raise ValueError(f"{where}: a mask needs a matte: call set_matte first (its feather, show and keep act on the mask)")
+        if mask is not None and self._key is not None:
+            raise ValueError(f"{where}: a mask and a matte key exclude each other: call clear_matte_key first")
         sticky = mask is None
         if sticky:
             mask = self._mask_sticky
@@ -602,6 +616,111 @@ class StreamAnimateDiffusionDepthWrapper:
             return None
         from .mask_io import raw_ref
         return raw_ref(slot.mask, slot.depth[None], self._matte, self.mask_input, self.height, self.width)
+
+
+    # ------------------------------------------------------------------ matte key (matte_key.py)
+    @property
+    def matte_key(self) -> Optional[dict]:
+        """the current matte key as {to, lo, hi, luma, radius, combine, invert}, or None; `to` is the (r, g, b) of a colour key,
+        "plate" (an image, or a captured frame) or "capture" (until the capture has happened)"""
+        if self._key is None:
+            return None
+        return dict(self._key, to="capture" if self._key_capture else self._key["to"])
+
+    def set_matte_key(self, to, *, lo=None, hi=None, luma=None, radius: int = 1, combine: str = "replace", invert: bool = False) -> None:
+        """Cut the frame by a colour or by a clean plate: the third source of a matte beside the depth ramp and a caller's mask.
+        Every pixel of the frame's source is compared, on the bytes a viewer would see, with the key (`matte_key.key_ref`);
+        where it differs is the subject, which the matte stylises (`keep` is not read under "replace"; `invert` flips the key).
+        `to`: an `(r, g, b)` triple of bytes -- a green or blue screen; an image (a uint8 [H,W,3] array, a PIL image or a
+        path, decoded here: a file that is no image raises ValueError now) -- a picture of the empty room taken by a camera
+        that does not move, cropped and resampled to the stream's size with the output size's filter
+        (`matte_key.plate_ref`); or "capture": the source frame of the next composited output becomes the plate -- what the
+        viewer sees at that moment --, and `matte_key["to"]` reads "plate" from then on (that one frame is keyed against
+        itself).  `lo`, `hi` (0..1024, byte levels of the colour distance averaged over a (2 `radius` + 1)^2 window, `radius`
+        0..4): at or below `lo` a pixel is the key's, at or above `hi` the subject's, a smoothstep between; `luma` (0..1):
+        how much a difference in brightness counts -- 0 ignores it, so a shadow on the screen stays screen.  None takes the
+        defaults, lo=40, hi=90, luma=0 for a colour and 0.25 for a plate: a guess, not tuned on camera footage.  `combine`:
+        "replace" (the key alone; depth is not read), "and" (the smaller of the depth ramp and the key: the screen, but only
+        what is nearer than the wall), "or" (the larger).
+
+        A setting beside the matte, like `set_matte_edge`: it needs a matte (`set_matte`), acts on its output types, and
+        `clear_matte` clears it.  The key is formed of the frame's own source out of the delay line, so it reaches the output
+        with its frame; edge refit, hold, feather, backdrop, `show` and `set_matte_source("camera")` act on it as on the ramp.
+        One more launch on the device at the head of the composite's list (two on a capturing frame), no synchronisation.  A
+        frame the near-duplicate filter repeats is keyed again from the same slot.  A key and a caller's mask exclude each
+        other.  May be called between any two frames; the change applies from the next output and restarts a matte hold.  The
+        constructor's `matte_key=` (a dict of these keywords, `to` among them) is set before any matte can be: it waits for
+        the first `set_matte`."""
+        self._set_matte_key(to, lo=lo, hi=hi, luma=luma, radius=radius, combine=combine, invert=invert)
+
+    def _set_matte_key(self, to, lo=None, hi=None, luma=None, radius=1, combine="replace", invert=False, needs_matte=True) -> None:
+        from . import matte_key as MK
+        if needs_matte and self._matte is None:
+            raise ValueError("set_matte_key: a key needs a matte: call set_matte first (its feather, show and keep act on the key)")
+        if self._mask_sticky is not None:
+            raise ValueError("set_matte_key: a matte key and a mask (set_mask) exclude each other: call clear_mask first")
+        capture = isinstance(to, str) and to == "capture"
+        color = MK.is_color(to)
+        if isinstance(to, (tuple, list)) and not color:
+            MK.check_color(to)
+        settings = MK.check_settings(lo, hi, luma, radius, combine, invert, plate=not color)
+        plate = None
+        if color:
+            settings["to"] = MK.check_color(to)
+        else:
+            settings["to"] = "plate"
+            if not capture:
+                if to is None or isinstance(to, (bool, int, float)):
+                    raise ValueError(f"matte key: to={to!r}: use an (r, g, b) triple, an image (an array, a PIL image or a path) or 'capture'")
+                if torch.is_tensor(to):
+                    to = to.detach().cpu().numpy()
+                plate = MK.plate_ref(to, self.height, self.width, self._backdrop_filter())        # (decoded now: a bad file is refused here)
+        self._key, self._key_capture, self._key_plate = settings, capture, plate
+        if self._key_dev is not None and plate is not None:
+            self._key_dev.set_plate(plate)
+        self._hold_init = True             # (a held matte starts again from the new raw matte)
+
+    def capture_matte_plate(self) -> None:
+        """Take the plate again: the source frame of the next composited output becomes it; the key's other settings stay."""
+        if self._key is None:
+            raise ValueError("capture_matte_plate: no matte key is set: call set_matte_key('capture') first")
+        self._key = dict(self._key, to="plate")          # (a colour key becomes a plate key; its lo, hi and luma are kept as they are)
+        self._key_capture, self._key_plate = True, None
+        self._hold_init = True
+
+    def clear_matte_key(self) -> None:
+        """No key: the frame is cut by the depth ramp alone again; no launch or buffer of the key is left in the frame's path."""
+        self._key = self._key_plate = self._key_dev = None
+        self._key_capture = False
+        self._hold_init = True
+
+    def _key_front(self, slot, device):
+        """`(records, keep, plane)` of L2D_OP_MATTE_KEY for the slot's source under the settings of this moment (on a capturing
+        frame L2D_OP_FRAME_PLANAR_BYTES in front of it), or None"""
+        if slot is None or self._key is None or self._matte is None:
+            return None
+        if self._key_dev is None:
+            from .matte_key import HipMatteKey
+            self._key_dev = HipMatteKey(self.height, self.width, device=device)
+            if self._key_plate is not None:
+                self._key_dev.set_plate(self._key_plate)
+        capture, self._key_capture = self._key_capture, False
+        return self._key_dev.record(slot, self._matte, self._key, capture=capture)
+
+    def _key_plane(self, slot) -> Optional[np.ndarray]:
+        """the raw matte of the key on the host route, fp32 [H,W]: `matte_key.raw_ref` where op 59 would run; or None"""
+        if slot is None or self._key is None or self._matte is None:
+            return None
+        from .matte_key import raw_ref
+        from .steady import source_bytes
+        if self._key_capture:
+            self._key_capture, self._key_plate = False, source_bytes(slot.source)
+        key = self._key["to"]
+        if isinstance(key, str):
+            if self._key_plate is None:
+                raise ValueError("matte key: no plate is set")
+            key = self._key_plate
+        return raw_ref(slot.source, key, slot.depth[None], self._matte, self._key)
 
     # ------------------------------------------------------------------ depth matte (matte.py, DESIGN.md section 8.z4)
     @property
@@ -636,6 +755,7 @@ class StreamAnimateDiffusionDepthWrapper:
         self._hold_dev = self._hold_state = None
         self._hold_init = True
         self._mask_tap = self._mask_sticky = self._mask_shared = None      # (a mask needs a matte: none outlives it)
+        self.clear_matte_key()                                             # (and so does a key)
         if self._matte_line is not None:
             self._matte_line.mask_source = None
             self._matte_line.drop_masks()
@@ -1315,6 +1435,8 @@ class StreamAnimateDiffusionDepthWrapper:
         if warmup_masks is not None:
             if self._matte is None:
                 raise ValueError("warmup_masks: a mask needs a matte: call set_matte first")
+            if self._key is not None:
+                raise ValueError("warmup_masks: a mask and a matte key exclude each other: call clear_matte_key first")
             n_frames = len(warmup_frames) if hasattr(warmup_frames, "__len__") else None
             if not hasattr(warmup_masks, "__len__") or len(warmup_masks) == 0 or (n_frames is not None and len(warmup_masks) != n_frames):
                 raise ValueError(f"warmup_masks: expected one mask per warm-up frame ({n_frames}), a batch [F,Hm,Wm] or a list")
@@ -1502,7 +1624,7 @@ class StreamAnimateDiffusionDepthWrapper:
             held = {}                       # (the keywords only with a hold or a mask: without them the calls are the parent's)
             if slot is not None and self._hold is not None:
                 held["hold"] = self._hold_step(dev, repeated)
-            front = self._mask_front(slot)
+            front = self._key_front(slot, dev) if self._key is not None else self._mask_front(slot)
             bdk = {}
             if front is not None:
                 held["mask"] = front
@@ -1541,7 +1663,7 @@ class StreamAnimateDiffusionDepthWrapper:
             if slot is not None:
                 from .matte import composite_ref
                 more = {}                   # (the keyword only with a backdrop: without one the call is the parent's)
-                raw = self._mask_plane(slot)
+                raw = self._key_plane(slot) if self._key is not None else self._mask_plane(slot)
                 if self._backdrop is not None and not self._matte["show"]:
                     from .backdrop import stream_ref
                     more["backdrop"] = stream_ref(self._backdrop, self._backdrop_image_host(), slot.source, slot.depth, self._matte,

@@ -1,0 +1,68 @@
+"""Timing of the matte key (csrc/matte_key.hip, live2diff_amd/matte_key.py) on the MI355X.
+
+    timeout -k 10 120 python tools/matte_key_time.py --out profiles/matte_key_time.txt
+
+L2D_OP_MATTE_KEY at 512x512 in both variants (a colour key and a plate key; radius 0, 1 and 4; "replace", and "and" at radius 1)
+and L2D_OP_FRAME_PLANAR_BYTES, beside L2D_OP_FRAME_MATTE_HOLD (radius 2, from the depth plane) -- the op whose tile form op 59
+takes -- in the same run: device events around `--reps` back-to-back replays after a warm-up, the median of five runs
+(microseconds per launch).  `tools/mask_time.py kernels` on the same box gives op 58's figures."""
+import argparse
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from mask_time import _timed  # noqa: E402
+from steady_time import say  # noqa: E402
+
+
+def kernels(args):
+    from live2diff_amd import _lib, ops
+    from live2diff_amd.matte import matte_params
+    from live2diff_amd.matte_key import key_params, luma_weight
+    from live2diff_amd.steady import steady_params
+    dev, H, W = "cuda", 512, 512
+    say(args.out, f"# matte_key_time: {_lib.device_name()}, {args.reps} back-to-back replays per figure (device events), median of 5 runs, "
+                  f"{W}x{H}")
+    g = torch.Generator().manual_seed(0)
+    src = (torch.randn(3, H, W, generator=g) * 0.6).half().to(dev)
+    depth = (torch.randn(H, W, generator=g) * 0.6).clamp(-1, 1).half().to(dev)
+    plate = torch.randint(0, 256, (3, H, W), generator=g, dtype=torch.uint8).to(dev)
+    plane = torch.empty(H, W, dtype=torch.float32, device=dev)
+    lo2, inv, hard = key_params(40, 90)
+    lo32, inv32, ramp_hard = matte_params(0.3, 0.7)
+    kw = dict(H=H, W=W, L=luma_weight(0.25), lo2=lo2, inv=inv, hard=hard)
+    med = {}
+    for name, key in (("colour", (0, 177, 64)), ("plate", plate)):
+        for r in (0, 1, 4):
+            med[name, r] = _timed(args.out, args.reps, f"op 59 matte key, {name}, r = {r}, replace", ops.matte_key(src, plane, None, key, r=r, **kw))
+        _timed(args.out, args.reps, f"op 59 matte key, {name}, r = 1, and",
+               ops.matte_key(src, plane, depth, key, r=1, combine="and", lo32=lo32, inv32=inv32, ramp_hard=ramp_hard, **kw))
+    bytes_ = torch.empty(3, H, W, dtype=torch.uint8, device=dev)
+    _timed(args.out, args.reps, "op 60 frame planar bytes (the plate capture)", ops.frame_planar_bytes(src, bytes_, H=H, W=W))
+    # the tile form's owner, in the same run: op 57 from the depth plane, radius 2, a steady state frame
+    rec = [(torch.zeros(H, W, device=dev), torch.zeros(3, H, W, dtype=torch.uint8, device=dev)) for _ in range(2)]
+    slo, sinv, shard = steady_params(2.0, 10.0)
+    base = _timed(args.out, args.reps, "op 57 matte hold, r = 2, depth plane",
+                  ops.frame_matte_hold(src, depth, rec[0][0], rec[0][1], rec[1][0], rec[1][1], H=H, W=W, lo32=slo, inv32=sinv,
+                                       s32=0.8, r=2, hard=shard, init=False, ramp_lo32=lo32, ramp_inv32=inv32, ramp_hard=ramp_hard, far=False))
+    say(args.out, f"op 59 against op 57: colour r = 1 {med['colour', 1] / base:.2f} x, plate r = 1 {med['plate', 1] / base:.2f} x, "
+                  f"plate r = 4 {med['plate', 4] / base:.2f} x")
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--out", default=None, help="append the result lines to this file")
+    ap.add_argument("--reps", type=int, default=200)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "needs a GPU"
+    kernels(args)
+
+
+if __name__ == "__main__":
+    main()

@@ -82,7 +82,14 @@ It needs `--matte`, whose feather and `far` keep acting on it.  `POST /mask` wit
 replaces it while the stream runs, an empty body or `off` clears it; `GET /mask` answers `{"size": [h, w]}` or `null`.
 `--mask-input COMBINE[,invert]` says how a mask meets the ramp (`wrapper.set_mask_input`: `replace`, `and` or `or`); `POST
 /mask-input` with the same text changes it, `GET /mask-input` answers the current settings as JSON.  A body either route
-refuses gets a 400 and is counted (`failed`)."""
+refuses gets a 400 and is counted (`failed`).
+
+`--matte-key RRGGBB|PATH|capture[,LO,HI[,LUMA[,RADIUS[,COMBINE[,invert]]]]]` cuts the frame by a key (`wrapper.set_matte_key`):
+six hex digits are a key colour (a green screen: `00b140`), a path is a clean plate (a picture of the empty room from a camera
+that does not move), `capture` takes the plate from the stream's next output.  It needs `--matte` and excludes `--mask`.  `POST
+/matte-key` with the same text changes it while the stream runs, an empty body or `off` clears it; `POST /matte-key/capture` (no
+body) takes the plate again with the settings kept; `GET /matte-key` answers the current settings as JSON (`to` is the colour,
+`"plate"` or, until it has happened, `"capture"`; `null`: off).  A body the routes refuse gets a 400 and is counted."""
 import argparse
 import json
 import os
@@ -497,6 +504,85 @@ class MaskBox:
             self.refused()
 
 
+def parse_matte_key_arg(text: str):
+    """`RRGGBB|PATH|capture[,LO,HI[,LUMA[,RADIUS[,COMBINE[,invert]]]]]` -> the keywords of `wrapper.set_matte_key` (`to` among
+    them: the colour's bytes, the image's uint8 [H,W,3] array, decoded here, or "capture"); `off` or nothing -> None; ValueError
+    otherwise.  Fields left out keep the defaults of the kind of key (`matte_key.DEFAULTS`, with luma 0.25 for a plate)."""
+    from live2diff_amd.backdrop import load_image
+    from live2diff_amd.matte_key import check_settings
+    text = text.strip()
+    if text in ("", "off"):
+        return None
+    usage = "use RRGGBB, the path of an image or capture, then [,LO,HI[,LUMA[,RADIUS[,COMBINE[,invert]]]]], or off"
+    parts = [t.strip() for t in text.split(",")]
+    head, rest = parts[0], parts[1:]
+    if len(rest) == 1 or len(rest) > 6 or (len(rest) == 6 and rest[5] != "invert"):
+        raise ValueError(f"matte key {text!r}: {usage}")
+    if len(head) == 6 and all(c in "0123456789abcdefABCDEF" for c in head):
+        to = tuple(int(head[i:i + 2], 16) for i in (0, 2, 4))
+    elif head == "capture":
+        to = "capture"
+    elif os.path.isfile(head):
+        to = load_image(head)
+    else:
+        raise ValueError(f"matte key {text!r}: {usage} (there is no such file)")
+    try:
+        lo, hi = (float(rest[i]) if len(rest) > i else None for i in (0, 1))
+        luma = float(rest[2]) if len(rest) > 2 else None
+        radius = int(rest[3]) if len(rest) > 3 else 1
+    except ValueError:
+        raise ValueError(f"matte key {text!r}: LO, HI and LUMA are numbers, RADIUS an integer from 0 to 4") from None
+    s = check_settings(lo, hi, luma, radius, rest[4] if len(rest) > 4 else "replace", len(rest) == 6, plate=not isinstance(to, tuple))
+    return dict(s, to=to)
+
+
+class MatteKeyBox:
+    """What `POST /matte-key` and `POST /matte-key/capture` deliver: the newest requested key (a dict of `set_matte_key` keywords,
+    or None for an empty body or `off`) and a request to take the plate again, applied by the producer between two frames.
+    `current` is what was last applied (the `matte_key` property, with the colour as a list); `failed` counts bodies the route
+    refused with a 400 and requests the wrapper refused (no matte, a sticky mask, a capture without a key)."""
+    _NOTHING = object()
+
+    def __init__(self, current=None):
+        self._lock = threading.Lock()
+        self.current, self._want, self._capture, self.failed = self.view(current), self._NOTHING, False, 0
+
+    @staticmethod
+    def view(key):
+        return None if key is None else dict(key, to=list(key["to"]) if isinstance(key["to"], tuple) else key["to"])
+
+    def put(self, settings) -> None:
+        with self._lock:
+            self._want, self._capture = settings, False       # (a new key supersedes a capture asked for before it)
+
+    def capture(self) -> None:
+        with self._lock:
+            self._capture = True
+
+    def refused(self) -> None:
+        with self._lock:
+            self.failed += 1
+
+    def apply(self, wrapper) -> None:
+        """(producer thread, between frames)"""
+        with self._lock:
+            want, self._want = self._want, self._NOTHING
+            capture, self._capture = self._capture, False
+        try:
+            if want is None:
+                wrapper.clear_matte_key()
+            elif want is not self._NOTHING:
+                wrapper.set_matte_key(**want)
+        except ValueError:
+            self.refused()
+        try:
+            if capture:
+                wrapper.capture_matte_plate()
+        except ValueError:
+            self.refused()
+        self.current = self.view(wrapper.matte_key)
+
+
 def parse_matte_edge_arg(text: str):
     """`R[,EPS]` -> the keywords of `wrapper.set_matte_edge`, `off` -> None; ValueError otherwise"""
     from live2diff_amd.matte import MAX_EDGE_RADIUS, check_edge
@@ -776,8 +862,8 @@ class Latest:
 def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = None, mattes: "MatteBox" = None, colors: "ColorBox" = None,
                  sizes: "SizeBox" = None, sources: "MatteSourceBox" = None, steadies: "SteadyBox" = None, details: "DetailBox" = None,
                  backdrops: "BackdropBox" = None, follows: "SteadyFollowBox" = None, holds: "MatteHoldBox" = None,
-                 masks: "MaskBox" = None, edges: "MatteEdgeBox" = None):
-    boxes = {"/matte": mattes, "/color": colors, "/size": sizes, "/matte-source": sources, "/steady": steadies, "/matte-edge": edges,
+                 masks: "MaskBox" = None, keys: "MatteKeyBox" = None, edges: "MatteEdgeBox" = None):
+    boxes = {"/matte-key": keys, "/matte": mattes, "/color": colors, "/size": sizes, "/matte-source": sources, "/steady": steadies, "/matte-edge": edges,
              "/detail": details, "/backdrop": backdrops, "/steady-follow": follows, "/matte-hold": holds}
     page = PAGE if inbox is None else CAMERA_PAGE
 
@@ -877,6 +963,33 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
             self.send_response(204)
             self.end_headers()
 
+        def do_matte_key(self):
+            try:
+                n = int(self.headers.get("Content-Length", ""))
+            except ValueError:
+                self.send_error(411)
+                return
+            capture = self.path == "/matte-key/capture"
+            if not 0 <= n <= 256:
+                self.send_error(413 if n > 256 else 400)
+                return
+            body = self.rfile.read(n) if n else b""
+            try:
+                if len(body) != n:
+                    raise ValueError("the body is shorter than its Content-Length")
+                if capture:
+                    if body.strip():
+                        raise ValueError("POST /matte-key/capture takes no body")
+                    keys.capture()
+                else:
+                    keys.put(parse_matte_key_arg(body.decode()))
+            except ValueError as e:                       # (UnicodeDecodeError is a ValueError)
+                keys.refused()
+                self.send_error(400, str(e.args[0] if e.args else e)[:200])
+                return
+            self.send_response(204)
+            self.end_headers()
+
         def do_style(self):
             from live2diff_amd.style_bank import parse_style
             try:
@@ -933,6 +1046,9 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
             if masks is not None and self.path in ("/mask", "/mask-input"):
                 self.do_mask()
                 return
+            if keys is not None and self.path in ("/matte-key", "/matte-key/capture"):
+                self.do_matte_key()
+                return
             if inbox is None or self.path != "/frame":
                 self.send_error(404)
                 return
@@ -958,10 +1074,10 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
 def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: StyleBox = None, mattes: MatteBox = None,
             colors: ColorBox = None, sizes: SizeBox = None, sources: MatteSourceBox = None, steadies: SteadyBox = None,
             details: DetailBox = None, backdrops: BackdropBox = None, follows: SteadyFollowBox = None,
-            holds: MatteHoldBox = None, masks: "MaskBox" = None, edges: MatteEdgeBox = None) -> None:
+            holds: MatteHoldBox = None, masks: "MaskBox" = None, keys: "MatteKeyBox" = None, edges: MatteEdgeBox = None) -> None:
     """the producer: loops `frames` through the wrapper until `stop` is set; a posted style, matte, colour lock, output size,
-    matte source, steady mode, follow setting, matte edge, matte hold, detail mode, backdrop, mask or mask input is applied between
-    two frames"""
+    matte source, steady mode, follow setting, matte edge, matte hold, detail mode, backdrop, mask, mask input or matte key is
+    applied between two frames"""
     from live2diff_amd.jpeg import mjpeg_part
     try:
         i = 0
@@ -990,6 +1106,8 @@ def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: Styl
                 backdrops.apply(wrapper)
             if masks is not None:
                 masks.apply(wrapper)
+            if keys is not None:
+                keys.apply(wrapper)
             latest.put(mjpeg_part(wrapper(frames[i % len(frames)])))
             i += 1
     finally:
@@ -1000,7 +1118,7 @@ def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: thr
                    mattes: MatteBox = None, colors: ColorBox = None, sizes: SizeBox = None, sources: MatteSourceBox = None,
                    steadies: SteadyBox = None, details: DetailBox = None, backdrops: BackdropBox = None,
                    follows: SteadyFollowBox = None, holds: "MatteHoldBox" = None,
-                   masks: "MaskBox" = None, edges: MatteEdgeBox = None) -> None:
+                   masks: "MaskBox" = None, keys: "MatteKeyBox" = None, edges: MatteEdgeBox = None) -> None:
     """the producer of `--input post`: the first frames posted warm the stream up, then the newest posted frame goes through the
     wrapper, for ever; a frame the wrapper refuses (ValueError: a damaged file) is dropped and counted in `inbox.failed`"""
     from live2diff_amd.jpeg import mjpeg_part
@@ -1037,6 +1155,8 @@ def produce_posted(wrapper, prompt: str, inbox: Inbox, latest: Latest, stop: thr
                 backdrops.apply(wrapper)
             if masks is not None:
                 masks.apply(wrapper)
+            if keys is not None:
+                keys.apply(wrapper)
             try:
                 latest.put(mjpeg_part(wrapper(frame)))
             except ValueError:
@@ -1102,10 +1222,23 @@ def main(argv=None):
                     help="a sticky mask: an image (mode L, 1, I;16 or F, any size) that cuts every frame in place of the depth ramp, or "
                          "combined with it (--mask-input); needs --matte; POST /mask with an image file as its body replaces it between "
                          "frames, an empty body (or `off`) clears it")
+    ap.add_argument("--matte-key", default=None, metavar="RRGGBB|PATH|capture[,LO,HI[,LUMA[,RADIUS[,COMBINE[,invert]]]]]",
+                    help="cut the frame by a colour (a green screen), by a clean plate (an image of the empty room) or by a plate "
+                         "captured from the stream's next output; needs --matte; POST /matte-key with the same text changes it "
+                         "between two frames, `off` clears it, POST /matte-key/capture takes the plate again")
     ap.add_argument("--mask-input", default=None, metavar="COMBINE[,invert]",
                     help="how a mask meets the depth ramp: replace (default), and, or; `invert` flips the mask first; POST /mask-input "
                          "with the same text changes it between frames")
     args = ap.parse_args(argv)
+    ap_key = args.matte_key
+    if ap_key is not None and not args.matte:
+        ap.error("--matte-key needs --matte (its feather and `far` act on the key)")
+    if ap_key is not None and args.mask is not None:
+        ap.error("--matte-key and --mask exclude each other")
+    try:
+        matte_key = parse_matte_key_arg(ap_key) if ap_key else None
+    except ValueError as e:
+        ap.error(str(e))
     if args.mask is not None and not args.matte:
         ap.error("--mask needs --matte (its feather and `far` act on the mask)")
     mask_input = parse_mask_input_arg(args.mask_input) if args.mask_input else None
@@ -1172,15 +1305,18 @@ def main(argv=None):
         w.set_mask(sticky)                   # (before `prepare`: the primed positions of the delay line carry it)
         mask_size = dict(size=[int(sticky.shape[0]), int(sticky.shape[1])])
     masks = MaskBox(mask_size, w.mask_input)
+    if matte_key is not None:
+        w.set_matte_key(**matte_key)
+    keys = MatteKeyBox(w.matte_key)
     prompt = args.prompt if args.prompt is not None else str(cfg.get("prompt", ""))
     latest, stop = Latest(), threading.Event()
     inbox = Inbox(sink) if post else None
     if post:
-        producer = threading.Thread(target=produce_posted, args=(w, prompt, inbox, latest, stop, styles, mattes, colors, sizes, sources, steadies, details, backdrops, follows, holds, masks, edges), name="producer", daemon=True)
+        producer = threading.Thread(target=produce_posted, args=(w, prompt, inbox, latest, stop, styles, mattes, colors, sizes, sources, steadies, details, backdrops, follows, holds, masks, keys, edges), name="producer", daemon=True)
     else:
         w.prepare(frames[:sink], prompt)
-        producer = threading.Thread(target=produce, args=(w, frames, latest, stop, styles, mattes, colors, sizes, sources, steadies, details, backdrops, follows, holds, masks, edges), name="producer", daemon=True)
-    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest, inbox, styles, mattes, colors, sizes, sources, steadies, details, backdrops, follows, holds, masks, edges))
+        producer = threading.Thread(target=produce, args=(w, frames, latest, stop, styles, mattes, colors, sizes, sources, steadies, details, backdrops, follows, holds, masks, keys, edges), name="producer", daemon=True)
+    server = ThreadingHTTPServer((args.host, args.port), make_handler(latest, inbox, styles, mattes, colors, sizes, sources, steadies, details, backdrops, follows, holds, masks, keys, edges))
     server.daemon_threads = True
     producer.start()
     print(f"http://{args.host}:{args.port}/  ({args.height}x{args.width}, quality {args.quality}; Ctrl-C stops)")
