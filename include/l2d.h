@@ -613,6 +613,21 @@ enum {
  * L2D_OP_FRAME_PLANAR_BYTES  one launch (the plate capture):  p0 source half [3][H][W] p1 out uint8 [3][H][W], planar (both
  *   16-byte aligned) ; i0 H i1 W (W % 8 == 0, 3 H W < 2^31).  out = the egress bytes of p0 (L2D_OP_FRAME_EGRESS's byte), one
  *   lane per 8 pixels, plain stores.  Refused: a null or misaligned pointer, W % 8 != 0, 3 H W >= 2^31, p1 overlapping p0.
+ * L2D_OP_MATTE_KEY_ADAPT  one launch (the plate key over a plate that follows drifting light; live2diff_amd/matte_key.py
+ *   key_adapt_ref):  p0 source p1 out p2 depth as L2D_OP_MATTE_KEY's p3 plate uint8 [3][H][W], planar (read only with
+ *   L2D_MATTE_KEY_ADAPT_INIT; may be null without; 8-byte aligned) p4 state in uint16 [3][H][W], planar (null under INIT) p5 state
+ *   out uint16 [3][H][W] (both 16-byte aligned) ; i0 H i1 W i2 r i3 flags (L2D_OP_MATTE_KEY's -- L2D_MATTE_KEY_PLATE is not read:
+ *   there is always a plate -- and L2D_MATTE_KEY_ADAPT_INIT) i4 L i5 a_bg = rint(65536 rate) i6 a_fg = rint(65536 absorb) (both
+ *   0..L2D_MATTE_KEY_MAX_RATE) ; f0 lo2 f1 inv f2 lo f3 inv as L2D_OP_MATTE_KEY's.  The state s is the plate in 8.8 fixed point, 0
+ *   <= s <= 65280 (INIT: s = 256 p3); the key's byte is k = (s + 128) >> 8, and p1 is formed and written exactly as
+ *   L2D_OP_MATTE_KEY with a plate of those bytes writes it.  P0 = P in front of INVERT (an integer 0..255); a = (a_bg (255 - P0) +
+ *   a_fg P0 + 127) / 255; per channel, with b the egress byte of p0: e = 256 b - s, s' = s + ((a e + 32768) >> 16) (arithmetic
+ *   shift); |a e| + 32768 <= 2,139,127,808 < 2^31 and s' stays in 0..65280.  p5 = s' is the next launch's p4: the two records
+ *   ping-pong, because a tile's halo reads what a neighbour would write.  L2D_OP_MATTE_KEY's tile form (13,824 bytes of LDS);
+ *   behind the plane's stores each lane writes the three channels of its 8 pixels with 16-byte stores; the state is read with
+ *   16-byte loads (element loads for the edge pixel a group beside the image repeats).  Every element of p1 and p5 is written by
+ *   a plain store on every launch: nothing has to be zeroed, no atomics.  Refused: everything L2D_OP_MATTE_KEY refuses, a rate out
+ *   of range, p5 (without INIT also p4) null or misaligned, INIT without p3, p5 overlapping p0 .. p4, p1 overlapping p4.
  */
 enum {
     L2D_OP_IGEMM = 1,
@@ -675,6 +690,7 @@ enum {
     L2D_OP_MASK_INGEST = 58,
     L2D_OP_MATTE_KEY = 59,
     L2D_OP_FRAME_PLANAR_BYTES = 60,
+    L2D_OP_MATTE_KEY_ADAPT = 61,
 };
 
 /* flag bits of L2D_OP_FRAME_MATTE (i4) and L2D_OP_FRAME_MATTE_UP (i6); HARD and FAR also of L2D_OP_FRAME_MATTE_EDGE (i3) */
@@ -750,6 +766,9 @@ enum {
 #define L2D_MATTE_KEY_RAMP_HARD 64 /* L2D_MATTE_HARD of the depth ramp */
 #define L2D_MATTE_KEY_RAMP_FAR 128 /* L2D_MATTE_FAR of the depth ramp */
 #define L2D_MATTE_KEY_MAX_R 4
+/* L2D_OP_MATTE_KEY_ADAPT: its flags (i3) are L2D_OP_MATTE_KEY's and INIT; its largest rate */
+#define L2D_MATTE_KEY_ADAPT_INIT 256 /* the state starts from the plate p3: s = 256 k, and p4 is not read */
+#define L2D_MATTE_KEY_MAX_RATE 32768 /* 65536 times a rate of 1 / 2 */
 
 /* sizes of L2D_OP_FRAME_RESIZE */
 #define L2D_RESIZE_MAX_KS 13 /* taps per output: Lanczos (support 3) at a 2x down-scale, 2 * 6 + 1 */

@@ -41,6 +41,7 @@ OP_FRAME_MATTE_HOLD = 57
 OP_MASK_INGEST = 58
 OP_MATTE_KEY = 59
 OP_FRAME_PLANAR_BYTES = 60
+OP_MATTE_KEY_ADAPT = 61
 ABI_VERSION = 6
 
 

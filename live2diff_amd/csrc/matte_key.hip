@@ -24,6 +24,16 @@
 // launch: nothing is zeroed, there is no atomic.
 //
 // L2D_OP_FRAME_PLANAR_BYTES is the plate capture: the fp16 source -> its planar egress bytes, one lane per 8 pixels.
+//
+// L2D_OP_MATTE_KEY_ADAPT is the plate key over a plate that follows drifting light.  The plate is a
+// state record, planar uint16 [3][H][W] in 8.8 fixed point (0 .. 65280); the byte the key compares against is k = (s + 128) >> 8,
+// and the plane is formed and written exactly as above.  Behind the plane's stores every lane moves the three channels of its 8
+// pixels towards the source's bytes and writes them to the NEXT record:
+//   P0 = P in front of INVERT, an integer 0 .. 255       a = (a_bg (255 - P0) + a_fg P0 + 127) / 255     a_bg, a_fg in 0 .. 32768
+//   e = 256 b - s                                        s' = s + ((a e + 32768) >> 16)                  arithmetic shift
+// |e| <= 65280 and a <= 32768, so |a e| + 32768 <= 2,139,127,808 < 2^31, and s' stays in 0 .. 65280 because a / 65536 <= 1 / 2
+// (the static_asserts below).  INIT reads the plate's bytes instead of a record: s = 256 k.  The record read is never the record
+// written, because a tile's halo reads what a neighbour would write: the two ping-pong (live2diff_amd/matte_key.py adapt_ref).
 #include "steady_px.h"                        // the tile's sizes, sd_weight; frame_px.h: px_byte, px_luma, px_pack8, px_ramp, the checks
 
 #define MK_MAX_R L2D_MATTE_KEY_MAX_R
@@ -34,6 +44,9 @@
 #define MK_OR L2D_MATTE_KEY_OR
 #define MK_RAMP_HARD L2D_MATTE_KEY_RAMP_HARD
 #define MK_RAMP_FAR L2D_MATTE_KEY_RAMP_FAR
+#define MK_ADAPT_INIT L2D_MATTE_KEY_ADAPT_INIT
+#define MK_MAX_RATE L2D_MATTE_KEY_MAX_RATE
+#define MK_MAX_STATE (255 * 256)              // a plate byte in 8.8 fixed point
 #define MK_DH (SD_TH + 2 * MK_MAX_R)          // the rows of D under one tile: 24
 #define MK_MAX_L 256
 #define MK_MAX_D (2 * 510 * 510 + ((MK_MAX_L * 255 * 255 + 128) >> 8))
@@ -43,6 +56,12 @@ static_assert(MK_LDS_BYTES == 13824, "DESIGN.md section 8.z17, l2d.h and tests/t
 static_assert(MK_MAX_R <= 8, "the halo is one 8-pixel group on either side");
 static_assert(MK_MAX_D == 585225 && MK_MAX_D < (1 << 20), "D stays below 2^20");
 static_assert((long long)MK_MAX_D * (2 * MK_MAX_R + 1) * (2 * MK_MAX_R + 1) < (1ll << 31), "a window sum of D fits 32 bits");
+static_assert((long long)MK_MAX_RATE * MK_MAX_STATE + 32768 == 2139127808ll && (long long)MK_MAX_RATE * MK_MAX_STATE + 32768 < (1ll << 31),
+              "|a e| + 32768 fits 32 bits");
+static_assert(2 * MK_MAX_RATE <= 65536, "a / 65536 <= 1 / 2: the state moves no further than half way, so it stays in 0 .. 65280");
+
+// where the key's bytes come from
+enum { MK_KEY_COLOR = 0, MK_KEY_PLATE = 1, MK_KEY_STATE = 2 };
 
 struct mk_params {
     sd_params th;                             // lo2, inv of the key's ramp; flags: SD_HARD; r
@@ -51,6 +70,33 @@ struct mk_params {
     float rlo, rinv;                          // the depth ramp (read only with AND / OR)
     int rflags;                               // L2D_MATTE_HARD | L2D_MATTE_FAR of the depth ramp
 };
+
+struct mk_adapt {                             // L2D_OP_MATTE_KEY_ADAPT beside mk_params
+    const uint16_t *state;                    // the record read (null under INIT)
+    uint16_t *next;                           // the record written
+    int a_bg, a_fg;                           // rint(65536 rate), rint(65536 absorb)
+};
+
+// the plate byte of a state word
+__device__ __forceinline__ int mk_state_byte(unsigned s) { return (int)((s + 128u) >> 8); }
+
+// one channel of 8 pixels: the state moves towards the source's bytes by a[e] / 65536 of the way, packed lowest pixel first
+__device__ __forceinline__ uint4 mk_adapt8(h16x8 c, const unsigned (&s)[8], const int (&a)[8]) {
+    unsigned n[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int d = 256 * (int)px_byte(c[e]) - (int)s[e];
+        n[e] = (unsigned)((int)s[e] + ((a[e] * d + 32768) >> 16));
+    }
+    return make_uint4(n[0] | (n[1] << 16), n[2] | (n[3] << 16), n[4] | (n[5] << 16), n[6] | (n[7] << 16));
+}
+
+// 8 state words as one 16-byte load, lowest pixel first
+__device__ __forceinline__ void mk_state8(const uint16_t *__restrict__ p, unsigned (&s)[8]) {
+    const uint4 v = *reinterpret_cast<const uint4 *>(p);
+    s[0] = v.x & 65535u; s[1] = v.x >> 16; s[2] = v.y & 65535u; s[3] = v.y >> 16;
+    s[4] = v.z & 65535u; s[5] = v.z >> 16; s[6] = v.w & 65535u; s[7] = v.w >> 16;
+}
 
 // D of one pixel: its bytes against the key's
 __device__ __forceinline__ unsigned mk_D(unsigned r, unsigned g, unsigned b, int kr, int kg, int kb, int L) {
@@ -63,9 +109,11 @@ __device__ __forceinline__ unsigned mk_D(unsigned r, unsigned g, unsigned b, int
 
 // D of the 8-pixel group at row yy (clamped by the caller), column gx (a multiple of 8, inside the image or one group beside it):
 // a group beside the image holds the edge pixel's value, which is what a clamped coordinate reads
-template <bool PLATE>
-__device__ __forceinline__ void mk_group(const h16 *__restrict__ source, const uint8_t *__restrict__ plate, int W, long long HW, int yy,
-                                         int gx, const mk_params &p, unsigned (&D)[8]) {
+template <int KEY>
+__device__ __forceinline__ void mk_group(const h16 *__restrict__ source, const uint8_t *__restrict__ plate,
+                                         const uint16_t *__restrict__ state, int W, long long HW, int yy, int gx, const mk_params &p,
+                                         unsigned (&D)[8]) {
+    constexpr bool PLATE = KEY == MK_KEY_PLATE;
     if (gx < 0 || gx >= W) {
         const long long e0 = (long long)yy * W + (gx < 0 ? 0 : W - 1);
         int kr = p.kr, kg = p.kg, kb = p.kb;
@@ -73,6 +121,11 @@ __device__ __forceinline__ void mk_group(const h16 *__restrict__ source, const u
             kr = plate[e0];
             kg = plate[HW + e0];
             kb = plate[2 * HW + e0];
+        }
+        if constexpr (KEY == MK_KEY_STATE) {
+            kr = mk_state_byte(state[e0]);
+            kg = mk_state_byte(state[HW + e0]);
+            kb = mk_state_byte(state[2 * HW + e0]);
         }
         const unsigned d = mk_D(px_byte(source[e0]), px_byte(source[HW + e0]), px_byte(source[2 * HW + e0]), kr, kg, kb, p.L);
 #pragma unroll
@@ -85,6 +138,12 @@ __device__ __forceinline__ void mk_group(const h16 *__restrict__ source, const u
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) k[ch] = *reinterpret_cast<const uint2 *>(plate + ch * HW + g0);
         }
+        unsigned sr[8] = {}, sg[8] = {}, sb[8] = {};
+        if constexpr (KEY == MK_KEY_STATE) {
+            mk_state8(state + g0, sr);
+            mk_state8(state + HW + g0, sg);
+            mk_state8(state + 2 * HW + g0, sb);
+        }
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             int kr = p.kr, kg = p.kg, kb = p.kb;
@@ -94,16 +153,24 @@ __device__ __forceinline__ void mk_group(const h16 *__restrict__ source, const u
                 kg = (int)(((e < 4 ? k[1].x : k[1].y) >> sh) & 255u);
                 kb = (int)(((e < 4 ? k[2].x : k[2].y) >> sh) & 255u);
             }
+            if constexpr (KEY == MK_KEY_STATE) {
+                kr = mk_state_byte(sr[e]);
+                kg = mk_state_byte(sg[e]);
+                kb = mk_state_byte(sb[e]);
+            }
             D[e] = mk_D(px_byte(R[e]), px_byte(G[e]), px_byte(B[e]), kr, kg, kb, p.L);
         }
     }
 }
 
 // grid (tiles x, tiles y), SD_THREADS lanes.  Every index into the frame is formed of a row clamped to [0, H - 1] and a column
-// group inside [0, W - 8] (or the edge pixel): nothing outside the source, the plate and the depth plane is read.
-template <bool PLATE>
+// group inside [0, W - 8] (or the edge pixel): nothing outside the source, the plate (or the state record) and the depth plane is
+// read.  ADAPT: the lane's 8 pixels of the next record are written behind the plane's; KEY says what the record is made of
+// (MK_KEY_PLATE: INIT).
+template <int KEY, bool ADAPT = false>
 __device__ __forceinline__ void mk_body(const h16 *__restrict__ source, float *__restrict__ out, const h16 *__restrict__ depth,
-                                        const uint8_t *__restrict__ plate, int H, int W, const mk_params &p) {
+                                        const uint8_t *__restrict__ plate, int H, int W, const mk_params &p,
+                                        const mk_adapt &ad = mk_adapt{nullptr, nullptr, 0, 0}) {
     __shared__ __attribute__((aligned(16))) unsigned dd[MK_DH][SD_DW];            // D of the tile and its halo
     __shared__ __attribute__((aligned(16))) unsigned hh[MK_DH][SD_TW];            // the row sums
     static_assert(sizeof(dd) + sizeof(hh) == MK_LDS_BYTES, "the LDS size the file states");
@@ -117,7 +184,7 @@ __device__ __forceinline__ void mk_body(const h16 *__restrict__ source, float *_
         if (r == 0 && (cg == 0 || cg == SD_DW / 8 - 1)) continue;                 // no tap reaches the side halo
         const int yy = px_clampi(y0 - r + j, 0, H - 1);
         unsigned D[8];
-        mk_group<PLATE>(source, plate, W, HW, yy, x0 - 8 + cg * 8, p, D);
+        mk_group<KEY>(source, plate, ad.state, W, HW, yy, x0 - 8 + cg * 8, p, D);
         uint4 *d4 = reinterpret_cast<uint4 *>(&dd[j][cg * 8]);
         d4[0] = make_uint4(D[0], D[1], D[2], D[3]);
         d4[1] = make_uint4(D[4], D[5], D[6], D[7]);
@@ -148,9 +215,14 @@ __device__ __forceinline__ void mk_body(const h16 *__restrict__ source, float *_
     const float n = (float)(taps * taps);
     const long long px = (long long)y * W + x;
     float m[8];
+    int a[8];                                    // (ADAPT only) the rate of each pixel
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         float P = rintf(__fmul_rn(255.0f, sd_weight(__fdiv_rn((float)S[e], n), p.th)));
+        if constexpr (ADAPT) {
+            const int P0 = (int)P;
+            a[e] = (ad.a_bg * (255 - P0) + ad.a_fg * P0 + 127) / 255;
+        }
         if (p.flags & MK_INVERT) P = __fsub_rn(255.0f, P);
         m[e] = __fdiv_rn(P, 255.0f);
     }
@@ -165,17 +237,44 @@ __device__ __forceinline__ void mk_body(const h16 *__restrict__ source, float *_
     f32x4 *op = reinterpret_cast<f32x4 *>(out + px);
     op[0] = f32x4{m[0], m[1], m[2], m[3]};
     op[1] = f32x4{m[4], m[5], m[6], m[7]};
+    if constexpr (ADAPT) {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            unsigned sv[8];
+            if constexpr (KEY == MK_KEY_STATE) {
+                mk_state8(ad.state + ch * HW + px, sv);
+            } else {
+                const uint2 k = *reinterpret_cast<const uint2 *>(plate + ch * HW + px);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) sv[e] = (((e < 4 ? k.x : k.y) >> (8 * (e & 3))) & 255u) << 8;
+            }
+            *reinterpret_cast<uint4 *>(ad.next + ch * HW + px) = mk_adapt8(l2d_ld8(source + ch * HW + px), sv, a);
+        }
+    }
 }
 
 __global__ __launch_bounds__(SD_THREADS) void matte_key_color_kernel(const h16 *__restrict__ source, float *__restrict__ out,
                                                                      const h16 *__restrict__ depth, int H, int W, mk_params p) {
-    mk_body<false>(source, out, depth, nullptr, H, W, p);
+    mk_body<MK_KEY_COLOR>(source, out, depth, nullptr, H, W, p);
 }
 
 __global__ __launch_bounds__(SD_THREADS) void matte_key_plate_kernel(const h16 *__restrict__ source, float *__restrict__ out,
                                                                      const h16 *__restrict__ depth, const uint8_t *__restrict__ plate,
                                                                      int H, int W, mk_params p) {
-    mk_body<true>(source, out, depth, plate, H, W, p);
+    mk_body<MK_KEY_PLATE>(source, out, depth, plate, H, W, p);
+}
+
+__global__ __launch_bounds__(SD_THREADS) void matte_key_adapt_init_kernel(const h16 *__restrict__ source, float *__restrict__ out,
+                                                                          const h16 *__restrict__ depth,
+                                                                          const uint8_t *__restrict__ plate, int H, int W, mk_params p,
+                                                                          mk_adapt ad) {
+    mk_body<MK_KEY_PLATE, true>(source, out, depth, plate, H, W, p, ad);
+}
+
+__global__ __launch_bounds__(SD_THREADS) void matte_key_adapt_state_kernel(const h16 *__restrict__ source, float *__restrict__ out,
+                                                                           const h16 *__restrict__ depth, int H, int W, mk_params p,
+                                                                           mk_adapt ad) {
+    mk_body<MK_KEY_STATE, true>(source, out, depth, nullptr, H, W, p, ad);
 }
 
 // one lane per 8 consecutive elements of the [3][H][W] frame: n8 = 3 H W / 8 groups
@@ -189,68 +288,85 @@ __global__ __launch_bounds__(256) void frame_planar_bytes_kernel(const h16 *__re
     *reinterpret_cast<uint2 *>(out + 8ll * g) = px_pack8(b);
 }
 
-int l2d_launch_matte_key(const l2d_op *op, hipStream_t s) {
+// what L2D_OP_MATTE_KEY and L2D_OP_MATTE_KEY_ADAPT refuse alike (`plate`: p3 is read; `colour`: i5 i6 i7 are): the frame's H W, or
+// -1 with the error set.  `known` are the flag bits of the op.
+static long long mk_check(const char *name, const l2d_op *op, int known, bool plate, bool colour) {
     const int H = op->i[0], W = op->i[1], r = op->i[2], flags = op->i[3], L = op->i[4];
-    if (flags & ~(MK_PLATE | MK_HARD | MK_INVERT | MK_AND | MK_OR | MK_RAMP_HARD | MK_RAMP_FAR)) {
-        l2d_set_error("matte_key(tag %d): unknown flag bits 0x%x (1 plate, 2 hard, 4 invert, 8 and, 16 or, 64 hard ramp, 128 far)", op->tag,
+    if (flags & ~known) {
+        l2d_set_error("%s(tag %d): unknown flag bits 0x%x (1 plate, 2 hard, 4 invert, 8 and, 16 or, 64 hard ramp, 128 far)", name, op->tag,
                       flags);
-        return L2D_EINVAL;
+        return -1;
     }
     if ((flags & MK_AND) && (flags & MK_OR)) {
-        l2d_set_error("matte_key(tag %d): flags 0x%x name two ways to combine", op->tag, flags);
-        return L2D_EINVAL;
+        l2d_set_error("%s(tag %d): flags 0x%x name two ways to combine", name, op->tag, flags);
+        return -1;
     }
-    const bool ramp = (flags & (MK_AND | MK_OR)) != 0, plate = (flags & MK_PLATE) != 0;
+    const bool ramp = (flags & (MK_AND | MK_OR)) != 0;
     if (!ramp && (flags & (MK_RAMP_HARD | MK_RAMP_FAR))) {
-        l2d_set_error("matte_key(tag %d): ramp flags without L2D_MATTE_KEY_AND / _OR (a replacing key reads no depth)", op->tag);
-        return L2D_EINVAL;
+        l2d_set_error("%s(tag %d): ramp flags without L2D_MATTE_KEY_AND / _OR (a replacing key reads no depth)", name, op->tag);
+        return -1;
     }
-    if (!px_check_pointers16("matte_key", op, 2)) return L2D_EINVAL;
+    if (!px_check_pointers16(name, op, 2)) return -1;
     if (ramp && (!op->p[2] || (((uintptr_t)op->p[2]) & 15))) {
-        l2d_set_error("matte_key(tag %d): pointer 2 (the depth plane of AND / OR) is null or not 16-byte aligned", op->tag);
-        return L2D_EINVAL;
+        l2d_set_error("%s(tag %d): pointer 2 (the depth plane of AND / OR) is null or not 16-byte aligned", name, op->tag);
+        return -1;
     }
     if (plate && (!op->p[3] || (((uintptr_t)op->p[3]) & 7))) {
-        l2d_set_error("matte_key(tag %d): pointer 3 (the plate) is null or not 8-byte aligned", op->tag);
-        return L2D_EINVAL;
+        l2d_set_error("%s(tag %d): pointer 3 (the plate) is null or not 8-byte aligned", name, op->tag);
+        return -1;
     }
-    const long long HW = px_check_frame("matte_key", op->tag, H, W);
-    if (HW < 0) return L2D_EINVAL;
+    const long long HW = px_check_frame(name, op->tag, H, W);
+    if (HW < 0) return -1;
     if (r < 0 || r > MK_MAX_R) {
-        l2d_set_error("matte_key(tag %d): radius %d, need 0..%d", op->tag, r, MK_MAX_R);
-        return L2D_EINVAL;
+        l2d_set_error("%s(tag %d): radius %d, need 0..%d", name, op->tag, r, MK_MAX_R);
+        return -1;
     }
     if (L < 0 || L > MK_MAX_L) {
-        l2d_set_error("matte_key(tag %d): luma weight L = %d, need 0..%d", op->tag, L, MK_MAX_L);
-        return L2D_EINVAL;
+        l2d_set_error("%s(tag %d): luma weight L = %d, need 0..%d", name, op->tag, L, MK_MAX_L);
+        return -1;
     }
-    if (!plate) {
+    if (colour) {
         for (int k = 5; k < 8; ++k) {
             if (op->i[k] < 0 || op->i[k] > 255) {
-                l2d_set_error("matte_key(tag %d): key colour (%d, %d, %d): need bytes", op->tag, op->i[5], op->i[6], op->i[7]);
-                return L2D_EINVAL;
+                l2d_set_error("%s(tag %d): key colour (%d, %d, %d): need bytes", name, op->tag, op->i[5], op->i[6], op->i[7]);
+                return -1;
             }
         }
     }
     const float lo2 = op->f[0], inv = op->f[1], rlo = op->f[2], rinv = op->f[3];
     if (!(lo2 >= 0.0f && lo2 <= 3.0e38f) || !(inv >= 0.0f && inv <= 3.0e38f) || ((flags & MK_HARD) != 0) != (inv == 0.0f)) {
-        l2d_set_error("matte_key(tag %d): lo2 = %g and inv = %g must be finite and not negative, inv 0 exactly when the hard flag is set",
+        l2d_set_error("%s(tag %d): lo2 = %g and inv = %g must be finite and not negative, inv 0 exactly when the hard flag is set", name,
                       op->tag, lo2, inv);
-        return L2D_EINVAL;
+        return -1;
     }
-    if (ramp && !px_check_ramp("matte_key", op->tag, rlo, rinv, (flags & MK_RAMP_HARD) != 0)) return L2D_EINVAL;
+    if (ramp && !px_check_ramp(name, op->tag, rlo, rinv, (flags & MK_RAMP_HARD) != 0)) return -1;
     if (px_overlap(op->p[1], 4 * HW, op->p[0], 6 * HW) || (ramp && px_overlap(op->p[1], 4 * HW, op->p[2], 2 * HW))
         || (plate && px_overlap(op->p[1], 4 * HW, op->p[3], 3 * HW))) {
-        l2d_set_error("matte_key(tag %d): the plane overlaps the source, the depth plane or the plate", op->tag);
-        return L2D_EINVAL;
+        l2d_set_error("%s(tag %d): the plane overlaps the source, the depth plane or the plate", name, op->tag);
+        return -1;
     }
-    L2D_DRY_RETURN();
+    return HW;
+}
+
+// the kernels' parameters of a checked record
+static mk_params mk_params_of(const l2d_op *op) {
+    const int flags = op->i[3];
     mk_params p;
-    p.th.lo = lo2; p.th.inv = inv; p.th.s = 0.0f; p.th.flags = (flags & MK_HARD) ? SD_HARD : 0; p.th.r = r;
-    p.L = L; p.kr = op->i[5]; p.kg = op->i[6]; p.kb = op->i[7];
+    p.th.lo = op->f[0]; p.th.inv = op->f[1]; p.th.s = 0.0f; p.th.flags = (flags & MK_HARD) ? SD_HARD : 0; p.th.r = op->i[2];
+    p.L = op->i[4]; p.kr = op->i[5]; p.kg = op->i[6]; p.kb = op->i[7];
     p.flags = flags & (MK_INVERT | MK_AND | MK_OR);
-    p.rlo = rlo; p.rinv = rinv;
+    p.rlo = op->f[2]; p.rinv = op->f[3];
     p.rflags = ((flags & MK_RAMP_HARD) ? L2D_MATTE_HARD : 0) | ((flags & MK_RAMP_FAR) ? L2D_MATTE_FAR : 0);
+    return p;
+}
+
+int l2d_launch_matte_key(const l2d_op *op, hipStream_t s) {
+    const int H = op->i[0], W = op->i[1];
+    const bool plate = (op->i[3] & MK_PLATE) != 0;
+    if (mk_check("matte_key", op, MK_PLATE | MK_HARD | MK_INVERT | MK_AND | MK_OR | MK_RAMP_HARD | MK_RAMP_FAR, plate, !plate) < 0)
+        return L2D_EINVAL;
+    L2D_DRY_RETURN();
+    const mk_params p = mk_params_of(op);
     const dim3 tiles((W + SD_TW - 1) / SD_TW, (H + SD_TH - 1) / SD_TH), threads(SD_THREADS);
     if (plate)
         hipLaunchKernelGGL(matte_key_plate_kernel, tiles, threads, 0, s, (const h16 *)op->p[0], (float *)op->p[1], (const h16 *)op->p[2],
@@ -259,6 +375,48 @@ int l2d_launch_matte_key(const l2d_op *op, hipStream_t s) {
         hipLaunchKernelGGL(matte_key_color_kernel, tiles, threads, 0, s, (const h16 *)op->p[0], (float *)op->p[1], (const h16 *)op->p[2], H,
                            W, p);
     return l2d_check_launch("matte_key", op->tag);
+}
+
+int l2d_launch_matte_key_adapt(const l2d_op *op, hipStream_t s) {
+    const int H = op->i[0], W = op->i[1], flags = op->i[3], a_bg = op->i[5], a_fg = op->i[6];
+    const bool init = (flags & MK_ADAPT_INIT) != 0;
+    const long long HW = mk_check("matte_key_adapt", op, MK_PLATE | MK_HARD | MK_INVERT | MK_AND | MK_OR | MK_RAMP_HARD | MK_RAMP_FAR | MK_ADAPT_INIT,
+                                  init, false);
+    if (HW < 0) return L2D_EINVAL;
+    if (a_bg < 0 || a_bg > MK_MAX_RATE || a_fg < 0 || a_fg > MK_MAX_RATE) {
+        l2d_set_error("matte_key_adapt(tag %d): rates a_bg = %d, a_fg = %d, need 0..%d (65536 times a rate of at most 1 / 2)", op->tag, a_bg,
+                      a_fg, MK_MAX_RATE);
+        return L2D_EINVAL;
+    }
+    if (!op->p[5] || (((uintptr_t)op->p[5]) & 15) || (!init && (!op->p[4] || (((uintptr_t)op->p[4]) & 15)))) {
+        l2d_set_error("matte_key_adapt(tag %d): pointer 5 (the state written) or, without INIT, pointer 4 (the state read) is null or not "
+                      "16-byte aligned", op->tag);
+        return L2D_EINVAL;
+    }
+    const bool ramp = (flags & (MK_AND | MK_OR)) != 0;
+    if ((!init && px_overlap(op->p[5], 6 * HW, op->p[4], 6 * HW)) || px_overlap(op->p[5], 6 * HW, op->p[0], 6 * HW)
+        || px_overlap(op->p[5], 6 * HW, op->p[1], 4 * HW) || (ramp && px_overlap(op->p[5], 6 * HW, op->p[2], 2 * HW))
+        || (init && px_overlap(op->p[5], 6 * HW, op->p[3], 3 * HW))) {
+        l2d_set_error("matte_key_adapt(tag %d): the state written overlaps the state read, the source, the plane, the depth plane or the "
+                      "plate", op->tag);
+        return L2D_EINVAL;
+    }
+    // (the plane against the state read, which takes the plate's place)
+    if (!init && px_overlap(op->p[1], 4 * HW, op->p[4], 6 * HW)) {
+        l2d_set_error("matte_key_adapt(tag %d): the plane overlaps the state read", op->tag);
+        return L2D_EINVAL;
+    }
+    L2D_DRY_RETURN();
+    const mk_params p = mk_params_of(op);
+    const mk_adapt ad = {init ? nullptr : (const uint16_t *)op->p[4], (uint16_t *)op->p[5], a_bg, a_fg};
+    const dim3 tiles((W + SD_TW - 1) / SD_TW, (H + SD_TH - 1) / SD_TH), threads(SD_THREADS);
+    if (init)
+        hipLaunchKernelGGL(matte_key_adapt_init_kernel, tiles, threads, 0, s, (const h16 *)op->p[0], (float *)op->p[1],
+                           (const h16 *)op->p[2], (const uint8_t *)op->p[3], H, W, p, ad);
+    else
+        hipLaunchKernelGGL(matte_key_adapt_state_kernel, tiles, threads, 0, s, (const h16 *)op->p[0], (float *)op->p[1],
+                           (const h16 *)op->p[2], H, W, p, ad);
+    return l2d_check_launch("matte_key_adapt", op->tag);
 }
 
 int l2d_launch_frame_planar_bytes(const l2d_op *op, hipStream_t s) {

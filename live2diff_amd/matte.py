@@ -604,7 +604,8 @@ def _front(owner, pl, slot: "_Slot", settings: dict, edge: Optional[dict], hold:
 def _mask_head(pl, mask) -> Optional[torch.Tensor]:
     """a composite's `mask=`: None, or `(record, keep, plane)` of L2D_OP_MASK_INGEST -- appended first, in front of the
     backdrop's records, which read its plane too.  A matte key (`matte_key.HipMatteKey.record`) hands in a list of records in
-    the same form: L2D_OP_MATTE_KEY, with a capture L2D_OP_FRAME_PLANAR_BYTES in front of it."""
+    the same form: L2D_OP_MATTE_KEY (L2D_OP_MATTE_KEY_ADAPT with an adaptive plate), with a capture L2D_OP_FRAME_PLANAR_BYTES in
+    front of it."""
     if mask is None:
         return None
     op, keep, plane = mask

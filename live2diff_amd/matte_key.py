@@ -13,7 +13,13 @@ fma.  With `mask_io.front_ref` it is the oracle of L2D_OP_MATTE_KEY, bit for bit
 `lo` and `hi` are in byte levels of the colour distance: at or below `lo` a pixel counts as the key (matte 0), at or above `hi`
 as the subject (matte 1), a smoothstep over the squared distance in between.  `luma` in [0, 1] weighs the brightness difference
 in: 0 ignores it, so a shadow on the screen stays screen.  `DEFAULTS` are a guess made on a synthetic green-screen frame; they
-are NOT tuned on camera footage (as the matte hold's are not)."""
+are NOT tuned on camera footage (as the matte hold's are not).
+
+The adaptive plate: a plate is a frozen record, and a cloud, a lamp warming up or a camera's exposure
+settling moves every background pixel off it.  With adaptation the plate is a state, uint16 [3,H,W] in 8.8 fixed point, that
+moves after each keyed frame a little towards the frame's source where the key says "background" (`rate`) and not, or much more
+slowly, where it says "subject" (`absorb`).  `key_adapt_ref` restates L2D_OP_MATTE_KEY_ADAPT in exact integers; with both rates 0
+it is `key_ref` against the plate on every frame.  `ADAPT_DEFAULTS` are a guess too, untuned on camera footage."""
 from typing import Optional, Tuple
 
 import numpy as np
@@ -29,6 +35,9 @@ MAX_LEVEL = 1024
 # grey subject in front of a grey wall differs in little else
 DEFAULTS = dict(lo=40.0, hi=90.0, luma=0.0, radius=1, combine="replace", invert=False)
 PLATE_DEFAULTS = dict(DEFAULTS, luma=0.25)
+ADAPT_DEFAULTS = dict(rate=1.0 / 32.0, absorb=0.0)        # untuned on camera footage
+MAX_RATE = 0.5                                    # the state moves at most half way per frame
+MAX_STATE = 255 * 256                             # a plate byte in 8.8 fixed point
 MAX_D = 2 * 510 * 510 + 255 * 255                 # |cb|, |cr| <= 510, (L dy^2 + 128) >> 8 <= 255^2 with L <= 256: 585,225 < 2^20
 
 
@@ -61,6 +70,22 @@ def check_settings(lo=None, hi=None, luma=None, radius=1, combine="replace", inv
     if not isinstance(invert, (bool, np.bool_)):
         raise ValueError(f"matte key: invert={invert!r}: use True or False")
     return dict(lo=float(lo), hi=float(hi), luma=float(luma), radius=int(radius), combine=combine, invert=bool(invert))
+
+
+def check_adapt(rate=ADAPT_DEFAULTS["rate"], absorb=ADAPT_DEFAULTS["absorb"]) -> dict:
+    """{rate, absorb} validated; ValueError names the keyword"""
+    for name, v in (("rate", rate), ("absorb", absorb)):
+        if not _number(v) or not 0.0 <= float(v) <= MAX_RATE:
+            raise ValueError(f"matte key adapt: {name}={v!r}: use a number in [0, {MAX_RATE}] (the part of the way the plate moves per frame)")
+    return dict(rate=float(rate), absorb=float(absorb))
+
+
+def adapt_params(rate: float, absorb: float = 0.0) -> Tuple[int, int]:
+    """(a_bg, a_fg) = (rint(65536 rate), rint(65536 absorb)), both in 0..32768"""
+    s = check_adapt(rate, absorb)
+    a_bg, a_fg = int(np.rint(65536.0 * s["rate"])), int(np.rint(65536.0 * s["absorb"]))
+    assert 0 <= a_bg <= ops.MATTE_KEY_MAX_RATE and 0 <= a_fg <= ops.MATTE_KEY_MAX_RATE
+    return a_bg, a_fg
 
 
 def check_color(to) -> Tuple[int, int, int]:
@@ -158,6 +183,71 @@ def raw_ref(source, key, depth, matte: dict, key_settings: dict) -> np.ndarray:
     return front_ref(P, depth, matte["lo"], matte["hi"], matte["keep"], s["combine"])
 
 
+# ----------------------------------------------------------------------------- the adaptive plate's oracle (numpy)
+def _state(state) -> np.ndarray:
+    s = np.asarray(state.detach().cpu().numpy() if torch.is_tensor(state) else state)
+    if s.dtype == np.int16:                       # (the bits of uint16 words)
+        s = s.view(np.uint16)
+    if s.dtype != np.uint16 or s.ndim != 3 or s.shape[0] != 3 or (s.size and int(s.max()) > MAX_STATE):
+        raise ValueError(f"matte key adapt: a state is planar uint16 [3,H,W] with values up to {MAX_STATE}, got {s.dtype} {s.shape}")
+    return s
+
+
+def state_of(plate) -> np.ndarray:
+    """uint16 [3,H,W]: s = 256 k of a plate that arrives as planar uint8 bytes; `plate_bytes(state_of(k)) == k`"""
+    k = np.asarray(plate)
+    if k.dtype != np.uint8 or k.ndim != 3 or k.shape[0] != 3:
+        raise ValueError(f"matte key adapt: a plate is a planar uint8 [3,H,W] array, got {k.dtype} {k.shape}")
+    return (k.astype(np.uint16) << 8).astype(np.uint16)
+
+
+def plate_bytes(state) -> np.ndarray:
+    """uint8 [3,H,W]: k = (s + 128) >> 8, the plate byte the key compares against"""
+    return ((_state(state).astype(np.int64) + 128) >> 8).astype(np.uint8)
+
+
+def adapt_ref(state, source_bytes_, P0, a_bg: int, a_fg: int) -> np.ndarray:
+    """uint16 [3,H,W] s': a = (a_bg (255 - P0) + a_fg P0 + 127) // 255 per pixel, with P0 the uint8 [H,W] plane in front of
+    `invert`; per channel e = 256 b - s, s' = s + ((a e + 32768) >> 16), the shift arithmetic (towards minus infinity)"""
+    s = _state(state).astype(np.int64)
+    b = np.asarray(source_bytes_)
+    P0 = np.asarray(P0)
+    if b.dtype != np.uint8 or b.shape != s.shape or P0.dtype != np.uint8 or P0.shape != s.shape[1:]:
+        raise ValueError(f"matte key adapt: expected uint8 {s.shape} bytes and a uint8 {s.shape[1:]} plane, got {b.dtype} {b.shape}, "
+                         f"{P0.dtype} {P0.shape}")
+    for name, v in (("a_bg", a_bg), ("a_fg", a_fg)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= ops.MATTE_KEY_MAX_RATE:
+            raise ValueError(f"matte key adapt: {name}={v!r}: use an integer from 0 to {ops.MATTE_KEY_MAX_RATE}")
+    p = P0.astype(np.int64)
+    a = (int(a_bg) * (255 - p) + int(a_fg) * p + 127) // 255
+    e = 256 * b.astype(np.int64) - s
+    t = a[None] * e + 32768
+    assert np.abs(e).max(initial=0) <= MAX_STATE and a.max(initial=0) <= ops.MATTE_KEY_MAX_RATE
+    assert np.abs(a[None] * e).max(initial=0) + 32768 <= ops.MATTE_KEY_MAX_RATE * MAX_STATE + 32768 == 2139127808 < 1 << 31
+    n = s + (t >> 16)
+    assert n.min(initial=0) >= 0 and n.max(initial=0) <= MAX_STATE
+    return n.astype(np.uint16)
+
+
+def key_adapt_ref(source, state, *, lo: float, hi: float, luma: float = 0.0, radius: int = 1, invert: bool = False,
+                  rate: float = ADAPT_DEFAULTS["rate"], absorb: float = ADAPT_DEFAULTS["absorb"]) -> Tuple[np.ndarray, np.ndarray]:
+    """(P, s'): the plane `key_ref` gives against `plate_bytes(state)`, and the state moved towards the source's bytes under
+    that plane in front of `invert` -- L2D_OP_MATTE_KEY_ADAPT without the depth ramp"""
+    a_bg, a_fg = adapt_params(rate, absorb)
+    b = source_bytes(source)
+    P0 = plane_of(distance_ref(b, plate_bytes(state), luma), lo=lo, hi=hi, radius=radius)
+    return ((np.uint8(255) - P0) if invert else P0), adapt_ref(state, b, P0, a_bg, a_fg)
+
+
+def raw_adapt_ref(source, state, depth, matte: dict, key_settings: dict, adapt: dict) -> Tuple[np.ndarray, np.ndarray]:
+    """(fp32 [H,W], s'): `mask_io.front_ref` of `key_adapt_ref`'s plane under the matte's and the key's settings, and the next
+    state -- op 61 on the host"""
+    s = key_settings
+    P, nxt = key_adapt_ref(source, state, lo=s["lo"], hi=s["hi"], luma=s["luma"], radius=s["radius"], invert=s["invert"],
+                           rate=adapt["rate"], absorb=adapt["absorb"])
+    return front_ref(P, depth, matte["lo"], matte["hi"], matte["keep"], s["combine"]), nxt
+
+
 def plate_ref(image, H: int, W: int, resample: str = "lanczos") -> np.ndarray:
     """planar uint8 [3,H,W]: `backdrop.image_ref` (the largest centred window of the stream's aspect ratio, resampled to the
     stream's size) transposed -- a plate from an array, a PIL image or a path"""
@@ -171,15 +261,40 @@ class HipMatteKey:
     `plane` from a `MatteLine` slot's source: L2D_OP_MATTE_KEY against `settings["to"]` (a colour) or the plate, with `capture`
     L2D_OP_FRAME_PLANAR_BYTES of the same source in front of it, which makes that frame the plate.  The composites put the
     records at the head of their `OpList`; nothing is zeroed: every launch writes the whole plane (and a capture the whole
-    plate).  `plane` and `plate` may be the caller's: tests place them inside guarded buffers."""
+    plate).  `plane` and `plate` may be the caller's: tests place them inside guarded buffers.
 
-    def __init__(self, height: int, width: int, device="cuda:0", plane=None, plate=None):
+    With `adapt` ({rate, absorb}) `record` gives L2D_OP_MATTE_KEY_ADAPT in place of L2D_OP_MATTE_KEY: the plate lives in two
+    uint16 records that ping-pong (`states`, the caller's or made on first use; `cur` is the one the next launch reads), and
+    starts from the plate's bytes on the first frame behind `set_plate`, a capture or `restart`.  `repeated` runs the launch
+    with both rates 0, so that the plate is not fed the same frame twice."""
+
+    def __init__(self, height: int, width: int, device="cuda:0", plane=None, plate=None, states=None):
         if width % 8 or height < 1 or 3 * height * width >= 1 << 31:
             raise ValueError(f"HipMatteKey: width {width} must be a multiple of 8, height {height} at least 1 and 3 H W below 2^31")
         self.height, self.width, self.device = int(height), int(width), torch.device(device)
         self.plane = plane if plane is not None else torch.empty(self.height, self.width, dtype=torch.float32, device=self.device)
         self.plate = plate                   # planar uint8 [3,H,W], made by the first `set_plate` or capture
         self.has_plate = False
+        self.states = list(states) if states is not None else [None, None]       # planar uint16 [3,H,W] each, 8.8 fixed point
+        self.cur = 0                         # the record the next adaptive launch reads
+        self.from_plate = True               # the next adaptive frame starts from the plate's bytes
+
+    def _state(self, j: int) -> torch.Tensor:
+        if self.states[j] is None:
+            self.states[j] = torch.empty(3, self.height, self.width, dtype=torch.uint16, device=self.device)
+        return self.states[j]
+
+    def restart(self) -> None:
+        """the next adaptive frame starts from the plate's bytes again"""
+        self.from_plate = True
+
+    def current_plate(self) -> np.ndarray:
+        """the plate of this moment on the host, uint8 [H,W,3]: `plate_bytes` of the state while one runs, else the plate's own
+        bytes (a copy that waits for the device)"""
+        if not self.has_plate:
+            raise ValueError("HipMatteKey: no plate is set (set_plate, or a capture)")
+        k = self.plate.cpu().numpy() if self.from_plate else plate_bytes(self._state(self.cur).cpu().numpy())
+        return np.ascontiguousarray(k.transpose(1, 2, 0))
 
     def _plate(self) -> torch.Tensor:
         if self.plate is None:
@@ -193,11 +308,14 @@ class HipMatteKey:
             raise ValueError(f"HipMatteKey: a plate is planar uint8 [3,{self.height},{self.width}], got {t.dtype} {tuple(t.shape)}")
         self._plate().copy_(t, non_blocking=t.is_cuda)
         self.has_plate = True
+        self.from_plate = True
 
-    def record(self, slot, matte: dict, settings: dict, capture: bool = False, out: Optional[torch.Tensor] = None):
+    def record(self, slot, matte: dict, settings: dict, capture: bool = False, out: Optional[torch.Tensor] = None,
+               adapt: Optional[dict] = None, repeated: bool = False):
         """(records, keep, plane): `slot.source` (and with "and" / "or" `slot.depth` under the matte's ramp) under the key's
         `settings` ({to: a colour or "plate", lo, hi, luma, radius, combine, invert}) -> `plane`; `records` is a list of L2D
-        records, `keep` the tensors they name"""
+        records, `keep` the tensors they name.  `adapt` ({rate, absorb}): the plate follows the source (op 61 in place of op 59;
+        the records are good for one run each: the state advances with every call); `repeated`: with both rates 0"""
         from .matte import matte_params
         H, W = self.height, self.width
         s = check_settings(settings["lo"], settings["hi"], settings["luma"], settings["radius"], settings["combine"], settings["invert"])
@@ -208,6 +326,7 @@ class HipMatteKey:
             records.append(op)
             keep.extend(k)
             self.has_plate = True
+            self.from_plate = True
             to = "plate"
         if isinstance(to, str):
             if to != "plate" or not self.has_plate:
@@ -221,6 +340,19 @@ class HipMatteKey:
             lo32, inv32, ramp_hard = matte_params(matte["lo"], matte["hi"])
             kw = dict(lo32=lo32, inv32=inv32, ramp_hard=ramp_hard, far=matte["keep"] == "far")
         plane = self.plane if out is None else out
+        if adapt is not None:
+            if not isinstance(to, str):
+                raise ValueError(f"HipMatteKey: to={to!r}: adaptation needs a plate, not a colour")
+            a_bg, a_fg = (0, 0) if repeated else adapt_params(adapt["rate"], adapt["absorb"])
+            init = self.from_plate
+            nxt = self.cur if init else 1 - self.cur
+            op, k = ops.matte_key_adapt(slot.source, plane, slot.depth, self.plate if init else None, None if init else self._state(self.cur),
+                                        self._state(nxt), H=H, W=W, r=s["radius"], L=luma_weight(s["luma"]), lo2=lo2, inv=inv, hard=hard,
+                                        a_bg=a_bg, a_fg=a_fg, combine=s["combine"], invert=s["invert"], **kw)
+            self.cur, self.from_plate = nxt, False
+            records.append(op)
+            keep.extend(k)
+            return records, tuple(keep), plane
         op, k = ops.matte_key(slot.source, plane, slot.depth, key, H=H, W=W, r=s["radius"], L=luma_weight(s["luma"]), lo2=lo2, inv=inv,
                               hard=hard, combine=s["combine"], invert=s["invert"], **kw)
         records.append(op)
@@ -228,11 +360,11 @@ class HipMatteKey:
         return records, tuple(keep), plane
 
     def key(self, source: torch.Tensor, depth: Optional[torch.Tensor], matte: dict, settings: dict, capture: bool = False,
-            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+            out: Optional[torch.Tensor] = None, adapt: Optional[dict] = None, repeated: bool = False) -> torch.Tensor:
         """one fp16 [3,H,W] source frame (and its fp16 [H,W] depth plane) -> the raw matte plane, in one run on the current
         stream (tests and tools; the wrapper goes through the delay line and `record`)"""
         import types
-        records, keep, plane = self.record(types.SimpleNamespace(source=source, depth=depth), matte, settings, capture, out)
+        records, keep, plane = self.record(types.SimpleNamespace(source=source, depth=depth), matte, settings, capture, out, adapt, repeated)
         pl = _lib.OpList()
         for j, op in enumerate(records):
             pl.append(op, *(keep if j == 0 else ()))

@@ -2052,6 +2052,59 @@ def matte_key(source, out, depth, key, *, H, W, r, L, lo2, inv, hard, combine="r
     return op, keep
 
 
+MATTE_KEY_ADAPT_INIT = 256                        # l2d.h L2D_MATTE_KEY_ADAPT_INIT
+MATTE_KEY_MAX_RATE = 32768                        # l2d.h L2D_MATTE_KEY_MAX_RATE: 65536 times a rate of 1 / 2
+_STATE_DTYPES = (torch.uint16, torch.int16)       # (int16: the bits of uint16 words)
+
+
+def _overlap(a, b) -> bool:
+    """do the bytes of two tensors overlap (l2d.h px_overlap)?"""
+    if a is None or b is None:
+        return False
+    x, y = a.data_ptr(), b.data_ptr()
+    return x < y + b.numel() * b.element_size() and y < x + a.numel() * a.element_size()
+
+
+def matte_key_adapt(source, out, depth, plate, state_in, state_out, *, H, W, r, L, lo2, inv, hard, a_bg, a_fg, combine="replace",
+                    invert=False, lo32=0.0, inv32=0.0, ramp_hard=False, far=False):
+    """`matte_key` against a plate that follows drifting light (matte_key.key_adapt_ref): fp16 [3,H,W] `source` -> fp32 [H,W]
+    `out`, and the next state.  The state is the plate in 8.8 fixed point, a planar uint16 [3,H,W] tensor (or int16: the same
+    bits); `state_in` None: the state starts from `plate` (planar uint8 [3,H,W]; not read otherwise, and may be None then).
+    `a_bg`, `a_fg`: `matte_key.adapt_params`; the rest as `matte_key`'s.  `state_out` is the next launch's `state_in`: it may
+    overlap nothing the launch reads."""
+    init = state_in is None
+    if init and not torch.is_tensor(plate):
+        raise ValueError(f"matte_key_adapt: plate={plate!r}: without state_in the state starts from a plate tensor")
+    if not init and plate is not None and not torch.is_tensor(plate):
+        raise ValueError(f"matte_key_adapt: plate={plate!r}: use a plate tensor or None")
+    # (everything `matte_key` refuses; a record that reads a state is checked as one of a colour key)
+    op, _ = matte_key(source, out, depth, plate if init else (0, 0, 0), H=H, W=W, r=r, L=L, lo2=lo2, inv=inv, hard=hard, combine=combine,
+                      invert=invert, lo32=lo32, inv32=inv32, ramp_hard=ramp_hard, far=far)
+    for name, v in (("a_bg", a_bg), ("a_fg", a_fg)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= MATTE_KEY_MAX_RATE:
+            raise ValueError(f"matte_key_adapt: {name}={v!r}: use an integer from 0 to {MATTE_KEY_MAX_RATE} (65536 times a rate in [0, 0.5])")
+    for name, t in (("state_in", state_in), ("state_out", state_out)):
+        if t is None and name == "state_in":
+            continue
+        if not torch.is_tensor(t) or t.dtype not in _STATE_DTYPES or tuple(t.shape) != (3, H, W) or not t.is_contiguous() \
+                or t.data_ptr() % 16:
+            raise ValueError(f"matte_key_adapt: {name}: expected a contiguous, 16-byte aligned planar uint16 [3,{H},{W}] tensor, got "
+                             f"{getattr(t, 'dtype', None)} {tuple(getattr(t, 'shape', ()))}")
+    if combine == "replace":
+        depth = None
+    reads = (source, out, depth, plate if init else None, state_in)
+    if any(_overlap(state_out, t) for t in reads) or _overlap(out, state_in):
+        raise ValueError("matte_key_adapt: state_out overlaps state_in, the source, the plane, the depth plane or the plate (or the plane "
+                         "state_in): the two records ping-pong")
+    op.kind = _lib.OP_MATTE_KEY_ADAPT
+    op.i[3] = (op.i[3] & ~MATTE_KEY_PLATE) | (MATTE_KEY_ADAPT_INIT if init else 0)
+    op.i[5], op.i[6], op.i[7] = int(a_bg), int(a_fg), 0
+    keep = (source, out, depth, plate if init else None, state_in, state_out)
+    for j, t in enumerate(keep):
+        op.p[j] = _ptr(t)
+    return op, keep
+
+
 def frame_planar_bytes(source, out, *, H, W):
     """fp16 [3,H,W] `source` -> planar uint8 [3,H,W] `out`: its egress bytes (steady.source_bytes) -- the plate capture"""
     if source.dtype != torch.float16 or source.numel() != 3 * H * W or tuple(source.shape[-3:]) != (3, H, W) or not source.is_contiguous():

@@ -323,6 +323,8 @@ class StreamAnimateDiffusionDepthWrapper:
     _key_plate = None                       # the plate on the host, planar uint8 [3,H,W]: of an image, or captured on the host route
     _key_capture = False                    # the next composited output's source frame becomes the plate
     _key_dev = None                         # matte_key.HipMatteKey, made by the first keyed frame on the device
+    _key_adapt = None                       # the adaptive plate's settings beside the key (set_matte_key_adapt), None: the plate stays
+    _key_state = None                       # the adaptive plate on the host route, uint16 [3,H,W]; None: it starts from the plate
     depth_source = "detector"               # "input": every frame brings its own depth and no detector was built (`_setup` sets it)
 
     def __init__(self, config_path: str, few_step_model_type: str, num_inference_steps: int,
@@ -338,7 +340,8 @@ class StreamAnimateDiffusionDepthWrapper:
                  output_resample: str = "lanczos", matte_source: str = "stream", steady: Optional[dict] = None,
                  matte_edge: Optional[dict] = None, detail: Optional[dict] = None, depth_input: Optional[dict] = None,
                  depth_source: str = "detector", backdrop: Optional[dict] = None, steady_follow: Optional[dict] = None,
-                 matte_hold: Optional[dict] = None, mask_input: Optional[dict] = None, matte_key: Optional[dict] = None):
+                 matte_hold: Optional[dict] = None, mask_input: Optional[dict] = None, matte_key: Optional[dict] = None,
+                 matte_key_adapt: Optional[dict] = None):
         _check_depth_source(depth_source)
         self._check_keywords(few_step_model_type=few_step_model_type, acceleration=acceleration, cfg_type=cfg_type,
                              use_denoising_batch=use_denoising_batch, frame_buffer_size=frame_buffer_size, device_ids=device_ids,
@@ -360,13 +363,14 @@ class StreamAnimateDiffusionDepthWrapper:
                     similar_image_filter_max_skip_frame=similar_image_filter_max_skip_frame, jpeg_quality=jpeg_quality,
                     jpeg_decode=jpeg_decode, output_size=output_size, output_resample=output_resample, matte_source=matte_source,
                     steady=steady, matte_edge=matte_edge, detail=detail, depth_input=depth_input, depth_source=depth_source,
-                    backdrop=backdrop, steady_follow=steady_follow, matte_hold=matte_hold, mask_input=mask_input, matte_key=matte_key)
+                    backdrop=backdrop, steady_follow=steady_follow, matte_hold=matte_hold, mask_input=mask_input, matte_key=matte_key,
+                    matte_key_adapt=matte_key_adapt)
 
     @classmethod
     def from_components(cls, pipe, *, num_inference_steps: int, t_index_list: Optional[List[int]] = None,
                         strength: Optional[float] = None, **kw):
         """The wrapper around an already assembled `pipe` namespace (tests, synthetic weights).  Keywords: those of the
-        constructor that do not name files (`jpeg_quality`, `jpeg_decode`, `output_size`, `output_resample`, `matte_source`, `steady`, `steady_follow`, `matte_edge`, `matte_hold`, `detail`, `backdrop`, `depth_input`, `mask_input`, `matte_key` and `depth_source` among them; with `depth_source="input"` the namespace needs no `depth_model`), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
+        constructor that do not name files (`jpeg_quality`, `jpeg_decode`, `output_size`, `output_resample`, `matte_source`, `steady`, `steady_follow`, `matte_edge`, `matte_hold`, `detail`, `backdrop`, `depth_input`, `mask_input`, `matte_key`, `matte_key_adapt` and `depth_source` among them; with `depth_source="input"` the namespace needs no `depth_model`), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
         self = cls.__new__(cls)
         cls._check_keywords(**{k: kw.pop(k) for k in ("acceleration", "cfg_type", "use_denoising_batch", "frame_buffer_size",
                                                       "device_ids", "opt_unet", "few_step_model_type") if k in kw},
@@ -407,8 +411,11 @@ class StreamAnimateDiffusionDepthWrapper:
                scheduler_kwargs=None, frame_pipelining=False, enable_similar_image_filter=False,
                similar_image_filter_threshold=0.98, similar_image_filter_max_skip_frame=10, jpeg_quality=75, jpeg_decode="device",
                output_size=None, output_resample="lanczos", matte_source="stream", steady=None, matte_edge=None, detail=None,
-               depth_input=None, depth_source="detector", backdrop=None, steady_follow=None, matte_hold=None, mask_input=None, matte_key=None):
+               depth_input=None, depth_source="detector", backdrop=None, steady_follow=None, matte_hold=None, mask_input=None, matte_key=None,
+               matte_key_adapt=None):
         self._check_matte_source(matte_source)
+        if matte_key_adapt is not None and not isinstance(matte_key_adapt, dict):
+            raise ValueError(f"matte_key_adapt={matte_key_adapt!r}: use a dict of set_matte_key_adapt's keywords, or None")
         if matte_key is not None and not isinstance(matte_key, dict):
             raise ValueError(f"matte_key={matte_key!r}: use a dict of set_matte_key's keywords (with `to`), or None")
         if mask_input is not None and not isinstance(mask_input, dict):
@@ -486,6 +493,8 @@ class StreamAnimateDiffusionDepthWrapper:
             if "to" not in matte_key:
                 raise ValueError(f"matte_key={matte_key!r}: the dict needs `to` (a colour, an image or 'capture')")
             self._set_matte_key(**matte_key, needs_matte=False)      # (no matte can be set yet: the key waits for the first set_matte)
+        if matte_key_adapt is not None:
+            self.set_matte_key_adapt(**matte_key_adapt)
 
     # ------------------------------------------------------------------ depth from the caller (depth_io.py)
     @property
@@ -650,7 +659,8 @@ class StreamAnimateDiffusionDepthWrapper:
         frame the near-duplicate filter repeats is keyed again from the same slot.  A key and a caller's mask exclude each
         other.  May be called between any two frames; the change applies from the next output and restarts a matte hold.  The
         constructor's `matte_key=` (a dict of these keywords, `to` among them) is set before any matte can be: it waits for
-        the first `set_matte`."""
+        the first `set_matte`.  A plate is a frozen picture: `set_matte_key_adapt` lets it follow drifting light (and then
+        refuses a colour here)."""
         self._set_matte_key(to, lo=lo, hi=hi, luma=luma, radius=radius, combine=combine, invert=invert)
 
     def _set_matte_key(self, to, lo=None, hi=None, luma=None, radius=1, combine="replace", invert=False, needs_matte=True) -> None:
@@ -663,6 +673,9 @@ class StreamAnimateDiffusionDepthWrapper:
         color = MK.is_color(to)
         if isinstance(to, (tuple, list)) and not color:
             MK.check_color(to)
+        if color and self._key_adapt is not None:
+            raise ValueError(f"set_matte_key: to={to!r}: the adaptive plate (set_matte_key_adapt) needs a plate, not a colour: call "
+                             "clear_matte_key_adapt first")
         settings = MK.check_settings(lo, hi, luma, radius, combine, invert, plate=not color)
         plate = None
         if color:
@@ -678,6 +691,7 @@ class StreamAnimateDiffusionDepthWrapper:
         self._key, self._key_capture, self._key_plate = settings, capture, plate
         if self._key_dev is not None and plate is not None:
             self._key_dev.set_plate(plate)
+        self._restart_key_state()          # (a new image or a new capture: the adaptive plate starts from it)
         self._hold_init = True             # (a held matte starts again from the new raw matte)
 
     def capture_matte_plate(self) -> None:
@@ -689,14 +703,79 @@ class StreamAnimateDiffusionDepthWrapper:
         self._hold_init = True
 
     def clear_matte_key(self) -> None:
-        """No key: the frame is cut by the depth ramp alone again; no launch or buffer of the key is left in the frame's path."""
+        """No key: the frame is cut by the depth ramp alone again; no launch or buffer of the key is left in the frame's path.
+        The adaptive plate (`set_matte_key_adapt`) goes with it."""
         self._key = self._key_plate = self._key_dev = None
+        self._key_adapt = self._key_state = None
         self._key_capture = False
         self._hold_init = True
 
-    def _key_front(self, slot, device):
+    # ------------------------------------------------------------------ the adaptive plate (matte_key.py, DESIGN.md section 8.z18)
+    @property
+    def matte_key_adapt(self) -> Optional[dict]:
+        """the adaptive plate's settings as {rate, absorb}, or None"""
+        return None if self._key_adapt is None else dict(self._key_adapt)
+
+    def set_matte_key_adapt(self, rate: float = 1.0 / 32.0, absorb: float = 0.0) -> None:
+        """Let the plate of a matte key follow drifting light.  A plate is a frozen picture of the empty room: a cloud, a lamp
+        warming up or a camera's exposure settling moves every background pixel off it, and once the distance passes `lo` the
+        whole wall turns into subject.  With this setting the plate moves after every keyed frame towards that frame's source
+        (`matte_key.key_adapt_ref`): by `rate` of the way where the key says background, by `absorb` of the way where it says
+        subject, in between under a soft key.  Both lie in [0, 0.5].  `absorb=0` never takes the subject into the plate, and
+        something that is put down and left there stays subject for good; a small `absorb` lets it sink into the background
+        in about 1 / `absorb` frames -- and a person who sits still with it.  The defaults, 1 / 32 and 0, are a guess, not
+        tuned on camera footage.  The plate is kept in 8.8 fixed point, so that a slow rate does move it.
+
+        A setting beside the key, like `set_steady_follow` beside `set_steady`: it needs a key against a plate
+        (`set_matte_key` with an image or "capture"), a colour key refuses it, and `clear_matte_key` and `clear_matte` clear
+        it.  On the device one launch (L2D_OP_MATTE_KEY_ADAPT) takes the key's place in the composite's list; it writes the
+        key's plane as before, so everything behind it is unchanged.  A frame the near-duplicate filter repeats is keyed again
+        but does not move the plate.  A new image or a new capture starts the plate again; a change of the rates does not.
+        `matte_key_plate()` returns the plate of this moment.  May be called between any two frames; the change applies from
+        the next output and restarts a matte hold."""
+        from .matte_key import check_adapt
+        settings = check_adapt(rate, absorb)
+        if self._key is None:
+            raise ValueError("set_matte_key_adapt: the adaptive plate needs a matte key against a plate: call set_matte_key with an image "
+                             "or 'capture' first")
+        if not isinstance(self._key["to"], str):
+            raise ValueError(f"set_matte_key_adapt: the key is the colour {self._key['to']!r}: adaptation needs a plate (set_matte_key with "
+                             "an image or 'capture')")
+        if self._key_adapt is None:
+            self._restart_key_state()      # (switched on: the plate of the key, not what an earlier run left)
+        self._key_adapt = settings
+        self._hold_init = True
+
+    def clear_matte_key_adapt(self) -> None:
+        """The plate stays as it was set or captured again: the key's own launch, and no buffer of the adaptive plate in the
+        frame's path."""
+        self._key_adapt = None
+        self._restart_key_state()
+        self._hold_init = True
+
+    def _restart_key_state(self) -> None:
+        self._key_state = None
+        if self._key_dev is not None:
+            self._key_dev.restart()
+
+    def matte_key_plate(self) -> np.ndarray:
+        """The plate of this moment as uint8 [H,W,3]: the adaptive plate's bytes (`matte_key.plate_bytes` of its state) while
+        one runs, else the plate as it was set or captured.  On the device a copy to the host that waits for the stream.
+        ValueError without a plate: no key, a colour key, or a capture that has not happened yet."""
+        if self._key is None or not isinstance(self._key["to"], str):
+            raise ValueError("matte_key_plate: no matte key against a plate is set")
+        if self._key_dev is not None and self._key_dev.has_plate and not self._key_capture:
+            return self._key_dev.current_plate()
+        if self._key_state is not None:
+            from .matte_key import plate_bytes
+            return np.ascontiguousarray(plate_bytes(self._key_state).transpose(1, 2, 0))
+        if self._key_plate is None or self._key_capture:
+            raise ValueError("matte_key_plate: no plate yet: the capture waits for the next composited output")
+        return np.ascontiguousarray(np.asarray(self._key_plate).transpose(1, 2, 0))
+
+    def _key_front(self, slot, device, repeated: bool = False):
         """`(records, keep, plane)` of L2D_OP_MATTE_KEY for the slot's source under the settings of this moment (on a capturing
-        frame L2D_OP_FRAME_PLANAR_BYTES in front of it), or None"""
+        frame L2D_OP_FRAME_PLANAR_BYTES in front of it), or None; with an adaptive plate L2D_OP_MATTE_KEY_ADAPT in its place"""
         if slot is None or self._key is None or self._matte is None:
             return None
         if self._key_dev is None:
@@ -705,16 +784,28 @@ class StreamAnimateDiffusionDepthWrapper:
             if self._key_plate is not None:
                 self._key_dev.set_plate(self._key_plate)
         capture, self._key_capture = self._key_capture, False
-        return self._key_dev.record(slot, self._matte, self._key, capture=capture)
+        if self._key_adapt is None:
+            return self._key_dev.record(slot, self._matte, self._key, capture=capture)        # (the parent's call)
+        return self._key_dev.record(slot, self._matte, self._key, capture=capture, adapt=self._key_adapt, repeated=repeated)
 
-    def _key_plane(self, slot) -> Optional[np.ndarray]:
-        """the raw matte of the key on the host route, fp32 [H,W]: `matte_key.raw_ref` where op 59 would run; or None"""
+    def _key_plane(self, slot, repeated: bool = False) -> Optional[np.ndarray]:
+        """the raw matte of the key on the host route, fp32 [H,W]: `matte_key.raw_ref` where op 59 would run (`raw_adapt_ref`
+        where op 61 would, on a uint16 state kept here); or None"""
         if slot is None or self._key is None or self._matte is None:
             return None
         from .matte_key import raw_ref
         from .steady import source_bytes
         if self._key_capture:
             self._key_capture, self._key_plate = False, source_bytes(slot.source)
+            self._key_state = None
+        if self._key_adapt is not None:
+            from .matte_key import raw_adapt_ref, state_of
+            if self._key_plate is None:
+                raise ValueError("matte key: no plate is set")
+            state = state_of(self._key_plate) if self._key_state is None else self._key_state
+            raw, self._key_state = raw_adapt_ref(slot.source, state, slot.depth[None], self._matte, self._key,
+                                                 dict(rate=0.0, absorb=0.0) if repeated else self._key_adapt)
+            return raw
         key = self._key["to"]
         if isinstance(key, str):
             if self._key_plate is None:
@@ -1624,7 +1715,7 @@ class StreamAnimateDiffusionDepthWrapper:
             held = {}                       # (the keywords only with a hold or a mask: without them the calls are the parent's)
             if slot is not None and self._hold is not None:
                 held["hold"] = self._hold_step(dev, repeated)
-            front = self._key_front(slot, dev) if self._key is not None else self._mask_front(slot)
+            front = self._key_front(slot, dev, repeated) if self._key is not None else self._mask_front(slot)
             bdk = {}
             if front is not None:
                 held["mask"] = front
@@ -1663,7 +1754,7 @@ class StreamAnimateDiffusionDepthWrapper:
             if slot is not None:
                 from .matte import composite_ref
                 more = {}                   # (the keyword only with a backdrop: without one the call is the parent's)
-                raw = self._key_plane(slot) if self._key is not None else self._mask_plane(slot)
+                raw = self._key_plane(slot, repeated) if self._key is not None else self._mask_plane(slot)
                 if self._backdrop is not None and not self._matte["show"]:
                     from .backdrop import stream_ref
                     more["backdrop"] = stream_ref(self._backdrop, self._backdrop_image_host(), slot.source, slot.depth, self._matte,

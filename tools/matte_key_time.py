@@ -5,11 +5,13 @@
 L2D_OP_MATTE_KEY at 512x512 in both variants (a colour key and a plate key; radius 0, 1 and 4; "replace", and "and" at radius 1)
 and L2D_OP_FRAME_PLANAR_BYTES, beside L2D_OP_FRAME_MATTE_HOLD (radius 2, from the depth plane) -- the op whose tile form op 59
 takes -- in the same run: device events around `--reps` back-to-back replays after a warm-up, the median of five runs
-(microseconds per launch).  `tools/mask_time.py kernels` on the same box gives op 58's figures."""
+(microseconds per launch).  `tools/mask_time.py kernels` on the same box gives op 58's figures.  L2D_OP_MATTE_KEY_ADAPT (the adaptive plate, section 8.z18)
+follows in the same run, INIT and STATE at the same radii: its yardstick is op 59 with a plate."""
 import argparse
 import os
 import sys
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,7 +26,7 @@ from steady_time import say  # noqa: E402
 def kernels(args):
     from live2diff_amd import _lib, ops
     from live2diff_amd.matte import matte_params
-    from live2diff_amd.matte_key import key_params, luma_weight
+    from live2diff_amd.matte_key import adapt_params, key_params, luma_weight, state_of
     from live2diff_amd.steady import steady_params
     dev, H, W = "cuda", 512, 512
     say(args.out, f"# matte_key_time: {_lib.device_name()}, {args.reps} back-to-back replays per figure (device events), median of 5 runs, "
@@ -43,6 +45,19 @@ def kernels(args):
             med[name, r] = _timed(args.out, args.reps, f"op 59 matte key, {name}, r = {r}, replace", ops.matte_key(src, plane, None, key, r=r, **kw))
         _timed(args.out, args.reps, f"op 59 matte key, {name}, r = 1, and",
                ops.matte_key(src, plane, depth, key, r=1, combine="and", lo32=lo32, inv32=inv32, ramp_hard=ramp_hard, **kw))
+    # the adaptive plate: the state read is the plate's own, the state written another record (they ping-pong)
+    state = torch.from_numpy(state_of(plate.cpu().numpy()).view(np.int16)).to(dev)
+    nxt = torch.empty_like(state)
+    a_bg, a_fg = adapt_params(1 / 32, 0.0)
+    for name, pl, st in (("init", plate, None), ("state", None, state)):
+        for r in (0, 1, 4):
+            med[name, r] = _timed(args.out, args.reps, f"op 61 matte key adapt, {name}, r = {r}, replace",
+                                  ops.matte_key_adapt(src, plane, None, pl, st, nxt, r=r, a_bg=a_bg, a_fg=a_fg, **kw))
+        _timed(args.out, args.reps, f"op 61 matte key adapt, {name}, r = 1, and",
+               ops.matte_key_adapt(src, plane, depth, pl, st, nxt, r=1, a_bg=a_bg, a_fg=a_fg, combine="and", lo32=lo32, inv32=inv32,
+                                   ramp_hard=ramp_hard, **kw))
+    say(args.out, "op 61 against op 59 with a plate: " + ", ".join(
+        f"{name} r = {r} {med[name, r] / med['plate', r]:.2f} x" for name in ("init", "state") for r in (0, 1, 4)))
     bytes_ = torch.empty(3, H, W, dtype=torch.uint8, device=dev)
     _timed(args.out, args.reps, "op 60 frame planar bytes (the plate capture)", ops.frame_planar_bytes(src, bytes_, H=H, W=W))
     # the tile form's owner, in the same run: op 57 from the depth plane, radius 2, a steady state frame

@@ -89,7 +89,14 @@ six hex digits are a key colour (a green screen: `00b140`), a path is a clean pl
 that does not move), `capture` takes the plate from the stream's next output.  It needs `--matte` and excludes `--mask`.  `POST
 /matte-key` with the same text changes it while the stream runs, an empty body or `off` clears it; `POST /matte-key/capture` (no
 body) takes the plate again with the settings kept; `GET /matte-key` answers the current settings as JSON (`to` is the colour,
-`"plate"` or, until it has happened, `"capture"`; `null`: off).  A body the routes refuse gets a 400 and is counted."""
+`"plate"` or, until it has happened, `"capture"`; `null`: off).  A body the routes refuse gets a 400 and is counted.
+
+`--matte-key-adapt RATE[,ABSORB]` lets the plate of the key follow drifting light (`wrapper.set_matte_key_adapt`): after every
+frame the plate moves by RATE of the way towards the frame where the key says background, by ABSORB of the way (default 0) where
+it says subject; both lie in [0, 0.5].  It needs a `--matte-key` against a plate (a path or `capture`).  `POST /matte-key/adapt`
+with the same text changes it while the stream runs, an empty body or `off` clears it; `GET /matte-key` then carries `"adapt":
+{"rate": ..., "absorb": ...}`.  `GET /matte-key/plate` answers the plate of this moment as a JPEG file (404 while there is
+none): the producer hands it over between two frames."""
 import argparse
 import json
 import os
@@ -536,20 +543,57 @@ def parse_matte_key_arg(text: str):
     return dict(s, to=to)
 
 
+def parse_matte_key_adapt_arg(text: str):
+    """`RATE[,ABSORB]` -> the keywords of `wrapper.set_matte_key_adapt`; `off` or nothing -> None; ValueError otherwise"""
+    from live2diff_amd.matte_key import check_adapt
+    text = text.strip()
+    if text in ("", "off"):
+        return None
+    parts = [t.strip() for t in text.split(",")]
+    if not 1 <= len(parts) <= 2:
+        raise ValueError(f"matte key adapt {text!r}: use RATE[,ABSORB] or off")
+    try:
+        rate, absorb = float(parts[0]), (float(parts[1]) if len(parts) > 1 else 0.0)
+    except ValueError:
+        raise ValueError(f"matte key adapt {text!r}: RATE and ABSORB are numbers in [0, 0.5]") from None
+    return check_adapt(rate, absorb)
+
+
 class MatteKeyBox:
     """What `POST /matte-key` and `POST /matte-key/capture` deliver: the newest requested key (a dict of `set_matte_key` keywords,
     or None for an empty body or `off`) and a request to take the plate again, applied by the producer between two frames.
     `current` is what was last applied (the `matte_key` property, with the colour as a list); `failed` counts bodies the route
-    refused with a 400 and requests the wrapper refused (no matte, a sticky mask, a capture without a key)."""
+    refused with a 400 and requests the wrapper refused (no matte, a sticky mask, a capture without a key).  `POST
+    /matte-key/adapt` delivers the adaptive plate's setting the same way (`current` then carries `adapt`), and `GET
+    /matte-key/plate` asks the producer for the plate of this moment: `take_plate` waits up to `plate_wait` seconds for it."""
     _NOTHING = object()
+    plate_wait = 2.0
 
-    def __init__(self, current=None):
+    def __init__(self, current=None, adapt=None):
         self._lock = threading.Lock()
-        self.current, self._want, self._capture, self.failed = self.view(current), self._NOTHING, False, 0
+        self._plate_ready = threading.Condition(self._lock)
+        self.current, self._want, self._capture, self.failed = self.view(current, adapt), self._NOTHING, False, 0
+        self._adapt, self._want_plate, self._plate = self._NOTHING, False, None
 
     @staticmethod
-    def view(key):
-        return None if key is None else dict(key, to=list(key["to"]) if isinstance(key["to"], tuple) else key["to"])
+    def view(key, adapt=None):
+        if key is None:
+            return None
+        out = dict(key, to=list(key["to"]) if isinstance(key["to"], tuple) else key["to"])
+        return out if adapt is None else dict(out, adapt=dict(adapt))
+
+    def put_adapt(self, settings) -> None:
+        with self._lock:
+            self._adapt = settings
+
+    def take_plate(self):
+        """(a handler thread) the plate the producer last handed over, uint8 [H,W,3], or None: asks for one and waits for it"""
+        with self._plate_ready:
+            if self._plate is None:
+                self._want_plate = True
+                self._plate_ready.wait_for(lambda: self._plate is not None, timeout=self.plate_wait)
+            plate, self._plate = self._plate, None
+            return plate
 
     def put(self, settings) -> None:
         with self._lock:
@@ -568,6 +612,8 @@ class MatteKeyBox:
         with self._lock:
             want, self._want = self._want, self._NOTHING
             capture, self._capture = self._capture, False
+            adapt, self._adapt = self._adapt, self._NOTHING
+            want_plate, self._want_plate = self._want_plate, False
         try:
             if want is None:
                 wrapper.clear_matte_key()
@@ -580,7 +626,22 @@ class MatteKeyBox:
                 wrapper.capture_matte_plate()
         except ValueError:
             self.refused()
-        self.current = self.view(wrapper.matte_key)
+        try:
+            if adapt is None:
+                wrapper.clear_matte_key_adapt()
+            elif adapt is not self._NOTHING:
+                wrapper.set_matte_key_adapt(**adapt)
+        except ValueError:                         # (no key, or a colour key)
+            self.refused()
+        self.current = self.view(wrapper.matte_key, getattr(wrapper, "matte_key_adapt", None))
+        if want_plate:
+            try:
+                plate = wrapper.matte_key_plate()
+            except ValueError:                     # (no plate at this moment: the request stays unanswered, the route says 404)
+                plate = None
+            with self._plate_ready:
+                self._plate = plate
+                self._plate_ready.notify_all()
 
 
 def parse_matte_edge_arg(text: str):
@@ -903,6 +964,23 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
                 self.send_header("Content-Length", str(len(body)))
                 self.end_headers()
                 self.wfile.write(body)
+            elif self.path == "/matte-key/plate" and keys is not None:
+                plate = keys.take_plate()
+                if plate is None:
+                    self.send_error(404, "no plate at this moment (no key against a plate, a capture that waits, or no stream)")
+                    return
+                import io
+
+                from PIL import Image
+                buf = io.BytesIO()
+                Image.fromarray(plate).save(buf, "JPEG", quality=90)
+                body = buf.getvalue()
+                self.send_response(200)
+                self.send_header("Content-Type", "image/jpeg")
+                self.send_header("Cache-Control", "no-store")
+                self.send_header("Content-Length", str(len(body)))
+                self.end_headers()
+                self.wfile.write(body)
             elif boxes.get(self.path) is not None or (masks is not None and self.path in ("/mask", "/mask-input")):
                 current = (boxes[self.path].current if self.path in boxes else
                            masks.current if self.path == "/mask" else masks.current_input)
@@ -981,6 +1059,8 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
                     if body.strip():
                         raise ValueError("POST /matte-key/capture takes no body")
                     keys.capture()
+                elif self.path == "/matte-key/adapt":
+                    keys.put_adapt(parse_matte_key_adapt_arg(body.decode()))
                 else:
                     keys.put(parse_matte_key_arg(body.decode()))
             except ValueError as e:                       # (UnicodeDecodeError is a ValueError)
@@ -1046,7 +1126,7 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
             if masks is not None and self.path in ("/mask", "/mask-input"):
                 self.do_mask()
                 return
-            if keys is not None and self.path in ("/matte-key", "/matte-key/capture"):
+            if keys is not None and self.path in ("/matte-key", "/matte-key/capture", "/matte-key/adapt"):
                 self.do_matte_key()
                 return
             if inbox is None or self.path != "/frame":
@@ -1226,6 +1306,11 @@ def main(argv=None):
                     help="cut the frame by a colour (a green screen), by a clean plate (an image of the empty room) or by a plate "
                          "captured from the stream's next output; needs --matte; POST /matte-key with the same text changes it "
                          "between two frames, `off` clears it, POST /matte-key/capture takes the plate again")
+    ap.add_argument("--matte-key-adapt", default=None, metavar="RATE[,ABSORB]",
+                    help="let the plate of --matte-key follow drifting light: it moves by RATE of the way towards each frame where the key "
+                         "says background, by ABSORB (default 0) where it says subject, both in [0, 0.5]; needs a --matte-key against a "
+                         "plate (a path or capture); POST /matte-key/adapt with the same text changes it between two frames, `off` clears "
+                         "it; GET /matte-key/plate answers the plate of this moment as a JPEG")
     ap.add_argument("--mask-input", default=None, metavar="COMBINE[,invert]",
                     help="how a mask meets the depth ramp: replace (default), and, or; `invert` flips the mask first; POST /mask-input "
                          "with the same text changes it between frames")
@@ -1237,6 +1322,13 @@ def main(argv=None):
         ap.error("--matte-key and --mask exclude each other")
     try:
         matte_key = parse_matte_key_arg(ap_key) if ap_key else None
+    except ValueError as e:
+        ap.error(str(e))
+    ap_adapt = args.matte_key_adapt
+    if ap_adapt is not None and (matte_key is None or isinstance(matte_key["to"], tuple)):
+        ap.error("--matte-key-adapt needs a --matte-key against a plate (a path or capture), not a colour")
+    try:
+        matte_key_adapt = parse_matte_key_adapt_arg(ap_adapt) if ap_adapt else None
     except ValueError as e:
         ap.error(str(e))
     if args.mask is not None and not args.matte:
@@ -1307,7 +1399,9 @@ def main(argv=None):
     masks = MaskBox(mask_size, w.mask_input)
     if matte_key is not None:
         w.set_matte_key(**matte_key)
-    keys = MatteKeyBox(w.matte_key)
+    if matte_key_adapt is not None:
+        w.set_matte_key_adapt(**matte_key_adapt)
+    keys = MatteKeyBox(w.matte_key, w.matte_key_adapt)
     prompt = args.prompt if args.prompt is not None else str(cfg.get("prompt", ""))
     latest, stop = Latest(), threading.Event()
     inbox = Inbox(sink) if post else None
