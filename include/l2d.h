@@ -628,6 +628,32 @@ enum {
  *   16-byte loads (element loads for the edge pixel a group beside the image repeats).  Every element of p1 and p5 is written by
  *   a plain store on every launch: nothing has to be zeroed, no atomics.  Refused: everything L2D_OP_MATTE_KEY refuses, a rate out
  *   of range, p5 (without INIT also p4) null or misaligned, INIT without p3, p5 overlapping p0 .. p4, p1 overlapping p4.
+ * L2D_OP_MATTE_KEY_GAIN_HIST  one launch (the plate gain's samples; live2diff_amd/matte_key.py gain_hist_ref):  p0 source half
+ *   [3][H][W] (16-byte aligned) p1 plate uint8 [3][H][W], planar (8-byte aligned), or with L2D_MATTE_KEY_GAIN_STATE the state
+ *   uint16 [3][H][W] of L2D_OP_MATTE_KEY_ADAPT (16-byte aligned), whose byte is k = (s + 128) >> 8 p2 partials uint32
+ *   [nblk][3][512] (16-byte aligned) ; i0 H i1 W (W % 8 == 0, 3 H W < 2^31) i2 flags (L2D_MATTE_KEY_GAIN_STATE) i3 nblk =
+ *   ceil(H W / L2D_MATTE_KEY_GAIN_BLOCK).  Per pixel and channel, with b the egress byte of p0: the sample is valid when 16 <= k
+ *   <= 239 and 4 <= b <= 251; q = min(511, (128 b + (k >> 1)) / k), the floor exactly; partial[block][c][q] counts the block's
+ *   valid samples.  One work-group of 512 lanes per L2D_MATTE_KEY_GAIN_BLOCK consecutive pixels (the last one ragged), 8 pixels
+ *   per lane: 16-byte loads of the fp16 rows, 8-byte loads of the plate (16-byte loads of the state); the block's
+ *   histogram is held in 6,144 bytes of LDS under integer LDS atomics (sums do not depend on order) and every entry of its
+ *   partial is written by a plain store: nothing has to be zeroed, no atomics on global memory.  Refused: a null or misaligned
+ *   pointer, W % 8 != 0, 3 H W >= 2^31, unknown flags, an nblk that is not ceil(H W / L2D_MATTE_KEY_GAIN_BLOCK), p2 overlapping
+ *   p0 or p1.
+ * L2D_OP_MATTE_KEY_GAIN  one launch (the plate gain; live2diff_amd/matte_key.py gain_of):  p0 partials uint32 [nblk][3][512] p1
+ *   record int32 [8] (both 16-byte aligned) ; i0 H i1 W i2 nblk (as L2D_OP_MATTE_KEY_GAIN_HIST's) i3 lim = rint(128 limit)
+ *   (128..511) i4 min_count (0..H W).  hist[c][q] = the sum of the partials; n_c = the sum of hist[c]; g_c = 128 if n_c <
+ *   min_count, else the smallest q with 2 cum_c(q) >= n_c (the lower median) clamped to [ceil(16384 / lim), lim]; the record is
+ *   {g_r, g_g, g_b, n_r, n_g, n_b, 0, 0}, in units of 1 / 128.  One work-group of 1,024 lanes: lanes j and 512 + j sum bin j of each
+ *   channel over the even and the odd partials, an inclusive scan in 6,144 bytes of LDS finds the medians; plain stores.  Every count is at most H W < 2^31
+ *   / 3, so 2 cum fits 32 bits.  Refused: a null or misaligned pointer, W % 8 != 0, 3 H W >= 2^31, an nblk that does not match H
+ *   W, lim or min_count out of range, p1 overlapping p0.
+ * L2D_MATTE_KEY_GAIN on L2D_OP_MATTE_KEY (with L2D_MATTE_KEY_PLATE) and L2D_OP_MATTE_KEY_ADAPT:  p6 record int32 [8] of
+ *   L2D_OP_MATTE_KEY_GAIN (16-byte aligned; g_c in 0..511, read by ordinary loads).  The key's byte becomes k' = min(255, (g_c k +
+ *   64) >> 7) (g_c k + 64 <= 511 * 255 + 64 < 2^17; g_c = 128: k' = k, the unflagged launch bit for bit) and everything else is as
+ *   without: under L2D_OP_MATTE_KEY_ADAPT the state still moves towards the source's own bytes, e = 256 b - s.  Compile-time
+ *   variants of the same tile body (13,824 bytes of LDS).  Refused: the flag with a colour key, p6 null or misaligned, p1
+ *   (L2D_OP_MATTE_KEY_ADAPT: or p5) overlapping p6.
  */
 enum {
     L2D_OP_IGEMM = 1,
@@ -691,6 +717,8 @@ enum {
     L2D_OP_MATTE_KEY = 59,
     L2D_OP_FRAME_PLANAR_BYTES = 60,
     L2D_OP_MATTE_KEY_ADAPT = 61,
+    L2D_OP_MATTE_KEY_GAIN_HIST = 62,
+    L2D_OP_MATTE_KEY_GAIN = 63,
 };
 
 /* flag bits of L2D_OP_FRAME_MATTE (i4) and L2D_OP_FRAME_MATTE_UP (i6); HARD and FAR also of L2D_OP_FRAME_MATTE_EDGE (i3) */
@@ -769,6 +797,12 @@ enum {
 /* L2D_OP_MATTE_KEY_ADAPT: its flags (i3) are L2D_OP_MATTE_KEY's and INIT; its largest rate */
 #define L2D_MATTE_KEY_ADAPT_INIT 256 /* the state starts from the plate p3: s = 256 k, and p4 is not read */
 #define L2D_MATTE_KEY_MAX_RATE 32768 /* 65536 times a rate of 1 / 2 */
+/* the plate gain: a flag of L2D_OP_MATTE_KEY and L2D_OP_MATTE_KEY_ADAPT (i3), the flag of L2D_OP_MATTE_KEY_GAIN_HIST (i2), sizes */
+#define L2D_MATTE_KEY_GAIN 512 /* the key is formed against the plate's bytes times the gains of the record p6 */
+#define L2D_MATTE_KEY_GAIN_STATE 1 /* L2D_OP_MATTE_KEY_GAIN_HIST: p1 is the uint16 state, not the uint8 plate */
+#define L2D_MATTE_KEY_GAIN_UNITY 128 /* a gain is an integer in units of 1 / 128 */
+#define L2D_MATTE_KEY_GAIN_BINS 512 /* the ratios 0..511; 511 holds everything above */
+#define L2D_MATTE_KEY_GAIN_BLOCK 4096 /* pixels per work-group of L2D_OP_MATTE_KEY_GAIN_HIST: 64 blocks at 512 x 512 */
 
 /* sizes of L2D_OP_FRAME_RESIZE */
 #define L2D_RESIZE_MAX_KS 13 /* taps per output: Lanczos (support 3) at a 2x down-scale, 2 * 6 + 1 */

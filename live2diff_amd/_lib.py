@@ -42,6 +42,8 @@ OP_MASK_INGEST = 58
 OP_MATTE_KEY = 59
 OP_FRAME_PLANAR_BYTES = 60
 OP_MATTE_KEY_ADAPT = 61
+OP_MATTE_KEY_GAIN_HIST = 62
+OP_MATTE_KEY_GAIN = 63
 ABI_VERSION = 6
 
 

@@ -605,7 +605,7 @@ def _mask_head(pl, mask) -> Optional[torch.Tensor]:
     """a composite's `mask=`: None, or `(record, keep, plane)` of L2D_OP_MASK_INGEST -- appended first, in front of the
     backdrop's records, which read its plane too.  A matte key (`matte_key.HipMatteKey.record`) hands in a list of records in
     the same form: L2D_OP_MATTE_KEY (L2D_OP_MATTE_KEY_ADAPT with an adaptive plate), with a capture L2D_OP_FRAME_PLANAR_BYTES in
-    front of it."""
+    front of it, and with a plate gain L2D_OP_MATTE_KEY_GAIN_HIST and L2D_OP_MATTE_KEY_GAIN between the two."""
     if mask is None:
         return None
     op, keep, plane = mask

@@ -19,7 +19,14 @@ The adaptive plate: a plate is a frozen record, and a 
 settling moves every background pixel off it.  With adaptation the plate is a state, uint16 [3,H,W] in 8.8 fixed point, that
 moves after each keyed frame a little towards the frame's source where the key says "background" (`rate`) and not, or much more
 slowly, where it says "subject" (`absorb`).  `key_adapt_ref` restates L2D_OP_MATTE_KEY_ADAPT in exact integers; with both rates 0
-it is `key_ref` against the plate on every frame.  `ADAPT_DEFAULTS` are a guess too, untuned on camera footage."""
+it is `key_ref` against the plate on every frame.  `ADAPT_DEFAULTS` are a guess too, untuned on camera footage.
+
+The plate gain: a camera's auto-exposure or auto-white-balance moves every background pixel at once,
+and the adaptive plate follows only at `rate`.  With the gain every keyed frame first measures one gain per channel between the
+plate and the frame's source -- the lower median of the per-pixel ratios b / k in units of 1 / 128 (`gain_hist_ref`, `gain_of`)
+-- and is then keyed against the plate times that gain (`gain_plate`).  A gain of 128 is unity and gives the plate's own bytes,
+so `key_ref` and `key_adapt_ref` with `gain=(128, 128, 128)` are what they are without.  The median holds while the subject
+covers less than half of the valid samples; past that it measures the subject (see `gain_of`).  `GAIN_DEFAULTS` are a guess."""
 from typing import Optional, Tuple
 
 import numpy as np
@@ -38,6 +45,10 @@ PLATE_DEFAULTS = dict(DEFAULTS, luma=0.25)
 ADAPT_DEFAULTS = dict(rate=1.0 / 32.0, absorb=0.0)        # untuned on camera footage
 MAX_RATE = 0.5                                    # the state moves at most half way per frame
 MAX_STATE = 255 * 256                             # a plate byte in 8.8 fixed point
+GAIN_DEFAULTS = dict(limit=2.0, min_share=1.0 / 16.0)      # untuned on camera footage
+GAIN_UNITY = ops.MATTE_KEY_GAIN_UNITY             # a gain is an integer in units of 1 / 128
+GAIN_BINS = ops.MATTE_KEY_GAIN_BINS               # the ratios 0 .. 511; 511 holds everything above
+MAX_GAIN_LIMIT = 3.99                             # lim = rint(128 limit) <= 511
 MAX_D = 2 * 510 * 510 + 255 * 255                 # |cb|, |cr| <= 510, (L dy^2 + 128) >> 8 <= 255^2 with L <= 256: 585,225 < 2^20
 
 
@@ -86,6 +97,24 @@ def adapt_params(rate: float, absorb: float = 0.0) -> Tuple[int, int]:
     a_bg, a_fg = int(np.rint(65536.0 * s["rate"])), int(np.rint(65536.0 * s["absorb"]))
     assert 0 <= a_bg <= ops.MATTE_KEY_MAX_RATE and 0 <= a_fg <= ops.MATTE_KEY_MAX_RATE
     return a_bg, a_fg
+
+
+def check_gain(limit=GAIN_DEFAULTS["limit"], min_share=GAIN_DEFAULTS["min_share"]) -> dict:
+    """{limit, min_share} validated; ValueError names the keyword"""
+    if not _number(limit) or not 1.0 <= float(limit) <= MAX_GAIN_LIMIT:
+        raise ValueError(f"matte key gain: limit={limit!r}: use a number in [1, {MAX_GAIN_LIMIT}] (the largest gain, and 1 / the smallest)")
+    if not _number(min_share) or not 0.0 <= float(min_share) <= 1.0:
+        raise ValueError(f"matte key gain: min_share={min_share!r}: use a number in [0, 1] (the part of the frame's pixels a channel "
+                         "needs as valid samples)")
+    return dict(limit=float(limit), min_share=float(min_share))
+
+
+def gain_params(limit: float, min_share: float, H: int, W: int) -> Tuple[int, int]:
+    """(lim, min_count) = (rint(128 limit), ceil(min_share H W)): 128 <= lim <= 511, 0 <= min_count <= H W"""
+    s = check_gain(limit, min_share)
+    lim, min_count = int(np.rint(128.0 * s["limit"])), int(np.ceil(s["min_share"] * H * W))
+    assert GAIN_UNITY <= lim < GAIN_BINS and 0 <= min_count <= H * W
+    return lim, min_count
 
 
 def check_color(to) -> Tuple[int, int, int]:
@@ -169,17 +198,21 @@ def plane_of(D, *, lo: float, hi: float, radius: int = 1, invert: bool = False) 
     return (np.uint8(255) - P) if invert else P
 
 
-def key_ref(source, key, *, lo: float, hi: float, luma: float = 0.0, radius: int = 1, invert: bool = False) -> np.ndarray:
+def key_ref(source, key, *, lo: float, hi: float, luma: float = 0.0, radius: int = 1, invert: bool = False, gain=None) -> np.ndarray:
     """uint8 [H,W] plane P of the finite fp16 [3,H,W] frame `source` against `key` (three bytes, or a plate as planar uint8
     [3,H,W]): `plane_of(distance_ref(steady.source_bytes(source), key, luma), ...)`.  255: differs from the key -- the subject,
-    which the matte formula source + m (styled - source) stylises."""
+    which the matte formula source + m (styled - source) stylises.  `gain` (three integers, 128: unity; a plate only): against
+    `gain_plate(key, gain)`."""
+    if gain is not None:
+        key = gain_plate(key.detach().cpu().numpy() if torch.is_tensor(key) else key, gain)
     return plane_of(distance_ref(source_bytes(source), key, luma), lo=lo, hi=hi, radius=radius, invert=invert)
 
 
-def raw_ref(source, key, depth, matte: dict, key_settings: dict) -> np.ndarray:
-    """fp32 [H,W]: `mask_io.front_ref(key_ref(...))` under the matte's and the key's settings -- op 59 on the host"""
+def raw_ref(source, key, depth, matte: dict, key_settings: dict, gain=None) -> np.ndarray:
+    """fp32 [H,W]: `mask_io.front_ref(key_ref(...))` under the matte's and the key's settings -- op 59 on the host (`gain`: under
+    L2D_MATTE_KEY_GAIN with that record)"""
     s = key_settings
-    P = key_ref(source, key, lo=s["lo"], hi=s["hi"], luma=s["luma"], radius=s["radius"], invert=s["invert"])
+    P = key_ref(source, key, lo=s["lo"], hi=s["hi"], luma=s["luma"], radius=s["radius"], invert=s["invert"], gain=gain)
     return front_ref(P, depth, matte["lo"], matte["hi"], matte["keep"], s["combine"])
 
 
@@ -230,22 +263,94 @@ def adapt_ref(state, source_bytes_, P0, a_bg: int, a_fg: int) -> np.ndarray:
 
 
 def key_adapt_ref(source, state, *, lo: float, hi: float, luma: float = 0.0, radius: int = 1, invert: bool = False,
-                  rate: float = ADAPT_DEFAULTS["rate"], absorb: float = ADAPT_DEFAULTS["absorb"]) -> Tuple[np.ndarray, np.ndarray]:
+                  rate: float = ADAPT_DEFAULTS["rate"], absorb: float = ADAPT_DEFAULTS["absorb"], gain=None) -> Tuple[np.ndarray, np.ndarray]:
     """(P, s'): the plane `key_ref` gives against `plate_bytes(state)`, and the state moved towards the source's bytes under
-    that plane in front of `invert` -- L2D_OP_MATTE_KEY_ADAPT without the depth ramp"""
+    that plane in front of `invert` -- L2D_OP_MATTE_KEY_ADAPT without the depth ramp.  `gain`: the key is formed against
+    `gain_plate(plate_bytes(state), gain)`; the update is unchanged, e = 256 b - s, towards the frame's own bytes."""
     a_bg, a_fg = adapt_params(rate, absorb)
     b = source_bytes(source)
-    P0 = plane_of(distance_ref(b, plate_bytes(state), luma), lo=lo, hi=hi, radius=radius)
+    k = plate_bytes(state) if gain is None else gain_plate(plate_bytes(state), gain)
+    P0 = plane_of(distance_ref(b, k, luma), lo=lo, hi=hi, radius=radius)
     return ((np.uint8(255) - P0) if invert else P0), adapt_ref(state, b, P0, a_bg, a_fg)
 
 
-def raw_adapt_ref(source, state, depth, matte: dict, key_settings: dict, adapt: dict) -> Tuple[np.ndarray, np.ndarray]:
+def raw_adapt_ref(source, state, depth, matte: dict, key_settings: dict, adapt: dict, gain=None) -> Tuple[np.ndarray, np.ndarray]:
     """(fp32 [H,W], s'): `mask_io.front_ref` of `key_adapt_ref`'s plane under the matte's and the key's settings, and the next
     state -- op 61 on the host"""
     s = key_settings
     P, nxt = key_adapt_ref(source, state, lo=s["lo"], hi=s["hi"], luma=s["luma"], radius=s["radius"], invert=s["invert"],
-                           rate=adapt["rate"], absorb=adapt["absorb"])
+                           rate=adapt["rate"], absorb=adapt["absorb"], gain=gain)
     return front_ref(P, depth, matte["lo"], matte["hi"], matte["keep"], s["combine"]), nxt
+
+
+# ----------------------------------------------------------------------------- the plate gain's oracle (numpy)
+def _bytes3(name, a) -> np.ndarray:
+    a = np.asarray(a)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[0] != 3:
+        raise ValueError(f"matte key gain: {name}: expected planar uint8 [3,H,W] bytes, got {a.dtype} {a.shape}")
+    return a
+
+
+def gain_hist_ref(b, k) -> np.ndarray:
+    """int64 [3,512] hist of the source's planar uint8 [3,H,W] bytes `b` against the plate's bytes `k`: per pixel and channel
+    the sample is valid when 16 <= k <= 239 and 4 <= b <= 251 (a clipped or near-black value says nothing about a ratio); q =
+    min(511, (128 b + (k >> 1)) // k), the ratio b / k in units of 1 / 128 rounded to nearest (b == k: exactly 128); hist[c][q]
+    counts the valid samples -- L2D_OP_MATTE_KEY_GAIN_HIST summed over its blocks"""
+    b, k = _bytes3("b", b).astype(np.int64), _bytes3("k", k).astype(np.int64)
+    if b.shape != k.shape:
+        raise ValueError(f"matte key gain: the bytes {b.shape} and the plate {k.shape} differ in shape")
+    assert 3 * b[0].size < 1 << 31                # every count is at most H W
+    valid = (k >= 16) & (k <= 239) & (b >= 4) & (b <= 251)
+    q = np.minimum(GAIN_BINS - 1, (128 * b + (k >> 1)) // np.maximum(k, 1))
+    hist = np.zeros((3, GAIN_BINS), np.int64)
+    for c in range(3):
+        hist[c] = np.bincount(q[c][valid[c]], minlength=GAIN_BINS)
+    return hist
+
+
+def gain_of(hist, lim: int, min_count: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(g, n), int64 [3] each, of a [3,512] histogram: n_c = the samples of channel c; g_c = 128 if n_c < min_count, else the
+    smallest q with 2 cum_c(q) >= n_c (the lower median), clamped to [ceil(16384 / lim), lim] -- L2D_OP_MATTE_KEY_GAIN.
+
+    The median is the subject's guard: it is the background's ratio while the subject (whose ratios lie anywhere) covers less
+    than half of the valid samples.  Past that it is not: with a subject over 60 % of the frame the measured gains are the
+    subject's against the wall behind it, and the key is wrong everywhere.  Nothing here detects that; `limit` only bounds it."""
+    h = np.asarray(hist)
+    if h.shape != (3, GAIN_BINS) or h.dtype.kind not in "iu" or (h.size and int(h.min()) < 0):
+        raise ValueError(f"matte key gain: a histogram is [3,{GAIN_BINS}] counts, got {h.dtype} {h.shape}")
+    for name, v, lo, hi in (("lim", lim, GAIN_UNITY, GAIN_BINS - 1), ("min_count", min_count, 0, (1 << 31) - 1)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise ValueError(f"matte key gain: {name}={v!r}: use an integer from {lo} to {hi}")
+    h = h.astype(np.int64)
+    cum = np.cumsum(h, axis=1)
+    n = cum[:, -1]
+    assert 3 * int(n.max(initial=0)) < 1 << 31    # 2 cum fits 32 bits
+    lim = int(lim)
+    lo = -(-GAIN_UNITY * GAIN_UNITY // lim)       # ceil(16384 / lim)
+    g = np.empty(3, np.int64)
+    for c in range(3):
+        g[c] = GAIN_UNITY if n[c] < int(min_count) else min(max(int(np.argmax(2 * cum[c] >= n[c])), lo), lim)
+    return g, n
+
+
+def _gain3(gain) -> np.ndarray:
+    g = np.asarray(gain)
+    if g.shape != (3,) or g.dtype.kind not in "iu" or int(g.min()) < 0 or int(g.max()) >= GAIN_BINS:
+        raise ValueError(f"matte key gain: a gain is three integers in 0..{GAIN_BINS - 1} (128: unity), got {gain!r}")
+    return g.astype(np.int64)
+
+
+def gain_plate(k, g) -> np.ndarray:
+    """uint8 [3,H,W] k' = min(255, (g_c k + 64) >> 7): the plate's bytes under the gains `g` (g = 128: k itself)"""
+    t = _gain3(g)[:, None, None] * _bytes3("k", k).astype(np.int64) + 64
+    assert t.max(initial=0) <= (GAIN_BINS - 1) * 255 + 64 < 1 << 17
+    return np.minimum(255, t >> 7).astype(np.uint8)
+
+
+def measure_gain(b, k, lim: int, min_count: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(g, n) = `gain_of(gain_hist_ref(b, k), lim, min_count)`"""
+    return gain_of(gain_hist_ref(b, k), lim, min_count)
+
 
 
 def plate_ref(image, H: int, W: int, resample: str = "lanczos") -> np.ndarray:
@@ -266,9 +371,13 @@ class HipMatteKey:
     With `adapt` ({rate, absorb}) `record` gives L2D_OP_MATTE_KEY_ADAPT in place of L2D_OP_MATTE_KEY: the plate lives in two
     uint16 records that ping-pong (`states`, the caller's or made on first use; `cur` is the one the next launch reads), and
     starts from the plate's bytes on the first frame behind `set_plate`, a capture or `restart`.  `repeated` runs the launch
-    with both rates 0, so that the plate is not fed the same frame twice."""
+    with both rates 0, so that the plate is not fed the same frame twice.
 
-    def __init__(self, height: int, width: int, device="cuda:0", plane=None, plate=None, states=None):
+    With `gain` ({limit, min_share}) `record` puts L2D_OP_MATTE_KEY_GAIN_HIST and L2D_OP_MATTE_KEY_GAIN in front of the key's
+    launch and sets L2D_MATTE_KEY_GAIN on it: the frame is keyed against the plate (or the state read) times the gains just
+    measured.  `partials` and `gain_record` are the caller's or made on first use; nothing is accumulated from frame to frame."""
+
+    def __init__(self, height: int, width: int, device="cuda:0", plane=None, plate=None, states=None, partials=None, gain_record=None):
         if width % 8 or height < 1 or 3 * height * width >= 1 << 31:
             raise ValueError(f"HipMatteKey: width {width} must be a multiple of 8, height {height} at least 1 and 3 H W below 2^31")
         self.height, self.width, self.device = int(height), int(width), torch.device(device)
@@ -278,6 +387,24 @@ class HipMatteKey:
         self.states = list(states) if states is not None else [None, None]       # planar uint16 [3,H,W] each, 8.8 fixed point
         self.cur = 0                         # the record the next adaptive launch reads
         self.from_plate = True               # the next adaptive frame starts from the plate's bytes
+        self.partials = partials             # uint32 [nblk,3,512] (as int32 bits): every block's histogram of the ratios
+        self.gain_record = gain_record       # int32 [8]: {g_r, g_g, g_b, n_r, n_g, n_b, 0, 0}
+        self.has_gain = False                # a record with `gain=` has been built: the record holds (or will hold) a measurement
+
+    def _gain_buffers(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        if self.partials is None:
+            self.partials = torch.empty(ops.matte_key_gain_blocks(self.height, self.width), 3, GAIN_BINS, dtype=torch.int32, device=self.device)
+        if self.gain_record is None:
+            self.gain_record = torch.empty(8, dtype=torch.int32, device=self.device)
+        return self.partials, self.gain_record
+
+    def current_gain(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(g, n), int64 [3] each: the gains (128: unity) and the valid samples of the last keyed frame, copied to the host (a
+        copy that waits for the device)"""
+        if not self.has_gain:
+            raise ValueError("HipMatteKey: no gain has been measured (record with gain=)")
+        r = self.gain_record.cpu().numpy().astype(np.int64)
+        return r[:3].copy(), r[3:6].copy()
 
     def _state(self, j: int) -> torch.Tensor:
         if self.states[j] is None:
@@ -311,11 +438,12 @@ class HipMatteKey:
         self.from_plate = True
 
     def record(self, slot, matte: dict, settings: dict, capture: bool = False, out: Optional[torch.Tensor] = None,
-               adapt: Optional[dict] = None, repeated: bool = False):
+               adapt: Optional[dict] = None, repeated: bool = False, gain: Optional[dict] = None):
         """(records, keep, plane): `slot.source` (and with "and" / "or" `slot.depth` under the matte's ramp) under the key's
         `settings` ({to: a colour or "plate", lo, hi, luma, radius, combine, invert}) -> `plane`; `records` is a list of L2D
         records, `keep` the tensors they name.  `adapt` ({rate, absorb}): the plate follows the source (op 61 in place of op 59;
-        the records are good for one run each: the state advances with every call); `repeated`: with both rates 0"""
+        the records are good for one run each: the state advances with every call); `repeated`: with both rates 0.  `gain`
+        ({limit, min_share}): ops 62 and 63 in front of the key's launch, which reads their record under L2D_MATTE_KEY_GAIN"""
         from .matte import matte_params
         H, W = self.height, self.width
         s = check_settings(settings["lo"], settings["hi"], settings["luma"], settings["radius"], settings["combine"], settings["invert"])
@@ -340,6 +468,18 @@ class HipMatteKey:
             lo32, inv32, ramp_hard = matte_params(matte["lo"], matte["hi"])
             kw = dict(lo32=lo32, inv32=inv32, ramp_hard=ramp_hard, far=matte["keep"] == "far")
         plane = self.plane if out is None else out
+        if gain is not None:
+            if not isinstance(to, str):
+                raise ValueError(f"HipMatteKey: to={to!r}: a gain needs a plate, not a colour")
+            lim, min_count = gain_params(gain["limit"], gain["min_share"], H, W)
+            partials, rec = self._gain_buffers()
+            against = self._state(self.cur) if adapt is not None and not self.from_plate else self.plate
+            for op, k in (ops.matte_key_gain_hist(slot.source, against, partials, H=H, W=W),
+                          ops.matte_key_gain(partials, rec, H=H, W=W, lim=lim, min_count=min_count)):
+                records.append(op)
+                keep.extend(k)
+            kw["gain"] = rec
+            self.has_gain = True
         if adapt is not None:
             if not isinstance(to, str):
                 raise ValueError(f"HipMatteKey: to={to!r}: adaptation needs a plate, not a colour")
@@ -360,11 +500,12 @@ class HipMatteKey:
         return records, tuple(keep), plane
 
     def key(self, source: torch.Tensor, depth: Optional[torch.Tensor], matte: dict, settings: dict, capture: bool = False,
-            out: Optional[torch.Tensor] = None, adapt: Optional[dict] = None, repeated: bool = False) -> torch.Tensor:
+            out: Optional[torch.Tensor] = None, adapt: Optional[dict] = None, repeated: bool = False,
+            gain: Optional[dict] = None) -> torch.Tensor:
         """one fp16 [3,H,W] source frame (and its fp16 [H,W] depth plane) -> the raw matte plane, in one run on the current
         stream (tests and tools; the wrapper goes through the delay line and `record`)"""
         import types
-        records, keep, plane = self.record(types.SimpleNamespace(source=source, depth=depth), matte, settings, capture, out, adapt, repeated)
+        records, keep, plane = self.record(types.SimpleNamespace(source=source, depth=depth), matte, settings, capture, out, adapt, repeated, gain)
         pl = _lib.OpList()
         for j, op in enumerate(records):
             pl.append(op, *(keep if j == 0 else ()))

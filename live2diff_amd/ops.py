@@ -1998,15 +1998,28 @@ def mask_ingest(src, out, depth, xmin, wx, ymin, wy, *, Hm, Wm, H, W, nh, nw, to
 MATTE_KEY_PLATE, MATTE_KEY_HARD, MATTE_KEY_INVERT, MATTE_KEY_AND, MATTE_KEY_OR, MATTE_KEY_RAMP_HARD, MATTE_KEY_RAMP_FAR = \
     1, 2, 4, 8, 16, 64, 128                                                                              # l2d.h L2D_MATTE_KEY_*
 MATTE_KEY_MAX_R = 4
+MATTE_KEY_GAIN = 512                              # l2d.h L2D_MATTE_KEY_GAIN: ops 59 and 61 key against the plate times the record p6
+MATTE_KEY_GAIN_STATE = 1                          # l2d.h L2D_MATTE_KEY_GAIN_STATE: op 62 reads the uint16 state, not the uint8 plate
+MATTE_KEY_GAIN_UNITY, MATTE_KEY_GAIN_BINS, MATTE_KEY_GAIN_BLOCK = 128, 512, 4096                         # l2d.h L2D_MATTE_KEY_GAIN_*
 MATTE_KEY_COMBINE = {"replace": 0, "and": MATTE_KEY_AND, "or": MATTE_KEY_OR}
 
 
+def _gain_record(name, gain, out):
+    """the checks of a gain record p6 of ops 59 / 61: an int32 [8] tensor, 16-byte aligned, that the plane does not overlap"""
+    if not torch.is_tensor(gain) or gain.dtype != torch.int32 or gain.numel() != 8 or not gain.is_contiguous() or gain.data_ptr() % 16:
+        raise ValueError(f"{name}: gain: expected a contiguous, 16-byte aligned int32 [8] record (matte_key_gain writes it), got "
+                         f"{getattr(gain, 'dtype', None)} {tuple(getattr(gain, 'shape', ()))}")
+    if _overlap(out, gain):
+        raise ValueError(f"{name}: the plane overlaps the gain record")
+
+
 def matte_key(source, out, depth, key, *, H, W, r, L, lo2, inv, hard, combine="replace", invert=False, lo32=0.0, inv32=0.0,
-              ramp_hard=False, far=False):
+              ramp_hard=False, far=False, gain=None):
     """fp16 [3,H,W] `source` -> fp32 [H,W] `out`: the raw matte of a key (mask_io.front_ref of matte_key.key_ref).  `key`: three
     bytes (a colour), or a planar uint8 [3,H,W] tensor (a plate); `r`: the window's radius; `L`: rint(256 luma); `lo2, inv,
     hard`: `matte_key.key_params`; `combine`: "replace", or "and" / "or" with the ramp `lo32, inv32, ramp_hard`
-    (`matte.matte_params`) and `far` over the fp16 [H,W] `depth` plane, which "replace" does not read (it may be None)."""
+    (`matte.matte_params`) and `far` over the fp16 [H,W] `depth` plane, which "replace" does not read (it may be None).  `gain`: the
+    int32 [8] record `matte_key_gain` writes -- the plate's bytes are multiplied by its gains first (a plate only)."""
     if source.dtype != torch.float16 or source.numel() != 3 * H * W or tuple(source.shape[-3:]) != (3, H, W) or not source.is_contiguous():
         raise ValueError(f"matte_key: source: expected a contiguous fp16 [3,{H},{W}] frame, got {source.dtype} {tuple(source.shape)}")
     if out.dtype != torch.float32 or out.numel() != H * W or not out.is_contiguous():
@@ -2039,6 +2052,10 @@ def matte_key(source, out, depth, key, *, H, W, r, L, lo2, inv, hard, combine="r
             colour = ()
         if len(colour) != 3 or any(isinstance(c, bool) or int(c) != c for c in key) or not all(0 <= c <= 255 for c in colour):
             raise ValueError(f"matte_key: key={key!r}: use three bytes (r, g, b), or a plate tensor")
+    if gain is not None:
+        if plate is None:
+            raise ValueError(f"matte_key: gain with the colour key={key!r}: a gain corrects a plate")
+        _gain_record("matte_key", gain, out)
     flags = ((MATTE_KEY_PLATE if plate is not None else 0) | (MATTE_KEY_HARD if hard else 0) | MATTE_KEY_COMBINE[combine]
              | (MATTE_KEY_INVERT if invert else 0) | (MATTE_KEY_RAMP_HARD if ramp_hard else 0) | (MATTE_KEY_RAMP_FAR if far else 0))
     op = L2dOp()
@@ -2046,6 +2063,10 @@ def matte_key(source, out, depth, key, *, H, W, r, L, lo2, inv, hard, combine="r
     keep = (source, out, depth, plate)
     for j, t in enumerate(keep):
         op.p[j] = _ptr(t)
+    if gain is not None:
+        flags |= MATTE_KEY_GAIN
+        op.p[6] = _ptr(gain)
+        keep = keep + (gain,)
     for j, v in enumerate([H, W, r, flags, L, *colour]):
         op.i[j] = int(v)
     op.f[0], op.f[1], op.f[2], op.f[3] = lo2, inv, float(lo32), float(inv32)
@@ -2066,12 +2087,13 @@ def _overlap(a, b) -> bool:
 
 
 def matte_key_adapt(source, out, depth, plate, state_in, state_out, *, H, W, r, L, lo2, inv, hard, a_bg, a_fg, combine="replace",
-                    invert=False, lo32=0.0, inv32=0.0, ramp_hard=False, far=False):
+                    invert=False, lo32=0.0, inv32=0.0, ramp_hard=False, far=False, gain=None):
     """`matte_key` against a plate that follows drifting light (matte_key.key_adapt_ref): fp16 [3,H,W] `source` -> fp32 [H,W]
     `out`, and the next state.  The state is the plate in 8.8 fixed point, a planar uint16 [3,H,W] tensor (or int16: the same
     bits); `state_in` None: the state starts from `plate` (planar uint8 [3,H,W]; not read otherwise, and may be None then).
     `a_bg`, `a_fg`: `matte_key.adapt_params`; the rest as `matte_key`'s.  `state_out` is the next launch's `state_in`: it may
-    overlap nothing the launch reads."""
+    overlap nothing the launch reads.  `gain`: as `matte_key`'s -- the key is formed against the state's bytes times the gains;
+    the state's update is unchanged."""
     init = state_in is None
     if init and not torch.is_tensor(plate):
         raise ValueError(f"matte_key_adapt: plate={plate!r}: without state_in the state starts from a plate tensor")
@@ -2096,12 +2118,88 @@ def matte_key_adapt(source, out, depth, plate, state_in, state_out, *, H, W, r, 
     if any(_overlap(state_out, t) for t in reads) or _overlap(out, state_in):
         raise ValueError("matte_key_adapt: state_out overlaps state_in, the source, the plane, the depth plane or the plate (or the plane "
                          "state_in): the two records ping-pong")
+    if gain is not None:
+        _gain_record("matte_key_adapt", gain, out)
+        if _overlap(state_out, gain):
+            raise ValueError("matte_key_adapt: state_out overlaps the gain record")
     op.kind = _lib.OP_MATTE_KEY_ADAPT
-    op.i[3] = (op.i[3] & ~MATTE_KEY_PLATE) | (MATTE_KEY_ADAPT_INIT if init else 0)
+    op.i[3] = (op.i[3] & ~MATTE_KEY_PLATE) | (MATTE_KEY_ADAPT_INIT if init else 0) | (MATTE_KEY_GAIN if gain is not None else 0)
     op.i[5], op.i[6], op.i[7] = int(a_bg), int(a_fg), 0
     keep = (source, out, depth, plate if init else None, state_in, state_out)
     for j, t in enumerate(keep):
         op.p[j] = _ptr(t)
+    if gain is not None:
+        op.p[6] = _ptr(gain)
+        keep = keep + (gain,)
+    return op, keep
+
+
+_COUNT_DTYPES = (torch.uint32, torch.int32)       # (int32: the bits of uint32 counts)
+
+
+def matte_key_gain_blocks(H: int, W: int) -> int:
+    """the work-groups of `matte_key_gain_hist`: one per MATTE_KEY_GAIN_BLOCK pixels, the last one ragged"""
+    return (int(H) * int(W) + MATTE_KEY_GAIN_BLOCK - 1) // MATTE_KEY_GAIN_BLOCK
+
+
+def _gain_partials(name, partials, H, W) -> int:
+    nblk = matte_key_gain_blocks(H, W)
+    if not torch.is_tensor(partials) or partials.dtype not in _COUNT_DTYPES or tuple(partials.shape) != (nblk, 3, MATTE_KEY_GAIN_BINS) \
+            or not partials.is_contiguous() or partials.data_ptr() % 16:
+        raise ValueError(f"{name}: partials: expected a contiguous, 16-byte aligned uint32 [{nblk},3,{MATTE_KEY_GAIN_BINS}] tensor "
+                         f"({nblk} blocks of {MATTE_KEY_GAIN_BLOCK} pixels over {H} x {W}), got {getattr(partials, 'dtype', None)} "
+                         f"{tuple(getattr(partials, 'shape', ()))}")
+    return nblk
+
+
+def matte_key_gain_hist(source, plate, partials, *, H, W):
+    """fp16 [3,H,W] `source` against `plate` -- planar uint8 [3,H,W] bytes, or the adaptive plate's planar uint16 [3,H,W] state
+    (int16: the same bits), whose bytes are (s + 128) >> 8 -- -> uint32 [nblk,3,512] `partials`: every block's histogram of the
+    per-pixel ratios (matte_key.gain_hist_ref is their sum).  Every entry is written on every launch."""
+    if W % 8 or H < 1 or 3 * H * W >= 1 << 31:
+        raise ValueError(f"matte_key_gain_hist: W = {W} must be a multiple of 8, H = {H} at least 1 and 3 H W below 2^31")
+    if not torch.is_tensor(source) or source.dtype != torch.float16 or tuple(source.shape[-3:]) != (3, H, W) or source.numel() != 3 * H * W \
+            or not source.is_contiguous() or source.data_ptr() % 16:
+        raise ValueError(f"matte_key_gain_hist: source: expected a contiguous, 16-byte aligned fp16 [3,{H},{W}] frame, got "
+                         f"{getattr(source, 'dtype', None)} {tuple(getattr(source, 'shape', ()))}")
+    state = torch.is_tensor(plate) and plate.dtype in _STATE_DTYPES
+    if not torch.is_tensor(plate) or (plate.dtype != torch.uint8 and not state) or tuple(plate.shape) != (3, H, W) \
+            or not plate.is_contiguous() or plate.data_ptr() % (16 if state else 8):
+        raise ValueError(f"matte_key_gain_hist: plate: expected a contiguous planar [3,{H},{W}] tensor, uint8 (8-byte aligned) or a uint16 "
+                         f"state (16-byte aligned), got {getattr(plate, 'dtype', None)} {tuple(getattr(plate, 'shape', ()))}")
+    nblk = _gain_partials("matte_key_gain_hist", partials, H, W)
+    if _overlap(partials, source) or _overlap(partials, plate):
+        raise ValueError("matte_key_gain_hist: the partials overlap the source or the plate")
+    op = L2dOp()
+    op.kind = _lib.OP_MATTE_KEY_GAIN_HIST
+    keep = (source, plate, partials)
+    for j, t in enumerate(keep):
+        op.p[j] = _ptr(t)
+    op.i[0], op.i[1], op.i[2], op.i[3] = int(H), int(W), MATTE_KEY_GAIN_STATE if state else 0, nblk
+    return op, keep
+
+
+def matte_key_gain(partials, record, *, H, W, lim, min_count):
+    """uint32 [nblk,3,512] `partials` of an H x W frame -> the int32 [8] `record` {g_r, g_g, g_b, n_r, n_g, n_b, 0, 0}
+    (matte_key.gain_of of their sum): `lim` = rint(128 limit) in 128..511, `min_count` in 0..H W (`matte_key.gain_params`)"""
+    if W % 8 or H < 1 or 3 * H * W >= 1 << 31:
+        raise ValueError(f"matte_key_gain: W = {W} must be a multiple of 8, H = {H} at least 1 and 3 H W below 2^31")
+    nblk = _gain_partials("matte_key_gain", partials, H, W)
+    if not torch.is_tensor(record) or record.dtype != torch.int32 or record.numel() != 8 or not record.is_contiguous() \
+            or record.data_ptr() % 16:
+        raise ValueError(f"matte_key_gain: record: expected a contiguous, 16-byte aligned int32 [8] tensor, got "
+                         f"{getattr(record, 'dtype', None)} {tuple(getattr(record, 'shape', ()))}")
+    for name, v, lo, hi in (("lim", lim, MATTE_KEY_GAIN_UNITY, MATTE_KEY_GAIN_BINS - 1), ("min_count", min_count, 0, H * W)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise ValueError(f"matte_key_gain: {name}={v!r}: use an integer from {lo} to {hi}")
+    if _overlap(record, partials):
+        raise ValueError("matte_key_gain: the record overlaps the partials")
+    op = L2dOp()
+    op.kind = _lib.OP_MATTE_KEY_GAIN
+    keep = (partials, record)
+    for j, t in enumerate(keep):
+        op.p[j] = _ptr(t)
+    op.i[0], op.i[1], op.i[2], op.i[3], op.i[4] = int(H), int(W), nblk, int(lim), int(min_count)
     return op, keep
 
 

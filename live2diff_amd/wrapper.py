@@ -324,6 +324,8 @@ class StreamAnimateDiffusionDepthWrapper:
     _key_capture = False                    # the next composited output's source frame becomes the plate
     _key_dev = None                         # matte_key.HipMatteKey, made by the first keyed frame on the device
     _key_adapt = None                       # the adaptive plate's settings beside the key (set_matte_key_adapt), None: the plate stays
+    _key_gain = None                        # the plate gain's settings beside the key (set_matte_key_gain), None: no gain is measured
+    _key_gain_last = None                   # (g, n) of the last frame keyed on the host route
     _key_state = None                       # the adaptive plate on the host route, uint16 [3,H,W]; None: it starts from the plate
     depth_source = "detector"               # "input": every frame brings its own depth and no detector was built (`_setup` sets it)
 
@@ -341,7 +343,7 @@ class StreamAnimateDiffusionDepthWrapper:
                  matte_edge: Optional[dict] = None, detail: Optional[dict] = None, depth_input: Optional[dict] = None,
                  depth_source: str = "detector", backdrop: Optional[dict] = None, steady_follow: Optional[dict] = None,
                  matte_hold: Optional[dict] = None, mask_input: Optional[dict] = None, matte_key: Optional[dict] = None,
-                 matte_key_adapt: Optional[dict] = None):
+                 matte_key_adapt: Optional[dict] = None, matte_key_gain: Optional[dict] = None):
         _check_depth_source(depth_source)
         self._check_keywords(few_step_model_type=few_step_model_type, acceleration=acceleration, cfg_type=cfg_type,
                              use_denoising_batch=use_denoising_batch, frame_buffer_size=frame_buffer_size, device_ids=device_ids,
@@ -364,13 +366,13 @@ class StreamAnimateDiffusionDepthWrapper:
                     jpeg_decode=jpeg_decode, output_size=output_size, output_resample=output_resample, matte_source=matte_source,
                     steady=steady, matte_edge=matte_edge, detail=detail, depth_input=depth_input, depth_source=depth_source,
                     backdrop=backdrop, steady_follow=steady_follow, matte_hold=matte_hold, mask_input=mask_input, matte_key=matte_key,
-                    matte_key_adapt=matte_key_adapt)
+                    matte_key_adapt=matte_key_adapt, matte_key_gain=matte_key_gain)
 
     @classmethod
     def from_components(cls, pipe, *, num_inference_steps: int, t_index_list: Optional[List[int]] = None,
                         strength: Optional[float] = None, **kw):
         """The wrapper around an already assembled `pipe` namespace (tests, synthetic weights).  Keywords: those of the
-        constructor that do not name files (`jpeg_quality`, `jpeg_decode`, `output_size`, `output_resample`, `matte_source`, `steady`, `steady_follow`, `matte_edge`, `matte_hold`, `detail`, `backdrop`, `depth_input`, `mask_input`, `matte_key`, `matte_key_adapt` and `depth_source` among them; with `depth_source="input"` the namespace needs no `depth_model`), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
+        constructor that do not name files (`jpeg_quality`, `jpeg_decode`, `output_size`, `output_resample`, `matte_source`, `steady`, `steady_follow`, `matte_edge`, `matte_hold`, `detail`, `backdrop`, `depth_input`, `mask_input`, `matte_key`, `matte_key_adapt`, `matte_key_gain` and `depth_source` among them; with `depth_source="input"` the namespace needs no `depth_model`), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
         self = cls.__new__(cls)
         cls._check_keywords(**{k: kw.pop(k) for k in ("acceleration", "cfg_type", "use_denoising_batch", "frame_buffer_size",
                                                       "device_ids", "opt_unet", "few_step_model_type") if k in kw},
@@ -412,8 +414,10 @@ class StreamAnimateDiffusionDepthWrapper:
                similar_image_filter_threshold=0.98, similar_image_filter_max_skip_frame=10, jpeg_quality=75, jpeg_decode="device",
                output_size=None, output_resample="lanczos", matte_source="stream", steady=None, matte_edge=None, detail=None,
                depth_input=None, depth_source="detector", backdrop=None, steady_follow=None, matte_hold=None, mask_input=None, matte_key=None,
-               matte_key_adapt=None):
+               matte_key_adapt=None, matte_key_gain=None):
         self._check_matte_source(matte_source)
+        if matte_key_gain is not None and not isinstance(matte_key_gain, dict):
+            raise ValueError(f"matte_key_gain={matte_key_gain!r}: use a dict of set_matte_key_gain's keywords, or None")
         if matte_key_adapt is not None and not isinstance(matte_key_adapt, dict):
             raise ValueError(f"matte_key_adapt={matte_key_adapt!r}: use a dict of set_matte_key_adapt's keywords, or None")
         if matte_key is not None and not isinstance(matte_key, dict):
@@ -495,6 +499,8 @@ class StreamAnimateDiffusionDepthWrapper:
             self._set_matte_key(**matte_key, needs_matte=False)      # (no matte can be set yet: the key waits for the first set_matte)
         if matte_key_adapt is not None:
             self.set_matte_key_adapt(**matte_key_adapt)
+        if matte_key_gain is not None:
+            self.set_matte_key_gain(**matte_key_gain)
 
     # ------------------------------------------------------------------ depth from the caller (depth_io.py)
     @property
@@ -676,6 +682,9 @@ class StreamAnimateDiffusionDepthWrapper:
         if color and self._key_adapt is not None:
             raise ValueError(f"set_matte_key: to={to!r}: the adaptive plate (set_matte_key_adapt) needs a plate, not a colour: call "
                              "clear_matte_key_adapt first")
+        if color and self._key_gain is not None:
+            raise ValueError(f"set_matte_key: to={to!r}: the plate gain (set_matte_key_gain) needs a plate, not a colour: call "
+                             "clear_matte_key_gain first")
         settings = MK.check_settings(lo, hi, luma, radius, combine, invert, plate=not color)
         plate = None
         if color:
@@ -704,9 +713,10 @@ class StreamAnimateDiffusionDepthWrapper:
 
     def clear_matte_key(self) -> None:
         """No key: the frame is cut by the depth ramp alone again; no launch or buffer of the key is left in the frame's path.
-        The adaptive plate (`set_matte_key_adapt`) goes with it."""
+        The adaptive plate (`set_matte_key_adapt`) and the plate gain (`set_matte_key_gain`) go with it."""
         self._key = self._key_plate = self._key_dev = None
         self._key_adapt = self._key_state = None
+        self._key_gain = self._key_gain_last = None
         self._key_capture = False
         self._hold_init = True
 
@@ -773,6 +783,62 @@ class StreamAnimateDiffusionDepthWrapper:
             raise ValueError("matte_key_plate: no plate yet: the capture waits for the next composited output")
         return np.ascontiguousarray(np.asarray(self._key_plate).transpose(1, 2, 0))
 
+    # ------------------------------------------------------------------ the plate gain (matte_key.py)
+    @property
+    def matte_key_gain(self) -> Optional[dict]:
+        """the plate gain's settings as {limit, min_share}, or None"""
+        return None if self._key_gain is None else dict(self._key_gain)
+
+    def set_matte_key_gain(self, limit: float = 2.0, min_share: float = 1.0 / 16.0) -> None:
+        """Let the key against a plate follow a sudden exposure or white-balance step.  A person walks in and the camera's
+        auto-exposure and auto-white-balance move every background pixel at once; the plate is wrong everywhere, and the
+        adaptive plate follows only at its `rate` (and with `absorb=0` not at all where the wall has already turned subject).
+        With this setting every keyed frame first measures one gain per channel between the plate and the frame's source --
+        the lower median of the per-pixel ratios, in units of 1 / 128 (`matte_key.gain_hist_ref`, `gain_of`) -- and is keyed
+        against the plate times that gain (`gain_plate`).  `limit` in [1, 3.99] bounds the gain to [1 / limit, limit];
+        a channel with fewer valid samples (neither clipped nor near black) than `min_share` of the frame's pixels keeps a
+        gain of 1.  The median holds while the subject covers less than half of the valid samples: past that the gains are
+        the subject's, and the key is wrong.  The defaults are a guess, not tuned on camera footage.
+
+        A setting beside the key, like `set_matte_key_adapt`, with or without it: it needs a key against a plate, a colour
+        key refuses it, and `clear_matte_key` and `clear_matte` clear it.  Under the adaptive plate the plate still moves
+        towards the frame's own bytes, so it absorbs the new exposure at `rate` and the measured gain walks back to 1.  On
+        the device two launches (L2D_OP_MATTE_KEY_GAIN_HIST, L2D_OP_MATTE_KEY_GAIN) stand in front of the key's, which reads
+        their record; nothing is carried from frame to frame.  `matte_key_gain_measured()` returns the last measurement.
+        May be called between any two frames; the change applies from the next output and restarts a matte hold."""
+        from .matte_key import check_gain
+        settings = check_gain(limit, min_share)
+        if self._key is None:
+            raise ValueError("set_matte_key_gain: the plate gain needs a matte key against a plate: call set_matte_key with an image or "
+                             "'capture' first")
+        if not isinstance(self._key["to"], str):
+            raise ValueError(f"set_matte_key_gain: the key is the colour {self._key['to']!r}: a gain needs a plate (set_matte_key with an "
+                             "image or 'capture')")
+        self._key_gain = settings
+        self._hold_init = True
+
+    def clear_matte_key_gain(self) -> None:
+        """No gain is measured: the key's own launch against the plate as it is, and no buffer of the gain in the frame's path."""
+        self._key_gain = self._key_gain_last = None
+        if self._key_dev is not None:
+            self._key_dev.has_gain = False
+        self._hold_init = True
+
+    def matte_key_gain_measured(self):
+        """The last keyed frame's measurement as `((g_r, g_g, g_b), (n_r, n_g, n_b))`: the gains as factors (g / 128) and the
+        valid samples as shares of the frame's pixels (n / H W).  On the device a copy to the host that waits for the stream.
+        ValueError while nothing has been measured."""
+        if self._key_gain is None:
+            raise ValueError("matte_key_gain_measured: no plate gain is set (set_matte_key_gain)")
+        if self._key_dev is not None and self._key_dev.has_gain:
+            g, n = self._key_dev.current_gain()
+        elif self._key_gain_last is not None:
+            g, n = self._key_gain_last
+        else:
+            raise ValueError("matte_key_gain_measured: no frame has been keyed yet")
+        hw = float(self.height * self.width)
+        return tuple(float(v) / 128.0 for v in g), tuple(float(v) / hw for v in n)
+
     def _key_front(self, slot, device, repeated: bool = False):
         """`(records, keep, plane)` of L2D_OP_MATTE_KEY for the slot's source under the settings of this moment (on a capturing
         frame L2D_OP_FRAME_PLANAR_BYTES in front of it), or None; with an adaptive plate L2D_OP_MATTE_KEY_ADAPT in its place"""
@@ -784,9 +850,10 @@ class StreamAnimateDiffusionDepthWrapper:
             if self._key_plate is not None:
                 self._key_dev.set_plate(self._key_plate)
         capture, self._key_capture = self._key_capture, False
+        more = {} if self._key_gain is None else dict(gain=self._key_gain)     # (the keyword only with a gain)
         if self._key_adapt is None:
-            return self._key_dev.record(slot, self._matte, self._key, capture=capture)        # (the parent's call)
-        return self._key_dev.record(slot, self._matte, self._key, capture=capture, adapt=self._key_adapt, repeated=repeated)
+            return self._key_dev.record(slot, self._matte, self._key, capture=capture, **more)        # (the parent's call)
+        return self._key_dev.record(slot, self._matte, self._key, capture=capture, adapt=self._key_adapt, repeated=repeated, **more)
 
     def _key_plane(self, slot, repeated: bool = False) -> Optional[np.ndarray]:
         """the raw matte of the key on the host route, fp32 [H,W]: `matte_key.raw_ref` where op 59 would run (`raw_adapt_ref`
@@ -798,20 +865,29 @@ class StreamAnimateDiffusionDepthWrapper:
         if self._key_capture:
             self._key_capture, self._key_plate = False, source_bytes(slot.source)
             self._key_state = None
+        more = {}                           # (the keyword only with a gain: without one the calls are the parent's)
+        if self._key_gain is not None:
+            from .matte_key import gain_params, measure_gain, plate_bytes
+            if self._key_plate is None:
+                raise ValueError("matte key: no plate is set")
+            k = self._key_plate if self._key_adapt is None or self._key_state is None else plate_bytes(self._key_state)
+            self._key_gain_last = measure_gain(source_bytes(slot.source), k, *gain_params(self._key_gain["limit"], self._key_gain["min_share"],
+                                                                                         self.height, self.width))
+            more["gain"] = self._key_gain_last[0]
         if self._key_adapt is not None:
             from .matte_key import raw_adapt_ref, state_of
             if self._key_plate is None:
                 raise ValueError("matte key: no plate is set")
             state = state_of(self._key_plate) if self._key_state is None else self._key_state
             raw, self._key_state = raw_adapt_ref(slot.source, state, slot.depth[None], self._matte, self._key,
-                                                 dict(rate=0.0, absorb=0.0) if repeated else self._key_adapt)
+                                                 dict(rate=0.0, absorb=0.0) if repeated else self._key_adapt, **more)
             return raw
         key = self._key["to"]
         if isinstance(key, str):
             if self._key_plate is None:
                 raise ValueError("matte key: no plate is set")
             key = self._key_plate
-        return raw_ref(slot.source, key, slot.depth[None], self._matte, self._key)
+        return raw_ref(slot.source, key, slot.depth[None], self._matte, self._key, **more)
 
     # ------------------------------------------------------------------ depth matte (matte.py)
     @property

@@ -6,7 +6,10 @@ L2D_OP_MATTE_KEY at 512x512 in both variants (a colour key and a plate key; radi
 and L2D_OP_FRAME_PLANAR_BYTES, beside L2D_OP_FRAME_MATTE_HOLD (radius 2, from the depth plane) -- the op whose tile form op 59
 takes -- in the same run: device events around `--reps` back-to-back replays after a warm-up, the median of five runs
 (microseconds per launch).  `tools/mask_time.py kernels` on the same box gives op 58's figures.  L2D_OP_MATTE_KEY_ADAPT (the adaptive plate, section 8.z18)
-follows in the same run, INIT and STATE at the same radii: its yardstick is op 59 with a plate."""
+follows in the same run, INIT and STATE at the same radii: its yardstick is op 59 with a plate.  The plate gain (section 8.z19)
+follows both: L2D_OP_MATTE_KEY_GAIN_HIST against the plate and against the state -- on the noise frame, whose ratios spread over
+the bins, and on the plate's own frame, where every valid sample lands in bin 128 (a still room: the worst case of the LDS
+atomics) --, L2D_OP_MATTE_KEY_GAIN, and ops 59 / 61 under L2D_MATTE_KEY_GAIN beside their unflagged rows above."""
 import argparse
 import os
 import sys
@@ -26,7 +29,8 @@ from steady_time import say  # noqa: E402
 def kernels(args):
     from live2diff_amd import _lib, ops
     from live2diff_amd.matte import matte_params
-    from live2diff_amd.matte_key import adapt_params, key_params, luma_weight, state_of
+    from live2diff_amd.backdrop import frame_of
+    from live2diff_amd.matte_key import adapt_params, gain_params, key_params, luma_weight, state_of
     from live2diff_amd.steady import steady_params
     dev, H, W = "cuda", 512, 512
     say(args.out, f"# matte_key_time: {_lib.device_name()}, {args.reps} back-to-back replays per figure (device events), median of 5 runs, "
@@ -58,6 +62,26 @@ def kernels(args):
                                    ramp_hard=ramp_hard, **kw))
     say(args.out, "op 61 against op 59 with a plate: " + ", ".join(
         f"{name} r = {r} {med[name, r] / med['plate', r]:.2f} x" for name in ("init", "state") for r in (0, 1, 4)))
+    # the plate gain: the samples, the medians, and the key's launches reading the record
+    still = torch.from_numpy(np.array(frame_of(plate.cpu().numpy()))).to(dev)
+    partials = torch.empty(ops.matte_key_gain_blocks(H, W), 3, ops.MATTE_KEY_GAIN_BINS, dtype=torch.int32, device=dev)
+    record = torch.empty(8, dtype=torch.int32, device=dev)
+    lim, min_count = gain_params(2.0, 1 / 16, H, W)
+    for name, key in (("plate", plate), ("state", state)):
+        _timed(args.out, args.reps, f"op 62 matte key gain hist, {name}, noise frame", ops.matte_key_gain_hist(src, key, partials, H=H, W=W))
+        _timed(args.out, args.reps, f"op 62 matte key gain hist, {name}, the plate's own frame",
+               ops.matte_key_gain_hist(still, key, partials, H=H, W=W))
+    _timed(args.out, args.reps, f"op 63 matte key gain, {partials.shape[0]} partials",
+           ops.matte_key_gain(partials, record, H=H, W=W, lim=lim, min_count=min_count))
+    for r in (0, 1, 4):
+        med["gain plate", r] = _timed(args.out, args.reps, f"op 59 matte key, plate, gain, r = {r}, replace",
+                                      ops.matte_key(src, plane, None, plate, r=r, gain=record, **kw))
+    for name, pl, st in (("init", plate, None), ("state", None, state)):
+        for r in (0, 1, 4):
+            med["gain " + name, r] = _timed(args.out, args.reps, f"op 61 matte key adapt, {name}, gain, r = {r}, replace",
+                                            ops.matte_key_adapt(src, plane, None, pl, st, nxt, r=r, a_bg=a_bg, a_fg=a_fg, gain=record, **kw))
+    say(args.out, "under L2D_MATTE_KEY_GAIN against the unflagged launch: " + ", ".join(
+        f"{name} r = {r} {med['gain ' + name, r] / med[name, r]:.2f} x" for name in ("plate", "init", "state") for r in (0, 1, 4)))
     bytes_ = torch.empty(3, H, W, dtype=torch.uint8, device=dev)
     _timed(args.out, args.reps, "op 60 frame planar bytes (the plate capture)", ops.frame_planar_bytes(src, bytes_, H=H, W=W))
     # the tile form's owner, in the same run: op 57 from the depth plane, radius 2, a steady state frame

@@ -96,7 +96,16 @@ frame the plate moves by RATE of the way towards the frame where the key says ba
 it says subject; both lie in [0, 0.5].  It needs a `--matte-key` against a plate (a path or `capture`).  `POST /matte-key/adapt`
 with the same text changes it while the stream runs, an empty body or `off` clears it; `GET /matte-key` then carries `"adapt":
 {"rate": ..., "absorb": ...}`.  `GET /matte-key/plate` answers the plate of this moment as a JPEG file (404 while there is
-none): the producer hands it over between two frames."""
+none): the producer hands it over between two frames.
+
+`--matte-key-gain [LIMIT[,MIN_SHARE]]` lets the key against a plate follow a sudden exposure or white-balance step
+(`wrapper.set_matte_key_gain`): every frame measures one gain per channel between the plate and the frame, the median over the
+frame's pixels, and is keyed against the plate times that gain.  LIMIT in [1, 3.99] (default 2) bounds the gain, MIN_SHARE in [0,
+1] (default 1/16) is the part of the frame a channel needs as valid samples; without a value (or `on`) the defaults.  It needs a
+`--matte-key` against a plate and works with or without `--matte-key-adapt`.  `POST /matte-key/gain` with the same text changes it
+while the stream runs, an empty body or `off` clears it; `GET /matte-key/gain` answers `{"limit", "min_share", "gain", "share"}`
+-- the setting and the last frame's measurement per channel (`null` before the first keyed frame) -- or 404 while it is off: the
+producer hands it over between two frames.  The body of `GET /matte-key` does not change."""
 import argparse
 import json
 import os
@@ -559,13 +568,33 @@ def parse_matte_key_adapt_arg(text: str):
     return check_adapt(rate, absorb)
 
 
+def parse_matte_key_gain_arg(text: str):
+    """`on` or `LIMIT[,MIN_SHARE]` -> the keywords of `wrapper.set_matte_key_gain`; `off` or nothing -> None; ValueError otherwise"""
+    from live2diff_amd.matte_key import GAIN_DEFAULTS, check_gain
+    text = text.strip()
+    if text in ("", "off"):
+        return None
+    if text == "on":
+        return dict(GAIN_DEFAULTS)
+    parts = [t.strip() for t in text.split(",")]
+    if not 1 <= len(parts) <= 2:
+        raise ValueError(f"matte key gain {text!r}: use on, LIMIT[,MIN_SHARE] or off")
+    try:
+        limit, min_share = float(parts[0]), (float(parts[1]) if len(parts) > 1 else GAIN_DEFAULTS["min_share"])
+    except ValueError:
+        raise ValueError(f"matte key gain {text!r}: LIMIT is a number in [1, 3.99], MIN_SHARE one in [0, 1]") from None
+    return check_gain(limit, min_share)
+
+
 class MatteKeyBox:
     """What `POST /matte-key` and `POST /matte-key/capture` deliver: the newest requested key (a dict of `set_matte_key` keywords,
     or None for an empty body or `off`) and a request to take the plate again, applied by the producer between two frames.
     `current` is what was last applied (the `matte_key` property, with the colour as a list); `failed` counts bodies the route
     refused with a 400 and requests the wrapper refused (no matte, a sticky mask, a capture without a key).  `POST
     /matte-key/adapt` delivers the adaptive plate's setting the same way (`current` then carries `adapt`), and `GET
-    /matte-key/plate` asks the producer for the plate of this moment: `take_plate` waits up to `plate_wait` seconds for it."""
+    /matte-key/plate` asks the producer for the plate of this moment: `take_plate` waits up to `plate_wait` seconds for it.  `POST
+    /matte-key/gain` delivers the plate gain's setting the same way; `current` does not carry it: `GET /matte-key/gain` asks the
+    producer for the setting and the last measurement (`take_gain`, which waits as `take_plate` does)."""
     _NOTHING = object()
     plate_wait = 2.0
 
@@ -574,6 +603,20 @@ class MatteKeyBox:
         self._plate_ready = threading.Condition(self._lock)
         self.current, self._want, self._capture, self.failed = self.view(current, adapt), self._NOTHING, False, 0
         self._adapt, self._want_plate, self._plate = self._NOTHING, False, None
+        self._gain, self._want_gain, self._gain_info = self._NOTHING, False, None
+
+    def put_gain(self, settings) -> None:
+        with self._lock:
+            self._gain = settings
+
+    def take_gain(self):
+        """(a handler thread) {limit, min_share, gain, share} as the producer last handed it over, or None: asks for it and waits"""
+        with self._plate_ready:
+            if self._gain_info is None:
+                self._want_gain = True
+                self._plate_ready.wait_for(lambda: self._gain_info is not None, timeout=self.plate_wait)
+            info, self._gain_info = self._gain_info, None
+            return info
 
     @staticmethod
     def view(key, adapt=None):
@@ -614,6 +657,8 @@ class MatteKeyBox:
             capture, self._capture = self._capture, False
             adapt, self._adapt = self._adapt, self._NOTHING
             want_plate, self._want_plate = self._want_plate, False
+            gain, self._gain = self._gain, self._NOTHING
+            want_gain, self._want_gain = self._want_gain, False
         try:
             if want is None:
                 wrapper.clear_matte_key()
@@ -633,7 +678,25 @@ class MatteKeyBox:
                 wrapper.set_matte_key_adapt(**adapt)
         except ValueError:                         # (no key, or a colour key)
             self.refused()
+        try:
+            if gain is None:
+                wrapper.clear_matte_key_gain()
+            elif gain is not self._NOTHING:
+                wrapper.set_matte_key_gain(**gain)
+        except ValueError:                         # (no key, or a colour key)
+            self.refused()
         self.current = self.view(wrapper.matte_key, getattr(wrapper, "matte_key_adapt", None))
+        if want_gain:
+            info = getattr(wrapper, "matte_key_gain", None)     # (None: off -- the request stays unanswered, the route says 404)
+            if info is not None:
+                try:
+                    g, share = wrapper.matte_key_gain_measured()
+                    info = dict(info, gain=list(g), share=list(share))
+                except ValueError:                 # (no frame has been keyed under it yet)
+                    info = dict(info, gain=None, share=None)
+            with self._plate_ready:
+                self._gain_info = info
+                self._plate_ready.notify_all()
         if want_plate:
             try:
                 plate = wrapper.matte_key_plate()
@@ -981,6 +1044,18 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
                 self.send_header("Content-Length", str(len(body)))
                 self.end_headers()
                 self.wfile.write(body)
+            elif self.path == "/matte-key/gain" and keys is not None:
+                info = keys.take_gain()
+                if info is None:
+                    self.send_error(404, "no plate gain at this moment (--matte-key-gain / POST /matte-key/gain is off, or no stream)")
+                    return
+                body = json.dumps(info).encode()
+                self.send_response(200)
+                self.send_header("Content-Type", "application/json")
+                self.send_header("Cache-Control", "no-store")
+                self.send_header("Content-Length", str(len(body)))
+                self.end_headers()
+                self.wfile.write(body)
             elif boxes.get(self.path) is not None or (masks is not None and self.path in ("/mask", "/mask-input")):
                 current = (boxes[self.path].current if self.path in boxes else
                            masks.current if self.path == "/mask" else masks.current_input)
@@ -1061,6 +1136,8 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
                     keys.capture()
                 elif self.path == "/matte-key/adapt":
                     keys.put_adapt(parse_matte_key_adapt_arg(body.decode()))
+                elif self.path == "/matte-key/gain":
+                    keys.put_gain(parse_matte_key_gain_arg(body.decode()))
                 else:
                     keys.put(parse_matte_key_arg(body.decode()))
             except ValueError as e:                       # (UnicodeDecodeError is a ValueError)
@@ -1126,7 +1203,7 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
             if masks is not None and self.path in ("/mask", "/mask-input"):
                 self.do_mask()
                 return
-            if keys is not None and self.path in ("/matte-key", "/matte-key/capture", "/matte-key/adapt"):
+            if keys is not None and self.path in ("/matte-key", "/matte-key/capture", "/matte-key/adapt", "/matte-key/gain"):
                 self.do_matte_key()
                 return
             if inbox is None or self.path != "/frame":
@@ -1311,6 +1388,12 @@ def main(argv=None):
                          "says background, by ABSORB (default 0) where it says subject, both in [0, 0.5]; needs a --matte-key against a "
                          "plate (a path or capture); POST /matte-key/adapt with the same text changes it between two frames, `off` clears "
                          "it; GET /matte-key/plate answers the plate of this moment as a JPEG")
+    ap.add_argument("--matte-key-gain", default=None, nargs="?", const="on", metavar="LIMIT[,MIN_SHARE]",
+                    help="let --matte-key against a plate follow a sudden exposure or white-balance step: every frame measures one gain "
+                         "per channel between the plate and the frame (the median over the frame) and is keyed against the plate times "
+                         "it; LIMIT in [1, 3.99] (default 2) bounds the gain, MIN_SHARE in [0, 1] (default 1/16) is the part of the frame "
+                         "a channel needs as valid samples; POST /matte-key/gain with the same text changes it between two frames, `off` "
+                         "clears it; GET /matte-key/gain answers the setting and the last measurement")
     ap.add_argument("--mask-input", default=None, metavar="COMBINE[,invert]",
                     help="how a mask meets the depth ramp: replace (default), and, or; `invert` flips the mask first; POST /mask-input "
                          "with the same text changes it between frames")
@@ -1329,6 +1412,13 @@ def main(argv=None):
         ap.error("--matte-key-adapt needs a --matte-key against a plate (a path or capture), not a colour")
     try:
         matte_key_adapt = parse_matte_key_adapt_arg(ap_adapt) if ap_adapt else None
+    except ValueError as e:
+        ap.error(str(e))
+    ap_gain = args.matte_key_gain
+    if ap_gain is not None and (matte_key is None or isinstance(matte_key["to"], tuple)):
+        ap.error("--matte-key-gain needs a --matte-key against a plate (a path or capture), not a colour")
+    try:
+        matte_key_gain = parse_matte_key_gain_arg(ap_gain) if ap_gain else None
     except ValueError as e:
         ap.error(str(e))
     if args.mask is not None and not args.matte:
@@ -1401,6 +1491,8 @@ def main(argv=None):
         w.set_matte_key(**matte_key)
     if matte_key_adapt is not None:
         w.set_matte_key_adapt(**matte_key_adapt)
+    if matte_key_gain is not None:
+        w.set_matte_key_gain(**matte_key_gain)
     keys = MatteKeyBox(w.matte_key, w.matte_key_adapt)
     prompt = args.prompt if args.prompt is not None else str(cfg.get("prompt", ""))
     latest, stop = Latest(), threading.Event()
