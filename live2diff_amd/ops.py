@@ -1276,25 +1276,163 @@ def vae_posterior(moments, eps, out, *, B, HW):
 
 
 # ----------------------------------------------------------------------------- frame I/O (frame_io.hip)
+# From here to the end of the file every builder checks its operands with the helpers below and ends in one call of `_record`:
+#   p   the tensors the kernel reads or writes, in the order of l2d.h's record; None is a null pointer.  A pointer that does not
+#       follow the others (the gain record in p[6]) goes in `at`
+#   i   sizes, radii and flag words; the bits of an fp32 value where l2d.h says so (`_f32_bits`)
+#   l   strides and other 64-bit sizes; the bits of a double where l2d.h says so (`_f64_bits`)
+#   f   the ramps and strengths the kernels take as float
+#   keep  every tensor whose pointer is in the record, in the record's order: the plan holds them for as long as it lives
+# One check per kind of operand, named after what it checks; the first argument is "<builder>: <operand>", the head of the message:
+#   _fp16_frame  [3,H,W] fp16 frame            _fp32_plane  [H,W] fp32 plane (matte values)      _int_in  an integer from lo to hi
+#   _u8_planes   [3,H,W] planar uint8 record   _fp16_depth  [H,W] fp16 depth plane
+#   _u8_frame    [H,W,3] uint8 frame           _i32_planes  [3,H,W] int32 planes
+#   _resample_tables  the index and weight tables of depth_ingest / mask_ingest;  _axis_table  one int32 table of an output axis
+# `_matte_input` is the `plane=` or `depth=` operand of the ops that cut by a matte, `_ramp_input` the `combine=` / depth pair of
+# the ops that write one.  A rejected operand is a ValueError; the frame I/O, JPEG and `frame_matte` builders assert, as they always did.
+def _record(kind, ptrs, i=(), l=(), f=(), at=None, keep=None):
+    """-> (op, keep): the record of `kind` with `ptrs` in p[0..], `at` ({slot: tensor or host address}) behind them, and the
+    `i`, `l` and `f` values in order; `keep`: the tensors to hold when they are not `ptrs` and `at`'s"""
+    op = L2dOp()
+    op.kind = kind
+    op.p[:len(ptrs)] = [None if t is None else t.data_ptr() for t in ptrs]
+    if at:
+        for j, t in at.items():
+            op.p[j] = t if isinstance(t, int) else _ptr(t)
+    if i:
+        op.i[:len(i)] = [int(v) for v in i]
+    if l:
+        op.l[:len(l)] = [int(v) for v in l]
+    if f:
+        op.f[:len(f)] = [float(v) for v in f]
+    if keep is None:
+        keep = tuple(ptrs) + tuple(at.values()) if at else tuple(ptrs)
+    return op, keep
+
+
+def _f32_bits(v) -> int:
+    """the bits of float32(v) as an int32: an fp32 value in an `i` field"""
+    return int(np.float32(v).view(np.int32))
+
+
+def _f64_bits(v) -> int:
+    """the bits of float64(v) as an int64: a double in an `l` field"""
+    return int(np.float64(v).view(np.int64))
+
+
+def _got(t) -> str:
+    return f"{getattr(t, 'dtype', None)} {tuple(getattr(t, 'shape', ()))}"
+
+
+def _fp16_frame(name, t, H, W, B=None, align=0):
+    """a contiguous fp16 [3,H,W] frame (unit dimensions in front are fine); `B`: a batch of B of them, checked by its size alone;
+    `align`: at a multiple of that many bytes -- and with it an operand that is no tensor is refused here too"""
+    if B is not None:
+        if t.dtype != torch.float16 or t.numel() != B * 3 * H * W or not t.is_contiguous():
+            raise ValueError(f"{name}: expected a contiguous fp16 [{B},3,{H},{W}] frame, got {_got(t)}")
+    elif (align and not torch.is_tensor(t)) or t.dtype != torch.float16 or tuple(t.shape[-3:]) != (3, H, W) or t.numel() != 3 * H * W \
+            or not t.is_contiguous() or (align and t.data_ptr() % align):
+        raise ValueError(f"{name}: expected a contiguous{f', {align}-byte aligned' if align else ''} fp16 [3,{H},{W}] frame, got {_got(t)}")
+
+
+def _u8_planes(name, t, H, W, what="record", exact=False):
+    """a contiguous planar uint8 [3,H,W] tensor: the bytes of a frame; `exact`: with no dimension in front"""
+    if t.dtype != torch.uint8 or not t.is_contiguous() or (tuple(t.shape) != (3, H, W) if exact else
+                                                          tuple(t.shape[-3:]) != (3, H, W) or t.numel() != 3 * H * W):
+        raise ValueError(f"{name}: expected a contiguous planar uint8 [3,{H},{W}] {what}, got {_got(t)}")
+
+
+def _u8_frame(name, t, H, W):
+    """a contiguous interleaved uint8 [H,W,3] frame"""
+    if t.dtype != torch.uint8 or tuple(t.shape[-3:]) != (H, W, 3) or t.numel() != H * W * 3 or not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous uint8 [{H},{W},3] frame, got {_got(t)}")
+
+
+def _i32_planes(name, t, H, W):
+    """contiguous int32 [3,H,W] planes: the detail gains"""
+    if t.dtype != torch.int32 or tuple(t.shape[-3:]) != (3, H, W) or t.numel() != 3 * H * W or not t.is_contiguous():
+        raise ValueError(f"{name}: expected contiguous int32 [3,{H},{W}] planes, got {_got(t)}")
+
+
+def _fp32_plane(name, t, H, W, B=None, flat=False):
+    """a contiguous fp32 [H,W] plane; `flat`: of any shape with that many elements; `B`: B planes, flat"""
+    if B is not None:
+        if t.dtype != torch.float32 or t.numel() != B * H * W or not t.is_contiguous():
+            raise ValueError(f"{name}: expected a contiguous float32 [{B},{H},{W}] plane, got {_got(t)}")
+    elif t.dtype != torch.float32 or t.numel() != H * W or not (flat or tuple(t.shape[-2:]) == (H, W)) or not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous float32 [{H},{W}] plane, got {_got(t)}")
+
+
+def _fp16_depth(name, t, H, W):
+    """a contiguous fp16 depth plane of H x W elements; None is refused like any other wrong operand"""
+    if t is None or t.dtype != torch.float16 or t.numel() != H * W or not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous fp16 [{H},{W}] plane, got {_got(t)}")
+
+
+def _int_in(name, v, lo, hi, strict=False, note=""):
+    """`v` (`name`: "<builder>: <argument>") is an integer from lo to hi: anything with an integer's value, or with `strict` an
+    int or a numpy integer; never a bool"""
+    if isinstance(v, bool) or (not isinstance(v, (int, np.integer)) if strict else int(v) != v) or not lo <= int(v) <= hi:
+        raise ValueError(f"{name}={v!r}: use an integer from {lo} to {hi}{note}")
+
+
+def _resample_tables(name, xmin, wx, ymin, wy, H, W):
+    """the tables of a separable resample to H x W: per axis the int32 [n] first source index and the fp32 [n, taps] weights"""
+    for axis, idx, w, n in (("x", xmin, wx, W), ("y", ymin, wy, H)):
+        if idx.dtype != torch.int32 or idx.numel() != n or w.dtype != torch.float32 or w.ndim != 2 or w.shape[0] != n \
+                or not idx.is_contiguous() or not w.is_contiguous():
+            raise ValueError(f"{name}: the {axis} tables must be contiguous int32 [{n}] and fp32 [{n}, taps]")
+
+
+def _axis_table(name, t, n_out, rows=0):
+    """the int32 table of one output axis of `n_out` pixels: `rows` x n_out elements, or with `rows=0` `resize.axis_table`'s
+    n_out x (2 + KS) -> KS.  `name`: "<builder>: tx" or "... ty" """
+    if t.dtype != torch.int32 or not t.is_contiguous() or (t.numel() != rows * n_out if rows else t.numel() % n_out or t.numel() // n_out < 3):
+        raise ValueError(f"{name} must be a contiguous int32 table of {f'{rows} x {n_out}' if rows else f'{n_out} x (2 + KS)'} elements, got "
+                         f"{_got(t)}")
+    return t.numel() // n_out - 2
+
+
+def _matte_input(name, depth, plane, hard, far, lo32, inv32, H, W, B=None, stride=0, hard_name="hard"):
+    """the matte input of an op that cuts by one -> (operand, lo32, inv32) as they go into the record: the fp16 `depth` under its
+    ramp, or `plane=` (fp32, with `depth=None`), ready matte values that carry the ramp, `hard` and `far`.  `B`: B planes `stride`
+    elements apart (`frame_matte`, `frame_matte_up`), of at least that size; there the depth is asserted"""
+    if plane is None:
+        if B is None:
+            _fp16_depth(name + ": depth", depth, H, W)
+        else:
+            assert depth.dtype == torch.float16 and depth.numel() >= (B - 1) * stride + H * W
+        return depth, lo32, inv32
+    if depth is not None or hard or far:
+        raise ValueError(f"{name}: plane= goes with depth=None, and without {hard_name} / far (the plane carries them)")
+    if B is None:
+        _fp32_plane(name + ": plane", plane, H, W)
+    elif plane.dtype != torch.float32 or not plane.is_contiguous() or plane.numel() < (B - 1) * stride + H * W:
+        raise ValueError(f"{name}: plane must be a contiguous float32 tensor of at least {(B - 1) * stride + H * W} elements, got {_got(plane)}")
+    return plane, 0.0, 0.0
+
+
+def _ramp_input(name, combine, flags, depth, lo32, inv32, hard, far, H, W):
+    """the second input of an op that writes a matte -> (depth, lo32, inv32, hard, far) as they go into the record: `combine` (a
+    key of `flags`) "and" / "or" reads the fp16 `depth` plane under the ramp; "replace" reads neither, and drops them"""
+    if combine not in flags:
+        raise ValueError(f"{name}: combine={combine!r}: use 'replace', 'and' or 'or'")
+    if combine == "replace":
+        return None, 0.0, 0.0, False, False
+    _fp16_depth(name + ": depth", depth, H, W)
+    return depth, lo32, inv32, hard, far
+
+
 def frame_ingest(src, dst, *, B, Hs, Ws, H, W, nh, nw, top, left):
     """uint8 [B,Hs,Ws,3] -> fp16 [B,3,H,W] in [-1, 1]: antialiased resize to (nh, nw) + crop at (top, left) (frame_io.geometry)."""
     assert src.dtype == torch.uint8 and dst.dtype == torch.float16
-    op = L2dOp()
-    op.kind = _lib.OP_FRAME_INGEST
-    op.p[0], op.p[1] = _ptr(src), _ptr(dst)
-    for j, v in enumerate([B, Hs, Ws, H, W, nh, nw, top, left]):
-        op.i[j] = int(v)
-    return op, (src, dst)
+    return _record(_lib.OP_FRAME_INGEST, (src, dst), (B, Hs, Ws, H, W, nh, nw, top, left))
 
 
 def frame_egress(src, dst, *, B, H, W):
     """fp16 [B,3,H,W] in [-1, 1] -> uint8 [B,H,W,3] with the reference's rounding points (image_utils.py:13,30)."""
     assert src.dtype == torch.float16 and dst.dtype == torch.uint8
-    op = L2dOp()
-    op.kind = _lib.OP_FRAME_EGRESS
-    op.p[0], op.p[1] = _ptr(src), _ptr(dst)
-    op.i[0], op.i[1], op.i[2] = int(B), int(H), int(W)
-    return op, (src, dst)
+    return _record(_lib.OP_FRAME_EGRESS, (src, dst), (B, H, W))
 
 
 # ----------------------------------------------------------------------------- baseline JPEG (jpeg.hip, jpeg.py)
@@ -1307,12 +1445,7 @@ def jpeg_dct(src, coef, *, B, H, W, quality):
     coefficients, zigzag order (jpeg.coefficients)"""
     assert src.dtype in (torch.float16, torch.uint8) and coef.dtype == torch.int16
     assert src.numel() >= B * H * W * 3 and coef.numel() >= B * H * W * 3 // 2
-    op = L2dOp()
-    op.kind = _lib.OP_JPEG_DCT
-    op.p[0], op.p[1] = _ptr(src), _ptr(coef)
-    for j, v in enumerate([B, H, W, int(src.dtype == torch.uint8), quality]):
-        op.i[j] = int(v)
-    return op, (src, coef)
+    return _record(_lib.OP_JPEG_DCT, (src, coef), (B, H, W, src.dtype == torch.uint8, quality))
 
 
 def jpeg_huff(coef, tables, staging, lengths, *, B, H, W, row_stride):
@@ -1320,25 +1453,14 @@ def jpeg_huff(coef, tables, staging, lengths, *, B, H, W, row_stride):
     (uint8 [B][H/16][row_stride]); `lengths` int32 [B][H/16]; `tables` int32 [544] (jpeg.Tables.packed)"""
     assert coef.dtype == torch.int16 and tables.dtype == torch.int32 and staging.dtype == torch.uint8 and lengths.dtype == torch.int32
     assert tables.numel() >= 544 and staging.numel() >= B * (H // 16) * row_stride and lengths.numel() >= B * (H // 16)
-    op = L2dOp()
-    op.kind = _lib.OP_JPEG_HUFF
-    op.p[0], op.p[1], op.p[2], op.p[3] = _ptr(coef), _ptr(tables), _ptr(staging), _ptr(lengths)
-    for j, v in enumerate([B, H, W, row_stride]):
-        op.i[j] = int(v)
-    return op, (coef, tables, staging, lengths)
+    return _record(_lib.OP_JPEG_HUFF, (coef, tables, staging, lengths), (B, H, W, row_stride))
 
 
 def jpeg_pack(staging, lengths, header, out, *, B, H, row_stride, out_stride):
     """rows -> per frame `out[b]` = int32 length, 12 unused bytes, header, rows (uint8 [B][out_stride])"""
     assert staging.dtype == header.dtype == out.dtype == torch.uint8 and lengths.dtype == torch.int32
     assert out.numel() >= B * out_stride
-    op = L2dOp()
-    op.kind = _lib.OP_JPEG_PACK
-    op.p[0], op.p[1], op.p[2], op.p[3] = _ptr(staging), _ptr(lengths), _ptr(header), _ptr(out)
-    for j, v in enumerate([B, H, row_stride, header.numel()]):
-        op.i[j] = int(v)
-    op.l[0] = int(out_stride)
-    return op, (staging, lengths, header, out)
+    return _record(_lib.OP_JPEG_PACK, (staging, lengths, header, out), (B, H, row_stride, header.numel()), (out_stride,))
 
 
 # ----------------------------------------------------------------------------- baseline JPEG decoder (jpeg_dec.hip, jpeg.py)
@@ -1366,38 +1488,22 @@ def jpeg_entropy_dec(file, offsets, dc_pred, blob, params, coef, status, *, n_mc
     assert dc_pred.dtype == coef.dtype == torch.int16
     assert offsets.numel() >= C + 1 and dc_pred.numel() >= 3 * C and blob.numel() >= 3648 and params.numel() >= 2
     assert coef.numel() >= n_mcu * (ny + 2) * 64
-    op = L2dOp()
-    op.kind = _lib.OP_JPEG_ENTROPY_DEC
-    keep = (file, offsets, dc_pred, blob, params, coef, status)
-    for j, t in enumerate(keep):
-        op.p[j] = _ptr(t)
-    for j, v in enumerate([n_mcu, ny, restart_interval, chunk_mcus, C, file.numel(), *dc_tab, *ac_tab]):
-        op.i[j] = int(v)
-    return op, keep
+    return _record(_lib.OP_JPEG_ENTROPY_DEC, (file, offsets, dc_pred, blob, params, coef, status),
+                   (n_mcu, ny, restart_interval, chunk_mcus, C, file.numel(), *dc_tab, *ac_tab))
 
 
 def jpeg_idct(coef, quant, planes, *, n_mcu, mcus_x, hs, vs):
     """coefficients -> the three uint8 component planes at their padded sizes (jpeg.planes_ref); `quant` uint16 [3][64] as bytes"""
     assert coef.dtype == torch.int16 and planes.dtype == torch.uint8 and quant.numel() * quant.element_size() >= 384
     assert coef.numel() >= n_mcu * (hs * vs + 2) * 64 and planes.numel() >= n_mcu * (hs * vs + 2) * 64
-    op = L2dOp()
-    op.kind = _lib.OP_JPEG_IDCT
-    op.p[0], op.p[1], op.p[2] = _ptr(coef), _ptr(quant), _ptr(planes)
-    for j, v in enumerate([n_mcu, mcus_x, hs, vs]):
-        op.i[j] = int(v)
-    return op, (coef, quant, planes)
+    return _record(_lib.OP_JPEG_IDCT, (coef, quant, planes), (n_mcu, mcus_x, hs, vs))
 
 
 def jpeg_rgb(planes, out, *, H, W, hs, vs):
     """component planes -> uint8 [H][W][3]: fancy up-sampling and colour conversion (jpeg.upsample_ref, jpeg.ycc_to_rgb_ref)"""
     assert planes.dtype == out.dtype == torch.uint8 and out.numel() >= H * W * 3
     assert planes.numel() >= (-(-W // (8 * hs))) * (-(-H // (8 * vs))) * (hs * vs + 2) * 64
-    op = L2dOp()
-    op.kind = _lib.OP_JPEG_RGB
-    op.p[0], op.p[1] = _ptr(planes), _ptr(out)
-    for j, v in enumerate([H, W, hs, vs]):
-        op.i[j] = int(v)
-    return op, (planes, out)
+    return _record(_lib.OP_JPEG_RGB, (planes, out), (H, W, hs, vs))
 
 
 # ----------------------------------------------------------------------------- style switch / blend (wblend.hip, style_bank.py)
@@ -1413,13 +1519,8 @@ def weight_blend(table_dev, table_host, weights, *, nt=None):
     uint8 tensor on the device; `table_host`: the same records as a numpy array of WBLEND_REC (the launcher validates on it)."""
     assert table_host.dtype == WBLEND_REC and table_host.flags["C_CONTIGUOUS"]
     assert table_dev.dtype == torch.uint8 and table_dev.numel() == table_host.nbytes
-    op = L2dOp()
-    op.kind = _lib.OP_WEIGHT_BLEND
-    op.p[0], op.p[1] = _ptr(table_dev), table_host.ctypes.data
-    op.i[0], op.i[1], op.i[2] = len(table_host), len(weights), int(WBLEND_NT if nt is None else nt)
-    for k, a in enumerate(list(weights)[:4]):
-        op.f[k] = float(a)
-    return op, (table_dev, table_host)
+    return _record(_lib.OP_WEIGHT_BLEND, (table_dev,), (len(table_host), len(weights), WBLEND_NT if nt is None else nt), f=list(weights)[:4],
+                   at={1: table_host.ctypes.data}, keep=(table_dev, table_host))
 
 
 # ----------------------------------------------------------------------------- depth matte (matte.hip, matte.py)
@@ -1428,13 +1529,6 @@ MATTE_MAX_R = 8                                  # l2d.h L2D_MATTE_MAX_R
 MATTE_PLANE = 16                                 # l2d.h L2D_MATTE_PLANE
 MATTE_EDGE_MAX_R = 8                             # l2d.h L2D_MATTE_EDGE_MAX_R
 MATTE_EDGE_PLANE = 32                            # l2d.h L2D_MATTE_EDGE_PLANE
-
-
-def _matte_plane(name, plane, B, H, W, stride):
-    """the `plane=` operand of `frame_matte` / `frame_matte_up`: fp32 matte values in place of the depth planes"""
-    if plane.dtype != torch.float32 or not plane.is_contiguous() or plane.numel() < (B - 1) * stride + H * W:
-        raise ValueError(f"{name}: plane must be a contiguous float32 tensor of at least {(B - 1) * stride + H * W} elements, got "
-                         f"{plane.dtype} {tuple(plane.shape)}")
 
 
 def frame_matte(styled, source, depth, dst, *, B, H, W, lo32=0.0, inv32=0.0, hard=False, far=False, show=False, r=0, depth_stride=None,
@@ -1446,23 +1540,10 @@ def frame_matte(styled, source, depth, dst, *, B, H, W, lo32=0.0, inv32=0.0, har
     assert styled.dtype == source.dtype == torch.float16 and dst.dtype == torch.uint8
     stride = H * W if depth_stride is None else int(depth_stride)
     assert styled.numel() >= B * 3 * H * W and source.numel() >= B * 3 * H * W and dst.numel() >= B * H * W * 3
-    if plane is not None:
-        if depth is not None or hard or far:
-            raise ValueError("frame_matte: plane= goes with depth=None, and without hard / far (the plane carries them)")
-        _matte_plane("frame_matte", plane, B, H, W, stride)
-        depth, lo32, inv32 = plane, 0.0, 0.0
-    else:
-        assert depth.dtype == torch.float16 and depth.numel() >= (B - 1) * stride + H * W
-    op = L2dOp()
-    op.kind = _lib.OP_FRAME_MATTE
-    op.p[0], op.p[1], op.p[2], op.p[3] = _ptr(styled), _ptr(source), _ptr(depth), _ptr(dst)
+    matte, lo32, inv32 = _matte_input("frame_matte", depth, plane, hard, far, lo32, inv32, H, W, B, stride)
     flags = ((MATTE_HARD if hard else 0) | (MATTE_FAR if far else 0) | (MATTE_SHOW if show else 0)
              | (MATTE_PLANE if plane is not None else 0))
-    for j, v in enumerate([B, H, W, r, flags]):
-        op.i[j] = int(v)
-    op.l[0] = stride
-    op.f[0], op.f[1] = float(lo32), float(inv32)
-    return op, (styled, source, depth, dst)
+    return _record(_lib.OP_FRAME_MATTE, (styled, source, matte, dst), (B, H, W, r, flags), (stride,), (lo32, inv32))
 
 
 def frame_matte_edge(source, depth, out, *, H, W, r, E, lo32=0.0, inv32=0.0, hard=False, far=False, plane=None):
@@ -1470,30 +1551,12 @@ def frame_matte_edge(source, depth, out, *, H, W, r, E, lo32=0.0, inv32=0.0, har
     by the source frame (matte.edge_ref).  `r`: the radius, 1..MATTE_EDGE_MAX_R; `E`: `matte.edge_E(r, eps)`, a Python float;
     `lo32, inv32, hard` as `matte.matte_params` returns them.  `plane` (fp32 [H,W], with `depth=None`): a ready raw matte, as
     `mask_ingest` writes it, in place of the depth plane; the ramp, `hard` and `far` do not apply."""
-    _lock_frame("frame_matte_edge: source", source, H, W)
-    if plane is not None:
-        if depth is not None or hard or far:
-            raise ValueError("frame_matte_edge: plane= goes with depth=None, and without hard / far (the plane carries them)")
-        _hold_plane("frame_matte_edge: plane", plane, H, W)
-        depth, lo32, inv32 = plane, 0.0, 0.0
-    elif depth is None or depth.dtype != torch.float16 or depth.numel() != H * W or not depth.is_contiguous():
-        raise ValueError(f"frame_matte_edge: depth: expected a contiguous fp16 [{H},{W}] plane, got "
-                         f"{getattr(depth, 'dtype', None)} {tuple(getattr(depth, 'shape', ()))}")
-    if out.dtype != torch.float32 or out.numel() != H * W or not out.is_contiguous():
-        raise ValueError(f"frame_matte_edge: out: expected a contiguous float32 [{H},{W}] plane, got {out.dtype} {tuple(out.shape)}")
-    if isinstance(r, bool) or int(r) != r or not 1 <= int(r) <= MATTE_EDGE_MAX_R:
-        raise ValueError(f"frame_matte_edge: r={r!r}: use an integer from 1 to {MATTE_EDGE_MAX_R}")
-    op = L2dOp()
-    op.kind = _lib.OP_FRAME_MATTE_EDGE
-    keep = (source, depth, out)
-    for j, t in enumerate(keep):
-        op.p[j] = _ptr(t)
+    _fp16_frame("frame_matte_edge: source", source, H, W)
+    matte, lo32, inv32 = _matte_input("frame_matte_edge", depth, plane, hard, far, lo32, inv32, H, W)
+    _fp32_plane("frame_matte_edge: out", out, H, W, flat=True)
+    _int_in("frame_matte_edge: r", r, 1, MATTE_EDGE_MAX_R)
     flags = (MATTE_HARD if hard else 0) | (MATTE_FAR if far else 0) | (MATTE_EDGE_PLANE if plane is not None else 0)
-    for j, v in enumerate([H, W, r, flags]):
-        op.i[j] = int(v)
-    op.l[0] = int(np.float64(E).view(np.int64))                                              # the bits of the double
-    op.f[0], op.f[1] = float(lo32), float(inv32)
-    return op, keep
+    return _record(_lib.OP_FRAME_MATTE_EDGE, (source, matte, out), (H, W, r, flags), (_f64_bits(E),), (lo32, inv32))
 
 
 # ----------------------------------------------------------------------------- backdrop blur (backdrop.hip, backdrop.py)
@@ -1508,30 +1571,13 @@ def frame_backdrop_blur(source, depth, out, *, H, W, r, passes, lo32=0.0, inv32=
     1..BACKDROP_MAX_R; `passes`: 1..BACKDROP_MAX_PASSES; `lo32, inv32, hard` as `matte.matte_params` returns them.  `plane` (fp32
     [H,W], with `depth=None`): a ready raw matte, as `mask_ingest` writes it, in place of the depth plane; the ramp, `hard` and
     `far` do not apply."""
-    _lock_frame("frame_backdrop_blur: source", source, H, W)
-    _lock_frame("frame_backdrop_blur: out", out, H, W)
-    if plane is not None:
-        if depth is not None or hard or far:
-            raise ValueError("frame_backdrop_blur: plane= goes with depth=None, and without hard / far (the plane carries them)")
-        _hold_plane("frame_backdrop_blur: plane", plane, H, W)
-        depth, lo32, inv32 = plane, 0.0, 0.0
-    elif depth is None or depth.dtype != torch.float16 or depth.numel() != H * W or not depth.is_contiguous():
-        raise ValueError(f"frame_backdrop_blur: depth: expected a contiguous fp16 [{H},{W}] plane, got "
-                         f"{getattr(depth, 'dtype', None)} {tuple(getattr(depth, 'shape', ()))}")
-    if isinstance(r, bool) or int(r) != r or not 1 <= int(r) <= BACKDROP_MAX_R:
-        raise ValueError(f"frame_backdrop_blur: r={r!r}: use an integer from 1 to {BACKDROP_MAX_R}")
-    if isinstance(passes, bool) or int(passes) != passes or not 1 <= int(passes) <= BACKDROP_MAX_PASSES:
-        raise ValueError(f"frame_backdrop_blur: passes={passes!r}: use an integer from 1 to {BACKDROP_MAX_PASSES}")
-    op = L2dOp()
-    op.kind = _lib.OP_FRAME_BACKDROP_BLUR
-    keep = (source, depth, out)
-    for j, t in enumerate(keep):
-        op.p[j] = _ptr(t)
+    _fp16_frame("frame_backdrop_blur: source", source, H, W)
+    _fp16_frame("frame_backdrop_blur: out", out, H, W)
+    matte, lo32, inv32 = _matte_input("frame_backdrop_blur", depth, plane, hard, far, lo32, inv32, H, W)
+    _int_in("frame_backdrop_blur: r", r, 1, BACKDROP_MAX_R)
+    _int_in("frame_backdrop_blur: passes", passes, 1, BACKDROP_MAX_PASSES)
     flags = (MATTE_HARD if hard else 0) | (MATTE_FAR if far else 0) | (BACKDROP_PLANE if plane is not None else 0)
-    for j, v in enumerate([H, W, r, passes, flags]):
-        op.i[j] = int(v)
-    op.f[0], op.f[1] = float(lo32), float(inv32)
-    return op, keep
+    return _record(_lib.OP_FRAME_BACKDROP_BLUR, (source, matte, out), (H, W, r, passes, flags), f=(lo32, inv32))
 
 
 # ----------------------------------------------------------------------------- colour lock (colorlock.hip, color_lock.py)
@@ -1545,64 +1591,40 @@ def color_lock_blocks(H, W):
     return -(-(int(H) * int(W)) // COLOR_LOCK_BLOCK_PIXELS)
 
 
-def _lock_frame(name, t, H, W):
-    if t.dtype != torch.float16 or tuple(t.shape[-3:]) != (3, H, W) or t.numel() != 3 * H * W or not t.is_contiguous():
-        raise ValueError(f"{name}: expected a contiguous fp16 [3,{H},{W}] frame, got {t.dtype} {tuple(t.shape)}")
-
-
 def frame_moments(frame, second, partials, *, H, W):
     """fp16 [3,H,W] `frame` (and `second`, or None) -> uint32 (as int32) partials [1 or 2][blocks][6]: per block of
     COLOR_LOCK_BLOCK_PIXELS pixels and per channel the sum and the sum of squares of the egress bytes (color_lock.sums_ref)"""
     nt, nblk = (1 if second is None else 2), color_lock_blocks(H, W)
-    _lock_frame("frame_moments: frame", frame, H, W)
+    _fp16_frame("frame_moments: frame", frame, H, W)
     if second is not None:
-        _lock_frame("frame_moments: second", second, H, W)
+        _fp16_frame("frame_moments: second", second, H, W)
     if partials.dtype != torch.int32 or partials.numel() < nt * nblk * 6:
-        raise ValueError(f"frame_moments: partials must be int32 with at least {nt * nblk * 6} elements, got {partials.dtype} {tuple(partials.shape)}")
-    op = L2dOp()
-    op.kind = _lib.OP_FRAME_MOMENTS
-    op.p[0], op.p[1], op.p[2] = _ptr(frame), (None if second is None else _ptr(second)), _ptr(partials)
-    for j, v in enumerate([H, W, nt, nblk]):
-        op.i[j] = int(v)
-    return op, (frame, second, partials)
+        raise ValueError(f"frame_moments: partials must be int32 with at least {nt * nblk * 6} elements, got {_got(partials)}")
+    return _record(_lib.OP_FRAME_MOMENTS, (frame, second, partials), (H, W, nt, nblk))
 
 
 def color_lock(styled, out, partials, state_in, state_out, coef, *, H, W, strength, rate, init=False, source=False, freeze=False):
     """fp16 [3,H,W] `styled` + the partials `frame_moments` wrote (of `styled`, and with `source` of the target frame behind them)
     + float64 [3,2] `state_in` -> fp16 [3,H,W] `out`, float64 [3,2] `state_out`, float32 [3,3] `coef`: color_lock.lock_ref"""
     nblk = color_lock_blocks(H, W)
-    _lock_frame("color_lock: styled", styled, H, W)
-    _lock_frame("color_lock: out", out, H, W)
+    _fp16_frame("color_lock: styled", styled, H, W)
+    _fp16_frame("color_lock: out", out, H, W)
     if partials.dtype != torch.int32 or partials.numel() < (2 if source else 1) * nblk * 6:
         raise ValueError(f"color_lock: partials must be int32 with at least {(2 if source else 1) * nblk * 6} elements")
     for name, t in (("state_in", state_in), ("state_out", state_out)):
         if t.dtype != torch.float64 or t.numel() != 6 or not t.is_contiguous():
-            raise ValueError(f"color_lock: {name} must be a contiguous float64 [3,2] record, got {t.dtype} {tuple(t.shape)}")
+            raise ValueError(f"color_lock: {name} must be a contiguous float64 [3,2] record, got {_got(t)}")
     if coef.dtype != torch.float32 or coef.numel() != 9 or not coef.is_contiguous():
-        raise ValueError(f"color_lock: coef must be a contiguous float32 [3,3] record, got {coef.dtype} {tuple(coef.shape)}")
-    op = L2dOp()
-    op.kind = _lib.OP_COLOR_LOCK
-    keep = (styled, out, partials, state_in, state_out, coef)
-    for j, t in enumerate(keep):
-        op.p[j] = _ptr(t)
+        raise ValueError(f"color_lock: coef must be a contiguous float32 [3,3] record, got {_got(coef)}")
     flags = (COLOR_LOCK_INIT if init else 0) | (COLOR_LOCK_SOURCE if source else 0) | (COLOR_LOCK_FREEZE if freeze else 0)
-    for j, v in enumerate([H, W, flags, nblk]):
-        op.i[j] = int(v)
-    op.l[0], op.l[1] = (int(np.float64(v).view(np.int64)) for v in (rate, strength))         # the bits of the two doubles
-    return op, keep
+    return _record(_lib.OP_COLOR_LOCK, (styled, out, partials, state_in, state_out, coef), (H, W, flags, nblk),
+                   (_f64_bits(rate), _f64_bits(strength)))
 
 
 # ----------------------------------------------------------------------------- output size (resize.hip, resize.py)
 RESIZE_MAX_KS = 13              # l2d.h L2D_RESIZE_MAX_KS
 RESIZE_MAX_SIZE = 4096          # l2d.h L2D_RESIZE_MAX_SIZE
 RESIZE_TILE = 32                # resize.hip RS_TW = RS_TH: a tile reads at most 2 * RESIZE_TILE + RESIZE_MAX_KS source pixels per axis
-
-
-def _resize_table(name, t, n_out):
-    if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() % n_out or t.numel() // n_out < 3:
-        raise ValueError(f"frame_resize: {name} must be a contiguous int32 table of {n_out} x (2 + KS) elements, got {t.dtype} "
-                         f"{tuple(t.shape)}")
-    return t.numel() // n_out - 2
 
 
 def frame_resize(src, dst, tx, ty, *, B, H, W, Ho, Wo, src_pitch=None):
@@ -1618,14 +1640,8 @@ def frame_resize(src, dst, tx, ty, *, B, H, W, Ho, Wo, src_pitch=None):
     else:
         assert src.numel() >= B * H * W * 3
     assert dst.numel() >= B * Ho * Wo * 3
-    ksx, ksy = _resize_table("tx", tx, Wo), _resize_table("ty", ty, Ho)
-    op = L2dOp()
-    op.kind = _lib.OP_FRAME_RESIZE
-    op.p[0], op.p[1], op.p[2], op.p[3] = _ptr(src), _ptr(dst), _ptr(tx), _ptr(ty)
-    for j, v in enumerate([B, H, W, Ho, Wo, int(src.dtype == torch.uint8), ksx, ksy]):
-        op.i[j] = int(v)
-    op.i[8] = pitch
-    return op, (src, dst, tx, ty)
+    ksx, ksy = _axis_table("frame_resize: tx", tx, Wo), _axis_table("frame_resize: ty", ty, Ho)
+    return _record(_lib.OP_FRAME_RESIZE, (src, dst, tx, ty), (B, H, W, Ho, Wo, src.dtype == torch.uint8, ksx, ksy, pitch))
 
 
 def frame_matte_up(styled, camera, depth, dst, tx, ty, *, B, H, W, Ho, Wo, lo32=0.0, inv32=0.0, hard=False, far=False, show=False, r=0,
@@ -1638,34 +1654,25 @@ def frame_matte_up(styled, camera, depth, dst, tx, ty, *, B, H, W, Ho, Wo, lo32=
     stride = H * W if depth_stride is None else int(depth_stride)
     n = B * Ho * Wo * 3
     assert styled.numel() >= n and camera.numel() >= n and dst.numel() >= n
-    if plane is not None:
-        if depth is not None or hard or far:
-            raise ValueError("frame_matte_up: plane= goes with depth=None, and without hard / far (the plane carries them)")
-        _matte_plane("frame_matte_up", plane, B, H, W, stride)
-        depth, lo32, inv32 = plane, 0.0, 0.0
-    else:
-        assert depth.dtype == torch.float16 and depth.numel() >= (B - 1) * stride + H * W
-    for name, t, n_out in (("tx", tx, Wo), ("ty", ty, Ho)):
-        if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != 3 * n_out:
-            raise ValueError(f"frame_matte_up: {name} must be a contiguous int32 table of 3 x {n_out} elements, got {t.dtype} "
-                             f"{tuple(t.shape)}")
-    op = L2dOp()
-    op.kind = _lib.OP_FRAME_MATTE_UP
-    keep = (styled, camera, depth, dst, tx, ty)
-    for j, t in enumerate(keep):
-        op.p[j] = _ptr(t)
+    matte, lo32, inv32 = _matte_input("frame_matte_up", depth, plane, hard, far, lo32, inv32, H, W, B, stride)
+    _axis_table("frame_matte_up: tx", tx, Wo, 3)
+    _axis_table("frame_matte_up: ty", ty, Ho, 3)
     flags = ((MATTE_HARD if hard else 0) | (MATTE_FAR if far else 0) | (MATTE_SHOW if show else 0)
              | (MATTE_PLANE if plane is not None else 0))
-    for j, v in enumerate([B, H, W, Ho, Wo, r, flags]):
-        op.i[j] = int(v)
-    op.l[0] = stride
-    op.f[0], op.f[1] = float(lo32), float(inv32)
-    return op, keep
+    return _record(_lib.OP_FRAME_MATTE_UP, (styled, camera, matte, dst, tx, ty), (B, H, W, Ho, Wo, r, flags), (stride,), (lo32, inv32))
 
 
 # ----------------------------------------------------------------------------- steady (steady.hip, steady.py)
 STEADY_HARD, STEADY_SHOW, STEADY_INIT = 1, 2, 4      # l2d.h L2D_STEADY_*
 STEADY_MAX_R = 8                                     # l2d.h L2D_STEADY_MAX_R
+
+
+def _steady_picture(name, show, picture, H, W):
+    """the fp16 [3,H,W] `picture` of the weight, there exactly with `show`"""
+    if bool(show) != (picture is not None):
+        raise ValueError(f"{name}: a picture buffer goes with show=True, and with nothing else")
+    if picture is not None:
+        _fp16_frame(name + ": picture", picture, H, W)
 
 
 def frame_steady(styled, source, prev_out, prev_bytes, out, next_bytes, *, H, W, lo32, inv32, s32, r=0, hard=False, show=False,
@@ -1674,32 +1681,19 @@ def frame_steady(styled, source, prev_out, prev_bytes, out, next_bytes, *, H, W,
     `next_bytes` (steady.steady_ref): the previous output held where the source's bytes did not move.  `lo32, inv32, hard` as
     `steady.steady_params` returns them, `s32` the strength; `show` also writes the picture of the weight to `picture`; with
     `init` the two `prev_*` operands are not read and may be None."""
-    _lock_frame("frame_steady: styled", styled, H, W)
-    _lock_frame("frame_steady: source", source, H, W)
-    _lock_frame("frame_steady: out", out, H, W)
+    _fp16_frame("frame_steady: styled", styled, H, W)
+    _fp16_frame("frame_steady: source", source, H, W)
+    _fp16_frame("frame_steady: out", out, H, W)
     if prev_out is not None or not init:
-        _lock_frame("frame_steady: prev_out", prev_out, H, W)
-    for name, t in (("prev_bytes", prev_bytes), ("next_bytes", next_bytes)):
-        if t is None and init and name == "prev_bytes":
-            continue
-        if t.dtype != torch.uint8 or tuple(t.shape[-3:]) != (3, H, W) or t.numel() != 3 * H * W or not t.is_contiguous():
-            raise ValueError(f"frame_steady: {name}: expected a contiguous planar uint8 [3,{H},{W}] record, got {t.dtype} {tuple(t.shape)}")
-    if bool(show) != (picture is not None):
-        raise ValueError("frame_steady: a picture buffer goes with show=True, and with nothing else")
-    if picture is not None:
-        _lock_frame("frame_steady: picture", picture, H, W)
-    if isinstance(r, bool) or int(r) != r or not 0 <= int(r) <= STEADY_MAX_R:
-        raise ValueError(f"frame_steady: r={r!r}: use an integer from 0 to {STEADY_MAX_R}")
-    op = L2dOp()
-    op.kind = _lib.OP_FRAME_STEADY
-    keep = (styled, source, prev_out, prev_bytes, out, next_bytes, picture)
-    for j, t in enumerate(keep):
-        op.p[j] = _ptr(t)
+        _fp16_frame("frame_steady: prev_out", prev_out, H, W)
+    if prev_bytes is not None or not init:
+        _u8_planes("frame_steady: prev_bytes", prev_bytes, H, W)
+    _u8_planes("frame_steady: next_bytes", next_bytes, H, W)
+    _steady_picture("frame_steady", show, picture, H, W)
+    _int_in("frame_steady: r", r, 0, STEADY_MAX_R)
     flags = (STEADY_HARD if hard else 0) | (STEADY_SHOW if show else 0) | (STEADY_INIT if init else 0)
-    for j, v in enumerate([H, W, r, flags]):
-        op.i[j] = int(v)
-    op.f[0], op.f[1], op.f[2] = float(lo32), float(inv32), float(s32)
-    return op, keep
+    return _record(_lib.OP_FRAME_STEADY, (styled, source, prev_out, prev_bytes, out, next_bytes, picture), (H, W, r, flags),
+                   f=(lo32, inv32, s32))
 
 
 # ----------------------------------------------------------------------------- follow (steady_follow.hip, steady.py)
@@ -1710,12 +1704,7 @@ FOLLOW_MAX_SEARCH, FOLLOW_MAX_BIAS = 8, 4096
 def _follow_field(name, field, H, W):
     shape = ((H + FOLLOW_BLOCK - 1) // FOLLOW_BLOCK, W // FOLLOW_BLOCK, 2)
     if field.dtype != torch.int8 or tuple(field.shape) != shape or not field.is_contiguous():
-        raise ValueError(f"{name}: field: expected a contiguous int8 {list(shape)} field, got {field.dtype} {tuple(field.shape)}")
-
-
-def _steady_plane(name, t, H, W):
-    if t.dtype != torch.uint8 or tuple(t.shape[-3:]) != (3, H, W) or t.numel() != 3 * H * W or not t.is_contiguous():
-        raise ValueError(f"{name}: expected a contiguous planar uint8 [3,{H},{W}] record, got {t.dtype} {tuple(t.shape)}")
+        raise ValueError(f"{name}: field: expected a contiguous int8 {list(shape)} field, got {_got(field)}")
 
 
 def frame_motion(source, prev_bytes, field, *, H, W, search, bias):
@@ -1723,21 +1712,12 @@ def frame_motion(source, prev_bytes, field, *, H, W, search, bias):
     `field`: per 8 x 8 block the vector (dy, dx) of the best match of the frame's bytes in the previous ones
     (steady.motion_ref).  `search`: 1..FOLLOW_MAX_SEARCH pixels; `bias`: 0..FOLLOW_MAX_BIAS summed byte levels per pixel of L1
     displacement."""
-    _lock_frame("frame_motion: source", source, H, W)
-    _steady_plane("frame_motion: prev_bytes", prev_bytes, H, W)
+    _fp16_frame("frame_motion: source", source, H, W)
+    _u8_planes("frame_motion: prev_bytes", prev_bytes, H, W)
     _follow_field("frame_motion", field, H, W)
-    if isinstance(search, bool) or int(search) != search or not 1 <= int(search) <= FOLLOW_MAX_SEARCH:
-        raise ValueError(f"frame_motion: search={search!r}: use an integer from 1 to {FOLLOW_MAX_SEARCH}")
-    if isinstance(bias, bool) or int(bias) != bias or not 0 <= int(bias) <= FOLLOW_MAX_BIAS:
-        raise ValueError(f"frame_motion: bias={bias!r}: use an integer from 0 to {FOLLOW_MAX_BIAS}")
-    op = L2dOp()
-    op.kind = _lib.OP_FRAME_MOTION
-    keep = (source, prev_bytes, field)
-    for j, t in enumerate(keep):
-        op.p[j] = _ptr(t)
-    for j, v in enumerate([H, W, search, bias]):
-        op.i[j] = int(v)
-    return op, keep
+    _int_in("frame_motion: search", search, 1, FOLLOW_MAX_SEARCH)
+    _int_in("frame_motion: bias", bias, 0, FOLLOW_MAX_BIAS)
+    return _record(_lib.OP_FRAME_MOTION, (source, prev_bytes, field), (H, W, search, bias))
 
 
 def frame_steady_follow(styled, source, prev_out, prev_bytes, out, next_bytes, field, *, H, W, lo32, inv32, s32, r=0, hard=False,
@@ -1745,36 +1725,20 @@ def frame_steady_follow(styled, source, prev_out, prev_bytes, out, next_bytes, f
     """`frame_steady` with the previous record fetched along `field` (`frame_motion`'s; steady.follow_ref): the previous output
     held where the source's bytes did not move relative to where they came from.  No `init`: an init frame is `frame_steady`'s."""
     for name, t in (("styled", styled), ("source", source), ("prev_out", prev_out), ("out", out)):
-        _lock_frame(f"frame_steady_follow: {name}", t, H, W)
-    _steady_plane("frame_steady_follow: prev_bytes", prev_bytes, H, W)
-    _steady_plane("frame_steady_follow: next_bytes", next_bytes, H, W)
+        _fp16_frame("frame_steady_follow: " + name, t, H, W)
+    _u8_planes("frame_steady_follow: prev_bytes", prev_bytes, H, W)
+    _u8_planes("frame_steady_follow: next_bytes", next_bytes, H, W)
     _follow_field("frame_steady_follow", field, H, W)
-    if bool(show) != (picture is not None):
-        raise ValueError("frame_steady_follow: a picture buffer goes with show=True, and with nothing else")
-    if picture is not None:
-        _lock_frame("frame_steady_follow: picture", picture, H, W)
-    if isinstance(r, bool) or int(r) != r or not 0 <= int(r) <= STEADY_MAX_R:
-        raise ValueError(f"frame_steady_follow: r={r!r}: use an integer from 0 to {STEADY_MAX_R}")
-    op = L2dOp()
-    op.kind = _lib.OP_FRAME_STEADY_FOLLOW
-    keep = (styled, source, prev_out, prev_bytes, out, next_bytes, picture, field)
-    for j, t in enumerate(keep):
-        op.p[j] = _ptr(t)
+    _steady_picture("frame_steady_follow", show, picture, H, W)
+    _int_in("frame_steady_follow: r", r, 0, STEADY_MAX_R)
     flags = (STEADY_HARD if hard else 0) | (STEADY_SHOW if show else 0)
-    for j, v in enumerate([H, W, r, flags]):
-        op.i[j] = int(v)
-    op.f[0], op.f[1], op.f[2] = float(lo32), float(inv32), float(s32)
-    return op, keep
+    return _record(_lib.OP_FRAME_STEADY_FOLLOW, (styled, source, prev_out, prev_bytes, out, next_bytes, picture, field), (H, W, r, flags),
+                   f=(lo32, inv32, s32))
 
 
 # ----------------------------------------------------------------------------- matte hold (matte_hold.hip, matte.py)
 MATTE_HOLD_HARD, MATTE_HOLD_INIT, MATTE_HOLD_PLANE, MATTE_HOLD_FOLLOW = 1, 4, 16, 32      # l2d.h L2D_MATTE_HOLD_*
 MATTE_HOLD_RAMP_HARD, MATTE_HOLD_RAMP_FAR = 64, 128
-
-
-def _hold_plane(name, t, H, W):
-    if t.dtype != torch.float32 or t.numel() != H * W or tuple(t.shape[-2:]) != (H, W) or not t.is_contiguous():
-        raise ValueError(f"{name}: expected a contiguous float32 [{H},{W}] plane, got {t.dtype} {tuple(t.shape)}")
 
 
 def frame_matte_hold(source, depth, prev_plane, prev_bytes, out_plane, next_bytes, *, H, W, lo32, inv32, s32, r=0, hard=False,
@@ -1785,38 +1749,23 @@ def frame_matte_hold(source, depth, prev_plane, prev_bytes, out_plane, next_byte
     (`matte.matte_params`) and `far`, or `plane` (fp32 [H,W], with `depth=None`): ready matte values, as `frame_matte_edge` writes
     them.  `lo32, inv32, hard` as `steady.steady_params` returns them, `s32` the strength; `field` (`frame_motion`'s): the
     previous record is fetched along it; with `init` the previous record and the field are not read and may be None."""
-    _lock_frame("frame_matte_hold: source", source, H, W)
-    if plane is not None:
-        if depth is not None or ramp_hard or far:
-            raise ValueError("frame_matte_hold: plane= goes with depth=None, and without ramp_hard / far (the plane carries them)")
-        _hold_plane("frame_matte_hold: plane", plane, H, W)
-        ramp_lo32 = ramp_inv32 = 0.0
-    elif depth is None or depth.dtype != torch.float16 or depth.numel() != H * W or not depth.is_contiguous():
-        raise ValueError(f"frame_matte_hold: depth: expected a contiguous fp16 [{H},{W}] plane, got "
-                         f"{getattr(depth, 'dtype', None)} {tuple(getattr(depth, 'shape', ()))}")
+    _fp16_frame("frame_matte_hold: source", source, H, W)
+    matte, ramp_lo32, ramp_inv32 = _matte_input("frame_matte_hold", depth, plane, ramp_hard, far, ramp_lo32, ramp_inv32, H, W,
+                                                hard_name="ramp_hard")
     if prev_plane is not None or not init:
-        _hold_plane("frame_matte_hold: prev_plane", prev_plane, H, W)
+        _fp32_plane("frame_matte_hold: prev_plane", prev_plane, H, W)
     if prev_bytes is not None or not init:
-        _steady_plane("frame_matte_hold: prev_bytes", prev_bytes, H, W)
-    _hold_plane("frame_matte_hold: out_plane", out_plane, H, W)
-    _steady_plane("frame_matte_hold: next_bytes", next_bytes, H, W)
+        _u8_planes("frame_matte_hold: prev_bytes", prev_bytes, H, W)
+    _fp32_plane("frame_matte_hold: out_plane", out_plane, H, W)
+    _u8_planes("frame_matte_hold: next_bytes", next_bytes, H, W)
     if field is not None:
         _follow_field("frame_matte_hold", field, H, W)
-    if isinstance(r, bool) or int(r) != r or not 0 <= int(r) <= STEADY_MAX_R:
-        raise ValueError(f"frame_matte_hold: r={r!r}: use an integer from 0 to {STEADY_MAX_R}")
-    op = L2dOp()
-    op.kind = _lib.OP_FRAME_MATTE_HOLD
-    keep = (source, depth if plane is None else plane, prev_plane, prev_bytes, out_plane, next_bytes, field)
-    for j, t in enumerate(keep):
-        op.p[j] = _ptr(t)
+    _int_in("frame_matte_hold: r", r, 0, STEADY_MAX_R)
     flags = ((MATTE_HOLD_HARD if hard else 0) | (MATTE_HOLD_INIT if init else 0) | (MATTE_HOLD_PLANE if plane is not None else 0)
              | (MATTE_HOLD_FOLLOW if field is not None else 0) | (MATTE_HOLD_RAMP_HARD if ramp_hard else 0)
              | (MATTE_HOLD_RAMP_FAR if far else 0))
-    for j, v in enumerate([H, W, r, flags]):
-        op.i[j] = int(v)
-    op.i[4], op.i[5] = (int(np.float32(v).view(np.int32)) for v in (ramp_lo32, ramp_inv32))       # the bits of the two floats
-    op.f[0], op.f[1], op.f[2] = float(lo32), float(inv32), float(s32)
-    return op, keep
+    return _record(_lib.OP_FRAME_MATTE_HOLD, (source, matte, prev_plane, prev_bytes, out_plane, next_bytes, field),
+                   (H, W, r, flags, _f32_bits(ramp_lo32), _f32_bits(ramp_inv32)), f=(lo32, inv32, s32))
 
 
 # ----------------------------------------------------------------------------- detail mode (detail.hip, detail.py)
@@ -1830,25 +1779,11 @@ def frame_detail_gain(frame, source, out, *, H, W, r, E):
     frame's bytes on the source frame's luma (detail.gains_ref).  `r`: the radius, 1..MATTE_EDGE_MAX_R; `E`:
     `matte.edge_E(r, eps)`, a Python float."""
     u8 = frame.dtype == torch.uint8
-    if u8:
-        if tuple(frame.shape[-3:]) != (H, W, 3) or frame.numel() != 3 * H * W or not frame.is_contiguous():
-            raise ValueError(f"frame_detail_gain: frame: expected a contiguous uint8 [{H},{W},3] frame, got {tuple(frame.shape)}")
-    else:
-        _lock_frame("frame_detail_gain: frame", frame, H, W)
-    _lock_frame("frame_detail_gain: source", source, H, W)
-    if out.dtype != torch.int32 or tuple(out.shape[-3:]) != (3, H, W) or out.numel() != 3 * H * W or not out.is_contiguous():
-        raise ValueError(f"frame_detail_gain: out: expected contiguous int32 [3,{H},{W}] planes, got {out.dtype} {tuple(out.shape)}")
-    if isinstance(r, bool) or int(r) != r or not 1 <= int(r) <= MATTE_EDGE_MAX_R:
-        raise ValueError(f"frame_detail_gain: r={r!r}: use an integer from 1 to {MATTE_EDGE_MAX_R}")
-    op = L2dOp()
-    op.kind = _lib.OP_FRAME_DETAIL_GAIN
-    keep = (frame, source, out)
-    for j, t in enumerate(keep):
-        op.p[j] = _ptr(t)
-    for j, v in enumerate([H, W, r, DETAIL_U8 if u8 else 0]):
-        op.i[j] = int(v)
-    op.l[0] = int(np.float64(E).view(np.int64))                                              # the bits of the double
-    return op, keep
+    (_u8_frame if u8 else _fp16_frame)("frame_detail_gain: frame", frame, H, W)
+    _fp16_frame("frame_detail_gain: source", source, H, W)
+    _i32_planes("frame_detail_gain: out", out, H, W)
+    _int_in("frame_detail_gain: r", r, 1, MATTE_EDGE_MAX_R)
+    return _record(_lib.OP_FRAME_DETAIL_GAIN, (frame, source, out), (H, W, r, DETAIL_U8 if u8 else 0), (_f64_bits(E),))
 
 
 def frame_detail(styled, camera, low, gains, tx, ty, dst, *, H, W, Ho, Wo, k, limit, show=False):
@@ -1857,29 +1792,17 @@ def frame_detail(styled, camera, low, gains, tx, ty, dst, *, H, W, Ho, Wo, k, li
     bilinearly (detail.inject_ref).  `tx`, `ty`: int32 [3, n_out] tables as `matte.table_words` builds them; `k`:
     float32(strength / (n 4096)); `show` writes 128 + the injected term."""
     for name, t in (("styled", styled), ("camera", camera), ("low", low), ("dst", dst)):
-        if t.dtype != torch.uint8 or tuple(t.shape[-3:]) != (Ho, Wo, 3) or t.numel() != Ho * Wo * 3 or not t.is_contiguous():
-            raise ValueError(f"frame_detail: {name}: expected a contiguous uint8 [{Ho},{Wo},3] frame, got {t.dtype} {tuple(t.shape)}")
-    if gains.dtype != torch.int32 or tuple(gains.shape[-3:]) != (3, H, W) or gains.numel() != 3 * H * W or not gains.is_contiguous():
-        raise ValueError(f"frame_detail: gains: expected contiguous int32 [3,{H},{W}] planes, got {gains.dtype} {tuple(gains.shape)}")
-    for name, t, n_out in (("tx", tx, Wo), ("ty", ty, Ho)):
-        if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != 3 * n_out:
-            raise ValueError(f"frame_detail: {name} must be a contiguous int32 table of 3 x {n_out} elements, got {t.dtype} "
-                             f"{tuple(t.shape)}")
+        _u8_frame("frame_detail: " + name, t, Ho, Wo)
+    _i32_planes("frame_detail: gains", gains, H, W)
+    _axis_table("frame_detail: tx", tx, Wo, 3)
+    _axis_table("frame_detail: ty", ty, Ho, 3)
     for name, t in (("styled", styled), ("camera", camera), ("low", low)):
         if t.data_ptr() == dst.data_ptr():
             raise ValueError(f"frame_detail: dst may not be the {name} frame")
     k, limit = float(k), float(limit)
     if not (np.isfinite(k) and k >= 0.0 and np.isfinite(limit) and limit >= 0.0):
         raise ValueError(f"frame_detail: k={k!r} and limit={limit!r} must be finite and not negative")
-    op = L2dOp()
-    op.kind = _lib.OP_FRAME_DETAIL
-    keep = (styled, camera, low, gains, tx, ty, dst)
-    for j, t in enumerate(keep):
-        op.p[j] = _ptr(t)
-    for j, v in enumerate([H, W, Ho, Wo, DETAIL_SHOW if show else 0]):
-        op.i[j] = int(v)
-    op.f[0], op.f[1] = k, limit
-    return op, keep
+    return _record(_lib.OP_FRAME_DETAIL, (styled, camera, low, gains, tx, ty, dst), (H, W, Ho, Wo, DETAIL_SHOW if show else 0), f=(k, limit))
 
 
 # ----------------------------------------------------------------------------- depth from the caller (depth_in.hip, depth_io.py)
@@ -1892,6 +1815,12 @@ def depth_tiles(H: int, W: int) -> int:
     return ((H + DEPTH_TILE_H - 1) // DEPTH_TILE_H) * ((W + DEPTH_TILE_W - 1) // DEPTH_TILE_W)
 
 
+def _depth_partials(name, partials, n):
+    """the fp32 [n,3] {min, max, any} records of `depth_ingest`, one per tile"""
+    if partials.dtype != torch.float32 or partials.numel() != n * 3 or not partials.is_contiguous():
+        raise ValueError(f"{name}: partials: expected contiguous fp32 [{n},3], got {_got(partials)}")
+
+
 def depth_ingest(src, R, partials, xmin, wx, ymin, wy, *, B, Hd, Wd, H, W, nh, nw, top, left, distance, invalid):
     """uint16 / fp32 [B,Hd,Wd] `src` -> fp32 [B,H,W] `R` (the normalised convolution of u = z or 1 / z over the valid samples,
     -1 where a pixel has no value) and fp32 [B tiles, 3] `partials` ({min, max, any} per tile): depth_io.resample_ref.
@@ -1901,15 +1830,9 @@ def depth_ingest(src, R, partials, xmin, wx, ymin, wy, *, B, Hd, Wd, H, W, nh, n
         raise ValueError(f"depth_ingest: src: expected uint16 or float32 samples, got {src.dtype}")
     if src.numel() != B * Hd * Wd or not src.is_contiguous():
         raise ValueError(f"depth_ingest: src: expected a contiguous [{B},{Hd},{Wd}] frame, got {tuple(src.shape)}")
-    if R.dtype != torch.float32 or R.numel() != B * H * W or not R.is_contiguous():
-        raise ValueError(f"depth_ingest: R: expected a contiguous fp32 [{B},{H},{W}] plane, got {R.dtype} {tuple(R.shape)}")
-    if partials.dtype != torch.float32 or partials.numel() != B * depth_tiles(H, W) * 3 or not partials.is_contiguous():
-        raise ValueError(f"depth_ingest: partials: expected contiguous fp32 [{B * depth_tiles(H, W)},3], got {partials.dtype} "
-                         f"{tuple(partials.shape)}")
-    for name, idx, w, n in (("x", xmin, wx, W), ("y", ymin, wy, H)):
-        if idx.dtype != torch.int32 or idx.numel() != n or w.dtype != torch.float32 or w.ndim != 2 or w.shape[0] != n \
-                or not idx.is_contiguous() or not w.is_contiguous():
-            raise ValueError(f"depth_ingest: the {name} tables must be contiguous int32 [{n}] and fp32 [{n}, taps]")
+    _fp32_plane("depth_ingest: R", R, H, W, B)
+    _depth_partials("depth_ingest", partials, B * depth_tiles(H, W))
+    _resample_tables("depth_ingest", xmin, wx, ymin, wy, H, W)
     flags = (DEPTH_F32 if f32 else 0) | (DEPTH_DISTANCE if distance else 0)
     inv_i, inv_f = 0, 0.0
     if invalid is not None:
@@ -1919,37 +1842,19 @@ def depth_ingest(src, R, partials, xmin, wx, ymin, wy, *, B, Hd, Wd, H, W, nh, n
         elif float(invalid) == int(invalid) and 0 <= int(invalid) <= 65535:     # (no uint16 sample equals any other value)
             flags |= DEPTH_HAS_INVALID
             inv_i = int(invalid)
-    op = L2dOp()
-    op.kind = _lib.OP_DEPTH_INGEST
-    keep = (src, R, partials, xmin, wx, ymin, wy)
-    for j, t in enumerate(keep):
-        op.p[j] = _ptr(t)
-    for j, v in enumerate([B, Hd, Wd, H, W, nh, nw, top, left, wx.shape[1], wy.shape[1], flags, inv_i]):
-        op.i[j] = int(v)
-    op.f[0] = inv_f
-    return op, keep
+    return _record(_lib.OP_DEPTH_INGEST, (src, R, partials, xmin, wx, ymin, wy),
+                   (B, Hd, Wd, H, W, nh, nw, top, left, wx.shape[1], wy.shape[1], flags, inv_i), f=(inv_f,))
 
 
 def depth_normalize(R, partials, out, *, B, H, W, fixed=None):
     """fp32 [B,H,W] `R` + the partials of all B frames -> fp16 [B,3,H,W] `out` in [-1, 1]: depth_io.normalize_ref.  `fixed`:
     (mn, mx) as float32 in units of u, or None: min and max over the partials"""
-    if R.dtype != torch.float32 or R.numel() != B * H * W or not R.is_contiguous():
-        raise ValueError(f"depth_normalize: R: expected a contiguous fp32 [{B},{H},{W}] plane, got {R.dtype} {tuple(R.shape)}")
-    if out.dtype != torch.float16 or out.numel() != B * 3 * H * W or not out.is_contiguous():
-        raise ValueError(f"depth_normalize: out: expected a contiguous fp16 [{B},3,{H},{W}] map, got {out.dtype} {tuple(out.shape)}")
+    _fp32_plane("depth_normalize: R", R, H, W, B)
+    _fp16_frame("depth_normalize: out", out, H, W, B)
     npart = B * depth_tiles(H, W)
-    if partials.dtype != torch.float32 or partials.numel() != npart * 3 or not partials.is_contiguous():
-        raise ValueError(f"depth_normalize: partials: expected contiguous fp32 [{npart},3], got {partials.dtype} {tuple(partials.shape)}")
-    op = L2dOp()
-    op.kind = _lib.OP_DEPTH_NORMALIZE
-    keep = (R, partials, out)
-    for j, t in enumerate(keep):
-        op.p[j] = _ptr(t)
-    for j, v in enumerate([B, H, W, npart, DEPTH_FIXED_RANGE if fixed is not None else 0]):
-        op.i[j] = int(v)
-    if fixed is not None:
-        op.f[0], op.f[1] = float(fixed[0]), float(fixed[1])
-    return op, keep
+    _depth_partials("depth_normalize", partials, npart)
+    return _record(_lib.OP_DEPTH_NORMALIZE, (R, partials, out), (B, H, W, npart, DEPTH_FIXED_RANGE if fixed is not None else 0),
+                   f=() if fixed is None else (fixed[0], fixed[1]))
 
 
 # ----------------------------------------------------------------------------- the matte from the caller (mask_in.hip, mask_io.py)
@@ -1968,30 +1873,13 @@ def mask_ingest(src, out, depth, xmin, wx, ymin, wy, *, Hm, Wm, H, W, nh, nw, to
         raise ValueError(f"mask_ingest: src: expected uint8, uint16 or float32 samples, got {src.dtype}")
     if src.numel() != Hm * Wm or not src.is_contiguous():
         raise ValueError(f"mask_ingest: src: expected a contiguous [{Hm},{Wm}] mask, got {tuple(src.shape)}")
-    if out.dtype != torch.float32 or out.numel() != H * W or not out.is_contiguous():
-        raise ValueError(f"mask_ingest: out: expected a contiguous float32 [{H},{W}] plane, got {out.dtype} {tuple(out.shape)}")
-    if combine not in MASK_COMBINE:
-        raise ValueError(f"mask_ingest: combine={combine!r}: use 'replace', 'and' or 'or'")
-    if combine == "replace":
-        depth, lo32, inv32, hard, far = None, 0.0, 0.0, False, False
-    elif depth is None or depth.dtype != torch.float16 or depth.numel() != H * W or not depth.is_contiguous():
-        raise ValueError(f"mask_ingest: depth: expected a contiguous fp16 [{H},{W}] plane, got "
-                         f"{getattr(depth, 'dtype', None)} {tuple(getattr(depth, 'shape', ()))}")
-    for name, idx, w, n in (("x", xmin, wx, W), ("y", ymin, wy, H)):
-        if idx.dtype != torch.int32 or idx.numel() != n or w.dtype != torch.float32 or w.ndim != 2 or w.shape[0] != n \
-                or not idx.is_contiguous() or not w.is_contiguous():
-            raise ValueError(f"mask_ingest: the {name} tables must be contiguous int32 [{n}] and fp32 [{n}, taps]")
+    _fp32_plane("mask_ingest: out", out, H, W, flat=True)
+    depth, lo32, inv32, hard, far = _ramp_input("mask_ingest", combine, MASK_COMBINE, depth, lo32, inv32, hard, far, H, W)
+    _resample_tables("mask_ingest", xmin, wx, ymin, wy, H, W)
     flags = (kinds[src.dtype] | MASK_COMBINE[combine] | (MASK_INVERT if invert else 0) | (MASK_RAMP_HARD if hard else 0)
              | (MASK_RAMP_FAR if far else 0))
-    op = L2dOp()
-    op.kind = _lib.OP_MASK_INGEST
-    keep = (src, out, depth, xmin, wx, ymin, wy)
-    for j, t in enumerate(keep):
-        op.p[j] = _ptr(t)
-    for j, v in enumerate([Hm, Wm, H, W, nh, nw, top, left, wx.shape[1], wy.shape[1], flags]):
-        op.i[j] = int(v)
-    op.f[0], op.f[1] = float(lo32), float(inv32)
-    return op, keep
+    return _record(_lib.OP_MASK_INGEST, (src, out, depth, xmin, wx, ymin, wy),
+                   (Hm, Wm, H, W, nh, nw, top, left, wx.shape[1], wy.shape[1], flags), f=(lo32, inv32))
 
 
 # ----------------------------------------------------------------------------- the matte key (matte_key.hip, matte_key.py)
@@ -2008,7 +1896,7 @@ def _gain_record(name, gain, out):
     """the checks of a gain record p6 of ops 59 / 61: an int32 [8] tensor, 16-byte aligned, that the plane does not overlap"""
     if not torch.is_tensor(gain) or gain.dtype != torch.int32 or gain.numel() != 8 or not gain.is_contiguous() or gain.data_ptr() % 16:
         raise ValueError(f"{name}: gain: expected a contiguous, 16-byte aligned int32 [8] record (matte_key_gain writes it), got "
-                         f"{getattr(gain, 'dtype', None)} {tuple(getattr(gain, 'shape', ()))}")
+                         f"{_got(gain)}")
     if _overlap(out, gain):
         raise ValueError(f"{name}: the plane overlaps the gain record")
 
@@ -2020,31 +1908,33 @@ def matte_key(source, out, depth, key, *, H, W, r, L, lo2, inv, hard, combine="r
     hard`: `matte_key.key_params`; `combine`: "replace", or "and" / "or" with the ramp `lo32, inv32, ramp_hard`
     (`matte.matte_params`) and `far` over the fp16 [H,W] `depth` plane, which "replace" does not read (it may be None).  `gain`: the
     int32 [8] record `matte_key_gain` writes -- the plate's bytes are multiplied by its gains first (a plate only)."""
-    if source.dtype != torch.float16 or source.numel() != 3 * H * W or tuple(source.shape[-3:]) != (3, H, W) or not source.is_contiguous():
-        raise ValueError(f"matte_key: source: expected a contiguous fp16 [3,{H},{W}] frame, got {source.dtype} {tuple(source.shape)}")
-    if out.dtype != torch.float32 or out.numel() != H * W or not out.is_contiguous():
-        raise ValueError(f"matte_key: out: expected a contiguous float32 [{H},{W}] plane, got {out.dtype} {tuple(out.shape)}")
+    depth, plate, flags, colour, f = _key_fields(source, out, depth, key, H, W, r, L, lo2, inv, hard, combine, invert, lo32, inv32, ramp_hard, far)
+    if gain is not None:
+        if plate is None:
+            raise ValueError(f"matte_key: gain with the colour key={key!r}: a gain corrects a plate")
+        _gain_record("matte_key", gain, out)
+        flags |= MATTE_KEY_GAIN
+    return _record(_lib.OP_MATTE_KEY, (source, out, depth, plate), (H, W, r, flags, L, *colour), f=f,
+                   at=None if gain is None else {6: gain})
+
+
+def _key_fields(source, out, depth, key, H, W, r, L, lo2, inv, hard, combine, invert, lo32, inv32, ramp_hard, far):
+    """what `matte_key` and `matte_key_adapt` share: every check of `matte_key` but the gain's -> (depth, plate, flags, colour,
+    f) as they go into the record, the depth and the plate None where the record has none"""
+    _fp16_frame("matte_key: source", source, H, W)
+    _fp32_plane("matte_key: out", out, H, W, flat=True)
     if W % 8:
         raise ValueError(f"matte_key: W = {W} must be a multiple of 8")
-    if combine not in MATTE_KEY_COMBINE:
-        raise ValueError(f"matte_key: combine={combine!r}: use 'replace', 'and' or 'or'")
-    if combine == "replace":
-        depth, lo32, inv32, ramp_hard, far = None, 0.0, 0.0, False, False
-    elif depth is None or depth.dtype != torch.float16 or depth.numel() != H * W or not depth.is_contiguous():
-        raise ValueError(f"matte_key: depth: expected a contiguous fp16 [{H},{W}] plane, got "
-                         f"{getattr(depth, 'dtype', None)} {tuple(getattr(depth, 'shape', ()))}")
-    if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 0 <= int(r) <= MATTE_KEY_MAX_R:
-        raise ValueError(f"matte_key: r={r!r}: use an integer from 0 to {MATTE_KEY_MAX_R}")
-    if isinstance(L, bool) or not isinstance(L, (int, np.integer)) or not 0 <= int(L) <= 256:
-        raise ValueError(f"matte_key: L={L!r}: use an integer from 0 to 256")
+    depth, lo32, inv32, ramp_hard, far = _ramp_input("matte_key", combine, MATTE_KEY_COMBINE, depth, lo32, inv32, ramp_hard, far, H, W)
+    _int_in("matte_key: r", r, 0, MATTE_KEY_MAX_R, strict=True)
+    _int_in("matte_key: L", L, 0, 256, strict=True)
     lo2, inv = float(lo2), float(inv)
     if not (np.isfinite(lo2) and lo2 >= 0.0 and np.isfinite(inv) and inv >= 0.0) or bool(hard) != (inv == 0.0):
         raise ValueError(f"matte_key: lo2={lo2!r} and inv={inv!r} must be finite and not negative, inv 0 exactly with hard={hard!r}")
     plate, colour = None, (0, 0, 0)
     if torch.is_tensor(key):
         plate = key
-        if plate.dtype != torch.uint8 or tuple(plate.shape) != (3, H, W) or not plate.is_contiguous():
-            raise ValueError(f"matte_key: key: a plate is a contiguous planar uint8 [3,{H},{W}] tensor, got {plate.dtype} {tuple(plate.shape)}")
+        _u8_planes("matte_key: key", plate, H, W, "tensor (a plate)", exact=True)
     else:
         try:
             colour = tuple(int(c) for c in key)
@@ -2052,25 +1942,9 @@ def matte_key(source, out, depth, key, *, H, W, r, L, lo2, inv, hard, combine="r
             colour = ()
         if len(colour) != 3 or any(isinstance(c, bool) or int(c) != c for c in key) or not all(0 <= c <= 255 for c in colour):
             raise ValueError(f"matte_key: key={key!r}: use three bytes (r, g, b), or a plate tensor")
-    if gain is not None:
-        if plate is None:
-            raise ValueError(f"matte_key: gain with the colour key={key!r}: a gain corrects a plate")
-        _gain_record("matte_key", gain, out)
     flags = ((MATTE_KEY_PLATE if plate is not None else 0) | (MATTE_KEY_HARD if hard else 0) | MATTE_KEY_COMBINE[combine]
              | (MATTE_KEY_INVERT if invert else 0) | (MATTE_KEY_RAMP_HARD if ramp_hard else 0) | (MATTE_KEY_RAMP_FAR if far else 0))
-    op = L2dOp()
-    op.kind = _lib.OP_MATTE_KEY
-    keep = (source, out, depth, plate)
-    for j, t in enumerate(keep):
-        op.p[j] = _ptr(t)
-    if gain is not None:
-        flags |= MATTE_KEY_GAIN
-        op.p[6] = _ptr(gain)
-        keep = keep + (gain,)
-    for j, v in enumerate([H, W, r, flags, L, *colour]):
-        op.i[j] = int(v)
-    op.f[0], op.f[1], op.f[2], op.f[3] = lo2, inv, float(lo32), float(inv32)
-    return op, keep
+    return depth, plate, flags, colour, (lo2, inv, lo32, inv32)
 
 
 MATTE_KEY_ADAPT_INIT = 256                        # l2d.h L2D_MATTE_KEY_ADAPT_INIT
@@ -2100,21 +1974,17 @@ def matte_key_adapt(source, out, depth, plate, state_in, state_out, *, H, W, r, 
     if not init and plate is not None and not torch.is_tensor(plate):
         raise ValueError(f"matte_key_adapt: plate={plate!r}: use a plate tensor or None")
     # (everything `matte_key` refuses; a record that reads a state is checked as one of a colour key)
-    op, _ = matte_key(source, out, depth, plate if init else (0, 0, 0), H=H, W=W, r=r, L=L, lo2=lo2, inv=inv, hard=hard, combine=combine,
-                      invert=invert, lo32=lo32, inv32=inv32, ramp_hard=ramp_hard, far=far)
+    depth, plate, flags, _, f = _key_fields(source, out, depth, plate if init else (0, 0, 0), H, W, r, L, lo2, inv, hard, combine, invert, lo32,
+                                            inv32, ramp_hard, far)
     for name, v in (("a_bg", a_bg), ("a_fg", a_fg)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= MATTE_KEY_MAX_RATE:
-            raise ValueError(f"matte_key_adapt: {name}={v!r}: use an integer from 0 to {MATTE_KEY_MAX_RATE} (65536 times a rate in [0, 0.5])")
+        _int_in("matte_key_adapt: " + name, v, 0, MATTE_KEY_MAX_RATE, strict=True, note=" (65536 times a rate in [0, 0.5])")
     for name, t in (("state_in", state_in), ("state_out", state_out)):
         if t is None and name == "state_in":
             continue
         if not torch.is_tensor(t) or t.dtype not in _STATE_DTYPES or tuple(t.shape) != (3, H, W) or not t.is_contiguous() \
                 or t.data_ptr() % 16:
-            raise ValueError(f"matte_key_adapt: {name}: expected a contiguous, 16-byte aligned planar uint16 [3,{H},{W}] tensor, got "
-                             f"{getattr(t, 'dtype', None)} {tuple(getattr(t, 'shape', ()))}")
-    if combine == "replace":
-        depth = None
-    reads = (source, out, depth, plate if init else None, state_in)
+            raise ValueError(f"matte_key_adapt: {name}: expected a contiguous, 16-byte aligned planar uint16 [3,{H},{W}] tensor, got {_got(t)}")
+    reads = (source, out, depth, plate, state_in)
     if any(_overlap(state_out, t) for t in reads) or _overlap(out, state_in):
         raise ValueError("matte_key_adapt: state_out overlaps state_in, the source, the plane, the depth plane or the plate (or the plane "
                          "state_in): the two records ping-pong")
@@ -2122,16 +1992,9 @@ def matte_key_adapt(source, out, depth, plate, state_in, state_out, *, H, W, r, 
         _gain_record("matte_key_adapt", gain, out)
         if _overlap(state_out, gain):
             raise ValueError("matte_key_adapt: state_out overlaps the gain record")
-    op.kind = _lib.OP_MATTE_KEY_ADAPT
-    op.i[3] = (op.i[3] & ~MATTE_KEY_PLATE) | (MATTE_KEY_ADAPT_INIT if init else 0) | (MATTE_KEY_GAIN if gain is not None else 0)
-    op.i[5], op.i[6], op.i[7] = int(a_bg), int(a_fg), 0
-    keep = (source, out, depth, plate if init else None, state_in, state_out)
-    for j, t in enumerate(keep):
-        op.p[j] = _ptr(t)
-    if gain is not None:
-        op.p[6] = _ptr(gain)
-        keep = keep + (gain,)
-    return op, keep
+    flags = (flags & ~MATTE_KEY_PLATE) | (MATTE_KEY_ADAPT_INIT if init else 0) | (MATTE_KEY_GAIN if gain is not None else 0)
+    return _record(_lib.OP_MATTE_KEY_ADAPT, (source, out, depth, plate, state_in, state_out), (H, W, r, flags, L, a_bg, a_fg, 0), f=f,
+                   at=None if gain is None else {6: gain})
 
 
 _COUNT_DTYPES = (torch.uint32, torch.int32)       # (int32: the bits of uint32 counts)
@@ -2147,8 +2010,7 @@ def _gain_partials(name, partials, H, W) -> int:
     if not torch.is_tensor(partials) or partials.dtype not in _COUNT_DTYPES or tuple(partials.shape) != (nblk, 3, MATTE_KEY_GAIN_BINS) \
             or not partials.is_contiguous() or partials.data_ptr() % 16:
         raise ValueError(f"{name}: partials: expected a contiguous, 16-byte aligned uint32 [{nblk},3,{MATTE_KEY_GAIN_BINS}] tensor "
-                         f"({nblk} blocks of {MATTE_KEY_GAIN_BLOCK} pixels over {H} x {W}), got {getattr(partials, 'dtype', None)} "
-                         f"{tuple(getattr(partials, 'shape', ()))}")
+                         f"({nblk} blocks of {MATTE_KEY_GAIN_BLOCK} pixels over {H} x {W}), got {_got(partials)}")
     return nblk
 
 
@@ -2158,25 +2020,16 @@ def matte_key_gain_hist(source, plate, partials, *, H, W):
     per-pixel ratios (matte_key.gain_hist_ref is their sum).  Every entry is written on every launch."""
     if W % 8 or H < 1 or 3 * H * W >= 1 << 31:
         raise ValueError(f"matte_key_gain_hist: W = {W} must be a multiple of 8, H = {H} at least 1 and 3 H W below 2^31")
-    if not torch.is_tensor(source) or source.dtype != torch.float16 or tuple(source.shape[-3:]) != (3, H, W) or source.numel() != 3 * H * W \
-            or not source.is_contiguous() or source.data_ptr() % 16:
-        raise ValueError(f"matte_key_gain_hist: source: expected a contiguous, 16-byte aligned fp16 [3,{H},{W}] frame, got "
-                         f"{getattr(source, 'dtype', None)} {tuple(getattr(source, 'shape', ()))}")
+    _fp16_frame("matte_key_gain_hist: source", source, H, W, align=16)
     state = torch.is_tensor(plate) and plate.dtype in _STATE_DTYPES
     if not torch.is_tensor(plate) or (plate.dtype != torch.uint8 and not state) or tuple(plate.shape) != (3, H, W) \
             or not plate.is_contiguous() or plate.data_ptr() % (16 if state else 8):
         raise ValueError(f"matte_key_gain_hist: plate: expected a contiguous planar [3,{H},{W}] tensor, uint8 (8-byte aligned) or a uint16 "
-                         f"state (16-byte aligned), got {getattr(plate, 'dtype', None)} {tuple(getattr(plate, 'shape', ()))}")
+                         f"state (16-byte aligned), got {_got(plate)}")
     nblk = _gain_partials("matte_key_gain_hist", partials, H, W)
     if _overlap(partials, source) or _overlap(partials, plate):
         raise ValueError("matte_key_gain_hist: the partials overlap the source or the plate")
-    op = L2dOp()
-    op.kind = _lib.OP_MATTE_KEY_GAIN_HIST
-    keep = (source, plate, partials)
-    for j, t in enumerate(keep):
-        op.p[j] = _ptr(t)
-    op.i[0], op.i[1], op.i[2], op.i[3] = int(H), int(W), MATTE_KEY_GAIN_STATE if state else 0, nblk
-    return op, keep
+    return _record(_lib.OP_MATTE_KEY_GAIN_HIST, (source, plate, partials), (H, W, MATTE_KEY_GAIN_STATE if state else 0, nblk))
 
 
 def matte_key_gain(partials, record, *, H, W, lim, min_count):
@@ -2187,34 +2040,18 @@ def matte_key_gain(partials, record, *, H, W, lim, min_count):
     nblk = _gain_partials("matte_key_gain", partials, H, W)
     if not torch.is_tensor(record) or record.dtype != torch.int32 or record.numel() != 8 or not record.is_contiguous() \
             or record.data_ptr() % 16:
-        raise ValueError(f"matte_key_gain: record: expected a contiguous, 16-byte aligned int32 [8] tensor, got "
-                         f"{getattr(record, 'dtype', None)} {tuple(getattr(record, 'shape', ()))}")
-    for name, v, lo, hi in (("lim", lim, MATTE_KEY_GAIN_UNITY, MATTE_KEY_GAIN_BINS - 1), ("min_count", min_count, 0, H * W)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
-            raise ValueError(f"matte_key_gain: {name}={v!r}: use an integer from {lo} to {hi}")
+        raise ValueError(f"matte_key_gain: record: expected a contiguous, 16-byte aligned int32 [8] tensor, got {_got(record)}")
+    _int_in("matte_key_gain: lim", lim, MATTE_KEY_GAIN_UNITY, MATTE_KEY_GAIN_BINS - 1, strict=True)
+    _int_in("matte_key_gain: min_count", min_count, 0, H * W, strict=True)
     if _overlap(record, partials):
         raise ValueError("matte_key_gain: the record overlaps the partials")
-    op = L2dOp()
-    op.kind = _lib.OP_MATTE_KEY_GAIN
-    keep = (partials, record)
-    for j, t in enumerate(keep):
-        op.p[j] = _ptr(t)
-    op.i[0], op.i[1], op.i[2], op.i[3], op.i[4] = int(H), int(W), nblk, int(lim), int(min_count)
-    return op, keep
+    return _record(_lib.OP_MATTE_KEY_GAIN, (partials, record), (H, W, nblk, lim, min_count))
 
 
 def frame_planar_bytes(source, out, *, H, W):
     """fp16 [3,H,W] `source` -> planar uint8 [3,H,W] `out`: its egress bytes (steady.source_bytes) -- the plate capture"""
-    if source.dtype != torch.float16 or source.numel() != 3 * H * W or tuple(source.shape[-3:]) != (3, H, W) or not source.is_contiguous():
-        raise ValueError(f"frame_planar_bytes: source: expected a contiguous fp16 [3,{H},{W}] frame, got {source.dtype} {tuple(source.shape)}")
-    if out.dtype != torch.uint8 or tuple(out.shape) != (3, H, W) or not out.is_contiguous():
-        raise ValueError(f"frame_planar_bytes: out: expected a contiguous planar uint8 [3,{H},{W}] tensor, got {out.dtype} {tuple(out.shape)}")
+    _fp16_frame("frame_planar_bytes: source", source, H, W)
+    _u8_planes("frame_planar_bytes: out", out, H, W, "tensor", exact=True)
     if W % 8:
         raise ValueError(f"frame_planar_bytes: W = {W} must be a multiple of 8")
-    op = L2dOp()
-    op.kind = _lib.OP_FRAME_PLANAR_BYTES
-    keep = (source, out)
-    for j, t in enumerate(keep):
-        op.p[j] = _ptr(t)
-    op.i[0], op.i[1] = int(H), int(W)
-    return op, keep
+    return _record(_lib.OP_FRAME_PLANAR_BYTES, (source, out), (H, W))
