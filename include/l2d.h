@@ -654,6 +654,19 @@ enum {
  *   without: under L2D_OP_MATTE_KEY_ADAPT the state still moves towards the source's own bytes, e = 256 b - s.  Compile-time
  *   variants of the same tile body (13,824 bytes of LDS).  Refused: the flag with a colour key, p6 null or misaligned, p1
  *   (L2D_OP_MATTE_KEY_ADAPT: or p5) overlapping p6.
+ *
+ * Re-warm (sink_commit.hip; the reference rewrites the sink slots only by running `prepare` again).
+ * L2D_OP_SINK_COMMIT  the sink slots 0..F-1 of every (row, k|v, token) line of every layer's KV cache copied from a source cache
+ *   list into a destination list, ONE launch however many layers:  p0 table of l2d_sink_rec in DEVICE memory (16-byte aligned) p1
+ *   the same table in HOST memory (read by the launcher only, to validate and to size the grid) ; i0 number of records.  A record is
+ *   one layer (below): `lines` = N * 2 * h * w lines, of which the first `line_bytes` = F * C * 2 bytes are copied; line j of the
+ *   destination starts at dst + j * dst_pitch (L * C * 2), of the source at src + j * src_pitch (the same, or F * C * 2 for a compact
+ *   source).  Every work-group walks all records and takes the 16-byte vectors blockIdx.x * 256 + lane, + gridDim.x * 256, ... of
+ *   each; offsets are int32 counts of 16-byte vectors.  16-byte loads and stores only; bits are moved as they are: no arithmetic, no
+ *   atomics, nothing zeroed, and nothing outside the first line_bytes of a destination line is written.  Refused: a null or not
+ *   16-byte aligned table, dst or src; no records; lines <= 0; line_bytes or a pitch that is not a positive multiple of 16;
+ *   line_bytes above either pitch; lines * pitch / 16 >= 2^31 for either pitch; a record whose destination range [dst, dst +
+ *   (lines - 1) dst_pitch + line_bytes) overlaps its source range.
  */
 enum {
     L2D_OP_IGEMM = 1,
@@ -719,6 +732,7 @@ enum {
     L2D_OP_MATTE_KEY_ADAPT = 61,
     L2D_OP_MATTE_KEY_GAIN_HIST = 62,
     L2D_OP_MATTE_KEY_GAIN = 63,
+    L2D_OP_SINK_COMMIT = 64,
 };
 
 /* flag bits of L2D_OP_FRAME_MATTE (i4) and L2D_OP_FRAME_MATTE_UP (i6); HARD and FAR also of L2D_OP_FRAME_MATTE_EDGE (i3) */
@@ -829,6 +843,16 @@ typedef struct l2d_wblend_rec {
     int32_t dtype;        /* L2D_WBLEND_F16 | L2D_WBLEND_F32 */
     int32_t pad[3];
 } l2d_wblend_rec;
+
+/* One record of L2D_OP_SINK_COMMIT's table: the KV cache of one layer, 48 bytes. */
+typedef struct l2d_sink_rec {
+    void *dst;
+    const void *src;
+    int64_t lines;        /* N * 2 * h * w */
+    int64_t line_bytes;   /* F * C * 2: what is copied of a line, a multiple of 16 */
+    int64_t dst_pitch;    /* bytes from one destination line to the next: L * C * 2 */
+    int64_t src_pitch;    /* ... of the source: >= line_bytes */
+} l2d_sink_rec;
 
 /* library / device ------------------------------------------------------------------------------ */
 int l2d_abi_version(void);

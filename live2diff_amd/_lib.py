@@ -44,6 +44,7 @@ OP_FRAME_PLANAR_BYTES = 60
 OP_MATTE_KEY_ADAPT = 61
 OP_MATTE_KEY_GAIN_HIST = 62
 OP_MATTE_KEY_GAIN = 63
+OP_SINK_COMMIT = 64
 ABI_VERSION = 6
 
 

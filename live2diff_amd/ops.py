@@ -1146,6 +1146,69 @@ def copy(src, dst, nbytes):
     return op, (src, dst)
 
 
+# ----------------------------------------------------------------------------- re-warm: the sink commit (sink_commit.hip)
+# (stands here, with the stream's own ops, and borrows `_record` and `_got` from the frame section below)
+SINK_REC = np.dtype([("dst", "<u8"), ("src", "<u8"), ("lines", "<i8"), ("line_bytes", "<i8"), ("dst_pitch", "<i8"),
+                     ("src_pitch", "<i8")])                                         # l2d_sink_rec
+
+
+def sink_commit_table(dst, src, *, F):
+    """The records of `sink_commit` for two lists of KV caches: `dst[j]` the live cache of layer j, contiguous fp16 [N,2,T,L,C];
+    `src[j]` its shadow, contiguous fp16 [N,2,T,Ls,C] with F <= Ls (Ls = L: a second cache list; Ls = F: a compact one).  Slots
+    0..F-1 of every (row, k|v, token) line are what the launch copies.  -> a numpy array of SINK_REC."""
+    dst, src = list(dst), list(src)
+    if not dst or len(dst) != len(src):
+        raise ValueError(f"sink_commit: {len(dst)} destination caches and {len(src)} source caches: need one source per destination, at least one")
+    rec = np.zeros(len(dst), dtype=SINK_REC)
+    for j, (d, s) in enumerate(zip(dst, src)):
+        for name, t in (("dst", d), ("src", s)):
+            if not torch.is_tensor(t) or t.dtype != torch.float16 or t.dim() != 5 or t.shape[1] != 2 or not t.is_contiguous():
+                raise ValueError(f"sink_commit: {name}[{j}]: expected a contiguous fp16 [N,2,T,L,C] cache, got {_got(t)}")
+        if d.shape[:3] != s.shape[:3] or d.shape[4] != s.shape[4]:
+            raise ValueError(f"sink_commit: src[{j}] {tuple(s.shape)} does not hold the lines of dst[{j}] {tuple(d.shape)}")
+        if not 1 <= F <= min(d.shape[3], s.shape[3]):
+            raise ValueError(f"sink_commit: F = {F} sink slots, dst[{j}] has {d.shape[3]} slots per line and src[{j}] {s.shape[3]}")
+        C = d.shape[4]
+        rec[j] = (d.data_ptr(), s.data_ptr(), d.shape[0] * 2 * d.shape[2], F * C * 2, d.shape[3] * C * 2, s.shape[3] * C * 2)
+    return rec
+
+
+def sink_commit_check(table_host) -> None:
+    """everything the launcher refuses (l2d.h L2D_OP_SINK_COMMIT), as a ValueError that names the record"""
+    if not isinstance(table_host, np.ndarray) or table_host.dtype != SINK_REC or table_host.ndim != 1 or not table_host.flags["C_CONTIGUOUS"]:
+        raise ValueError("sink_commit: the host table must be a contiguous 1-d numpy array of SINK_REC")
+    if len(table_host) == 0:
+        raise ValueError("sink_commit: no records")
+    for r, c in enumerate(table_host):
+        dst, src, lines, nb, dp, sp = (int(c[k]) for k in SINK_REC.names)
+        if not dst or not src:
+            raise ValueError(f"sink_commit: record {r} has a null {'src' if dst else 'dst'}")
+        if (dst | src) % 16:
+            raise ValueError(f"sink_commit: record {r}: dst or src is not 16-byte aligned")
+        if lines <= 0:
+            raise ValueError(f"sink_commit: record {r} has {lines} lines, need at least one")
+        if nb <= 0 or dp <= 0 or sp <= 0 or (nb | dp | sp) % 16:
+            raise ValueError(f"sink_commit: record {r}: bytes per line {nb}, pitches {dp} / {sp}: need positive multiples of 16")
+        if nb > dp or nb > sp:
+            raise ValueError(f"sink_commit: record {r}: {nb} bytes per line do not fit the pitches {dp} / {sp}")
+        if lines * (max(dp, sp) // 16) >= 1 << 31:
+            raise ValueError(f"sink_commit: record {r}: {lines} lines of pitch {max(dp, sp)} do not fit 2^31 16-byte vectors (the kernel's index)")
+        if dst < src + (lines - 1) * sp + nb and src < dst + (lines - 1) * dp + nb:
+            raise ValueError(f"sink_commit: record {r}: the destination range overlaps the source range")
+
+
+def sink_commit(table_dev, table_host):
+    """Slots 0..F-1 of every line of every record's destination <- its source, one launch, bits as they are.  `table_dev`: the
+    l2d_sink_rec records as a uint8 tensor on the device (16-byte aligned); `table_host`: the same records as a numpy array of
+    SINK_REC (`sink_commit_table`; the launcher validates on it and sizes the grid from it)."""
+    sink_commit_check(table_host)
+    if not torch.is_tensor(table_dev) or table_dev.dtype != torch.uint8 or table_dev.numel() != table_host.nbytes \
+            or not table_dev.is_contiguous() or table_dev.data_ptr() % 16:
+        raise ValueError(f"sink_commit: the device table must be a contiguous, 16-byte aligned uint8 tensor of the host table's "
+                         f"{table_host.nbytes} bytes, got {_got(table_dev)}")
+    return _record(_lib.OP_SINK_COMMIT, (table_dev,), (len(table_host),), at={1: table_host.ctypes.data}, keep=(table_dev, table_host))
+
+
 def run(op_and_keep, stream=None):
     """Run a single op immediately (unit tests)."""
     op, keep = op_and_keep
@@ -2055,3 +2118,4 @@ def frame_planar_bytes(source, out, *, H, W):
     if W % 8:
         raise ValueError(f"frame_planar_bytes: W = {W} must be a multiple of 8")
     return _record(_lib.OP_FRAME_PLANAR_BYTES, (source, out), (H, W))
+

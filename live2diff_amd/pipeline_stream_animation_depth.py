@@ -104,7 +104,8 @@ class StreamAnimateDiffusionDepth:
                  height: int = 512, do_add_noise: bool = True, use_denoising_batch: bool = True,
                  frame_buffer_size: int = 1, clip_skip: int = 1,
                  cfg_type: Literal["none", "full", "self", "initialize"] = "none",
-                 warmup_frames: int = WARMUP_FRAMES, window_size: int = WINDOW_SIZE, scheduler_kwargs: Optional[dict] = None):
+                 warmup_frames: int = WARMUP_FRAMES, window_size: int = WINDOW_SIZE, scheduler_kwargs: Optional[dict] = None,
+                 keep_recent: bool = False):
         self.device = pipe.device
         self.dtype = torch_dtype
         self.generator = None
@@ -157,6 +158,15 @@ class StreamAnimateDiffusionDepth:
         # the next frame -- and the device-side ingest, created by the first such frame on the device.
         self.depth_input = dict(kind="distance", invalid=0, range=None)
         self._depth_ingest = None
+        # Re-warm (`rewarm`): the window `prepare` warmed with, the shadow caches and the commit's table
+        # (made by the first re-warm and kept), the count of completed re-warms; `keep_recent`: a ring of the last `warmup_frames`
+        # frames' latents as they enter row 0 (`recent_window`), two small device copies per frame; False: no ring, no copy.
+        self.keep_recent = bool(keep_recent)
+        self._warm_window = None
+        self._shadow = self._commit = None
+        self._recent = None
+        self._recent_seen = 0
+        self.rewarms = 0
 
     @property
     def depth_glue(self):
@@ -284,21 +294,141 @@ class StreamAnimateDiffusionDepth:
                              f"{tuple(getattr(warmup_depths, 'shape', ()))}")
         depth_latent = self.encode_depth(warmup_x, tap=getattr(getattr(self, "matte_tap", None), "prime", None),
                                          depth=warmup_depths).transpose(0, 1)[None]
+        # what `rewarm()` runs on again: the window as it enters the loop (clones: nothing is drawn, nothing else is launched)
+        self._warm_window = (x_t_latent.clone(), depth_latent.clone())
+        self._seed, self.rewarms, self._recent, self._recent_seen = int(seed), 0, None, 0
+        x_0_pred = self._warm_rows(x_t_latent, depth_latent, self.kv_cache_list, lambda x: torch.randn_like(x))
+        frames = self.decode_image(x_0_pred[0].transpose(0, 1))
+        self.warmup_engine()
+        return frames
+
+    def _warm_rows(self, x_t_latent, depth_latent, kv_cache, noise_like):
+        """The row loop of `prepare` (reference :315-338): warm-up pass `idx` fills slots 0..F-1 of row `idx` of every cache of
+        `kv_cache`, its x0 prediction is noised again (`noise_like(x0)` is the noise) for the next row.  -> the last x0 prediction."""
         warm = self.unet_warmup if self.unet_warmup is not None else self.unet
         for idx, t in enumerate(self.sub_timesteps_tensor):
             if hasattr(warm, "warmup"):
                 pred = warm.warmup(x_t_latent, t.view(1), encoder_hidden_states=self.prompt_embeds[0:1],
-                                   depth_sample=depth_latent, kv_cache=self.kv_cache_list, row=idx)["sample"]
+                                   depth_sample=depth_latent, kv_cache=kv_cache, row=idx)["sample"]
             else:   # a reference-style warm-up module
                 pred = warm(x_t_latent, t.view(1), temporal_attention_mask=None, depth_sample=depth_latent,
-                            encoder_hidden_states=self.prompt_embeds[0:1], kv_cache=[c[idx] for c in self.kv_cache_list],
+                            encoder_hidden_states=self.prompt_embeds[0:1], kv_cache=[c[idx] for c in kv_cache],
                             return_dict=True)["sample"]
             x_0_pred = self.scheduler_step_batch(pred, x_t_latent, idx)
             if idx < len(self.sub_timesteps_tensor) - 1:
-                x_t_latent = self.alpha_prod_t_sqrt[idx + 1] * x_0_pred + self.beta_prod_t_sqrt[idx + 1] * torch.randn_like(x_0_pred)
-        frames = self.decode_image(x_0_pred[0].transpose(0, 1))
-        self.warmup_engine()
-        return frames
+                x_t_latent = self.alpha_prod_t_sqrt[idx + 1] * x_0_pred + self.beta_prod_t_sqrt[idx + 1] * noise_like(x_0_pred)
+        return x_0_pred
+
+    # ------------------------------------------------------------------ re-warm (not in the reference; DESIGN.md section 8.z20)
+    def rewarm_generator(self) -> torch.Generator:
+        """The private generator the next `rewarm` draws from when it is given none: on the stream's device, seeded from the
+        stream's seed and the count of completed re-warms -- never the global RNG, `self.generator` or the device step's counter,
+        so the stream's own noise sequence is the one it would have had without the re-warm."""
+        if self._warm_window is None:
+            raise RuntimeError("rewarm_generator() needs prepare() first")
+        g = torch.Generator(device=self._warm_window[0].device)
+        g.manual_seed((self._seed * 1000003 + 7919 * (self.rewarms + 1)) & (2 ** 63 - 1))
+        return g
+
+    @property
+    def warmup_window(self):
+        """the (x_t_latent, depth_latent) pair `prepare` warmed with, [1,4,F,h,w] each: what `rewarm()` runs on again"""
+        if self._warm_window is None:
+            raise RuntimeError("warmup_window needs prepare() first")
+        return self._warm_window
+
+    def _window_shape(self):
+        return (1, 4, self.warmup_frames, self.latent_height, self.latent_width)
+
+    @torch.no_grad()
+    def rewarm(self, x_t_latent=None, depth_latent=None, *, generator: Optional[torch.Generator] = None) -> None:
+        """Refresh the sink slots 0..F-1 of every row of every KV cache under the weights and the prompt the stream has NOW,
+        without a new `prepare`.  `x_t_latent` / `depth_latent`: the window's latents, [1,4,F,h,w] each as `prepare` forms them
+        (`recent_window()` returns such a pair); both None: the window `prepare` warmed with.  The row loop of `prepare` runs
+        against SHADOW caches (a second list of the live list's shapes, made by the first re-warm and kept), then the sink slots
+        are committed to the live caches: one L2D_OP_SINK_COMMIT launch behind the last warm-up row on the current stream on the
+        device, a slice copy per cache on the host route.  A re-warm that fails on the way changes no live cache; one that
+        succeeds takes effect between two frames.  The noise between rows comes from `generator`, or from `rewarm_generator()`.
+        Nothing else of the running stream is touched: window slots, the stream batch, the ring state, the frame counter, the
+        prompt, `init_noise`, the device step and its graph, the objects in `kv_cache_list`."""
+        if self._warm_window is None:
+            raise RuntimeError("rewarm() needs prepare() first: there is no stream to re-warm")
+        if (x_t_latent is None) != (depth_latent is None):
+            raise ValueError("rewarm: x_t_latent and depth_latent go together (both, or neither for the window of prepare)")
+        if x_t_latent is None:
+            x_t_latent, depth_latent = self._warm_window
+        for name, t in (("x_t_latent", x_t_latent), ("depth_latent", depth_latent)):
+            if not torch.is_tensor(t) or tuple(t.shape) != self._window_shape():
+                raise ValueError(f"rewarm: {name}: expected latents shaped {self._window_shape()}, got {tuple(getattr(t, 'shape', ()))}")
+        live = self.kv_cache_list
+        if self._shadow is None or len(self._shadow) != len(live) or any(s.shape != c.shape or s.device != c.device
+                                                                          for s, c in zip(self._shadow, live)):
+            self._shadow, self._commit = [torch.zeros_like(c) for c in live], None
+        gen = generator if generator is not None else self.rewarm_generator()
+        to = dict(device=self.device, dtype=self.dtype)
+        self._warm_rows(x_t_latent.to(**to), depth_latent.to(**to), self._shadow,
+                        lambda x: torch.randn(x.shape, generator=gen, device=x.device, dtype=x.dtype))
+        self._commit_sinks(live, self._shadow)
+        self.rewarms += 1
+
+    def _commit_sinks(self, live, shadow) -> None:
+        F_ = self.warmup_frames
+        if not (live[0].is_cuda and live[0].dtype == torch.float16):
+            for c, s in zip(live, shadow):                    # the host route: CPU tensors, the mocks
+                c[:, :, :, :F_].copy_(s[:, :, :, :F_])
+            return
+        from . import ops
+        hit = self._commit
+        if hit is None or any(a is not b for a, b in zip(hit[2], live)):
+            host = ops.sink_commit_table(live, shadow, F=F_)
+            dev = torch.from_numpy(host.view(np.uint8).reshape(-1).copy()).to(live[0].device)
+            hit = self._commit = (dev, host, tuple(live))
+        ops.run(ops.sink_commit(hit[0], hit[1]))
+
+    @torch.no_grad()
+    def encode_window(self, warmup_frames, warmup_depths=None, *, generator: Optional[torch.Generator] = None):
+        """A window of frames ([F,3,H,W] in [0,1], what `prepare` takes) -> the pair of latents `rewarm` takes, encoded exactly as
+        `prepare` encodes them (the detector, or `warmup_depths`) but WITHOUT the matte tap, and with `generator` (default:
+        `rewarm_generator()`) in place of the stream's own for the draws of the encode, whose state therefore stays."""
+        if self._warm_window is None:
+            raise RuntimeError("encode_window() needs prepare() first")
+        to = dict(dtype=self.dtype, device=self.device)
+        xs = [self.image_processor.preprocess(f, self.height, self.width).to(**to) for f in warmup_frames]
+        warmup_x = torch.cat(xs, dim=0)
+        if warmup_x.shape[0] != self.warmup_frames:
+            raise ValueError(f"rewarm: expected {self.warmup_frames} frames, got {warmup_x.shape[0]}")
+        if warmup_depths is not None and (getattr(warmup_depths, "ndim", 0) != 3 or warmup_depths.shape[0] != warmup_x.shape[0]):
+            raise ValueError(f"depths: expected a batch [{warmup_x.shape[0]},Hd,Wd], one depth frame per frame, got "
+                             f"{tuple(getattr(warmup_depths, 'shape', ()))}")
+        keep, self.generator = self.generator, generator if generator is not None else self.rewarm_generator()
+        try:
+            x_t_latent = self.encode_image(warmup_x).transpose(0, 1)[None]
+            depth_latent = self.encode_depth(warmup_x, tap=None, depth=warmup_depths).transpose(0, 1)[None]
+        finally:
+            self.generator = keep
+        return x_t_latent, depth_latent
+
+    def _record_recent(self, x_t_latent, depth_latent) -> None:
+        """`keep_recent`: the frame's latents, as they enter row 0, into slot `frames seen % F` of the ring (two device copies on
+        the current stream; in push / pop mode that is behind the side stream's event)"""
+        F_ = self.warmup_frames
+        if self._recent is None:
+            shape = (F_, 4, self.latent_height, self.latent_width)
+            self._recent = (torch.zeros(shape, dtype=self.dtype, device=self.device), torch.zeros(shape, dtype=self.dtype, device=self.device))
+        slot = self._recent_seen % F_
+        self._recent[0][slot].copy_(x_t_latent.reshape(self._recent[0].shape[1:]))
+        self._recent[1][slot].copy_(depth_latent.reshape(self._recent[1].shape[1:]))
+        self._recent_seen += 1
+
+    def recent_window(self):
+        """the last F frames' (x_t_latent, depth_latent) as two [1,4,F,h,w] tensors, oldest first (`keep_recent=True`)"""
+        F_ = self.warmup_frames
+        if not self.keep_recent:
+            raise ValueError("recent_window: this stream keeps no recent window: build it with keep_recent=True")
+        if self._recent is None or self._recent_seen < F_:
+            raise ValueError(f"recent_window: {self._recent_seen} frames since prepare, the window needs {F_}")
+        order = [(self._recent_seen + k) % F_ for k in range(F_)]
+        return tuple(r[order].transpose(0, 1)[None].contiguous() for r in self._recent)
 
     def warmup_engine(self):
         """reference :346-366 (TensorRT engine warm-up); the HIP plan needs none."""
@@ -466,6 +596,8 @@ class StreamAnimateDiffusionDepth:
         """reference :573-623 (stream-batch shift register). `noise` lets tests inject the re-noising tensor."""
         n = self.denoising_steps_num
         ds = getattr(self, "_device_step", None)
+        if self.keep_recent:
+            self._record_recent(x_t_latent, depth_latent)
         if ds is not None:
             if noise is not None:
                 raise ValueError("device step is enabled: its ring buffer / latent rows live on the device and the host "

@@ -343,7 +343,7 @@ class StreamAnimateDiffusionDepthWrapper:
                  matte_edge: Optional[dict] = None, detail: Optional[dict] = None, depth_input: Optional[dict] = None,
                  depth_source: str = "detector", backdrop: Optional[dict] = None, steady_follow: Optional[dict] = None,
                  matte_hold: Optional[dict] = None, mask_input: Optional[dict] = None, matte_key: Optional[dict] = None,
-                 matte_key_adapt: Optional[dict] = None, matte_key_gain: Optional[dict] = None):
+                 matte_key_adapt: Optional[dict] = None, matte_key_gain: Optional[dict] = None, keep_recent: bool = False):
         _check_depth_source(depth_source)
         self._check_keywords(few_step_model_type=few_step_model_type, acceleration=acceleration, cfg_type=cfg_type,
                              use_denoising_batch=use_denoising_batch, frame_buffer_size=frame_buffer_size, device_ids=device_ids,
@@ -366,13 +366,13 @@ class StreamAnimateDiffusionDepthWrapper:
                     jpeg_decode=jpeg_decode, output_size=output_size, output_resample=output_resample, matte_source=matte_source,
                     steady=steady, matte_edge=matte_edge, detail=detail, depth_input=depth_input, depth_source=depth_source,
                     backdrop=backdrop, steady_follow=steady_follow, matte_hold=matte_hold, mask_input=mask_input, matte_key=matte_key,
-                    matte_key_adapt=matte_key_adapt, matte_key_gain=matte_key_gain)
+                    matte_key_adapt=matte_key_adapt, matte_key_gain=matte_key_gain, keep_recent=keep_recent)
 
     @classmethod
     def from_components(cls, pipe, *, num_inference_steps: int, t_index_list: Optional[List[int]] = None,
                         strength: Optional[float] = None, **kw):
         """The wrapper around an already assembled `pipe` namespace (tests, synthetic weights).  Keywords: those of the
-        constructor that do not name files (`jpeg_quality`, `jpeg_decode`, `output_size`, `output_resample`, `matte_source`, `steady`, `steady_follow`, `matte_edge`, `matte_hold`, `detail`, `backdrop`, `depth_input`, `mask_input`, `matte_key`, `matte_key_adapt`, `matte_key_gain` and `depth_source` among them; with `depth_source="input"` the namespace needs no `depth_model`), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
+        constructor that do not name files (`jpeg_quality`, `jpeg_decode`, `output_size`, `output_resample`, `matte_source`, `steady`, `steady_follow`, `matte_edge`, `matte_hold`, `detail`, `backdrop`, `depth_input`, `mask_input`, `matte_key`, `matte_key_adapt`, `matte_key_gain`, `keep_recent` and `depth_source` among them; with `depth_source="input"` the namespace needs no `depth_model`), plus `clip_skip`, `warmup_frames`, `window_size`, `scheduler_kwargs`."""
         self = cls.__new__(cls)
         cls._check_keywords(**{k: kw.pop(k) for k in ("acceleration", "cfg_type", "use_denoising_batch", "frame_buffer_size",
                                                       "device_ids", "opt_unet", "few_step_model_type") if k in kw},
@@ -414,7 +414,7 @@ class StreamAnimateDiffusionDepthWrapper:
                similar_image_filter_threshold=0.98, similar_image_filter_max_skip_frame=10, jpeg_quality=75, jpeg_decode="device",
                output_size=None, output_resample="lanczos", matte_source="stream", steady=None, matte_edge=None, detail=None,
                depth_input=None, depth_source="detector", backdrop=None, steady_follow=None, matte_hold=None, mask_input=None, matte_key=None,
-               matte_key_adapt=None, matte_key_gain=None):
+               matte_key_adapt=None, matte_key_gain=None, keep_recent=False):
         self._check_matte_source(matte_source)
         if matte_key_gain is not None and not isinstance(matte_key_gain, dict):
             raise ValueError(f"matte_key_gain={matte_key_gain!r}: use a dict of set_matte_key_gain's keywords, or None")
@@ -461,7 +461,8 @@ class StreamAnimateDiffusionDepthWrapper:
                                                   strength=strength, torch_dtype=dtype, width=width, height=height,
                                                   do_add_noise=do_add_noise, frame_buffer_size=1, use_denoising_batch=True,
                                                   cfg_type="none", clip_skip=clip_skip, warmup_frames=warmup_frames,
-                                                  window_size=window_size, scheduler_kwargs=scheduler_kwargs)
+                                                  window_size=window_size, scheduler_kwargs=scheduler_kwargs,
+                                                  keep_recent=keep_recent)
         self.batch_size = len(self.stream.t_list)
         self.stream.load_warmup_unet(None)
         self.stream.prepare_cache(height=height, width=width, denoising_steps_num=self.batch_size)
@@ -1562,16 +1563,21 @@ class StreamAnimateDiffusionDepthWrapper:
             if inst._blender is not None:
                 inst._blender.forget(ps.W)             # (a blend table keeps the sets it reads alive)
 
-    def set_style(self, style) -> None:
+    def set_style(self, style, rewarm=False) -> None:
         """Switch to a registered style (a name) or to an affine mix of up to four ({name: weight}, weights summing to 1) between
         two frames: one blend launch each over the UNet's and the text encoder's packed weights on the current stream, then the
         current prompt re-encoded by the new text encoder and handed to the stream like `update_prompt` does.  No plan or graph is
         rebuilt; the VAE, the depth detector, the KV caches, the stream batch, the ring state and the noise counter are not
         touched.  Takes effect with the next frame, in `__call__` and in push / pop mode (the side stream of `push` never touches
         these weights).  K / V of earlier frames were projected by the old weights: window slots age out within `window_size`
-        frames -- that is the cross-fade -- and the sink slots written by `prepare` keep the old projections until `prepare` runs
-        again."""
+        frames -- that is the cross-fade -- and the sink slots written by `prepare` keep the old projections until they are
+        re-warmed: `rewarm=True` does it right here on the window `prepare` was given, `rewarm="recent"` on the last frames
+        (`rewarm(...)`, behind the mix and the re-encoded prompt); False, the default, leaves them."""
         from .style_bank import drop_zero_terms, parse_style
+        if rewarm not in (False, True, "warmup", "recent"):
+            raise ValueError(f"rewarm={rewarm!r}: use False, True (the window of prepare) or 'recent'")
+        if rewarm == "recent" and not self.stream.keep_recent:
+            raise ValueError("rewarm='recent' needs a wrapper built with keep_recent=True")
         bank = self._need_bank()
         mix = parse_style(style, bank.sets)
         names, weights = drop_zero_terms(list(mix), list(mix.values()))
@@ -1580,6 +1586,71 @@ class StreamAnimateDiffusionDepthWrapper:
         bank.current = dict(zip(names, weights))
         if self._prompt is not None:
             self.stream.update_prompt(self._prompt)
+        if rewarm:
+            self.rewarm("recent" if rewarm == "recent" else "warmup")
+
+    # ------------------------------------------------------------------ re-warm
+    @property
+    def rewarms(self) -> int:
+        """completed re-warms since `prepare`"""
+        return self.stream.rewarms
+
+    def rewarm(self, source="warmup", *, depths=None) -> None:
+        """Refresh the sink slots of every temporal layer under the weights and the prompt the stream has now, without a new
+        `prepare` (`StreamAnimateDiffusionDepth.rewarm`).  source: "warmup", the window `prepare` was given; "recent", the last F
+        frames that entered the stream (`keep_recent=True`); or frames -- anything `prepare` takes as `warmup_frames`, encoded as
+        `prepare` encodes them (the detector, or `depths` as `prepare`'s `warmup_depths`) but without the matte tap.  It restarts
+        nothing: the matte's delay line, the colour lock, steady, the matte hold, the key's plate and the output size carry on.
+        Legal with frames pushed and not yet popped: it runs on the caller's stream and their UNet steps run behind it."""
+        if isinstance(source, str):
+            if source not in ("warmup", "recent"):
+                raise ValueError(f"source={source!r}: use 'warmup', 'recent' or a window of frames")
+            if depths is not None:
+                raise ValueError(f"depths= goes with frames, not with source={source!r}: that window's depth is already encoded")
+            if source == "recent":
+                if not self.stream.keep_recent:
+                    raise ValueError("source='recent' needs a wrapper built with keep_recent=True")
+                if self.stream._warm_window is None:
+                    raise RuntimeError("rewarm() needs prepare() first: there is no stream to re-warm")
+                self.stream.rewarm(*self.stream.recent_window())
+            else:
+                self.stream.rewarm()
+            return
+        if isinstance(depths, (list, tuple)):
+            items = [self._depth_arg(d, "depths") for d in depths]
+            depths = torch.stack(items) if torch.is_tensor(items[0]) else np.stack(items)
+        depths = self._depth_arg(depths, "depths")
+        side = getattr(self.stream, "_pre_stream", None)
+        if side is not None and getattr(self.stream, "_pending", None):
+            # the encodes below use the plan buffers (TAESD encoder, depth detector) the pushed frames' side-stream work may still hold
+            torch.cuda.current_stream().wait_stream(side)
+        gen = self.stream.rewarm_generator()              # one generator: the encode's draws, then the noise between rows
+        x, d = self._on_window(source, lambda frames: self.stream.encode_window(frames, depths, generator=gen))
+        self.stream.rewarm(x, d, generator=gen)
+
+    def _on_window(self, warmup_frames, run):
+        """`run(frames)` on a warm-up window as `prepare` takes it: a list of JPEG files is decoded, a uint8 batch goes through one
+        batched ingest launch, float frames pass as they are"""
+        if isinstance(warmup_frames, (list, tuple)) and warmup_frames and all(_is_jpeg(f) for f in warmup_frames):
+            # (a device frame is a view of one of the decoder's two static slots: it is copied before the slot's next turn)
+            decoded = [d.clone() if torch.is_tensor(d) else torch.from_numpy(d).to(self.io.device) if self.io is not None else d
+                       for d in map(self._decode_jpeg, warmup_frames)]
+            warmup_frames = torch.stack(decoded) if torch.is_tensor(decoded[0]) else np.stack(decoded)
+            self._check_jpeg()
+        dt = getattr(warmup_frames, "dtype", None)
+        if dt == torch.uint8 or dt == np.uint8:
+            from .frame_io import _PassThrough
+            if self.io is None:
+                raise ValueError("uint8 warm-up frames need the device-side frame I/O (a cuda device)")
+            x = self.io.ingest(warmup_frames)
+            # the pipeline preprocesses frame by frame and only then concatenates: through a static ingest slot all rows would be
+            # views of the last frame, and a normalised frame must never reach a [0, 1]-or-[-1, 1] probe
+            keep, self.stream.image_processor = self.stream.image_processor, _PassThrough()
+            try:
+                return run(x)
+            finally:
+                self.stream.image_processor = keep
+        return run(warmup_frames)
 
     # ------------------------------------------------------------------ prepare
     def prepare(self, warmup_frames, prompt: str, negative_prompt: str = "", guidance_scale: float = 1.2, delta: float = 1.0,
@@ -1616,27 +1687,7 @@ class StreamAnimateDiffusionDepthWrapper:
             self._lock_state = None
         self._steady_init, self._steady_last, self._steady_state = True, None, None      # the steady mode starts again too
         self._hold_init, self._hold_state = True, None                                   # and the matte hold
-        if isinstance(warmup_frames, (list, tuple)) and warmup_frames and all(_is_jpeg(f) for f in warmup_frames):
-            # (a device frame is a view of one of the decoder's two static slots: it is copied before the slot's next turn)
-            decoded = [d.clone() if torch.is_tensor(d) else torch.from_numpy(d).to(self.io.device) if self.io is not None else d
-                       for d in map(self._decode_jpeg, warmup_frames)]
-            warmup_frames = torch.stack(decoded) if torch.is_tensor(decoded[0]) else np.stack(decoded)
-            self._check_jpeg()
-        dt = getattr(warmup_frames, "dtype", None)
-        if dt == torch.uint8 or dt == np.uint8:
-            from .frame_io import _PassThrough
-            if self.io is None:
-                raise ValueError("uint8 warm-up frames need the device-side frame I/O (a cuda device)")
-            x = self.io.ingest(warmup_frames)
-            # the pipeline preprocesses frame by frame and only then concatenates: through a static ingest slot all rows would be
-            # views of the last frame, and a normalised frame must never reach a [0, 1]-or-[-1, 1] probe
-            keep, self.stream.image_processor = self.stream.image_processor, _PassThrough()
-            try:
-                frames = self.stream.prepare(warmup_frames=x, **kw)
-            finally:
-                self.stream.image_processor = keep
-        else:
-            frames = self.stream.prepare(warmup_frames=warmup_frames, **kw)
+        frames = self._on_window(warmup_frames, lambda x: self.stream.prepare(warmup_frames=x, **kw))
         from .unet_hip import HipStreamingUNet
         if isinstance(self.stream.unet, HipStreamingUNet):
             self.stream.enable_device_step(seed=self.seed)

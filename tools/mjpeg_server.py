@@ -19,7 +19,10 @@ is dropped and counted.
 `--style NAME=DREAMBOOTH[,LORA:ALPHA...]` (repeatable) registers further styles beside the config's own (`"default"`); their packed
 weights stay resident on the device.  `POST /style` with a JSON body `{name: weight}` (up to four names, weights summing to 1)
 switches or blends the running stream: the producer thread applies it between two frames (`wrapper.set_style`), without a
-re-warm.  `GET /style` answers `{"styles": [...], "current": {...}}`.
+re-warm -- unless the body also holds `"rewarm": true` (the sinks are re-warmed on the warm-up window right behind the switch) or
+`"rewarm": "recent"` (on the last frames; needs `--keep-recent`); a style cannot be named "rewarm" on this route.  `GET /style`
+answers `{"styles": [...], "current": {...}}`.  `POST /rewarm` with `{"source": "warmup"}` or `{"source": "recent"}` re-warms the
+sinks alone, between two frames (`wrapper.rewarm`); `GET /rewarm` answers `{"rewarms": n, "failed": m}`.
 
 `--matte LO,HI[,FEATHER[,far]]` stylises only the near side (`far`: the far side) of a ramp over the frame's own depth map and
 keeps the real picture elsewhere (`wrapper.set_matte`: composited on the device, in front of the JPEG encoder).  `POST /matte`
@@ -180,31 +183,75 @@ class Inbox:
 
 class StyleBox:
     """What `POST /style` delivers: the newest requested mix, applied by the producer between two frames.  `names` are the styles the
-    wrapper knows; `current` is the mix last applied; `failed` counts requests the wrapper refused."""
+    wrapper knows; `current` is the mix last applied; `failed` counts requests the wrapper refused.  What `POST /rewarm` delivers
+    waits here too -- the newest requested source, applied behind a posted style between the same two frames.  `keep_recent`: whether
+    the wrapper keeps a recent window ("recent" is refused at the door without one); `rewarms` counts the re-warms done,
+    `rewarm_failed` those the wrapper refused (fewer than F frames since `prepare`, say)."""
 
-    def __init__(self, names, current=None):
+    def __init__(self, names, current=None, keep_recent: bool = False):
         self._lock = threading.Lock()
         self.names, self.current, self._want, self.failed = list(names), dict(current or {}), None, 0
+        self._rewarm = False
+        self.keep_recent, self._source, self.rewarms, self.rewarm_failed = bool(keep_recent), None, 0, 0
 
-    def put(self, mix: dict) -> None:
+    def put(self, mix: dict, rewarm=False) -> None:
+        """`rewarm`: False, True (the warm-up window) or "recent" -- `set_style`'s keyword, for this request"""
         with self._lock:
-            self._want = dict(mix)
+            self._want, self._rewarm = dict(mix), rewarm
 
     def take(self):
         with self._lock:
             mix, self._want = self._want, None
             return mix
 
+    def put_rewarm(self, source: str) -> None:
+        if source not in REWARM_SOURCES:
+            raise ValueError(f"source={source!r}: use 'warmup' or 'recent'")
+        if source == "recent" and not self.keep_recent:
+            raise ValueError("source 'recent' needs a server started with --keep-recent")
+        with self._lock:
+            self._source = source
+
     def apply(self, wrapper) -> None:
         """(producer thread, between frames)"""
-        mix = self.take()
-        if mix is None:
-            return
-        try:
-            wrapper.set_style(mix)
-            self.current = dict(wrapper.style)
-        except (KeyError, ValueError):
-            self.failed += 1
+        with self._lock:
+            mix, rewarm, self._want, self._rewarm = self._want, self._rewarm, None, False
+            source, self._source = self._source, None
+        if mix is not None:
+            try:
+                if rewarm:
+                    wrapper.set_style(mix, rewarm=rewarm)
+                else:
+                    wrapper.set_style(mix)
+                self.current = dict(wrapper.style)
+            except (KeyError, ValueError):
+                self.failed += 1
+        if source is not None:
+            try:
+                wrapper.rewarm(source)
+                self.rewarms += 1
+            except (ValueError, RuntimeError):
+                self.rewarm_failed += 1
+
+
+REWARM_SOURCES = ("warmup", "recent")
+
+
+def parse_rewarm_body(body: bytes) -> str:
+    """the body of `POST /rewarm`, `{"source": "warmup" | "recent"}` -> the source"""
+    req = json.loads(body.decode())                       # (json.JSONDecodeError and UnicodeDecodeError are ValueErrors)
+    if not isinstance(req, dict) or set(req) != {"source"} or req["source"] not in REWARM_SOURCES:
+        raise ValueError('use {"source": "warmup"} or {"source": "recent"}')
+    return req["source"]
+
+
+def parse_style_rewarm(value):
+    """the "rewarm" entry of a `POST /style` body -> `set_style`'s keyword"""
+    if value is False or value is True or value == "recent":
+        return value
+    if value == "warmup":
+        return True
+    raise ValueError('"rewarm": use true, false, "warmup" or "recent"')
 
 
 def parse_matte_arg(text: str):
@@ -1027,6 +1074,13 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
                 self.send_header("Content-Length", str(len(body)))
                 self.end_headers()
                 self.wfile.write(body)
+            elif self.path == "/rewarm" and styles is not None:
+                body = json.dumps({"rewarms": styles.rewarms, "failed": styles.rewarm_failed}).encode()
+                self.send_response(200)
+                self.send_header("Content-Type", "application/json")
+                self.send_header("Content-Length", str(len(body)))
+                self.end_headers()
+                self.wfile.write(body)
             elif self.path == "/matte-key/plate" and keys is not None:
                 plate = keys.take_plate()
                 if plate is None:
@@ -1158,17 +1212,44 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
                 self.send_error(413 if n > 4096 else 400)
                 return
             try:
-                mix = parse_style(json.loads(self.rfile.read(n).decode()), styles.names)
+                req = json.loads(self.rfile.read(n).decode())
+                rewarm = parse_style_rewarm(req.pop("rewarm")) if isinstance(req, dict) and "rewarm" in req else False
+                if rewarm == "recent" and not styles.keep_recent:
+                    raise ValueError('"rewarm": "recent" needs a server started with --keep-recent')
+                mix = parse_style(req, styles.names)
             except (KeyError, ValueError) as e:           # (json.JSONDecodeError and UnicodeDecodeError are ValueErrors)
                 self.send_error(400, str(e.args[0] if e.args else e)[:200])
                 return
-            styles.put(mix)
+            if rewarm:
+                styles.put(mix, rewarm=rewarm)
+            else:
+                styles.put(mix)
+            self.send_response(204)
+            self.end_headers()
+
+        def do_rewarm(self):
+            try:
+                n = int(self.headers.get("Content-Length", ""))
+            except ValueError:
+                self.send_error(411)
+                return
+            if not 2 <= n <= 256:
+                self.send_error(413 if n > 256 else 400)
+                return
+            try:
+                styles.put_rewarm(parse_rewarm_body(self.rfile.read(n)))
+            except ValueError as e:
+                self.send_error(400, str(e.args[0] if e.args else e)[:200])
+                return
             self.send_response(204)
             self.end_headers()
 
         def do_POST(self):
             if self.path == "/style" and styles is not None:
                 self.do_style()
+                return
+            if self.path == "/rewarm" and styles is not None:
+                self.do_rewarm()
                 return
             if self.path == "/matte" and mattes is not None:
                 self.do_matte()
@@ -1232,7 +1313,7 @@ def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: Styl
             colors: ColorBox = None, sizes: SizeBox = None, sources: MatteSourceBox = None, steadies: SteadyBox = None,
             details: DetailBox = None, backdrops: BackdropBox = None, follows: SteadyFollowBox = None,
             holds: MatteHoldBox = None, masks: "MaskBox" = None, keys: "MatteKeyBox" = None, edges: MatteEdgeBox = None) -> None:
-    """the producer: loops `frames` through the wrapper until `stop` is set; a posted style, matte, colour lock, output size,
+    """the producer: loops `frames` through the wrapper until `stop` is set; a posted style, re-warm, matte, colour lock, output size,
     matte source, steady mode, follow setting, matte edge, matte hold, detail mode, backdrop, mask, mask input or matte key is
     applied between two frames"""
     from live2diff_amd.jpeg import mjpeg_part
@@ -1337,6 +1418,9 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--style", action="append", default=[], metavar="NAME=DREAMBOOTH[,LORA:ALPHA...]",
                     help="register a further style (repeatable); POST /style {name: weight} switches or blends between frames")
+    ap.add_argument("--keep-recent", action="store_true",
+                    help="keep the last frames' latents on the device (two small copies per frame): POST /rewarm {\"source\": \"recent\"} "
+                         "and \"rewarm\": \"recent\" in POST /style re-warm the sinks on them")
     ap.add_argument("--matte", default=None, metavar="LO,HI[,FEATHER[,far]]",
                     help="stylise only the near (`far`: the far) side of a depth ramp from LO to HI in [0, 1], 1 = nearest; POST /matte "
                          "with the same text, or `off`, changes it between frames")
@@ -1448,10 +1532,11 @@ def main(argv=None):
                                            t_index_list=cfg.get("t_index_list"), strength=cfg.get("strength"), output_type="jpeg",
                                            jpeg_quality=args.quality, height=args.height, width=args.width, seed=args.seed,
                                            engine_dir=args.engine_dir, output_size=size and (size["height"], size["width"]),
-                                           output_resample=size["resample"] if size else "lanczos", matte_source=args.matte_source)
+                                           output_resample=size["resample"] if size else "lanczos", matte_source=args.matte_source,
+                                           keep_recent=args.keep_recent)
     for name, db, loras in style_args:
         w.add_style(name, dreambooth_path=db, lora_dict=loras or None)
-    styles = StyleBox(w.styles, w.style)
+    styles = StyleBox(w.styles, w.style, keep_recent=args.keep_recent)
     if matte is not None:
         w.set_matte(matte["lo"], matte["hi"], keep=matte["keep"], feather=matte["feather"])      # (before `prepare`: the line is primed)
     mattes = MatteBox(w.matte)
