@@ -667,6 +667,29 @@ enum {
  *   16-byte aligned table, dst or src; no records; lines <= 0; line_bytes or a pitch that is not a positive multiple of 16;
  *   line_bytes above either pitch; lines * pitch / 16 >= 2^31 for either pitch; a record whose destination range [dst, dst +
  *   (lines - 1) dst_pitch + line_bytes) overlaps its source range.
+ *
+ * Cut detection (cut.hip; live2diff_amd/cut.py is the arithmetic, held to equality; not in the reference).  A state is (thumb
+ * uint16 [H/8][W/8], hist uint32 [64], rec int32 [8]); two of them ping-pong.  H and W are multiples of 8 and H W <= 2^22.
+ * L2D_OP_FRAME_CUT_SIG  one launch (cut.signature_ref and the shares of Dt):  p0 source half [3][H][W] p1 the thumbnail of the frame
+ *   before, uint16 [H/8][W/8] (NULL and not read under L2D_CUT_INIT) p2 thumbnail out p3 partials uint32 [nwg][68] (all 16-byte
+ *   aligned) ; i0 H i1 W i2 flags (L2D_CUT_INIT) i3 nwg = ceil(H / 64) ceil(W / 64).  Per pixel Y = the integer luma (77 R + 150 G +
+ *   29 B + 128) >> 8 of the egress bytes of p0; p2[by][bx] = the sum of Y over the 8 x 8 block (<= 16,320); partial[tile] = {the 64
+ *   counts of Y >> 2 over the tile, the tile's share of Dt = sum |p2 - p1| (0 under INIT), 0, 0, 0}.  One work-group of 512 lanes
+ *   per 64 x 64 pixels, ragged in whole blocks at the right and the bottom: a wave is one row of 8 blocks, a lane one 8-pixel row
+ *   of a block (16-byte loads), the block sums are cross-lane adds, the histogram and the share live in 272 bytes of LDS under
+ *   integer LDS adds.  Every entry of p2 and p3 is written by a plain store on every launch: nothing has to be zeroed, no atomics
+ *   on global memory.  Refused: a size that is not a positive multiple of 8 or H W > 2^22, a wrong nwg, unknown flags, a null
+ *   (p1: without INIT) or misaligned pointer, p2 or p3 overlapping p0, p1 or each other.
+ * L2D_OP_FRAME_CUT  one launch (cut.measure_ref):  p0 partials p1 hist of the frame before, uint32 [64] p2 its record, int32 [8]
+ *   (p1, p2: NULL and not read under L2D_CUT_INIT) p3 hist out p4 record out (all 16-byte aligned) ; i0 H i1 W i2 nwg i3 flags
+ *   (L2D_CUT_INIT) i4 Tt (0..255 H W) i5 Th (0..2 H W) i6 R (0, or 256..16384: 256 times the ratio) i7 gap (0..255).  hist = the
+ *   partials' sum, Dt = the shares' sum (64-bit), Dh = sum |hist - p1|; the record is {cut, Dt, Dh, since, n, E_lo, E_hi, flags}: E
+ *   an int64 in units of 256 Dt, the running level over the frames that were not cuts, bit 0 of flags "has a level".  INIT writes
+ *   {0, 0, 0, L2D_CUT_NEVER, 0, 0, 0, 0}.  Otherwise s = min(since' + 1, 2^30), cut = Dt >= Tt and Dh >= Th and s > gap and (R == 0
+ *   or no level or 65536 Dt >= R E); on a cut since = 0 and E stays; else since = s and E = 256 Dt without a level, E + ((256 Dt -
+ *   E) >> 3) (a floor shift) with one; n = n' + 1.  One work-group of 256 lanes, 1,056 bytes of LDS; plain stores.  Refused: what
+ *   L2D_OP_FRAME_CUT_SIG refuses of the size, nwg and the flags, a null (p1, p2: without INIT) or misaligned pointer, a threshold
+ *   out of range, p3 or p4 overlapping p0, p1, p2 or each other.
  */
 enum {
     L2D_OP_IGEMM = 1,
@@ -733,6 +756,8 @@ enum {
     L2D_OP_MATTE_KEY_GAIN_HIST = 62,
     L2D_OP_MATTE_KEY_GAIN = 63,
     L2D_OP_SINK_COMMIT = 64,
+    L2D_OP_FRAME_CUT_SIG = 65,
+    L2D_OP_FRAME_CUT = 66,
 };
 
 /* flag bits of L2D_OP_FRAME_MATTE (i4) and L2D_OP_FRAME_MATTE_UP (i6); HARD and FAR also of L2D_OP_FRAME_MATTE_EDGE (i3) */
@@ -817,6 +842,17 @@ enum {
 #define L2D_MATTE_KEY_GAIN_UNITY 128 /* a gain is an integer in units of 1 / 128 */
 #define L2D_MATTE_KEY_GAIN_BINS 512 /* the ratios 0..511; 511 holds everything above */
 #define L2D_MATTE_KEY_GAIN_BLOCK 4096 /* pixels per work-group of L2D_OP_MATTE_KEY_GAIN_HIST: 64 blocks at 512 x 512 */
+/* cut detection: the flag of L2D_OP_FRAME_CUT_SIG (i2) and L2D_OP_FRAME_CUT (i3), sizes and ranges */
+#define L2D_CUT_INIT 1 /* the first frame: no previous state is read */
+#define L2D_CUT_BLOCK 8 /* a thumbnail entry is 8 x 8 pixels */
+#define L2D_CUT_BINS 64 /* histogram bins of Y >> 2 */
+#define L2D_CUT_TILE 64 /* pixels per side of a work-group's tile: 64 tiles at 512 x 512 */
+#define L2D_CUT_PARTIAL 68 /* uint32 words of a partial: 64 counts, the share of Dt, three zeros */
+#define L2D_CUT_MAX_PIXELS 4194304 /* H W at most: 2^22 */
+#define L2D_CUT_NEVER 1073741824 /* `since` before the first cut, and where it saturates: 2^30 */
+#define L2D_CUT_MIN_R 256
+#define L2D_CUT_MAX_R 16384
+#define L2D_CUT_MAX_GAP 255
 
 /* sizes of L2D_OP_FRAME_RESIZE */
 #define L2D_RESIZE_MAX_KS 13 /* taps per output: Lanczos (support 3) at a 2x down-scale, 2 * 6 + 1 */

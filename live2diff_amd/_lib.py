@@ -45,6 +45,8 @@ OP_MATTE_KEY_ADAPT = 61
 OP_MATTE_KEY_GAIN_HIST = 62
 OP_MATTE_KEY_GAIN = 63
 OP_SINK_COMMIT = 64
+OP_FRAME_CUT_SIG = 65
+OP_FRAME_CUT = 66
 ABI_VERSION = 6
 
 

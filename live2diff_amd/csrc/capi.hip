@@ -93,6 +93,8 @@ static int run_one(const l2d_op *op, hipStream_t s) {
         case L2D_OP_MATTE_KEY_GAIN_HIST: return l2d_launch_matte_key_gain_hist(op, s);
         case L2D_OP_MATTE_KEY_GAIN: return l2d_launch_matte_key_gain(op, s);
         case L2D_OP_SINK_COMMIT: return l2d_launch_sink_commit(op, s);
+        case L2D_OP_FRAME_CUT_SIG: return l2d_launch_frame_cut_sig(op, s);
+        case L2D_OP_FRAME_CUT: return l2d_launch_frame_cut(op, s);
         case L2D_OP_COPY: {
             if (!op->p[0] || !op->p[1] || op->l[0] <= 0) {
                 l2d_set_error("copy(tag %d): invalid arguments", op->tag);

@@ -94,6 +94,8 @@ int l2d_launch_matte_key_adapt(const l2d_op *op, hipStream_t s);
 int l2d_launch_matte_key_gain_hist(const l2d_op *op, hipStream_t s);
 int l2d_launch_matte_key_gain(const l2d_op *op, hipStream_t s);
 int l2d_launch_sink_commit(const l2d_op *op, hipStream_t s);
+int l2d_launch_frame_cut_sig(const l2d_op *op, hipStream_t s);
+int l2d_launch_frame_cut(const l2d_op *op, hipStream_t s);
 
 #ifdef __HIPCC__
 // SiLU / GELU are evaluated per output element inside GEMM epilogues and the GroupNorm apply pass (tens of millions of

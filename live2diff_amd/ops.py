@@ -1338,6 +1338,82 @@ def vae_posterior(moments, eps, out, *, B, HW):
     return op, (moments, eps, out)
 
 
+# ----------------------------------------------------------------------------- cut detection (cut.hip)
+# (The section below runs to the end of the file and its builders are pinned one by one in tests/test_frame_records_cpu.py; these
+# two stand in front of it and use its helpers: `_record`, `_fp16_frame`, `_int_in`, `_overlap`, `_got` and the dtype tuples.)
+CUT_BLOCK, CUT_BINS, CUT_TILE, CUT_PARTIAL = 8, 64, 64, 68                                               # l2d.h L2D_CUT_*
+CUT_MAX_PIXELS = 1 << 22                          # l2d.h L2D_CUT_MAX_PIXELS: H W at most
+CUT_NEVER = 1 << 30                               # l2d.h L2D_CUT_NEVER: `since` before the first cut, and where it saturates
+CUT_INIT = 1                                      # l2d.h L2D_CUT_INIT: the first frame, no previous state is read
+CUT_MAX_GAP, CUT_MIN_R, CUT_MAX_R = 255, 256, 16384
+
+
+def frame_cut_tiles(H: int, W: int) -> int:
+    """the work-groups of `frame_cut_sig`: one per 64 x 64 pixels, ragged in whole 8 x 8 blocks at the right and the bottom"""
+    return ((int(H) + CUT_TILE - 1) // CUT_TILE) * ((int(W) + CUT_TILE - 1) // CUT_TILE)
+
+
+def _cut_size(name, H, W):
+    if H < CUT_BLOCK or W < CUT_BLOCK or H % CUT_BLOCK or W % CUT_BLOCK or H * W > CUT_MAX_PIXELS:
+        raise ValueError(f"{name}: {H} x {W}: H and W must be positive multiples of {CUT_BLOCK} with H W <= 2^22")
+
+
+def _cut_state(name, t, dtypes, shape, what):
+    """one tensor of a cut state -- the uint16 [H/8,W/8] thumbnail, the uint32 [64] histogram, the int32 [8] record, or the
+    partials: contiguous, 16-byte aligned, of exactly that shape (int16 / int32: the bits of uint16 / uint32 words)"""
+    if not torch.is_tensor(t) or t.dtype not in dtypes or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.data_ptr() % 16:
+        raise ValueError(f"{name}: expected a contiguous, 16-byte aligned {str(dtypes[0]).replace('torch.', '')} {list(shape)} tensor "
+                         f"({what}), got {_got(t)}")
+
+
+def frame_cut_sig(source, prev_thumb, thumb, partials, *, H, W):
+    """fp16 [3,H,W] `source` -> its uint16 [H/8,W/8] `thumb` (cut.signature_ref's) and uint32 [nwg,68] `partials`: per 64 x 64 tile
+    the 64 counts of its luma histogram, its share of Dt = sum |thumb - prev_thumb|, three zeros.  `prev_thumb` None: INIT, the
+    shares are zero.  Every entry of `thumb` and `partials` is written on every launch."""
+    _cut_size("frame_cut_sig", H, W)
+    _fp16_frame("frame_cut_sig: source", source, H, W, align=16)
+    shape = (H // CUT_BLOCK, W // CUT_BLOCK)
+    if prev_thumb is not None:
+        _cut_state("frame_cut_sig: prev_thumb", prev_thumb, _STATE_DTYPES, shape, "the thumbnail of the frame before, or None")
+    _cut_state("frame_cut_sig: thumb", thumb, _STATE_DTYPES, shape, "the thumbnail")
+    nwg = frame_cut_tiles(H, W)
+    _cut_state("frame_cut_sig: partials", partials, _COUNT_DTYPES, (nwg, CUT_PARTIAL), f"{nwg} tiles of {CUT_TILE} x {CUT_TILE} pixels")
+    outs, reads = (thumb, partials), (source, prev_thumb)
+    if any(_overlap(o, r) for o in outs for r in reads) or _overlap(thumb, partials):
+        raise ValueError("frame_cut_sig: thumb or the partials overlap the source, prev_thumb or each other: the two states ping-pong")
+    return _record(_lib.OP_FRAME_CUT_SIG, (source, prev_thumb, thumb, partials), (H, W, CUT_INIT if prev_thumb is None else 0, nwg))
+
+
+def frame_cut(partials, prev, state, *, H, W, Tt, Th, R, gap):
+    """uint32 [nwg,68] `partials` of an H x W frame and the state `prev` = (thumb, hist, rec) of the frame before -> `state`'s
+    uint32 [64] histogram and int32 [8] record (cut.measure_ref).  `prev` None: INIT.  The thumbnails are `frame_cut_sig`'s and
+    only checked here; `Tt`, `Th`, `R`, `gap`: `cut.cut_params`."""
+    _cut_size("frame_cut", H, W)
+    nwg = frame_cut_tiles(H, W)
+    _cut_state("frame_cut: partials", partials, _COUNT_DTYPES, (nwg, CUT_PARTIAL), f"{nwg} tiles of {CUT_TILE} x {CUT_TILE} pixels")
+    shape = (H // CUT_BLOCK, W // CUT_BLOCK)
+    for name, st in (("prev", prev), ("state", state)):
+        if st is None and name == "prev":
+            continue
+        if not isinstance(st, (tuple, list)) or len(st) != 3:
+            raise ValueError(f"frame_cut: {name}: expected a (thumb, hist, rec) state, got {st!r}")
+        _cut_state(f"frame_cut: {name}: thumb", st[0], _STATE_DTYPES, shape, "the thumbnail")
+        _cut_state(f"frame_cut: {name}: hist", st[1], _COUNT_DTYPES, (CUT_BINS,), "the histogram")
+        _cut_state(f"frame_cut: {name}: rec", st[2], (torch.int32,), (8,), "the record")
+    _int_in("frame_cut: Tt", Tt, 0, 255 * H * W, strict=True)
+    _int_in("frame_cut: Th", Th, 0, 2 * H * W, strict=True)
+    _int_in("frame_cut: R", R, 0, CUT_MAX_R, strict=True)
+    if 0 < R < CUT_MIN_R:
+        raise ValueError(f"frame_cut: R={R!r}: use 0 (no level test) or an integer from {CUT_MIN_R} to {CUT_MAX_R}")
+    _int_in("frame_cut: gap", gap, 0, CUT_MAX_GAP, strict=True)
+    reads = (partials,) + (tuple(prev) if prev is not None else ())
+    if any(_overlap(o, r) for o in state for r in reads) or any(_overlap(a, b) for j, a in enumerate(state) for b in state[j + 1:]):
+        raise ValueError("frame_cut: the state written overlaps the partials, the state read or itself: the two states ping-pong")
+    ph, pr = (None, None) if prev is None else (prev[1], prev[2])
+    return _record(_lib.OP_FRAME_CUT, (partials, ph, pr, state[1], state[2]), (H, W, nwg, CUT_INIT if prev is None else 0, Tt, Th, R, gap),
+                   keep=(partials,) + (tuple(prev) if prev is not None else ()) + tuple(state))
+
+
 # ----------------------------------------------------------------------------- frame I/O (frame_io.hip)
 # From here to the end of the file every builder checks its operands with the helpers below and ends in one call of `_record`:
 #   p   the tensors the kernel reads or writes, in the order of l2d.h's record; None is a null pointer.  A pointer that does not

@@ -18,6 +18,7 @@ near-duplicate frame gate (reference image_filter.py) defaults to this package's
 `stream.similar_filter` may be replaced by any object with `__call__(x) -> x | None`, `set_threshold`,
 `set_max_skip_frame`.
 """
+import collections
 import time
 from typing import List, Literal, Optional, Tuple, Union
 
@@ -167,6 +168,15 @@ class StreamAnimateDiffusionDepth:
         self._recent = None
         self._recent_seen = 0
         self.rewarms = 0
+        # Cut detection (cut.HipCutDetect): every frame that enters the stream batch is measured against
+        # the one before -- two small launches and one asynchronous 32-byte copy, no synchronisation of its own; the records come
+        # out in `cut_records` behind the synchronisation `__call__` / `pop` end with.  None, the default: nothing is launched.
+        # `n` of a record in `cut_records` is the frame's index since `prepare` (the index in the `keep_recent` ring), whenever the
+        # detector was switched on: `_frames_in` counts the frames that passed the near-duplicate filter, a detector's first frame
+        # notes it as its `base`.
+        self.cut_detector = None
+        self.cut_records = collections.deque(maxlen=256)
+        self._frames_in = 0
 
     @property
     def depth_glue(self):
@@ -297,6 +307,10 @@ class StreamAnimateDiffusionDepth:
         # what `rewarm()` runs on again: the window as it enters the loop (clones: nothing is drawn, nothing else is launched)
         self._warm_window = (x_t_latent.clone(), depth_latent.clone())
         self._seed, self.rewarms, self._recent, self._recent_seen = int(seed), 0, None, 0
+        if self.cut_detector is not None:                  # the first frame behind a prepare has nothing to be compared with
+            self.cut_detector.restart()
+        self.cut_records.clear()
+        self._frames_in = 0
         x_0_pred = self._warm_rows(x_t_latent, depth_latent, self.kv_cache_list, lambda x: torch.randn_like(x))
         frames = self.decode_image(x_0_pred[0].transpose(0, 1))
         self.warmup_engine()
@@ -430,6 +444,24 @@ class StreamAnimateDiffusionDepth:
         order = [(self._recent_seen + k) % F_ for k in range(F_)]
         return tuple(r[order].transpose(0, 1)[None].contiguous() for r in self._recent)
 
+    def _enter(self, x) -> None:
+        """a frame enters the stream: it is counted, and measured when there is a cut detector (two launches and one asynchronous
+        copy on the current stream; without a detector nothing is launched)"""
+        det = self.cut_detector
+        if det is not None:
+            if det.frames == 0:
+                det.base = self._frames_in          # a detector switched on mid-stream starts its own count here
+            det.measure(x)
+        self._frames_in += 1
+
+    def _collect_cuts(self, stream=None) -> None:
+        """behind a host synchronisation: the detector's finished records into `cut_records`, `n` counted since `prepare`"""
+        det = self.cut_detector
+        for rec in det.collect(stream):
+            rec = rec.copy()                        # (on the host route the record is also the detector's state)
+            rec[4] += det.base
+            self.cut_records.append(rec)
+
     def warmup_engine(self):
         """reference :346-366 (TensorRT engine warm-up); the HIP plan needs none."""
         return
@@ -555,6 +587,7 @@ class StreamAnimateDiffusionDepth:
             raise RuntimeError("push() needs enable_frame_pipelining() first")
         cur = torch.cuda.current_stream()
         x = self.image_processor.preprocess(x, self.height, self.width).to(device=self.device, dtype=self.dtype)
+        self._enter(x)                                        # (the cut detector: on the caller's stream, which `pop` synchronises)
         self._pre_stream.wait_stream(cur)                     # the frame is ready; earlier consumers of the side buffers are done
         with torch.cuda.stream(self._pre_stream):
             x_t_latent = self.encode_image(x)
@@ -587,6 +620,8 @@ class StreamAnimateDiffusionDepth:
         self.prev_image_result = x_output
         end.record()
         cur.synchronize()                                     # (this stream only: the next frame's side-stream work keeps running)
+        if self.cut_detector is not None:                     # every frame pushed from this stream so far has its record
+            self._collect_cuts(cur)
         inference_time = start.elapsed_time(end) / 1000
         self.inference_time_ema = 0.9 * self.inference_time_ema + 0.1 * inference_time
         self.inference_time_list.append(inference_time)
@@ -641,6 +676,7 @@ class StreamAnimateDiffusionDepth:
             if x is None:
                 time.sleep(self.inference_time_ema)
                 return self.prev_image_result
+        self._enter(x)                                        # (a dropped frame is not counted or measured: n is its index in the ring)
         x_t_latent = self.encode_image(x)
         sd, ed = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         sd.record()
@@ -651,6 +687,8 @@ class StreamAnimateDiffusionDepth:
         self.prev_image_result = x_output
         end.record()
         torch.cuda.synchronize()
+        if self.cut_detector is not None:                     # the frame's own record: its copy lies in front of the synchronize
+            self._collect_cuts()
         inference_time = start.elapsed_time(end) / 1000
         depth_time = sd.elapsed_time(ed) / 1000
         self.inference_time_ema = 0.9 * self.inference_time_ema + 0.1 * inference_time

@@ -327,6 +327,11 @@ class StreamAnimateDiffusionDepthWrapper:
     _key_gain = None                        # the plate gain's settings beside the key (set_matte_key_gain), None: no gain is measured
     _key_gain_last = None                   # (g, n) of the last frame keyed on the host route
     _key_state = None                       # the adaptive plate on the host route, uint16 [3,H,W]; None: it starts from the plate
+    _cut_settings = None                    # the cut detector's settings (set_cut_detect), None: off
+    _auto_rewarm = False                    # re-warm by itself behind a cut (set_auto_rewarm)
+    _rewarm_due = None                      # the count of frames entered at which the automatic re-warm runs, None: none is pending
+    auto_rewarms = 0                        # automatic re-warms since `prepare`
+    last_cut_record = None                  # the newest collected record, `cut.record_dict`'s dict
     depth_source = "detector"               # "input": every frame brings its own depth and no detector was built (`_setup` sets it)
 
     def __init__(self, config_path: str, few_step_model_type: str, num_inference_steps: int,
@@ -474,6 +479,7 @@ class StreamAnimateDiffusionDepthWrapper:
             self.io = HipFrameIO(height, width, device=pipe.device)
             self.stream.image_processor = FrameProcessor(self.io)
         self._init_styles(pipe)
+        self._init_cut_detect()
         self.set_matte_source(matte_source)
         if steady is not None:
             self.set_steady(**steady)
@@ -1601,7 +1607,12 @@ class StreamAnimateDiffusionDepthWrapper:
         frames that entered the stream (`keep_recent=True`); or frames -- anything `prepare` takes as `warmup_frames`, encoded as
         `prepare` encodes them (the detector, or `depths` as `prepare`'s `warmup_depths`) but without the matte tap.  It restarts
         nothing: the matte's delay line, the colour lock, steady, the matte hold, the key's plate and the output size carry on.
-        Legal with frames pushed and not yet popped: it runs on the caller's stream and their UNet steps run behind it."""
+        Legal with frames pushed and not yet popped: it runs on the caller's stream and their UNet steps run behind it.
+        A pending automatic re-warm (`set_auto_rewarm`) is cancelled once this one has succeeded: it has done its work."""
+        self._rewarm(source, depths)
+        self._rewarm_due = None
+
+    def _rewarm(self, source, depths) -> None:
         if isinstance(source, str):
             if source not in ("warmup", "recent"):
                 raise ValueError(f"source={source!r}: use 'warmup', 'recent' or a window of frames")
@@ -1652,6 +1663,95 @@ class StreamAnimateDiffusionDepthWrapper:
                 self.stream.image_processor = keep
         return run(warmup_frames)
 
+    # ------------------------------------------------------------------ cut detection and the automatic re-warm
+    CUTS_KEPT = 256
+
+    def _init_cut_detect(self) -> None:
+        import collections
+        self.cuts = collections.deque(maxlen=self.CUTS_KEPT)     # the frame indices, since `prepare`, of the cuts reported
+
+    @property
+    def cut_detect(self) -> Optional[dict]:
+        """the cut detector's settings as {thumb, hist, ratio, gap}, or None"""
+        return None if self._cut_settings is None else dict(self._cut_settings)
+
+    @cut_detect.setter
+    def cut_detect(self, settings: Optional[dict]) -> None:
+        if settings is None:
+            self.clear_cut_detect()
+        elif isinstance(settings, dict):
+            self.set_cut_detect(**settings)
+        else:
+            raise ValueError(f"cut_detect={settings!r}: use a dict of set_cut_detect's keywords, or None")
+
+    def set_cut_detect(self, thumb=20.0, hist=0.35, ratio=3.0, gap=8) -> None:
+        """Measure every frame that enters the stream against the one before, on the device (`cut.HipCutDetect`: two small
+        launches and one asynchronous 32-byte copy per frame, no synchronisation added), and report scene cuts in `cuts` /
+        `last_cut_record`.  A frame is a cut when its block-luma thumbnail moved by `thumb` byte levels on average AND `hist` of
+        its pixels changed histogram bin AND (`ratio` > 0) the thumbnail moved `ratio` times the running level of the frames
+        before; `gap` frames behind a cut none is reported.  The defaults are a guess, untuned on footage.  May be called before
+        or after `prepare` and between any two frames; on a running detector only the thresholds change."""
+        from . import cut
+        settings = cut.check_settings(thumb, hist, ratio, gap)
+        det = self.stream.cut_detector
+        if det is None:
+            self.stream.cut_detector = cut.HipCutDetect(self.height, self.width, settings, device=self.device)
+        else:
+            det.configure(settings)
+        self._cut_settings = settings
+
+    def clear_cut_detect(self) -> None:
+        """No detector: every launch of a frame is again what it was without one.  A pending automatic re-warm is dropped and
+        `auto_rewarm` goes off with it; `cuts` stays as a record of what was found."""
+        self.stream.cut_detector = None
+        self.stream.cut_records.clear()
+        self._cut_settings, self._auto_rewarm, self._rewarm_due = None, False, None
+
+    @property
+    def auto_rewarm(self) -> bool:
+        return self._auto_rewarm
+
+    @auto_rewarm.setter
+    def auto_rewarm(self, on) -> None:
+        self.set_auto_rewarm(on)
+
+    def set_auto_rewarm(self, on=True) -> None:
+        """Re-warm the sinks by themselves behind a cut: a cut at frame n makes `rewarm("recent")` due once the recent window holds
+        frames n .. n + F - 1, all of the new scene; it runs at the head of the next `img2img` / `pop`, in front of that frame's
+        UNet step.  A further cut before that moves the due point (it does not stack); a manual `rewarm` or `set_style(...,
+        rewarm=...)` in between cancels it.  Needs `keep_recent=True` and a cut detector."""
+        if not isinstance(on, (bool, np.bool_)):
+            raise ValueError(f"auto_rewarm={on!r}: use True or False")
+        if on and not self.stream.keep_recent:
+            raise ValueError("auto_rewarm needs a wrapper built with keep_recent=True")
+        if on and self._cut_settings is None:
+            raise ValueError("auto_rewarm needs a cut detector: call set_cut_detect first")
+        self._auto_rewarm = bool(on)
+        if not on:
+            self._rewarm_due = None
+
+    def _cut_head(self) -> None:
+        """the head of a frame: the automatic re-warm, when one is due"""
+        due = self._rewarm_due
+        if due is not None and self.stream._recent_seen >= due:
+            self._rewarm_due = None               # (first: one that raises is not tried again at every frame)
+            self.rewarm("recent")
+            self.auto_rewarms += 1
+
+    def _cut_tail(self) -> None:
+        """behind a frame: the records the pipeline collected at its synchronisation"""
+        records = self.stream.cut_records
+        if not records:
+            return
+        from .cut import record_dict
+        while records:
+            rec = record_dict(records.popleft())
+            self.last_cut_record = rec
+            if rec["cut"]:
+                self.cuts.append(rec["n"])
+                if self._auto_rewarm:
+                    self._rewarm_due = rec["n"] + self.stream.warmup_frames
+
     # ------------------------------------------------------------------ prepare
     def prepare(self, warmup_frames, prompt: str, negative_prompt: str = "", guidance_scale: float = 1.2, delta: float = 1.0,
                 warmup_depths=None, warmup_masks=None) -> torch.Tensor:
@@ -1687,6 +1787,8 @@ class StreamAnimateDiffusionDepthWrapper:
             self._lock_state = None
         self._steady_init, self._steady_last, self._steady_state = True, None, None      # the steady mode starts again too
         self._hold_init, self._hold_state = True, None                                   # and the matte hold
+        self.cuts.clear()                                                                # and the cut detector's count (the pipeline restarts it)
+        self.last_cut_record, self._rewarm_due, self.auto_rewarms = None, None, 0
         frames = self._on_window(warmup_frames, lambda x: self.stream.prepare(warmup_frames=x, **kw))
         from .unet_hip import HipStreamingUNet
         if isinstance(self.stream.unet, HipStreamingUNet):
@@ -1718,6 +1820,19 @@ class StreamAnimateDiffusionDepthWrapper:
             self._update_prompt(prompt)
         self._camera_begin(image)
         self._mask_begin(mask)
+        if self._cut_settings is not None:
+            return self._img2img_cut(image, dk)
+        return self._img2img(image, dk)
+
+    def _img2img_cut(self, image, dk):
+        """`_img2img` with a cut detector: a due re-warm at the head, the frame's record behind it"""
+        self._cut_head()
+        try:
+            return self._img2img(image, dk)
+        finally:
+            self._cut_tail()
+
+    def _img2img(self, image, dk):
         line = self._matte_line
         if line is None and self._lock is None and self._size is None:
             return self.postprocess_image(self.stream(self.preprocess_image(image), **dk), output_type=self.output_type)
@@ -1748,7 +1863,11 @@ class StreamAnimateDiffusionDepthWrapper:
             self.io.release(self.io.last_view, self.stream._pending[-1][2])
 
     def pop(self):
+        if self._cut_settings is not None:
+            self._cut_head()
         out = self.stream.pop()
+        if self._cut_settings is not None:
+            self._cut_tail()
         if self._matte_line is None and self._lock is None and self._size is None:
             return self.postprocess_image(out, output_type=self.output_type)
         slot = None

@@ -108,7 +108,15 @@ frame's pixels, and is keyed against the plate times that gain.  LIMIT in [1, 3.
 `--matte-key` against a plate and works with or without `--matte-key-adapt`.  `POST /matte-key/gain` with the same text changes it
 while the stream runs, an empty body or `off` clears it; `GET /matte-key/gain` answers `{"limit", "min_share", "gain", "share"}`
 -- the setting and the last frame's measurement per channel (`null` before the first keyed frame) -- or 404 while it is off: the
-producer hands it over between two frames.  The body of `GET /matte-key` does not change."""
+producer hands it over between two frames.  The body of `GET /matte-key` does not change.
+
+`--cut-detect [THUMB,HIST[,RATIO[,GAP]]]` finds scene cuts on the device (`wrapper.set_cut_detect`): every
+frame that enters the stream is measured against the one before, two small launches and no synchronisation; without a value (or
+`on`) the defaults, which are a guess, untuned on footage.  `--auto-rewarm` (implies `--keep-recent`, needs `--cut-detect`) re-warms
+the sinks by themselves once the last frames all lie behind a cut (`wrapper.set_auto_rewarm`).  `POST /cut-detect` with the same
+text, `on` or `off`, and `POST /auto-rewarm` with `on` or `off`, change them between two frames; `GET /cut-detect` and `GET
+/auto-rewarm` answer the current settings, `GET /cuts` answers `{"cuts": [frame indices since prepare], "auto_rewarms": n, "last":
+{the newest record}}` as of the last frame."""
 import argparse
 import json
 import os
@@ -186,9 +194,11 @@ class StyleBox:
     wrapper knows; `current` is the mix last applied; `failed` counts requests the wrapper refused.  What `POST /rewarm` delivers
     waits here too -- the newest requested source, applied behind a posted style between the same two frames.  `keep_recent`: whether
     the wrapper keeps a recent window ("recent" is refused at the door without one); `rewarms` counts the re-warms done,
-    `rewarm_failed` those the wrapper refused (fewer than F frames since `prepare`, say)."""
+    `rewarm_failed` those the wrapper refused (fewer than F frames since `prepare`, say).  `cuts`: the `CutBox` of the cut detector
+    and the automatic re-warm, or None; it is applied behind the style and the re-warm, between the same two frames."""
 
-    def __init__(self, names, current=None, keep_recent: bool = False):
+    def __init__(self, names, current=None, keep_recent: bool = False, cuts: "CutBox" = None):
+        self.cuts = cuts
         self._lock = threading.Lock()
         self.names, self.current, self._want, self.failed = list(names), dict(current or {}), None, 0
         self._rewarm = False
@@ -232,9 +242,85 @@ class StyleBox:
                 self.rewarms += 1
             except (ValueError, RuntimeError):
                 self.rewarm_failed += 1
+        if self.cuts is not None:
+            self.cuts.apply(wrapper)
 
 
 REWARM_SOURCES = ("warmup", "recent")
+
+
+class CutBox:
+    """What `POST /cut-detect` and `POST /auto-rewarm` deliver: the newest requested detector settings (`"off"`: none) and the newest
+    requested switch, applied by the producer between two frames, the detector first.  `current` is the setting last applied;
+    `failed` counts requests the wrapper refused (an automatic re-warm without a detector, say).  `keep_recent`: whether the wrapper
+    keeps a recent window (switching the automatic re-warm on is refused at the door without one).  `report` is what `GET /cuts`
+    answers, copied from the wrapper by the producer behind every `apply`."""
+
+    _NOTHING = object()
+
+    def __init__(self, current=None, auto: bool = False, keep_recent: bool = False):
+        self._lock = threading.Lock()
+        self.current, self.auto, self.keep_recent, self.failed = current, bool(auto), bool(keep_recent), 0
+        self._want, self._want_auto = self._NOTHING, None
+        self.report = {"cuts": [], "auto_rewarms": 0, "last": None}
+
+    def put(self, settings) -> None:
+        with self._lock:
+            self._want = settings
+
+    def put_auto(self, on: bool) -> None:
+        if on and not self.keep_recent:
+            raise ValueError("the automatic re-warm needs a server started with --auto-rewarm or --keep-recent")
+        with self._lock:
+            self._want_auto = bool(on)
+
+    def apply(self, wrapper) -> None:
+        """(producer thread, between frames)"""
+        with self._lock:
+            want, auto, self._want, self._want_auto = self._want, self._want_auto, self._NOTHING, None
+        if want is not self._NOTHING:
+            try:
+                if want is None:
+                    wrapper.clear_cut_detect()
+                else:
+                    wrapper.set_cut_detect(**want)
+            except ValueError:
+                self.failed += 1
+        if auto is not None:
+            try:
+                wrapper.set_auto_rewarm(auto)
+            except ValueError:
+                self.failed += 1
+        report = {"cuts": [int(n) for n in wrapper.cuts], "auto_rewarms": int(wrapper.auto_rewarms), "last": wrapper.last_cut_record}
+        with self._lock:
+            self.current, self.auto, self.report = wrapper.cut_detect, bool(wrapper.auto_rewarm), report
+
+
+def parse_cut_detect_arg(text: str):
+    """`on` or `THUMB,HIST[,RATIO[,GAP]]` -> the keywords of `wrapper.set_cut_detect`; `off` -> None; ValueError otherwise"""
+    from live2diff_amd.cut import check_settings
+    text = text.strip()
+    if text == "off":
+        return None
+    if text == "on":
+        return check_settings()
+    parts = [p.strip() for p in text.split(",")]
+    if not 2 <= len(parts) <= 4 or not all(parts):
+        raise ValueError("use on, off or THUMB,HIST[,RATIO[,GAP]]")
+    kw = dict(thumb=float(parts[0]), hist=float(parts[1]))
+    if len(parts) > 2:
+        kw["ratio"] = float(parts[2])
+    if len(parts) > 3:
+        kw["gap"] = int(parts[3])
+    return check_settings(**kw)
+
+
+def parse_auto_rewarm_arg(text: str) -> bool:
+    """`on` / `off` -> True / False; ValueError otherwise"""
+    text = text.strip()
+    if text not in ("on", "off"):
+        raise ValueError("use on or off")
+    return text == "on"
 
 
 def parse_rewarm_body(body: bytes) -> str:
@@ -1034,6 +1120,9 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
                  sizes: "SizeBox" = None, sources: "MatteSourceBox" = None, steadies: "SteadyBox" = None, details: "DetailBox" = None,
                  backdrops: "BackdropBox" = None, follows: "SteadyFollowBox" = None, holds: "MatteHoldBox" = None,
                  masks: "MaskBox" = None, keys: "MatteKeyBox" = None, edges: "MatteEdgeBox" = None):
+    # (The cut detector's box rides with the styles' box, as the re-warm's requests do: tests pin `edges` as the last parameter of
+    # this function and of the two producers.  It is the one the `StyleBox` was built with.)
+    cuts = styles.cuts if styles is not None else None
     boxes = {"/matte-key": keys, "/matte": mattes, "/color": colors, "/size": sizes, "/matte-source": sources, "/steady": steadies, "/matte-edge": edges,
              "/detail": details, "/backdrop": backdrops, "/steady-follow": follows, "/matte-hold": holds}
     page = PAGE if inbox is None else CAMERA_PAGE
@@ -1078,6 +1167,14 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
                 body = json.dumps({"rewarms": styles.rewarms, "failed": styles.rewarm_failed}).encode()
                 self.send_response(200)
                 self.send_header("Content-Type", "application/json")
+                self.send_header("Content-Length", str(len(body)))
+                self.end_headers()
+                self.wfile.write(body)
+            elif cuts is not None and self.path in ("/cuts", "/cut-detect", "/auto-rewarm"):
+                body = json.dumps(cuts.report if self.path == "/cuts" else cuts.current if self.path == "/cut-detect" else cuts.auto).encode()
+                self.send_response(200)
+                self.send_header("Content-Type", "application/json")
+                self.send_header("Cache-Control", "no-store")
                 self.send_header("Content-Length", str(len(body)))
                 self.end_headers()
                 self.wfile.write(body)
@@ -1244,9 +1341,33 @@ def make_handler(latest: Latest, inbox: "Inbox" = None, styles: "StyleBox" = Non
             self.send_response(204)
             self.end_headers()
 
+        def do_cut(self):
+            try:
+                n = int(self.headers.get("Content-Length", ""))
+            except ValueError:
+                self.send_error(411)
+                return
+            if not 1 <= n <= 256:
+                self.send_error(413 if n > 256 else 400)
+                return
+            try:
+                text = self.rfile.read(n).decode()
+                if self.path == "/cut-detect":
+                    cuts.put(parse_cut_detect_arg(text))
+                else:
+                    cuts.put_auto(parse_auto_rewarm_arg(text))
+            except ValueError as e:                       # (UnicodeDecodeError is a ValueError)
+                self.send_error(400, str(e.args[0] if e.args else e)[:200])
+                return
+            self.send_response(204)
+            self.end_headers()
+
         def do_POST(self):
             if self.path == "/style" and styles is not None:
                 self.do_style()
+                return
+            if cuts is not None and self.path in ("/cut-detect", "/auto-rewarm"):
+                self.do_cut()
                 return
             if self.path == "/rewarm" and styles is not None:
                 self.do_rewarm()
@@ -1314,8 +1435,8 @@ def produce(wrapper, frames, latest: Latest, stop: threading.Event, styles: Styl
             details: DetailBox = None, backdrops: BackdropBox = None, follows: SteadyFollowBox = None,
             holds: MatteHoldBox = None, masks: "MaskBox" = None, keys: "MatteKeyBox" = None, edges: MatteEdgeBox = None) -> None:
     """the producer: loops `frames` through the wrapper until `stop` is set; a posted style, re-warm, matte, colour lock, output size,
-    matte source, steady mode, follow setting, matte edge, matte hold, detail mode, backdrop, mask, mask input or matte key is
-    applied between two frames"""
+    matte source, steady mode, follow setting, matte edge, matte hold, detail mode, backdrop, mask, mask input, matte key, cut
+    detector or automatic re-warm is applied between two frames"""
     from live2diff_amd.jpeg import mjpeg_part
     try:
         i = 0
@@ -1421,6 +1542,15 @@ def main(argv=None):
     ap.add_argument("--keep-recent", action="store_true",
                     help="keep the last frames' latents on the device (two small copies per frame): POST /rewarm {\"source\": \"recent\"} "
                          "and \"rewarm\": \"recent\" in POST /style re-warm the sinks on them")
+    ap.add_argument("--cut-detect", default=None, nargs="?", const="on", metavar="THUMB,HIST[,RATIO[,GAP]]",
+                    help="find scene cuts on the device: a frame is a cut when its 8 x 8 block luma moved by THUMB byte levels on average "
+                         "(default 20) and HIST of its pixels changed histogram bin (default 0.35) and it moved RATIO times as far as the "
+                         "frames before (default 3; 0: no such test), GAP frames (default 8) behind a cut none is reported -- defaults that "
+                         "are a guess, untuned on footage; POST /cut-detect with the same text, `on` or `off` changes it between two "
+                         "frames; GET /cuts answers the cuts found")
+    ap.add_argument("--auto-rewarm", action="store_true",
+                    help="re-warm the sinks by themselves once the last frames all lie behind a cut (implies --keep-recent; needs "
+                         "--cut-detect or a POST /cut-detect); POST /auto-rewarm with `on` or `off` switches it between two frames")
     ap.add_argument("--matte", default=None, metavar="LO,HI[,FEATHER[,far]]",
                     help="stylise only the near (`far`: the far) side of a depth ramp from LO to HI in [0, 1], 1 = nearest; POST /matte "
                          "with the same text, or `off`, changes it between frames")
@@ -1482,6 +1612,14 @@ def main(argv=None):
                     help="how a mask meets the depth ramp: replace (default), and, or; `invert` flips the mask first; POST /mask-input "
                          "with the same text changes it between frames")
     args = ap.parse_args(argv)
+    if args.auto_rewarm:
+        args.keep_recent = True
+    try:
+        cut_detect = parse_cut_detect_arg(args.cut_detect) if args.cut_detect else None
+    except ValueError as e:
+        ap.error("--cut-detect: " + str(e))
+    if args.auto_rewarm and cut_detect is None:
+        ap.error("--auto-rewarm needs --cut-detect")
     ap_key = args.matte_key
     if ap_key is not None and not args.matte:
         ap.error("--matte-key needs --matte (its feather and `far` act on the key)")
@@ -1536,7 +1674,12 @@ def main(argv=None):
                                            keep_recent=args.keep_recent)
     for name, db, loras in style_args:
         w.add_style(name, dreambooth_path=db, lora_dict=loras or None)
-    styles = StyleBox(w.styles, w.style, keep_recent=args.keep_recent)
+    if cut_detect is not None:
+        w.set_cut_detect(**cut_detect)
+    if args.auto_rewarm:
+        w.set_auto_rewarm(True)
+    styles = StyleBox(w.styles, w.style, keep_recent=args.keep_recent,
+                      cuts=CutBox(w.cut_detect, w.auto_rewarm, keep_recent=args.keep_recent))
     if matte is not None:
         w.set_matte(matte["lo"], matte["hi"], keep=matte["keep"], feather=matte["feather"])      # (before `prepare`: the line is primed)
     mattes = MatteBox(w.matte)

@@ -131,7 +131,22 @@ def main(argv=None):
     ap.add_argument("--mask", default=None, help="folder of mask images named like the frames (or .npy [F,Hm,Wm]): the matte from the caller")
     ap.add_argument("--mask-input", default="replace", help="COMBINE[,invert]: replace (default), and, or -- how a mask meets the depth ramp")
     ap.add_argument("--matte", default=None, help="LO,HI[,FEATHER[,far]]: the depth matte (with --mask, default 0,1: the ramp `and` / `or` read)")
+    ap.add_argument("--cut-detect", default=None, nargs="?", const="on", metavar="THUMB,HIST[,RATIO[,GAP]]",
+                    help="find scene cuts on the device (wrapper.set_cut_detect; the defaults are a guess, untuned on footage); their frame "
+                         "indices are printed at the end")
+    ap.add_argument("--auto-rewarm", action="store_true",
+                    help="re-warm the sinks by themselves once the last frames all lie behind a cut (keeps the recent window; needs --cut-detect)")
     args = ap.parse_args(argv)
+    cut_detect = None
+    if args.cut_detect is not None:
+        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+        from mjpeg_server import parse_cut_detect_arg
+        try:
+            cut_detect = parse_cut_detect_arg(args.cut_detect)
+        except ValueError as e:
+            ap.error("--cut-detect: " + str(e))
+    if args.auto_rewarm and cut_detect is None:
+        ap.error("--auto-rewarm needs --cut-detect")
 
     from PIL import Image
 
@@ -162,7 +177,10 @@ def main(argv=None):
     w = StreamAnimateDiffusionDepthWrapper(args.config, few_step_model_type="lcm", num_inference_steps=cfg.get("num_inference_steps", 50),
                                            t_index_list=cfg.get("t_index_list"), strength=cfg.get("strength"), output_type="u8",
                                            height=args.height, width=args.width, use_tiny_vae=not args.full_vae, seed=args.seed,
-                                           engine_dir=args.engine_dir, **more)
+                                           engine_dir=args.engine_dir, keep_recent=args.auto_rewarm, **more)
+    if cut_detect is not None:
+        w.set_cut_detect(**cut_detect)
+        w.set_auto_rewarm(args.auto_rewarm)
     prompt = args.prompt if args.prompt is not None else str(cfg.get("prompt", ""))
     os.makedirs(args.output, exist_ok=True)
     if matte is not None:
@@ -180,6 +198,9 @@ def main(argv=None):
         Image.fromarray(o).save(os.path.join(args.output, f"{sink + i:05d}.png"))
     print(f"{len(warm)} warm-up + {len(outs)} frames -> {args.output}; inference_time_ema {w.stream.inference_time_ema * 1e3:.2f} ms "
           f"({1.0 / max(w.stream.inference_time_ema, 1e-9):.1f} fps)")
+    if cut_detect is not None:
+        # (indices count the frames behind the warm-up window; file names are `sink` further on)
+        print(f"cuts at frames {[sink + n for n in w.cuts]} ({len(w.cuts)}); {w.auto_rewarms} automatic re-warms")
 
 
 if __name__ == "__main__":
